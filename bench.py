@@ -16,6 +16,10 @@ all-gather or the feature-sharded variants instead).
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 3
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what the headline does not need: the
+CPU baseline with its parity check, the HBM traffic counted live by two rocprofv3 --pmc child runs, the sustained leg and,
+with more than one rank, the alt_partitions legs.  --dump-outputs DIR writes what the last timed step returned as .npy files.
 """
 import argparse
 import json
@@ -73,7 +77,7 @@ def parse():
     ap.add_argument("--alt-timeout", type=float, default=300.0,
                     help="seconds the extra partitions may take before the measured line is printed without them")
     ap.add_argument("--alt-partitions", default="auto", choices=["auto", "off"],
-                    help="more than one rank, halo partition: after the timed loop, also time a few steps of the partitions that DO "
+                    help="--full, more than one rank, halo partition: after the timed loop, also time a few steps of the partitions that DO "
                          "move operand rows over xGMI (all-gather of the [N, W] operand; all-to-all-v of the listed halo rows) and "
                          "print them as alt_partitions")
     ap.add_argument("--alt-steps", type=int, default=5)
@@ -101,22 +105,34 @@ def parse():
                     help="where the next forward's table build branches off inside a replayed share: under the look-up or "
                          "under the aggregation (default: measured 0.919 against 0.944 ms on the slowest 1/8 share)")
     ap.add_argument("--index-buckets", type=int, default=0, help="cells per feature of the direct-index look-up (0: the library's default)")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0,
+    ap.add_argument("--sustain-seconds", type=float, default=None,
                     help="one GPU: after the timed region (and the CPU baseline) keep issuing the same step for this long, so "
                          "that an outside sampler of GPU activity sees the kernels (the timed region is ~0.1 s of a run whose "
-                         "wall time is mostly the CPU baseline); reported as sustained_ms_per_step, never as `value`.  0: off")
-    ap.add_argument("--traffic", default="measure", choices=["measure", "committed", "off"],
+                         "wall time is mostly the CPU baseline); reported as sustained_ms_per_step, never as `value`.  0: off "
+                         "(default: 10 with --full, else 0)")
+    ap.add_argument("--traffic", default=None, choices=["measure", "committed", "off"],
                     help="roofline.traffic: measure = two short rocprofv3 --pmc child runs of this very command (FETCH_SIZE, "
                          "WRITE_SIZE; one GPU), falling back to the committed figure of profiles/hbm_traffic.json; committed = "
-                         "that figure only")
+                         "that figure only (default: measure with --full, else committed)")
     ap.add_argument("--set", action="append", default=[], metavar="MODULE.NAME=VALUE",
                     help="A/B aid: set a module-level constant of the package before the run, e.g. --set "
                          "aggregate.HOT_ROWS_IN_LDS=False (the library and the package read no environment switches for "
                          "kernel selection)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (and its parity check), the live "
+                         "traffic counters, the sustained leg, the alt_partitions legs; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-nodes", type=int, default=500_000, help="upper bound of the CPU shape-function sample")
     ap.add_argument("--cpu-rows", type=int, default=2_000_000, help="rows of the CPU aggregation sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (the forward's output; c3: and the gradients) "
+                         "as DIR/<name>.npy, float32 (float64 stays float64), at most 64 MB in all")
     args = ap.parse_args()
+    if args.sustain_seconds is None:
+        args.sustain_seconds = 10.0 if args.full else 0.0
+    if args.traffic is None:
+        args.traffic = "measure" if args.full else "committed"
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
     if args.config == "c5":                                  # papers100M-shaped: same generator, scale 27, bf16 operand rows
         given = set(a.split("=")[0] for a in sys.argv[1:])
         if "--scale" not in given:
@@ -329,6 +345,26 @@ def _event_ms(fn, steps, warmup):
     return ts[len(ts) // 2], ts[0]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor, what the last timed step returned) as ``dirname/<name>.npy``, float64 kept,
+    every other dtype as float32.  Should they exceed 64 MB in all, each keeps the same share of its rows: a sorted sample
+    drawn with seed 0 from the row count alone, hence the same rows in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach()
+        if total > DUMP_MAX_BYTES and t.dim() > 0:
+            keep = max(1, int(t.shape[0] * DUMP_MAX_BYTES / total))
+            rows = np.unique(np.random.default_rng(0).integers(0, t.shape[0], keep))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def apply_sets(args):
     """--set MODULE.NAME=VALUE: module-level constants of the package, before the run (A/B aid)."""
     import ast
@@ -454,6 +490,9 @@ def run_c3(args):
         out = fwd_bwd()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out, **{"grad." + k: p.grad for k, p in model.named_parameters()
+                                                       if p.grad is not None}})
     fb_ms, fb_min = _event_ms(fwd_bwd, args.steps, 0)
     # ... and the same step replayed from ONE hipGraph launch (what gnan_amd.harness does with a full-batch epoch from its
     # third pass on): the eager step above is bound by the host issuing ~60 launches, not by the device
@@ -528,7 +567,7 @@ def run_c3(args):
         result["reference_loop"] = reference_loop_leg(model, [labelled] * 20, C, False, epochs=3)
         if args.fresh_inputs:
             result["reference_loop_fresh_inputs"] = reference_loop_leg(model, [labelled] * 20, C, False, epochs=3, fresh_inputs=True)
-    if not args.no_cpu_baseline:
+    if args.cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_c3(args, model, g, x, fwd())
     print(json.dumps(result), flush=True)
 
@@ -628,6 +667,8 @@ def run_c2(args, rank=0, world=1):
         elapsed, total_pairs = float(tm[0]), int(t[1])
     if rank != 0:
         return
+    if args.dump_outputs:                                    # one number per graph (more than one rank: rank 0's graphs)
+        dump_outputs(args.dump_outputs, {"out": torch.cat([o.reshape(-1) for o in outs])})
     # replayed per shape through the harness (what a training run does after every epoch: trainer.py:89-154)
     from gnan_amd import harness
     loss_fn = torch.nn.BCEWithLogitsLoss()
@@ -695,7 +736,7 @@ def run_c2(args, rank=0, world=1):
         result["reference_loop"] = ref_loop
     if ref_fresh is not None:
         result["reference_loop_fresh_inputs"] = ref_fresh
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.cpu_baseline:
         from oracle import gnan_oracle as O
         sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         p64 = {k: v.double() for k, v in sd.items()}
@@ -742,7 +783,7 @@ def measure_traffic(kernel_prefix="spmm_kernel<"):
     import tempfile
     if shutil.which("rocprofv3") is None:
         return None, "rocprofv3 not on PATH"
-    drop = {"--traffic", "--sustain-seconds", "--steps", "--warmup"}
+    drop = {"--traffic", "--sustain-seconds", "--steps", "--warmup", "--dump-outputs"}
     argv, skip = [], False
     for a in sys.argv[1:]:
         if skip:
@@ -751,9 +792,9 @@ def measure_traffic(kernel_prefix="spmm_kernel<"):
         if a.split("=")[0] in drop:
             skip = "=" not in a
             continue
-        if a != "--no-cpu-baseline":
+        if a not in ("--no-cpu-baseline", "--full"):
             argv.append(a)
-    argv += ["--traffic", "off", "--sustain-seconds", "0", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    argv += ["--traffic", "off", "--sustain-seconds", "0", "--steps", "2", "--warmup", "1"]
     found = {}
     tmp = tempfile.mkdtemp(prefix="gnan_pmc_", dir="/tmp")
     try:
@@ -974,7 +1015,8 @@ def main():
     else:                                        # whole graph, this rank's feature columns
         g = syn.hop1_csr(src, dst, N)
         x = syn.block_features(N, F, 0, N, seed=1, device=dev)[:, fpart.lo:fpart.hi].contiguous()
-    want_alt = grouped and not emulated and args.alt_partitions != "off" and partition == "halo" and args.order == "reference"
+    want_alt = (args.full and grouped and not emulated and args.alt_partitions != "off" and partition == "halo"
+                and args.order == "reference")
     if not want_alt:
         del src, dst
     torch.manual_seed(0)
@@ -1157,6 +1199,8 @@ def main():
     if grouped and partition != "feature":      # row-partitioned output: add the ranks' shares (feature: already whole)
         dist.all_reduce(checksum, op=dist.ReduceOp.SUM)
     checksum = float(checksum)
+    if args.dump_outputs and (rank == 0 or emulated):   # (more than one rank: rank 0's share of the output)
+        dump_outputs(args.dump_outputs, {"out": out})
 
     stages = {n: 0.0 for n in stage_names}
     per_step = []                                    # device time of every timed step (HIP events on the compute stream)
@@ -1239,7 +1283,7 @@ def main():
             # bf16 operand rows are an inference format: the library has no backward through them
             "backward": False if args.operand == "bf16" else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             with torch.no_grad():
                 from gnan_amd.functional import feature_mlps
                 operand = feature_mlps(x, stacked, args.order == "sum_first")

@@ -226,8 +226,9 @@ def test_bench_line_survives_extra_partitions_that_do_not_finish():
         pytest.fail("GPU tests need a visible MI355X")
     env_had = os.environ.pop("WORLD_SIZE", None)
     try:
-        cut = _bench_line(["--gpus", "2", "--same-device", "--backend", "gloo", "--partition", "halo", "--alt-timeout", "0.001"])
-        full = _bench_line(["--gpus", "2", "--same-device", "--backend", "gloo", "--partition", "halo"])
+        cut = _bench_line(["--full", "--gpus", "2", "--same-device", "--backend", "gloo", "--partition", "halo",
+                          "--alt-timeout", "0.001"])
+        full = _bench_line(["--full", "--gpus", "2", "--same-device", "--backend", "gloo", "--partition", "halo"])
     finally:
         if env_had is not None:
             os.environ["WORLD_SIZE"] = env_had

@@ -16,12 +16,12 @@ python3 tools/train_step_c4.py > $OUT/train_step_noprof.log 2>&1
 PER_LAYER=1 python3 tools/train_step_c4.py > $OUT/train_step_per_layer.log 2>&1              # the optimizer over model.parameters() (torch's per-tensor overhead on top)
 python3 bench.py --config c5 --traffic off --sustain-seconds 0 --no-cpu-baseline --steps 5 --warmup 2 > $OUT/c5_bench.log 2>&1
 python3 bench.py --config c5 --operand f32 --order sum_first --traffic off --sustain-seconds 0 --no-cpu-baseline --steps 5 --warmup 2 > $OUT/c5_sum_first_bench.log 2>&1
-python3 bench.py --config c3 --steps 20 --warmup 5 > $OUT/c3_bench.log 2>&1
+python3 bench.py --full --config c3 --steps 20 --warmup 5 > $OUT/c3_bench.log 2>&1
 python3 bench.py --config c3 --out 40 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/c3_c40_bench.log 2>&1
-python3 bench.py --config c2 --steps 3 --warmup 1 > $OUT/c2_bench.log 2>&1
+python3 bench.py --full --config c2 --steps 3 --warmup 1 > $OUT/c2_bench.log 2>&1
 bash tools/emulate_shares.sh > $OUT/emulated_shares.txt 2>&1
 SHARE_GRAPH=off bash tools/emulate_shares.sh > $OUT/emulated_shares_eager.txt 2>&1
-python3 bench.py > $OUT/bench_full.log 2>&1                                                   # the driver's command: traffic measured, CPU baseline, sustained leg
+python3 bench.py --full > $OUT/bench_full.log 2>&1                                            # traffic measured, CPU baseline, sustained leg
 python3 tools/lookup_ab.py > $OUT/lookup_ab.jsonl 2> $OUT/lookup_ab.err
 tools/_bin/lookup_ceiling > $OUT/lookup_ceiling.jsonl 2>&1
 bash tools/pmc_sq_cmd.sh $OUT/sq_fwd python3 bench.py --traffic off --sustain-seconds 0 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/sq_fwd.txt 2>&1
@@ -48,7 +48,7 @@ python3 tools/pb_bench.py 1 2 > $OUT/pb_bench.jsonl 2> $OUT/pb_bench.err        
 bash tools/pmc_narrow.sh $OUT > $OUT/pmc_narrow.log 2>&1                                                                       # L2 hit / miss / fabric requests of the narrow kernels, old and new
 for f in "" "--flat"; do python3 tools/reference_loop_bench.py arxiv cora muta $f 2>/dev/null | grep -v "by phase"; python3 tools/reference_loop_bench.py arxiv cora muta --fresh-inputs $f 2>/dev/null; done > $OUT/reference_loop_faces.jsonl
 python3 bench.py --config c3 --loop reference --fresh-inputs --no-cpu-baseline > $OUT/c3_loop_reference_fresh.log 2>&1
-python3 bench.py --force-dist --traffic off --sustain-seconds 0 --no-cpu-baseline --steps 20 --partition halo > $OUT/bench_force_dist_alt_partitions.log 2>&1   # one rank, RCCL group: alt_partitions code path
+python3 bench.py --full --force-dist --traffic off --sustain-seconds 0 --no-cpu-baseline --steps 20 --partition halo > $OUT/bench_force_dist_alt_partitions.log 2>&1   # one rank, RCCL group: alt_partitions code path
 python3 tools/c1_cpu.py 3 > $OUT/c1_cpu.json 2> $OUT/c1_cpu.err                                                                # config 1 on the box's host cores
 find $OUT -name "*_kernel_trace.csv" -delete
 find $OUT -name "*.db" -delete
