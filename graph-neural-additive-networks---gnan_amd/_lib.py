@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNAN_HIP_LIB: development aid for same-box A/B runs of two builds of the library (tools/ab_lib.sh)
 LIB_PATH = os.environ.get("GNAN_HIP_LIB") or os.path.join(_HERE, "libgnan_hip.so")
-ABI_VERSION = 45
+ABI_VERSION = 46
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # enum gnan_status
 
 GNAN_F32, GNAN_BF16 = 0, 1
@@ -125,6 +125,18 @@ class SpmmArgs(C.Structure):
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("s_by_code", C.c_int32), ("nnz", C.c_int64), ("packed_index", C.c_int32),
         ("hot_lo", C.c_int64), ("hot_rows", C.c_int32), ("shell_out", C.c_void_p),
+        ("cls_index", C.c_void_p), ("cls_slice_start", C.c_void_p), ("cls_slice_row", C.c_void_p), ("cls_slot_slice", C.c_void_p),
+        ("cls_n_slots", C.c_int32),
+    ]
+
+
+class ClassedPlanArgs(C.Structure):
+    _fields_ = [
+        ("rowptr", C.c_void_p), ("rowptr_is64", C.c_int32), ("col", C.c_void_p), ("code", C.c_void_p), ("row_ids", C.c_void_p),
+        ("long_rows", C.c_void_p), ("n_long", C.c_int32), ("slice_edges", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("totals", C.c_void_p),
+        ("index", C.c_void_p), ("slice_start", C.c_void_p), ("slice_row", C.c_void_p), ("slice_ptr", C.c_void_p),
+        ("slot_slice", C.c_void_p), ("n_slots", C.c_int64),
     ]
 
 
@@ -404,6 +416,9 @@ SYMBOLS = {
     "gnan_long_row_plan_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gnan_long_row_plan_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnan_classed_plan_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnan_classed_plan_count": (C.c_int, [C.POINTER(ClassedPlanArgs), C.c_void_p]),
+    "gnan_classed_plan_fill": (C.c_int, [C.POINTER(ClassedPlanArgs), C.c_void_p]),
     "gnan_csr_transpose_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "gnan_csr_transpose": (C.c_int, [C.POINTER(CsrTransposeArgs), C.c_void_p]),
     "gnan_pb_plan_long_row_threshold": (C.c_int32, []),

@@ -46,6 +46,9 @@ def _spmm_args(g: HopGraph, S, lut, use_cnt, s_total, out, row_ids, per_row_lut,
         workspace=_lib.ptr(workspace), workspace_bytes=(workspace.numel() * 4 if workspace is not None else 0),
         s_by_code=int(s_by_code), nnz=(0 if (g.col is None or not WIDE_INDEX_LOADS) else int(g.col.numel())),
         packed_index=int(packed))
+    if getattr(plan, "index", None) is not None and plan.n_long > 0:
+        a.cls_index, a.cls_slice_start = _lib.ptr(plan.index), _lib.ptr(plan.slice_start)
+        a.cls_slice_row, a.cls_slot_slice, a.cls_n_slots = _lib.ptr(plan.slice_row), _lib.ptr(plan.slot_slice), plan.n_slots
     if hot_rows and packed and HOT_ROWS_IN_LDS:
         # the appended compact copy of the most listed rows sits behind the real ones: its head is served from LDS — where it
         # receives enough of the pairs to pay for the persistent kernel's lower occupancy (10M-node R-MAT: 32 % at W = 1,
@@ -72,6 +75,9 @@ HOT_ROWS_IN_LDS = True           # ... and serve the head of that copy from LDS 
 HOT_LDS_FLOATS = 16384                                                   # 64 KB per workgroup, two workgroups per CU
 HOT_LDS_MIN_SHARE = 0.25                                                 # ... from this share of the pairs listing the LDS-resident rows
 DEGREE_SORTED_COPY = True      # ... through a degree-sorted copy of the CSR (HopGraph.degree_sorted_copy) instead of an index
+XCD_CLASSED_HUBS = True        # wide forward rows of large graphs: hub slices of one column class each, a class per XCD (classed_hub_plan)
+CLASSED_MIN_ROW_BYTES = 128    # ... from operand rows of this many bytes (fp32 W >= 32, bf16 W >= 64)
+CLASSED_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs
 
 
 def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -174,6 +180,14 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
             scatter = True
     else:
         plan = g.narrow_row_plan() if (narrow and NARROW_ROW_SLICING and row_ids is None) else g.long_row_plan(row_ids)
+    if (XCD_CLASSED_HUBS and plan is not None and not g.is_dense and S.shape[1] * S.element_size() >= CLASSED_MIN_ROW_BYTES
+            and g.nnz >= CLASSED_MIN_NNZ and not weight_by_col and not minus_rest and not s_by_code and not g._cnt_by_col
+            and n_hot == 0):
+        # the same hub rows, their slices grouped by column class so that each XCD's L2 caches one eighth of the hot operand rows
+        # (DESIGN.md 4.1); every walk of the call takes it (scatter_out 2: the copy's own rows; else slot q reads row_ids[q])
+        classed = g.classed_hub_plan(row_ids if scatter != 2 else None)
+        if classed is not None:
+            plan = classed
     if from_counts:
         lut = lut_of_counts(g.cnt).detach().float().contiguous()          # rows of THIS graph (a sorted copy carries its own counts)
         per_row = True

@@ -650,3 +650,234 @@ extern "C" int gnan_long_row_plan_fill(const void* rowptr, int32_t rowptr_is64, 
   if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "long_row_plan_fill: scan: %s", hipGetErrorString(e));
   return GNAN_OK;
 }
+
+// =============================================================================================
+// The classed hub plan (HopGraph.classed_hub_plan): the pairs of every hub row partitioned stably by the column class
+// g = col & 7 into a plan-owned packed index (col | code << 29; within a class the CSR order is kept), slices cut per (row, class)
+// at slice_edges, and one slice queue per class — workgroup b of the aggregation takes entry b >> 3 of queue b & 7, so that the
+// round-robin dispatch puts a class on one XCD and its L2 sees only that class's operand rows (gnan_hip.h).
+// Workspace: per (row, class) counts, slice counts (row-major and class-major) and their exclusive scans.
+// =============================================================================================
+namespace {
+
+constexpr int kClasses = 8;
+
+struct ClsLayout {
+  size_t cnt, nsl, nsl_t, pair_off, slice_off, q_off, temp, temp_bytes, total;
+};
+
+ClsLayout cls_layout(int64_t n_long) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t m = static_cast<size_t>(n_long) * kClasses + 1;
+  ClsLayout l{};
+  size_t at = 0;
+  l.cnt = at; at += up(m * 4);
+  l.nsl = at; at += up(m * 4);
+  l.nsl_t = at; at += up(m * 4);
+  l.pair_off = at; at += up(m * 8);
+  l.slice_off = at; at += up(m * 4);
+  l.q_off = at; at += up(m * 4);
+  size_t s1 = 0, s2 = 0;
+  int32_t* in = nullptr;
+  int64_t* o64 = nullptr;
+  auto in64 = rocprim::make_transform_iterator(in, ToI64{});
+  (void)rocprim::exclusive_scan(nullptr, s1, in64, o64, int64_t{0}, m, rocprim::plus<int64_t>());
+  (void)rocprim::exclusive_scan(nullptr, s2, in, in, 0, m, rocprim::plus<int>());
+  l.temp = at;
+  l.temp_bytes = s1 > s2 ? s1 : s2;
+  at += up(l.temp_bytes);
+  l.total = at;
+  return l;
+}
+
+// one wave per hub slot r: pairs per class of adjacency row adj(long_rows[r]); the last of the m entries stays 0 (scan total)
+__global__ __launch_bounds__(256) void cls_count_kernel(const void* rowptr, int is64, const int32_t* col, const int32_t* row_ids,
+                                                        const int32_t* long_rows, int n_long, int64_t slice_edges, int32_t* cnt,
+                                                        int32_t* nsl, int32_t* nsl_t) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int r = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+  if (r >= n_long) {
+    if (r == n_long && lane == 0) cnt[r * kClasses] = nsl[r * kClasses] = nsl_t[r * kClasses] = 0;
+    return;
+  }
+  const int64_t q = long_rows[r];
+  const int64_t i = row_ids ? static_cast<int64_t>(row_ids[q]) : q;
+  const int64_t lo = load_ptr(rowptr, is64, i), hi = load_ptr(rowptr, is64, i + 1);
+  int c[kClasses] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t e = lo + lane; e < hi; e += kWave) {
+    const int g = col[e] & (kClasses - 1);
+#pragma unroll
+    for (int k = 0; k < kClasses; ++k) c[k] += g == k ? 1 : 0;
+  }
+#pragma unroll
+  for (int k = 0; k < kClasses; ++k)
+    for (int off = kWave / 2; off > 0; off >>= 1) c[k] += __shfl_xor(c[k], off);
+  if (lane < kClasses) {
+    int v = c[0];
+#pragma unroll
+    for (int k = 1; k < kClasses; ++k) v = lane == k ? c[k] : v;
+    const int n = static_cast<int>((v + slice_edges - 1) / slice_edges);
+    cnt[r * kClasses + lane] = v;
+    nsl[r * kClasses + lane] = n;
+    nsl_t[static_cast<int64_t>(lane) * n_long + r] = n;
+  }
+}
+
+// totals[0] = slices, totals[1] = the longest class queue, totals[2] = pairs of the hub rows
+__global__ void cls_totals_kernel(const int64_t* pair_off, const int32_t* slice_off, const int32_t* q_off, int n_long, int64_t* totals) {
+  const int64_t m = static_cast<int64_t>(n_long) * kClasses;
+  int longest = 0;
+  for (int k = 0; k < kClasses; ++k) {
+    const int len = q_off[(k + 1) * static_cast<int64_t>(n_long)] - q_off[k * static_cast<int64_t>(n_long)];
+    longest = len > longest ? len : longest;
+  }
+  totals[0] = slice_off[m];
+  totals[1] = longest;
+  totals[2] = pair_off[m];
+}
+
+struct ClsFill {
+  const void* rowptr;
+  int is64;
+  const int32_t* col;
+  const uint8_t* code;
+  const int32_t* row_ids;
+  const int32_t* long_rows;
+  int n_long;
+  int64_t slice_edges;
+  const int32_t* nsl;
+  const int64_t* pair_off;
+  const int32_t* slice_off;
+  const int32_t* q_off;
+  int32_t* index;
+  int64_t* slice_start;
+  int32_t* slice_row;
+  int32_t* slice_ptr;
+  int32_t* slot_slice;
+  int64_t n_slots;
+};
+
+// one wave per hub slot: a stable partition of the row's pairs by class (one ballot per class and 64 pairs)
+__global__ __launch_bounds__(256) void cls_fill_kernel(const ClsFill f) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int r = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+  if (r >= f.n_long) return;
+  const int64_t q = f.long_rows[r];
+  const int64_t i = f.row_ids ? static_cast<int64_t>(f.row_ids[q]) : q;
+  const int64_t lo = load_ptr(f.rowptr, f.is64, i), hi = load_ptr(f.rowptr, f.is64, i + 1);
+  int64_t at[kClasses];
+#pragma unroll
+  for (int k = 0; k < kClasses; ++k) at[k] = f.pair_off[r * kClasses + k];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int64_t e0 = lo; e0 < hi; e0 += kWave) {
+    const int64_t e = e0 + lane;
+    int g = kClasses;
+    uint32_t v = 0;
+    if (e < hi) {
+      const uint32_t c = static_cast<uint32_t>(f.col[e]);
+      g = static_cast<int>(c & (kClasses - 1));
+      v = c | (static_cast<uint32_t>(f.code[e]) << 29);
+    }
+#pragma unroll
+    for (int k = 0; k < kClasses; ++k) {
+      const unsigned long long m = __ballot(g == k);
+      if (g == k) f.index[at[k] + __popcll(m & below)] = static_cast<int32_t>(v);
+      at[k] += __popcll(m);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cls_pad_kernel(int32_t* slot_slice, int64_t n) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t < n) slot_slice[t] = -1;
+}
+
+// one thread per (slot, class): its slices, their start in the index, their hub slot and their place in the class queue
+__global__ __launch_bounds__(256) void cls_slices_kernel(const ClsFill f) {
+  const int64_t m = static_cast<int64_t>(f.n_long) * kClasses;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t > m) return;
+  if (t == m) {
+    f.slice_start[f.slice_off[m]] = f.pair_off[m];
+    f.slice_ptr[f.n_long] = f.slice_off[m];
+    return;
+  }
+  const int r = static_cast<int>(t / kClasses), k = static_cast<int>(t % kClasses);
+  const int s0 = f.slice_off[t], n = f.nsl[t];
+  if (k == 0) f.slice_ptr[r] = s0;
+  const int64_t kn = static_cast<int64_t>(k) * f.n_long;
+  const int e0 = f.q_off[kn + r] - f.q_off[kn];
+  for (int j = 0; j < n; ++j) {
+    f.slice_start[s0 + j] = f.pair_off[t] + static_cast<int64_t>(j) * f.slice_edges;
+    f.slice_row[s0 + j] = r;
+    const int64_t b = static_cast<int64_t>(e0 + j) * kClasses + k;
+    if (b < f.n_slots) f.slot_slice[b] = s0 + j;
+  }
+}
+
+int cls_check(const gnan_classed_plan_args* a, const char* who) {
+  GNAN_REQUIRE(a && a->rowptr && a->col && a->code && a->long_rows && a->workspace && a->n_long > 0 && a->slice_edges > 0,
+               "%s: bad arguments", who);
+  GNAN_REQUIRE(a->workspace_bytes >= gnan_classed_plan_workspace_bytes(a->n_long) &&
+               reinterpret_cast<uintptr_t>(a->workspace) % 256 == 0,
+               "%s: workspace of %zu bytes, 256-byte aligned", who, gnan_classed_plan_workspace_bytes(a->n_long));
+  return GNAN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gnan_classed_plan_workspace_bytes(int64_t n_long) { return cls_layout(n_long > 0 ? n_long : 1).total; }
+
+// Phase 1: per (slot, class) pair and slice counts, their scans, totals [3] = {slices, longest queue, pairs} (device)
+extern "C" int gnan_classed_plan_count(const gnan_classed_plan_args* a, gnan_stream_t stream) {
+  if (int rc = cls_check(a, "classed_plan_count")) return rc;
+  GNAN_REQUIRE(a->totals, "classed_plan_count: null totals");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ClsLayout l = cls_layout(a->n_long);
+  char* ws = static_cast<char*>(a->workspace);
+  int32_t* cnt = reinterpret_cast<int32_t*>(ws + l.cnt);
+  int32_t* nsl = reinterpret_cast<int32_t*>(ws + l.nsl);
+  int32_t* nsl_t = reinterpret_cast<int32_t*>(ws + l.nsl_t);
+  int64_t* pair_off = reinterpret_cast<int64_t*>(ws + l.pair_off);
+  int32_t* slice_off = reinterpret_cast<int32_t*>(ws + l.slice_off);
+  int32_t* q_off = reinterpret_cast<int32_t*>(ws + l.q_off);
+  const size_t m = static_cast<size_t>(a->n_long) * kClasses + 1;
+  hipLaunchKernelGGL(cls_count_kernel, dim3(static_cast<unsigned>(a->n_long / 4 + 1)), dim3(256), 0, st, a->rowptr, a->rowptr_is64,
+                     a->col, a->row_ids, a->long_rows, a->n_long, static_cast<int64_t>(a->slice_edges), cnt, nsl, nsl_t);
+  if (int rc = gnan::check_launch("cls_count_kernel")) return rc;
+  size_t tb = l.temp_bytes;
+  auto in64 = rocprim::make_transform_iterator(cnt, ToI64{});
+  hipError_t e = rocprim::exclusive_scan(ws + l.temp, tb, in64, pair_off, int64_t{0}, m, rocprim::plus<int64_t>(), st);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(ws + l.temp, tb, nsl, slice_off, 0, m, rocprim::plus<int>(), st);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(ws + l.temp, tb, nsl_t, q_off, 0, m, rocprim::plus<int>(), st);
+  if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "classed_plan_count: scan: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(cls_totals_kernel, dim3(1), dim3(1), 0, st, pair_off, slice_off, q_off, a->n_long, a->totals);
+  return gnan::check_launch("cls_totals_kernel");
+}
+
+// Phase 2 (same workspace, untouched since phase 1): index [pairs], slice_start [slices + 1], slice_row [slices], slice_ptr [n_long + 1],
+// slot_slice [n_slots = 8 * longest queue] (-1 = padding)
+extern "C" int gnan_classed_plan_fill(const gnan_classed_plan_args* a, gnan_stream_t stream) {
+  if (int rc = cls_check(a, "classed_plan_fill")) return rc;
+  GNAN_REQUIRE(a->index && a->slice_start && a->slice_row && a->slice_ptr && a->slot_slice && a->n_slots > 0 &&
+               a->n_slots % kClasses == 0, "classed_plan_fill: null output or n_slots not a positive multiple of 8");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ClsLayout l = cls_layout(a->n_long);
+  char* ws = static_cast<char*>(a->workspace);
+  ClsFill f;
+  f.rowptr = a->rowptr; f.is64 = a->rowptr_is64; f.col = a->col; f.code = a->code; f.row_ids = a->row_ids;
+  f.long_rows = a->long_rows; f.n_long = a->n_long; f.slice_edges = a->slice_edges;
+  f.nsl = reinterpret_cast<const int32_t*>(ws + l.nsl);
+  f.pair_off = reinterpret_cast<const int64_t*>(ws + l.pair_off);
+  f.slice_off = reinterpret_cast<const int32_t*>(ws + l.slice_off);
+  f.q_off = reinterpret_cast<const int32_t*>(ws + l.q_off);
+  f.index = a->index; f.slice_start = a->slice_start; f.slice_row = a->slice_row; f.slice_ptr = a->slice_ptr;
+  f.slot_slice = a->slot_slice; f.n_slots = a->n_slots;
+  hipLaunchKernelGGL(cls_fill_kernel, dim3(static_cast<unsigned>((a->n_long + 3) / 4)), dim3(256), 0, st, f);
+  if (int rc = gnan::check_launch("cls_fill_kernel")) return rc;
+  hipLaunchKernelGGL(cls_pad_kernel, dim3(static_cast<unsigned>((a->n_slots + 255) / 256)), dim3(256), 0, st, a->slot_slice, a->n_slots);
+  if (int rc = gnan::check_launch("cls_pad_kernel")) return rc;
+  const int64_t m = static_cast<int64_t>(a->n_long) * kClasses + 1;
+  hipLaunchKernelGGL(cls_slices_kernel, dim3(static_cast<unsigned>((m + 255) / 256)), dim3(256), 0, st, f);
+  return gnan::check_launch("cls_slices_kernel");
+}

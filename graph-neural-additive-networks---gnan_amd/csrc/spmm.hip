@@ -54,6 +54,13 @@ struct Params {
   int64_t hot_lo;  // spmm_hot_kernel: operand rows [hot_lo, hot_lo + hot_n) are served from an LDS copy
   int hot_n;
   float* shell_out;  // [n_rows, D - 1] raw per-code sums of the operand over the row's pairs (W == 1, small-D route, a lane per row)
+  // classed hub plan (gnan_spmm_args.cls_*): each wave of a slice workgroup takes one slice of the plan-owned packed index
+  const int32_t* cls_index;
+  const int64_t* cls_slice_start;
+  const int32_t* cls_slice_row;
+  const int32_t* cls_slot_slice;
+  int cls_n_slots;
+  int n_slice_blocks;  // workgroups in front of the row blocks: n_slices, or 8 ceil(queue / 4) with the classed plan (a wave per slice)
 };
 
 __device__ __forceinline__ int64_t load_rowptr(const Params& p, int64_t i) {
@@ -478,10 +485,10 @@ __device__ __forceinline__ void rows_body(const Params& p, const int64_t block_i
 }
 
 // ---------------------------------------------------------------------------------------------
-// long kernel: one 256-thread workgroup per slice of a hub row
+// long kernel: one 256-thread workgroup per slice of a hub row (classed hub plan: one wave per slice, one class per workgroup)
 // ---------------------------------------------------------------------------------------------
 template <int VEC, int LPR, bool SMALLD, bool DENSE, bool BYCODE, bool PACKED = false>
-__device__ __forceinline__ void slice_body(const Params& p, const int s) {
+__device__ __forceinline__ void slice_body(const Params& p, const int blk) {
   constexpr int G = kWave / LPR;
   constexpr int TILE = LPR * VEC;
   constexpr int NW = 4;  // waves per workgroup
@@ -490,19 +497,37 @@ __device__ __forceinline__ void slice_body(const Params& p, const int s) {
   const int wave = threadIdx.x / kWave;
   const int sub = lane % LPR;
   const int slot = lane / LPR;
-  // which hub row owns slice s: last r with long_slice_ptr[r] <= s
-  int a = 0, b = p.n_long;
-  while (b - a > 1) {
-    const int mid = (a + b) >> 1;
-    if (p.long_slice_ptr[mid] <= s) a = mid; else b = mid;
+  // classed plan (CSR only): the block's queue entry names the slice, the slice its range of the plan's packed index and its hub slot
+  const bool classed = !DENSE && p.cls_index != nullptr;
+  int s = blk, a = 0;
+  int64_t lo, hi;
+  if (classed) {
+    // one slice per WAVE: the waves of block blk take entries 4 (blk >> 3) .. + 3 of class blk & 7's queue (a class's slices
+    // are short — 175 pairs on average on C4 — and a workgroup per slice idled three waves and paid an LDS reduction for each)
+    const int e = ((blk >> 3) * NW + wave) * 8 + (blk & 7);
+    s = e < p.cls_n_slots ? p.cls_slot_slice[e] : -1;
+    if (s < 0) return;                      // past the end of this class's queue (no barrier follows on this path)
+    a = p.cls_slice_row[s];
+    lo = p.cls_slice_start[s];
+    hi = p.cls_slice_start[s + 1];
+  } else {
+    // which hub row owns slice s: last r with long_slice_ptr[r] <= s
+    int b = p.n_long;
+    while (b - a > 1) {
+      const int mid = (a + b) >> 1;
+      if (p.long_slice_ptr[mid] <= s) a = mid; else b = mid;
+    }
   }
   const int64_t q = p.long_rows[a];
   const int64_t i = adj_row(p, q);
-  // dense layout: the "pairs" of row i are all n_cols neighbours, the column is the position, codes sit at i*n_cols
-  const int64_t row_lo = DENSE ? 0 : load_rowptr(p, i), row_hi = DENSE ? p.n_cols : load_rowptr(p, i + 1);
   const int64_t code_base = DENSE ? i * p.n_cols : 0;
-  const int64_t lo = row_lo + static_cast<int64_t>(s - p.long_slice_ptr[a]) * p.slice_edges;
-  const int64_t hi = lo + p.slice_edges < row_hi ? lo + p.slice_edges : row_hi;
+  if (!classed) {
+    // dense layout: the "pairs" of row i are all n_cols neighbours, the column is the position, codes sit at i*n_cols
+    const int64_t row_lo = DENSE ? 0 : load_rowptr(p, i), row_hi = DENSE ? p.n_cols : load_rowptr(p, i + 1);
+    lo = row_lo + static_cast<int64_t>(s - p.long_slice_ptr[a]) * p.slice_edges;
+    hi = lo + p.slice_edges < row_hi ? lo + p.slice_edges : row_hi;
+  }
+  const int32_t* idx = classed ? p.cls_index : p.col;
   const int rest = p.D - 1;
   SmallW sw;
   if constexpr (SMALLD) sw = small_weights(p, i);
@@ -513,15 +538,20 @@ __device__ __forceinline__ void slice_body(const Params& p, const int s) {
     Vec<VEC> acc, all;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc.v[v] = all.v[v] = 0.f;
-    // wave `wave` takes 64-edge chunks wave, wave+NW, ...
-    for (int64_t base = lo + static_cast<int64_t>(wave) * kWave; base < hi; base += NW * kWave) {
+    // wave `wave` takes 64-edge chunks wave, wave+NW, ... (classed plan: the wave's own slice, every chunk)
+    const int64_t step = classed ? kWave : NW * kWave;
+    for (int64_t base = lo + (classed ? 0 : static_cast<int64_t>(wave) * kWave); base < hi; base += step) {
       const int64_t e = base + lane;
       int colv = 0, codev = 0;
       if (e < hi) {
-        colv = DENSE ? static_cast<int>(e) : p.col[e];
-        if constexpr (!PACKED) codev = p.code[code_base + e];
+        colv = DENSE ? static_cast<int>(e) : idx[e];
+        if constexpr (!PACKED && !DENSE) {
+          if (!classed) codev = p.code[e];
+        } else if constexpr (!PACKED) {
+          codev = p.code[code_base + e];
+        }
       }
-      if constexpr (PACKED) {
+      if (PACKED || classed) {
         codev = static_cast<int>(static_cast<unsigned>(colv) >> kPackShift);
         colv = static_cast<int>(static_cast<unsigned>(colv) & kPackMask);
       }
@@ -557,6 +587,17 @@ __device__ __forceinline__ void slice_body(const Params& p, const int s) {
         all.v[v] += __shfl_xor(all.v[v], off);
       }
     }
+    if (classed) {
+      if (slot == 0 && col_ok) {
+        float* out = p.partial + static_cast<int64_t>(s) * 2 * p.W;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          out[cw + v] = acc.v[v];
+          out[p.W + cw + v] = all.v[v];
+        }
+      }
+      continue;
+    }
     __syncthreads();
     if (slot == 0) {
 #pragma unroll
@@ -591,11 +632,11 @@ template <int VEC, int LPR, bool DENSE, bool SMALLD, bool BYCODE = false, bool P
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SMALLD && LPR >= 8) ? 8 : 1)))
 void spmm_kernel(const Params p) {
   if constexpr (!DENSE) {
-    if (static_cast<int>(blockIdx.x) < p.n_slices) {
+    if (static_cast<int>(blockIdx.x) < p.n_slice_blocks) {
       slice_body<VEC, LPR, SMALLD, false, BYCODE, PACKED>(p, static_cast<int>(blockIdx.x));
       return;
     }
-    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED>(p, static_cast<int64_t>(blockIdx.x) - p.n_slices);
+    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED>(p, static_cast<int64_t>(blockIdx.x) - p.n_slice_blocks);
   } else {
     if (p.n_slices > 0) {      // few rows, many neighbours: every row is cut into slices, there are no row blocks
       slice_body<VEC, LPR, SMALLD, true, false>(p, static_cast<int>(blockIdx.x));
@@ -867,7 +908,7 @@ constexpr int kHotLdsFloats = 16384;   // 64 KB of hot operand rows per workgrou
 bool hot_kernel_applies(const gnan_spmm_args* a) {
   auto aligned = [](const void* ptr, size_t n) { return (reinterpret_cast<uintptr_t>(ptr) % n) == 0; };
   const int W = a->W;
-  return a->hot_rows > 0 && a->rowptr != nullptr && a->packed_index && a->s_dtype == GNAN_F32 && (W == 1 || W == 2 || W == 4) &&
+  return a->hot_rows > 0 && a->cls_index == nullptr && a->rowptr != nullptr && a->packed_index && a->s_dtype == GNAN_F32 && (W == 1 || W == 2 || W == 4) &&
          a->s_stride == W && a->Cw == 1 && a->D <= 4 && !a->weight_by_col && !a->minus_rest && !a->s_by_code && a->reduce_cr == 0 &&
          aligned(a->S, 16) && aligned(a->Y, 4 * static_cast<size_t>(W)) && a->y_stride % W == 0 &&
          (!a->s_total || aligned(a->s_total, 4 * static_cast<size_t>(W))) && a->hot_lo >= 0 &&
@@ -992,7 +1033,7 @@ int launch(const Params& p, bool dense, bool smalld, hipStream_t st) {
   constexpr int G = kWave / LPR;
   const int rows_per_block = 4 * G;
   const int n_slices = p.n_slices;
-  const int64_t blocks = dense && n_slices > 0 ? n_slices : (p.n_rows + rows_per_block - 1) / rows_per_block + n_slices;
+  const int64_t blocks = dense && n_slices > 0 ? n_slices : (p.n_rows + rows_per_block - 1) / rows_per_block + p.n_slice_blocks;
   if (blocks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many rows for one launch");
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
   if (p.s_by_code) {
@@ -1079,6 +1120,11 @@ int validate(const gnan_spmm_args* a) {
                  "spmm: a row plan for the dense layout must slice every row (n_long == n_rows, long_threshold == 0)");
     GNAN_REQUIRE(a->long_rows && a->long_slice_ptr && a->slice_edges > 0 && a->n_slices > 0,
                  "spmm: incomplete long-row plan");
+    if (a->cls_index) {
+      GNAN_REQUIRE(a->rowptr != nullptr && a->cls_slice_start && a->cls_slice_row && a->cls_slot_slice && a->cls_n_slots > 0 &&
+                   a->cls_n_slots % 8 == 0 && a->n_cols <= static_cast<int64_t>(kPackMask) + 1 && a->D <= 8,
+                   "spmm: incomplete classed hub plan (CSR, slot table of a positive multiple of 8, n_cols <= 2^29, D <= 8)");
+    }
   }
   return GNAN_OK;
 }
@@ -1113,6 +1159,11 @@ Params make_params(const gnan_spmm_args* a) {
   p.partial = static_cast<float*>(a->workspace);
   p.hot_lo = a->hot_lo; p.hot_n = a->hot_rows;
   p.shell_out = a->shell_out;
+  const bool classed = a->n_long > 0 && a->cls_index != nullptr;
+  p.cls_index = classed ? a->cls_index : nullptr;
+  p.cls_slice_start = a->cls_slice_start; p.cls_slice_row = a->cls_slice_row; p.cls_slot_slice = a->cls_slot_slice;
+  p.cls_n_slots = a->cls_n_slots;
+  p.n_slice_blocks = classed ? 8 * ((a->cls_n_slots / 8 + 3) / 4) : p.n_slices;
   return p;
 }
 
@@ -1935,6 +1986,7 @@ extern "C" int gnan_spmm_lut_grad(const gnan_spmm_lut_grad_args* g, gnan_stream_
   void* workspace = g->workspace;
   const size_t workspace_bytes = g->workspace_bytes;
   if (int rc = validate(a)) return rc;
+  GNAN_REQUIRE(a->cls_index == nullptr, "lut_grad: the classed hub plan is read by gnan_spmm_fwd only");
   GNAN_REQUIRE(!a->packed_index, "lut_grad: packed index entries are read by gnan_spmm_fwd only");
   GNAN_REQUIRE(dwt != nullptr, "lut_grad: null output");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2218,6 +2270,7 @@ extern "C" int gnan_spmm_bwd_narrow(const gnan_spmm_bwd_narrow_args* g, gnan_str
   void* workspace = g->workspace;
   const size_t workspace_bytes = g->workspace_bytes;
   if (int rc = validate(a)) return rc;
+  GNAN_REQUIRE(a->cls_index == nullptr, "bwd_narrow: the classed hub plan is read by gnan_spmm_fwd only");
   GNAN_REQUIRE(!a->packed_index || a->W == 2, "bwd_narrow: packed index entries are read for one-channel operands only (W == 2)");
   GNAN_REQUIRE(dS != nullptr && dlut != nullptr && (s_rows != nullptr || a->n_rows == 0), "bwd_narrow: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2278,6 +2331,7 @@ extern "C" int gnan_spmm_bwd_narrow(const gnan_spmm_bwd_narrow_args* g, gnan_str
 
 extern "C" int gnan_spmm_shell_sums(const gnan_spmm_args* a, gnan_stream_t stream) {
   if (int rc = validate(a)) return rc;
+  GNAN_REQUIRE(a->cls_index == nullptr, "shell_sums: the classed hub plan is read by gnan_spmm_fwd only");
   GNAN_REQUIRE(!a->packed_index, "shell_sums: packed index entries are read by gnan_spmm_fwd only");
   if (a->n_rows == 0) return GNAN_OK;
   GNAN_REQUIRE(!a->weight_by_col, "shell_sums: weight_by_col has no meaning here");

@@ -36,6 +36,10 @@ HOT_COLUMNS_MIN_SHARE = 0.15     # ... and so does a graph whose K most listed n
 
 
 LONG_PLAN_IN_HIP = True     # HopGraph.long_row_plan() by gnan_long_row_plan_count / _fill
+HUB_CLASSES = 8                 # classed hub plan (HopGraph.classed_hub_plan): column class col & 7, one per XCD of the MI355X
+CLASSED_HUB_THRESHOLD = 512     # ... its hub rows: more listed pairs than this
+CLASSED_SLICE_EDGES = 2048      # ... pairs per slice of one (hub row, class)
+CLASSED_PLAN_IN_HIP = True      # ... by gnan_classed_plan_count / _fill (False: the framework route below; CPU tensors always)
 TRANSPOSE_IN_HIP = True     # HopGraph.transposed() by gnan_csr_transpose
 PB_PLAN_IN_HIP = True       # the pair-level work of HopGraph.pb_plan by gnan_pb_plan_* (False: framework ops; CPU tensors always)
 SORTED_COPY_IN_HIP = True   # the degree-sorted copy by gnan_degree_sorted_csr (False: the framework ops below; CPU tensors always)
@@ -82,6 +86,20 @@ class LongRowPlan:
 
 
 @dataclass
+class ClassedHubPlan(LongRowPlan):
+    """A hub-row plan whose slices each hold the pairs of ONE column class ``col & 7`` (``gnan_spmm_args.cls_*``): ``rows`` are
+    the hub slots, ``slice_ptr`` a slot's slices (class-major, so the fix-up adds them in a fixed order); the slots' pairs are
+    copied, stably partitioned by class, into ``index`` (``col | code << 29``); slice ``s`` covers ``index[slice_start[s],
+    slice_start[s + 1])`` of slot ``slice_row[s]``; slice workgroup ``b`` takes ``slot_slice[b]`` — entry ``b >> 3`` of class
+    ``b & 7``'s queue, ``-1`` past its end — so that the round-robin dispatch keeps a class on one XCD and its L2."""
+    index: Optional[torch.Tensor] = None         # int32 [pairs of the hub slots]
+    slice_start: Optional[torch.Tensor] = None   # int64 [n_slices + 1]
+    slice_row: Optional[torch.Tensor] = None     # int32 [n_slices]
+    slot_slice: Optional[torch.Tensor] = None    # int32 [n_slots]
+    n_slots: int = 0
+
+
+@dataclass
 class HopGraph:
     n_rows: int
     n_cols: int
@@ -97,6 +115,7 @@ class HopGraph:
     _degree_plan: Optional[LongRowPlan] = field(default=None, repr=False)
     _dense_plans: dict = field(default_factory=dict, repr=False)
     _plans: dict = field(default_factory=dict, repr=False)          # hub-row plans by threshold (other than the default)
+    _classed: dict = field(default_factory=dict, repr=False)        # classed_hub_plan(): (order, threshold, slice_edges) -> plan
     _sorted_copy: Optional["HopGraph"] = field(default=None, repr=False)
     _hot: Optional[tuple] = field(default=None, repr=False)           # hot_columns(): (ids or None,)
     _sorted_copy_hot: Optional["HopGraph"] = field(default=None, repr=False)
@@ -296,6 +315,93 @@ class HopGraph:
             ptr[1:] = torch.cumsum(n_sl, 0)
             plan = LongRowPlan(long_rows.to(torch.int32), ptr.to(torch.int32), n_long, int(ptr[-1]), threshold=threshold)
         return plan
+
+    def classed_hub_plan(self, row_ids: Optional[torch.Tensor] = None, threshold: Optional[int] = None,
+                         slice_edges: Optional[int] = None) -> Optional[LongRowPlan]:
+        """The hub rows of :meth:`long_row_plan` (``row_ids``: slot ``q`` is adjacency row ``row_ids[q]``) as a
+        :class:`ClassedHubPlan`, the plain plan when there are no hub rows, ``None`` where the packed entries cannot hold the
+        graph (dense, more than 2^29 neighbours or 8 codes).  Cached for the identity order and for :meth:`degree_schedule`'s."""
+        if self.is_dense or self.n_cols > (1 << PACK_SHIFT) or self.n_codes > 8:
+            return None
+        threshold = CLASSED_HUB_THRESHOLD if threshold is None else threshold
+        slice_edges = CLASSED_SLICE_EDGES if slice_edges is None else slice_edges
+        order = "id" if row_ids is None else ("degree" if row_ids is self._degree_order else None)
+        key = (order, int(threshold), int(slice_edges))
+        if order is not None and key in self._classed:
+            return self._classed[key]
+        base = self.long_row_plan(row_ids, threshold)
+        if base.n_long == 0:
+            plan = base
+        elif CLASSED_PLAN_IN_HIP and self.rowptr.is_cuda and self.nnz < 2 ** 31:
+            plan = self._classed_hub_plan_hip(base, row_ids, slice_edges)
+        else:
+            plan = self._classed_hub_plan_torch(base, row_ids, slice_edges)
+        if order is not None:
+            self._classed[key] = plan
+        return plan
+
+    def _classed_hub_plan_hip(self, base: LongRowPlan, row_ids, slice_edges: int) -> ClassedHubPlan:
+        """gnan_classed_plan_count / _fill (csrc/graph_build.hip): the same arrays as the framework route below."""
+        L, dev = _lib.lib(), self.device
+        n_long = int(base.n_long)
+        need = L.gnan_classed_plan_workspace_bytes(n_long)
+        ws = torch.empty((need + 255) // 256 * 64, dtype=torch.int32, device=dev)
+        totals = torch.empty(3, dtype=torch.int64, device=dev)
+        rid = row_ids.to(torch.int32).contiguous() if row_ids is not None else None
+        a = _lib.ClassedPlanArgs(rowptr=_lib.ptr(self.rowptr), rowptr_is64=int(self.rowptr.dtype == torch.int64),
+                                 col=_lib.ptr(self.col), code=_lib.ptr(self.code), row_ids=_lib.ptr(rid),
+                                 long_rows=_lib.ptr(base.rows), n_long=n_long, slice_edges=int(slice_edges),
+                                 workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4, totals=_lib.ptr(totals))
+        st = _lib.stream_of(self.rowptr)
+        _lib.check(L.gnan_classed_plan_count(a, st), "gnan_classed_plan_count")
+        n_slices, longest, pairs = (int(v) for v in totals.tolist())
+        index = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
+        slice_start = torch.empty(n_slices + 1, dtype=torch.int64, device=dev)
+        slice_row = torch.empty(n_slices, dtype=torch.int32, device=dev)
+        slice_ptr = torch.empty(n_long + 1, dtype=torch.int32, device=dev)
+        slot_slice = torch.empty(HUB_CLASSES * longest, dtype=torch.int32, device=dev)
+        a.index, a.slice_start, a.slice_row = _lib.ptr(index), _lib.ptr(slice_start), _lib.ptr(slice_row)
+        a.slice_ptr, a.slot_slice, a.n_slots = _lib.ptr(slice_ptr), _lib.ptr(slot_slice), int(slot_slice.numel())
+        _lib.check(L.gnan_classed_plan_fill(a, st), "gnan_classed_plan_fill")
+        return ClassedHubPlan(base.rows, slice_ptr, n_long, n_slices, threshold=base.threshold, slice_edges=int(slice_edges),
+                              index=index[:pairs], slice_start=slice_start, slice_row=slice_row, slot_slice=slot_slice,
+                              n_slots=int(slot_slice.numel()))
+
+    def _classed_hub_plan_torch(self, base: LongRowPlan, row_ids, slice_edges: int) -> ClassedHubPlan:
+        dev, K, SE = self.device, HUB_CLASSES, int(slice_edges)
+        q = base.rows.long()
+        i = row_ids.long()[q] if row_ids is not None else q
+        rp = self.rowptr.long()
+        lo, deg = rp[i], rp[i + 1] - rp[i]
+        R = int(q.numel())
+        slot = torch.repeat_interleave(torch.arange(R, device=dev), deg)
+        first = torch.cumsum(deg, 0) - deg
+        e = lo[slot] + torch.arange(int(slot.numel()), device=dev) - first[slot]
+        c = self.col[e].long()
+        v = c | (self.code[e].long() << PACK_SHIFT)
+        key = slot * K + (c & (K - 1))
+        index = torch.where(v >= (1 << 31), v - (1 << 32), v)[torch.argsort(key, stable=True)].to(torch.int32)
+        cnt = torch.bincount(key, minlength=R * K)
+        nsl = (cnt + SE - 1) // SE
+        pair_off = torch.cumsum(cnt, 0) - cnt
+        slice_off = torch.cumsum(nsl, 0) - nsl
+        n_slices = int(nsl.sum())
+        t = torch.repeat_interleave(torch.arange(R * K, device=dev), nsl)              # (slot, class) of every slice
+        j = torch.arange(n_slices, device=dev) - slice_off[t]
+        slice_start = torch.cat([pair_off[t] + j * SE, cnt.sum().view(1)])
+        g = t % K
+        pos = torch.empty(n_slices, dtype=torch.int64, device=dev)                    # place in its class's queue (slice order)
+        longest = 0
+        for k in range(K):
+            m = torch.nonzero(g == k).flatten()
+            pos[m] = torch.arange(int(m.numel()), device=dev)
+            longest = max(longest, int(m.numel()))
+        slot_slice = torch.full((K * longest,), -1, dtype=torch.int32, device=dev)
+        slot_slice[pos * K + g] = torch.arange(n_slices, dtype=torch.int32, device=dev)
+        slice_ptr = torch.cat([slice_off.view(R, K)[:, 0], torch.tensor([n_slices], device=dev)]).to(torch.int32)
+        return ClassedHubPlan(base.rows, slice_ptr, R, n_slices, threshold=base.threshold, slice_edges=SE, index=index,
+                              slice_start=slice_start, slice_row=(t // K).to(torch.int32), slot_slice=slot_slice,
+                              n_slots=K * longest)
 
     def narrow_row_plan(self) -> LongRowPlan:
         """Hub-row plan for operand rows of one or two lanes: the low threshold while only a FEW rows exceed it (the tail

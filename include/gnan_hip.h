@@ -26,7 +26,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: exactly the functions declared in this header are exported */
 #pragma GCC visibility push(default)
 
-#define GNAN_ABI_VERSION 45
+#define GNAN_ABI_VERSION 46
 
 typedef void* gnan_stream_t; /* hipStream_t */
 
@@ -489,6 +489,17 @@ typedef struct gnan_spmm_args {
                                   * hop code (before any weight) — what a training forward keeps so that its backward is a pass over
                                   * rows (gnan_spmm_pack_z).  One-column operand (W == 1), global one-channel table with D <= 4, CSR,
                                   * no hub-row slices (n_slices == 0), no fused read-out, no hot rows; GNAN_ERR_UNSUPPORTED otherwise */
+  /* classed hub plan (ABI 46; gnan_spmm_fwd only, CSR, gnan_classed_plan_count / _fill): with cls_index set, hub slice s reads the
+   * packed entries (column | hop code << 29) cls_index[cls_slice_start[s], cls_slice_start[s + 1]) and belongs to hub slot
+   * cls_slice_row[s] (an index into long_rows; long_slice_ptr is the plan's slice_ptr, n_slices its slice count).  A slice is
+   * taken by one wave: the launch has 8 ceil(cls_n_slots / 32) slice workgroups, wave w of workgroup b taking slice
+   * cls_slot_slice[8 (4 (b >> 3) + w) + (b & 7)] (-1 or past cls_n_slots: none).  Each slice holds pairs of one column class
+   * (column & 7), and b & 7 is that class: placement only, the result does not depend on where a workgroup runs */
+  const int32_t* cls_index;
+  const int64_t* cls_slice_start;
+  const int32_t* cls_slice_row;
+  const int32_t* cls_slot_slice;
+  int32_t cls_n_slots;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
@@ -532,6 +543,38 @@ int gnan_long_row_plan_count(const void* rowptr, int32_t rowptr_is64, int64_t n_
                              size_t workspace_bytes, int32_t* total, gnan_stream_t stream);
 int gnan_long_row_plan_fill(const void* rowptr, int32_t rowptr_is64, int64_t n_rows, int64_t threshold, int64_t slice_edges, int64_t n_long,
                             void* workspace, size_t workspace_bytes, int32_t* long_rows, int32_t* slice_ptr, gnan_stream_t stream);
+
+/* The classed hub plan (ABI 46; gnan_spmm_args.cls_*, gnan_amd.graph.HopGraph.classed_hub_plan): for the hub slots long_rows [n_long]
+ * (ascending; slot q reads adjacency row row_ids[q], or q without row_ids) the row's pairs partitioned stably by the column class
+ * col & 7, class-major, into index (col | code << 29; codes below 8), slices cut per (slot, class) at slice_edges pairs —
+ * slice_start [slices + 1] (offsets into index), slice_row [slices] (the slot's position in long_rows), slice_ptr [n_long + 1]
+ * (a slot's slices, class-major) — and one queue per class: slot_slice[8 e + g] = the e-th slice of class g in slot order, -1 past
+ * the end of that queue.  Two calls around ONE read-back: _count leaves totals [3] = {slices, longest queue, pairs} in device memory,
+ * the caller sizes the outputs (n_slots = 8 * longest queue) and calls _fill with the SAME workspace
+ * (gnan_classed_plan_workspace_bytes(n_long), 256-byte aligned).  Index work only, deterministic. */
+typedef struct gnan_classed_plan_args {
+  const void* rowptr;
+  int32_t rowptr_is64;
+  const int32_t* col;
+  const uint8_t* code;
+  const int32_t* row_ids;
+  const int32_t* long_rows;
+  int32_t n_long;
+  int32_t slice_edges;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t* totals;
+  int32_t* index;
+  int64_t* slice_start;
+  int32_t* slice_row;
+  int32_t* slice_ptr;
+  int32_t* slot_slice;
+  int64_t n_slots;
+} gnan_classed_plan_args;
+
+size_t gnan_classed_plan_workspace_bytes(int64_t n_long);
+int gnan_classed_plan_count(const gnan_classed_plan_args* a, gnan_stream_t stream);
+int gnan_classed_plan_fill(const gnan_classed_plan_args* a, gnan_stream_t stream);
 
 /* The transposed adjacency of a hop-coded CSR (gnan_amd.graph.HopGraph.transposed: what the backward walks): row j of the result
  * lists the rows i that list neighbour j, in ascending i (a stable sort of the pairs by column id), with the pairs' hop codes;
