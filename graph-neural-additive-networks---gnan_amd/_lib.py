@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNAN_HIP_LIB: development aid for same-box A/B runs of two builds of the library (tools/ab_lib.sh)
 LIB_PATH = os.environ.get("GNAN_HIP_LIB") or os.path.join(_HERE, "libgnan_hip.so")
-ABI_VERSION = 46
+ABI_VERSION = 47
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # enum gnan_status
 
 GNAN_F32, GNAN_BF16 = 0, 1
@@ -61,8 +61,7 @@ class FpwlIndexArgs(C.Structure):
     ]
 
 
-FPWL_MOMENTS_GENERAL, FPWL_LOCATE_SORTED, FPWL_INDEX_HALF_LINES, FPWL_INDEX_BS512, FPWL_INDEX_BS1024 = 1, 2, 4, 8, 16   # gnan_fpwl_args.flags
-FPWL_ROWS_MOMENTS_LANE_PER_CHANNEL = 32
+FPWL_MOMENTS_GENERAL, FPWL_INDEX_HALF_LINES, FPWL_INDEX_BS512, FPWL_INDEX_BS1024 = 1, 4, 8, 16   # gnan_fpwl_args.flags
 
 
 class PwlBuildArgs(C.Structure):
@@ -185,8 +184,7 @@ class SpmmPbArgs(C.Structure):
         ("n_bins", C.c_int32), ("acc_per_bin", C.c_int32), ("bin_order", C.c_void_p), ("bin_entry_ptr", C.c_void_p),
         ("bin_row_ptr", C.c_void_p), ("slot_ptr", C.c_void_p), ("n_acc", C.c_int32), ("code_base", C.c_int32),
         ("self_col", C.c_void_p), ("headroom_bits", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-        ("flags", C.c_int32), ("self_is_row", C.c_int32),
-        ("shell_out", C.c_void_p), ("S_self", C.c_void_p), ("out_add", C.c_void_p), ("out_add_scale", C.c_void_p),
+        ("self_is_row", C.c_int32), ("shell_out", C.c_void_p), ("S_self", C.c_void_p), ("out_add", C.c_void_p), ("out_add_scale", C.c_void_p),
     ]
 
 

@@ -64,7 +64,6 @@ def _spmm_args(g: HopGraph, S, lut, use_cnt, s_total, out, row_ids, per_row_lut,
 FUSABLE_READOUT = (1, 2, 4)   # channel counts the aggregation kernel can sum over features in its epilogue
 DEGREE_SCHEDULE_MIN_WIDTH = 8  # operand widths from which the degree-sorted row schedule pays (measured: W >= 8)
 DEGREE_SORTED_COPY_MIN_ROWS = 1 << 16   # below this the copy's one-off index work outweighs what the kernel saves
-NARROW_ROW_SLICING = True   # A/B switch of LONG_ROW_THRESHOLD_NARROW
 WIDE_INDEX_LOADS = True      # a lane's run of index entries as 16-byte loads (gnan_spmm_args.nnz)
 PACKED_INDEX = True         # degree-sorted copies are read as one (col | code << 29) stream
 NARROW_SORTED_MIN_NNZ = 1 << 23   # below ~8M pairs the sorted walk's tail (the longest rows run last) and its scattered stores cost
@@ -164,7 +163,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         # of its wavefront: W = 2 on the 10M-node graph 2.68 -> 1.68 ms), and a compact copy of the most listed
         # neighbours' rows behind the operand (HopGraph.hot_columns: -> 1.33 ms; W = 1: 1.86 -> 1.79 -> 1.52 ms)
         g, row_ids, hot = narrow_walk(g)
-        plan = g.narrow_row_plan() if (narrow and NARROW_ROW_SLICING) else g.long_row_plan()
+        plan = g.narrow_row_plan() if narrow else g.long_row_plan()
         if hot is not None:
             S = append_hot_rows(S, hot, g.n_codes if s_by_code else 1, room=room)
             n_hot = 0 if s_by_code else int(hot.numel())
@@ -179,7 +178,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
             row_ids, plan = g.degree_schedule()      # process rows by degree, store them in place
             scatter = True
     else:
-        plan = g.narrow_row_plan() if (narrow and NARROW_ROW_SLICING and row_ids is None) else g.long_row_plan(row_ids)
+        plan = g.narrow_row_plan() if (narrow and row_ids is None) else g.long_row_plan(row_ids)
     if (XCD_CLASSED_HUBS and plan is not None and not g.is_dense and S.shape[1] * S.element_size() >= CLASSED_MIN_ROW_BYTES
             and g.nnz >= CLASSED_MIN_NNZ and not weight_by_col and not minus_rest and not s_by_code and not g._cnt_by_col
             and n_hot == 0):
@@ -253,10 +252,9 @@ def rows_bwd1_launch(g: HopGraph, dY: torch.Tensor, shell: torch.Tensor, lut: to
     return dS, dlut
 
 
-PB_NARROW = True            # narrow fp32 rows of large CSR graphs go through the propagation-blocked kernels (gnan_spmm_pb_fwd)
+PB_NARROW = True            # narrow fp32 rows of large CSR graphs go through the propagation-blocked kernels (gnan_spmm_pb_fwd),
+                            # and so does the one-column backward (gnan_spmm_pb_bwd over the transposed graph's copy)
 PB_WIDTHS = (1, 2, 4)
-PB_FLAGS = 0                # gnan_spmm_pb_args.flags (A/B switches of the kernels)
-PB_BACKWARD = True          # ... and so does the one-column backward (gnan_spmm_pb_bwd over the transposed graph's copy)
 PB_MIN_NNZ = 1 << 23        # below, the row-parallel kernel's gathers stay in L2 and three launches cost more than they save
 PB_MAX_NNZ = 1 << 29        # above, building the bucketed copy (a sort of the pairs, ~80 B of temporaries per pair) is not attempted
 
@@ -281,7 +279,7 @@ def pb_launch(g: HopGraph, pb, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool
                         cb_chunk_ptr=_lib.ptr(pb.cb_chunk_ptr), n_bins=pb.n_bins, acc_per_bin=pb.acc_per_bin,
                         bin_order=_lib.ptr(pb.bin_order), bin_entry_ptr=_lib.ptr(pb.bin_entry_ptr),
                         bin_row_ptr=_lib.ptr(pb.bin_row_ptr), slot_ptr=_lib.ptr(pb.slot_ptr), n_acc=pb.n_acc,
-                        code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits, flags=PB_FLAGS, self_is_row=int(pb.self_is_row))
+                        code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits, self_is_row=int(pb.self_is_row))
     if shell_out is not None:
         a.shell_out = _lib.ptr(shell_out)
     if S_self is not None:
@@ -301,7 +299,7 @@ PB_BACKWARD_ONE_COLUMN = True   # the one-column backward from the forward's kep
 def pb_bwd1_applies(g: HopGraph, W: int, D: int, with_rest: bool, add_to_rows: bool, shell):
     """``(forward plan, transposed W = 1 plan)`` when the one-column backward can run WITHOUT the packed second column
     (``gnan_spmm_pb_pack1`` + ``gnan_spmm_pb_fwd`` over the transposed adjacency), else None."""
-    if not (PB_NARROW and PB_BACKWARD and PB_BACKWARD_ONE_COLUMN and shell is not None and W == 1 and not g.is_dense and D <= 4
+    if not (PB_NARROW and PB_BACKWARD_ONE_COLUMN and shell is not None and W == 1 and not g.is_dense and D <= 4
             and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ and (add_to_rows or not with_rest)):
         return None
     fwd = g.pb_plan(1)
@@ -346,7 +344,7 @@ def pb_bwd1_launch(g: HopGraph, plans, dY: torch.Tensor, S: torch.Tensor, shell:
 
 def pb_bwd_applies(g: HopGraph, W: int, D: int):
     """The transposed graph's bucketed copy when the ONE-column backward can take the propagation-blocked route, else None."""
-    if not (PB_NARROW and PB_BACKWARD and W == 1 and not g.is_dense and D <= 4 and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ):
+    if not (PB_NARROW and W == 1 and not g.is_dense and D <= 4 and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ):
         return None
     pb = g.transposed().pb_plan(2)
     return pb if (pb is not None and pb.n_acc == 1) else None
@@ -373,7 +371,7 @@ def pb_bwd_launch(gt: HopGraph, pb, V: torch.Tensor, S_rows: torch.Tensor, lut: 
                         cb_chunk_ptr=_lib.ptr(pb.cb_chunk_ptr), n_bins=pb.n_bins, acc_per_bin=pb.acc_per_bin,
                         bin_order=_lib.ptr(pb.bin_order), bin_entry_ptr=_lib.ptr(pb.bin_entry_ptr),
                         bin_row_ptr=_lib.ptr(pb.bin_row_ptr), slot_ptr=_lib.ptr(pb.slot_ptr), n_acc=pb.n_acc,
-                        code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits, flags=PB_FLAGS, self_is_row=int(pb.self_is_row))
+                        code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits, self_is_row=int(pb.self_is_row))
     ga = _lib.SpmmPbBwdArgs(pb=a, v_self=_lib.ptr(V[0]) if pb.code_base else None, s_rows=_lib.ptr(S_rows),
                             s_rows_stride=S_rows.stride(0), with_rest=int(with_rest), dS=_lib.ptr(dS), ds_stride=dS.stride(0),
                             dlut=_lib.ptr(dlut))
@@ -523,7 +521,7 @@ def bwd_narrow_launch(gt: HopGraph, V: torch.Tensor, S_rows: torch.Tensor, lut: 
         V3 = V.view(D, -1, V.shape[1])
         V = torch.cat([V3, V3.index_select(1, hot)], dim=1).view(-1, V.shape[1])
     scatter = 0 if order is None else 2
-    plan = gt.narrow_row_plan() if (V.shape[1] * 4 <= 8 and NARROW_ROW_SLICING) else gt.long_row_plan()
+    plan = gt.narrow_row_plan() if V.shape[1] * 4 <= 8 else gt.long_row_plan()
     # one channel (packed rows of 2 floats) over a sorted copy: one packed index stream, persistent workgroups
     # (spmm_bwd_hot_kernel) — 10M-node R-MAT: 1.19 -> see DESIGN.md section 4.6
     packed = V.shape[1] == 2 and order is not None and NARROW_BWD_PERSISTENT

@@ -1422,7 +1422,7 @@ int launch_locate_tree(LocateTreeParams lp, hipStream_t st) {
 int gnan_locate_tree(const gnan_fpwl_args* a, int32_t* piece, float* dx, hipStream_t st) {
   // (small batches: the sorted-array kernel's few large workgroups win — arxiv-shaped 0.102 against 0.141 ms; 10M nodes
   //  x 64 features: 3.4 ms against 1.6 ms the other way)
-  if (a->max_pieces > 1024 || a->n < 262144 || (a->flags & GNAN_FPWL_LOCATE_SORTED)) return -1;
+  if (a->max_pieces > 1024 || a->n < 262144) return -1;
   LocateTreeParams lp;
   gnan_fpwl_args b = *a;
   b.features_per_group = 16;                        // the search has its own grouping, whatever the tables were planned for

@@ -553,7 +553,7 @@ extern "C" int gnan_fpwl_rows_moments_fixed(const gnan_fpwl_args* a, const int32
   if (p.wgs_per_chunk * n_chunks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_rows_moments: too many nodes for one launch");
   const dim3 grid(static_cast<unsigned>(p.wgs_per_chunk * n_chunks));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (cc > 32 && 3 * ((cc + 1) / 2) <= kWave && !(a->flags & GNAN_FPWL_ROWS_MOMENTS_LANE_PER_CHANNEL)) {
+  if (cc > 32 && 3 * ((cc + 1) / 2) <= kWave) {
     // 33..42 channels: a pair of channels per lane, three nodes per step (see fpwl_rows_moments_pairs_kernel)
     if (lds > 64 * 1024) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fpwl_rows_moments_pairs_kernel),

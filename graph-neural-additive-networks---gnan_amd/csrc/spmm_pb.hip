@@ -101,11 +101,11 @@ __device__ __forceinline__ void expand_store(const PbParams& p, const float* sbl
   }
 }
 
-// BATCH: a wave takes 64 chunks at a time — lane l fetches chunk_q[k + l] with ONE coalesced load, the 16 wave-iterations of
-// the batch (four chunks of 16 entries each) read their offsets from it by ds_bpermute, so that every iteration is
+// A wave takes 64 chunks at a time: lane l fetches chunk_q[k + l] with ONE coalesced load, the 16 wave-iterations of the
+// batch (four chunks of 16 entries each) read their offsets from it by ds_bpermute, so that every iteration is
 // "entry column -> LDS -> store" with nothing in front of it and the 16 column loads of a batch are in flight together.
 // (Reading chunk_q inside every iteration put a dependent global load in front of each: 293 us per launch.)
-template <int W, bool BATCH>
+template <int W>
 __global__ __launch_bounds__(kThreads) void pb_expand_kernel(const PbParams p) {
   extern __shared__ __attribute__((aligned(16))) float sblk[];          // [cb_width * W]
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -143,74 +143,44 @@ __global__ __launch_bounds__(kThreads) void pb_expand_kernel(const PbParams p) {
   __syncthreads();
   const int k_lo = p.cb_chunk_ptr[cb], k_hi = p.cb_chunk_ptr[cb + 1];
   const int g = lane >> 4, l16 = lane & 15;
-  if constexpr (BATCH) {
-    int per = (k_hi - k_lo + p.n_split - 1) / p.n_split;
-    per = (per + 63) & ~63;                           // whole batches
-    const int lo = k_lo + part * per;
-    const int hi = lo + per < k_hi ? lo + per : k_hi;
-    for (int kb = lo + wave * kWave; kb < hi; kb += (kThreads / kWave) * kWave) {
-      const int cq = kb + lane < hi ? p.chunk_q[kb + lane] : -1;
-      int q[16];
-      unsigned s[16];
+  int per = (k_hi - k_lo + p.n_split - 1) / p.n_split;
+  per = (per + 63) & ~63;                           // whole batches
+  const int lo = k_lo + part * per;
+  const int hi = lo + per < k_hi ? lo + per : k_hi;
+  for (int kb = lo + wave * kWave; kb < hi; kb += (kThreads / kWave) * kWave) {
+    const int cq = kb + lane < hi ? p.chunk_q[kb + lane] : -1;
+    int q[16];
+    unsigned s[16];
 #pragma unroll
-      for (int it = 0; it < 16; ++it) {
-        const int q0 = __shfl(cq, it * 4 + g);
-        q[it] = q0 < 0 ? -1 : q0 + l16;
-      }
-#pragma unroll
-      for (int it = 0; it < 16; ++it) s[it] = p.src[q[it] < 0 ? 0 : q[it]];
-#pragma unroll
-      for (int it = 0; it < 16; ++it) expand_store<W>(p, sblk, s[it], q[it], q[it] >= 0);
+    for (int it = 0; it < 16; ++it) {
+      const int q0 = __shfl(cq, it * 4 + g);
+      q[it] = q0 < 0 ? -1 : q0 + l16;
     }
-  } else {
-    int per = (k_hi - k_lo + p.n_split - 1) / p.n_split;
-    per = (per + 3) & ~3;                               // whole wave-iterations (four chunks of 16 entries)
-    const int lo = k_lo + part * per;
-    const int hi = lo + per < k_hi ? lo + per : k_hi;
-    constexpr int U = 4;                                // wave-iterations in flight
-    for (int kw = lo + wave * 4; kw < hi; kw += (kThreads / kWave) * 4 * U) {
-      int q[U];
-      unsigned s[U];
-      bool ok[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = kw + u * (kThreads / kWave) * 4 + g;
-        ok[u] = k < hi;
-        q[u] = p.chunk_q[ok[u] ? k : lo] + l16;
-      }
+    for (int it = 0; it < 16; ++it) s[it] = p.src[q[it] < 0 ? 0 : q[it]];
 #pragma unroll
-      for (int u = 0; u < U; ++u) s[u] = p.src[q[u]];
-#pragma unroll
-      for (int u = 0; u < U; ++u) expand_store<W>(p, sblk, s[u], q[u], ok[u]);
-    }
+    for (int it = 0; it < 16; ++it) expand_store<W>(p, sblk, s[it], q[it], q[it] >= 0);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
 // phase 2: one row bin per workgroup; 64-bit fixed-point accumulators in LDS
 // ---------------------------------------------------------------------------------------------
-// v * 2^shift as a 64-bit integer.  BITS: from the float's own mantissa and exponent (a 24-bit integer shifted into place:
-// ~10 integer instructions, truncation toward zero below 2^-shift); otherwise through float64 (convert, multiply, and the
-// compiler's multi-instruction double -> int64 sequence; round to nearest).
-template <bool BITS>
-__device__ __forceinline__ long long to_fixed(float v, double scale, int shift) {
-  if constexpr (BITS) {
-    const unsigned b = __float_as_uint(v);
-    const int ex = static_cast<int>((b >> 23) & 0xffu);
-    const long long m = static_cast<long long>((b & 0x7fffffu) | (ex ? 0x800000u : 0u));
-    const int sh = (ex ? ex : 1) - 150 + shift;                    // v = +-m * 2^(ex - 150)
-    // both shifts are always executed (one of the two amounts is zero): a `sh >= 0 ? << : >>` became a divergent branch per entry
-    const int up = sh > 0 ? (sh > 62 ? 62 : sh) : 0, down = sh < 0 ? (sh < -63 ? 63 : -sh) : 0;
-    const long long x = (m << up) >> down;
-    return (b >> 31) ? -x : x;
-  } else {
-    return __double2ll_rn(static_cast<double>(v) * scale);
-  }
+// v * 2^shift as a 64-bit integer, from the float's own mantissa and exponent (a 24-bit integer shifted into place: ~10 integer
+// instructions, truncation toward zero below 2^-shift).
+__device__ __forceinline__ long long to_fixed(float v, int shift) {
+  const unsigned b = __float_as_uint(v);
+  const int ex = static_cast<int>((b >> 23) & 0xffu);
+  const long long m = static_cast<long long>((b & 0x7fffffu) | (ex ? 0x800000u : 0u));
+  const int sh = (ex ? ex : 1) - 150 + shift;                    // v = +-m * 2^(ex - 150)
+  // both shifts are always executed (one of the two amounts is zero): a `sh >= 0 ? << : >>` became a divergent branch per entry
+  const int up = sh > 0 ? (sh > 62 ? 62 : sh) : 0, down = sh < 0 ? (sh < -63 ? 63 : -sh) : 0;
+  const long long x = (m << up) >> down;
+  return (b >> 31) ? -x : x;
 }
 
-template <bool BITS>
-__device__ __forceinline__ void lds_add(long long* acc, int idx, float v, double scale, int shift) {
-  const long long x = to_fixed<BITS>(v, scale, shift);
+__device__ __forceinline__ void lds_add(long long* acc, int idx, float v, int shift) {
+  const long long x = to_fixed(v, shift);
   atomicAdd(reinterpret_cast<unsigned long long*>(acc + idx), static_cast<unsigned long long>(x));
 }
 
@@ -358,7 +328,7 @@ __device__ __forceinline__ void bwd_rows(const PbParams& p, const long long* acc
   }
 }
 
-template <int W, bool BWD = false, bool BITS = false, int U = 2>
+template <int W, bool BWD = false>
 __global__ __launch_bounds__(kThreads) void pb_reduce_kernel(const PbParams p) {
   extern __shared__ __attribute__((aligned(16))) long long acc[];     // [acc_per_bin * W]
   const int tid = threadIdx.x;
@@ -370,9 +340,10 @@ __global__ __launch_bounds__(kThreads) void pb_reduce_kernel(const PbParams p) {
   int e = 0;
   if (!bad && mx > 0.f) (void)frexpf(mx, &e);
   const int shift = 62 - p.headroom_bits - e;
-  const double scale = bad ? 0.0 : ldexp(1.0, shift), inv_scale = bad ? 0.0 : ldexp(1.0, -shift);
+  const double inv_scale = bad ? 0.0 : ldexp(1.0, -shift);
   __syncthreads();
   const int q_lo = p.bin_entry_ptr[b], q_hi = p.bin_entry_ptr[b + 1];   // multiples of kChunk
+  constexpr int U = 2;                                                  // rounds of loads in flight per thread
   for (int base = q_lo + tid * 4; base < q_hi; base += kThreads * 4 * U) {
     uint2 d[U];
     float4 v[U][W];
@@ -394,21 +365,21 @@ __global__ __launch_bounds__(kThreads) void pb_reduce_kernel(const PbParams p) {
       const int i0 = ok[u] ? static_cast<int>(d[u].x & 0xffffu) : dummy, i1 = ok[u] ? static_cast<int>(d[u].x >> 16) : dummy;
       const int i2 = ok[u] ? static_cast<int>(d[u].y & 0xffffu) : dummy, i3 = ok[u] ? static_cast<int>(d[u].y >> 16) : dummy;
       if constexpr (W == 1) {
-        lds_add<BITS>(acc, i0, v[u][0].x, scale, shift);
-        lds_add<BITS>(acc, i1, v[u][0].y, scale, shift);
-        lds_add<BITS>(acc, i2, v[u][0].z, scale, shift);
-        lds_add<BITS>(acc, i3, v[u][0].w, scale, shift);
+        lds_add(acc, i0, v[u][0].x, shift);
+        lds_add(acc, i1, v[u][0].y, shift);
+        lds_add(acc, i2, v[u][0].z, shift);
+        lds_add(acc, i3, v[u][0].w, shift);
       } else if constexpr (W == 2) {
-        lds_add<BITS>(acc, 2 * i0, v[u][0].x, scale, shift); lds_add<BITS>(acc, 2 * i0 + 1, v[u][0].y, scale, shift);
-        lds_add<BITS>(acc, 2 * i1, v[u][0].z, scale, shift); lds_add<BITS>(acc, 2 * i1 + 1, v[u][0].w, scale, shift);
-        lds_add<BITS>(acc, 2 * i2, v[u][1].x, scale, shift); lds_add<BITS>(acc, 2 * i2 + 1, v[u][1].y, scale, shift);
-        lds_add<BITS>(acc, 2 * i3, v[u][1].z, scale, shift); lds_add<BITS>(acc, 2 * i3 + 1, v[u][1].w, scale, shift);
+        lds_add(acc, 2 * i0, v[u][0].x, shift); lds_add(acc, 2 * i0 + 1, v[u][0].y, shift);
+        lds_add(acc, 2 * i1, v[u][0].z, shift); lds_add(acc, 2 * i1 + 1, v[u][0].w, shift);
+        lds_add(acc, 2 * i2, v[u][1].x, shift); lds_add(acc, 2 * i2 + 1, v[u][1].y, shift);
+        lds_add(acc, 2 * i3, v[u][1].z, shift); lds_add(acc, 2 * i3 + 1, v[u][1].w, shift);
       } else {
         const int idx[4] = {i0, i1, i2, i3};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          lds_add<BITS>(acc, 4 * idx[j], v[u][j].x, scale, shift); lds_add<BITS>(acc, 4 * idx[j] + 1, v[u][j].y, scale, shift);
-          lds_add<BITS>(acc, 4 * idx[j] + 2, v[u][j].z, scale, shift); lds_add<BITS>(acc, 4 * idx[j] + 3, v[u][j].w, scale, shift);
+          lds_add(acc, 4 * idx[j], v[u][j].x, shift); lds_add(acc, 4 * idx[j] + 1, v[u][j].y, shift);
+          lds_add(acc, 4 * idx[j] + 2, v[u][j].z, shift); lds_add(acc, 4 * idx[j] + 3, v[u][j].w, shift);
         }
       }
     }
@@ -644,23 +615,14 @@ size_t pb_bytes(const gnan_spmm_pb_args* a) {
 }
 
 template <int W, bool BWD = false>
-int launch(const PbParams& p, hipStream_t st, int flags) {
+int launch(const PbParams& p, hipStream_t st) {
   hipLaunchKernelGGL(pb_prep_kernel, dim3(1), dim3(64), 0, st, p.absmax);
   if (int rc = gnan::check_launch("pb_prep_kernel")) return rc;
   const size_t lds1 = static_cast<size_t>(p.cb_width) * W * sizeof(float);
-  const dim3 grid1(static_cast<unsigned>(p.n_cblocks) * p.n_split);
-  if (flags & GNAN_PB_EXPAND_PER_ITERATION)
-    hipLaunchKernelGGL((pb_expand_kernel<W, false>), grid1, dim3(kThreads), lds1, st, p);
-  else
-    hipLaunchKernelGGL((pb_expand_kernel<W, true>), grid1, dim3(kThreads), lds1, st, p);
+  hipLaunchKernelGGL(pb_expand_kernel<W>, dim3(static_cast<unsigned>(p.n_cblocks) * p.n_split), dim3(kThreads), lds1, st, p);
   if (int rc = gnan::check_launch("pb_expand_kernel")) return rc;
   const size_t lds2 = static_cast<size_t>(p.acc_per_bin) * W * sizeof(long long);
-  const dim3 grid2(static_cast<unsigned>(p.n_bins));
-  const bool dbl = (flags & GNAN_PB_FIXED_VIA_DOUBLE) != 0, u4 = (flags & GNAN_PB_REDUCE_UNROLL4) != 0;
-  if (dbl && u4) hipLaunchKernelGGL((pb_reduce_kernel<W, BWD, false, 4>), grid2, dim3(kThreads), lds2, st, p);
-  else if (dbl) hipLaunchKernelGGL((pb_reduce_kernel<W, BWD, false, 2>), grid2, dim3(kThreads), lds2, st, p);
-  else if (u4) hipLaunchKernelGGL((pb_reduce_kernel<W, BWD, true, 4>), grid2, dim3(kThreads), lds2, st, p);
-  else hipLaunchKernelGGL((pb_reduce_kernel<W, BWD, true, 2>), grid2, dim3(kThreads), lds2, st, p);
+  hipLaunchKernelGGL((pb_reduce_kernel<W, BWD>), dim3(static_cast<unsigned>(p.n_bins)), dim3(kThreads), lds2, st, p);
   return gnan::check_launch("pb_reduce_kernel");
 }
 
@@ -677,8 +639,7 @@ PbParams make_params(const gnan_spmm_pb_args* a) {
   p.absmax = static_cast<unsigned*>(a->workspace);
   p.E = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 256);
   // enough workgroups per column block that the launch is >> the resident ones (two per CU) whatever the block count
-  int split = (2048 + a->n_cblocks - 1) / a->n_cblocks;
-  if ((a->flags >> 8) & 0xff) split = (a->flags >> 8) & 0xff;          // A/B: workgroups per column block
+  const int split = (2048 + a->n_cblocks - 1) / a->n_cblocks;
   p.n_split = split < 1 ? 1 : (split > 64 ? 64 : split);
   return p;
 }
@@ -703,9 +664,9 @@ extern "C" int gnan_spmm_pb_fwd(const gnan_spmm_pb_args* a, gnan_stream_t stream
   const PbParams p = make_params(a);
   hipStream_t st = static_cast<hipStream_t>(stream);
   switch (a->W) {
-    case 1: return launch<1>(p, st, a->flags);
-    case 2: return launch<2>(p, st, a->flags);
-    default: return launch<4>(p, st, a->flags);
+    case 1: return launch<1>(p, st);
+    case 2: return launch<2>(p, st);
+    default: return launch<4>(p, st);
   }
 }
 
@@ -734,7 +695,7 @@ extern "C" int gnan_spmm_pb_bwd(const gnan_spmm_pb_bwd_args* g, gnan_stream_t st
   p.dS = g->dS; p.ds_stride = g->ds_stride; p.ds_add = g->ds_add; p.ds_add_scale = g->ds_add_scale;
   p.dlut_partial = reinterpret_cast<double*>(static_cast<char*>(a.workspace) + (pb_bytes(&a) + 15) / 16 * 16);
   if (a.n_rows > 0) {
-    if (int rc = launch<2, true>(p, st, a.flags)) return rc;
+    if (int rc = launch<2, true>(p, st)) return rc;
   }
   hipLaunchKernelGGL(pb_dlut_final_kernel, dim3(1), dim3(256), 0, st, p.dlut_partial, a.n_rows > 0 ? a.n_bins : 0, a.D, a.code_base,
                      g->with_rest, g->rest_total, g->rest_q, g->dlut);

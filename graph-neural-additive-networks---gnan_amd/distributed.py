@@ -54,8 +54,6 @@ import torch.distributed as dist
 # one-GPU box) a rank talks to its group whatever its size: communicator creation, every collective's RCCL launch and the
 # all-reduce captured in :class:`SharePipeline`'s hipGraphs run on a world of one exactly as they would on eight.
 ALWAYS_COMMUNICATE = False
-# halo recompute, inference: look the owned rows up first and all-reduce their column sums under the halo rows' look-up
-SPLIT_HALO_LOOKUP = True
 
 
 def _communicates(world: int) -> bool:
@@ -374,7 +372,7 @@ def halo_recompute_forward(x_compact: torch.Tensor, plan: HaloPlan, stacked, lut
         kw["tables"] = tables      # built ahead of time on a side stream (functional.TablePrefetch; inference loops)
     sum_first = order == "sum_first"
     rc = out_channels if order == "reference" else 0
-    if (SPLIT_HALO_LOOKUP and compute is None and _communicates(part.world) and not torch.is_grad_enabled() and stacked is not None
+    if (compute is None and _communicates(part.world) and not torch.is_grad_enabled() and stacked is not None
             and stacked.F % 16 == 0 and 0 < plan.n_own < plan.n_needed):
         # inference: the OWNED rows' look-up first — the column sums are theirs alone — then the all-reduce of those 4*W bytes
         # runs under the halo rows' look-up (more than half of a share's look-up work on an R-MAT graph) and has landed when the

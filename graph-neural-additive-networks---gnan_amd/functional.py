@@ -84,7 +84,6 @@ SUM_VIA_FEATURES_MAX_NODES = 32768   # table look-up with a feature sum and C > 
 
 
 MOMENTS_GENERAL = False   # A/B aid: the general moment kernel where the C = 1 kernel applies
-LOCATE_SORTED = False              # A/B aid: the sorted-array search where the tree search applies
 
 
 INDEX_FLAGS = 0               # A/B aid: _lib.FPWL_INDEX_HALF_LINES / FPWL_INDEX_BS512 for the direct-index look-up
@@ -92,11 +91,9 @@ INDEX_FLAGS = 0               # A/B aid: _lib.FPWL_INDEX_HALF_LINES / FPWL_INDEX
 
 def _fpwl_flags() -> int:
     """``gnan_fpwl_args.flags`` from this module's switches (the library itself reads no environment variables)."""
-    return ((_lib.FPWL_MOMENTS_GENERAL if MOMENTS_GENERAL else 0) | (_lib.FPWL_LOCATE_SORTED if LOCATE_SORTED else 0) | INDEX_FLAGS
-            | (_lib.FPWL_ROWS_MOMENTS_LANE_PER_CHANNEL if ROWS_MOMENTS_LANE_PER_CHANNEL else 0))
+    return (_lib.FPWL_MOMENTS_GENERAL if MOMENTS_GENERAL else 0) | INDEX_FLAGS
 
 
-ROWS_MOMENTS_LANE_PER_CHANNEL = False   # A/B: 33..42 channels with a lane per channel instead of a pair of channels per lane
 FPWL_ROWS = True   # several output channels: two-phase look-up (csrc/fpwl_rows.hip)
 FPWL_ROWS_MIN_NODES = 32768
 # fewer channels: locating the pieces separately costs more than it saves (GNAN_FPWL_ROWS_MIN_C: A/B aid).  10M nodes x 64
@@ -185,7 +182,6 @@ def _fpwl_index(a: "_lib.FpwlArgs", x: torch.Tensor, t, x_range: torch.Tensor) -
     return [table, key]
 
 
-KEEP_PIECES = True   # C == 1 training: the forward's pieces (a byte each) serve the backward
 LOCATED_KEEP_MAX_BYTES = 2 << 30   # (piece, dx) of a forward are kept for its backward pass while they stay below 2 GiB
 
 
@@ -263,7 +259,7 @@ def _fpwl_launch(x: torch.Tensor, t, sum_features: bool, want_total: bool = Fals
         ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
         a.total, a.total_workspace, a.total_workspace_bytes = _lib.ptr(total), _lib.ptr(ws), need
         a.total_rows = n if total_rows is None else int(total_rows)
-    if (located is not None and KEEP_PIECES and C == 1 and sum_features and fpg % 4 == 0 and t.max_pieces <= 256 and n > 0
+    if (located is not None and C == 1 and sum_features and fpg % 4 == 0 and t.max_pieces <= 256 and n > 0
             and n * F <= LOCATED_KEEP_MAX_BYTES):
         # training, one channel: the fast feature-sum kernel also stores the piece of every look-up (one byte each) and the
         # moment kernel of the backward pass skips its search (C4 training step: look-up 1.11 -> 1.22 ms, moments 1.25 -> 0.95 ms)

@@ -64,7 +64,6 @@ GRAPH_CACHE_ENTRIES = 8192   # hop-coded graphs kept per model (graph tasks cycl
 # optimizer one face or the other, never both.  True: ``parameters()`` itself yields the flat buffers, as in round 5 — an opt-in for
 # an unchanged ``Adam(model.parameters())`` (main.py:141) that wants the cheap step and knows what it gives up.
 FLAT_PARAMETERS = False
-PAD_STORE_FEATURES = True    # FlatMLPStore keeps room for F rounded up to 16 features (all-zero shape functions): see rebuild()
 
 
 class FlatMLPStore:
@@ -97,7 +96,7 @@ class FlatMLPStore:
         # ``buf`` / ``grad`` / the flat Parameters are the first F features (contiguous: one layer per buffer), ``pbuf`` /
         # ``pgrad`` the whole padded storage the kernels may take instead (``stacked(...).w_last.gnan_padded``) — what
         # functional._padded_stack builds with six concatenations per forward, for free.
-        pad = PAD_STORE_FEATURES and self.F >= 16 and self.F % 16 and self.C == 1 and L in (2, 3)
+        pad = self.F >= 16 and self.F % 16 and self.C == 1 and L in (2, 3)
         self.Fp = (self.F + 15) // 16 * 16 if pad else self.F
 
         def home(layers, attr):                       # stack [len(layers), Fp, ...] and turn the Parameters into views

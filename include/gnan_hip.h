@@ -26,7 +26,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: exactly the functions declared in this header are exported */
 #pragma GCC visibility push(default)
 
-#define GNAN_ABI_VERSION 46
+#define GNAN_ABI_VERSION 47
 
 typedef void* gnan_stream_t; /* hipStream_t */
 
@@ -192,12 +192,9 @@ typedef struct gnan_fpwl_args {
 /* gnan_fpwl_args.flags (the library reads no environment variables: switches are the caller's, passed per call) */
 enum gnan_fpwl_flags {
   GNAN_FPWL_MOMENTS_GENERAL = 1, /* gnan_fpwl_moments_fixed: the general kernel also where the one-channel kernel applies */
-  GNAN_FPWL_LOCATE_SORTED = 2,   /* gnan_fpwl_locate: the sorted-array search also where the tree search applies */
   GNAN_FPWL_INDEX_HALF_LINES = 4, /* direct-index look-up: 16-feature groups (half lines of x per workgroup) where 32 would fit */
   GNAN_FPWL_INDEX_BS512 = 8,     /* direct-index look-up with 32-feature groups: 512-thread workgroups whatever the mode */
-  GNAN_FPWL_INDEX_BS1024 = 16,   /* ... 1024-thread workgroups whatever the mode */
-  GNAN_FPWL_ROWS_MOMENTS_LANE_PER_CHANNEL = 32 /* gnan_fpwl_rows_moments_fixed, 33..42 channels: a lane per channel (one node per step)
-                                  * instead of a pair of channels per lane and three nodes per step (A/B; same bits) */
+  GNAN_FPWL_INDEX_BS1024 = 16    /* ... 1024-thread workgroups whatever the mode */
 };
 
 size_t gnan_fpwl_total_workspace_bytes(const gnan_fpwl_args* a);
@@ -691,11 +688,6 @@ int gnan_pb_plan_fill(const gnan_pb_fill_args* a, gnan_stream_t stream);
  * workspace: gnan_spmm_pb_workspace_bytes(a) bytes, 16-byte aligned (the expanded operand, n_entries * W floats).
  * A non-finite operand value yields NaN in every output row.
  * ------------------------------------------------------------------------------------------- */
-enum gnan_pb_flags {
-  GNAN_PB_EXPAND_PER_ITERATION = 1,  /* phase 1 reads a chunk's offset inside every wave-iteration (default: 64 offsets per load) */
-  GNAN_PB_FIXED_VIA_DOUBLE = 2,      /* phase 2 converts v * 2^shift through float64 (default: from the float's mantissa / exponent) */
-  GNAN_PB_REDUCE_UNROLL4 = 4         /* phase 2 keeps four rounds of loads in flight per thread (default: two) */
-};
 typedef struct gnan_spmm_pb_args {
   int64_t n_rows;
   int64_t n_cols;
@@ -728,7 +720,6 @@ typedef struct gnan_spmm_pb_args {
   int32_t headroom_bits;
   void* workspace;
   size_t workspace_bytes;
-  int32_t flags;             /* A/B switches (enum gnan_pb_flags): 0 = the defaults; bits 8-15 = workgroups per column block */
   int32_t self_is_row;       /* the hop-code-0 pair of EVERY row i lists operand row i (a hop-coded graph's self pairs, n_cols >=
                                 n_rows): self_col is not read and may be NULL */
   /* optional, W == 1 (ABI 45) — what lets the SAME two phases serve the one-column backward without moving a second column
