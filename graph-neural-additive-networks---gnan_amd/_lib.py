@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNAN_HIP_LIB: development aid for same-box A/B runs of two builds of the library (tools/ab_lib.sh)
 LIB_PATH = os.environ.get("GNAN_HIP_LIB") or os.path.join(_HERE, "libgnan_hip.so")
-ABI_VERSION = 47
+ABI_VERSION = 48
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # enum gnan_status
 
 GNAN_F32, GNAN_BF16 = 0, 1
@@ -126,6 +126,7 @@ class SpmmArgs(C.Structure):
         ("hot_lo", C.c_int64), ("hot_rows", C.c_int32), ("shell_out", C.c_void_p),
         ("cls_index", C.c_void_p), ("cls_slice_start", C.c_void_p), ("cls_slice_row", C.c_void_p), ("cls_slot_slice", C.c_void_p),
         ("cls_n_slots", C.c_int32),
+        ("short_lmax", C.c_int32), ("short_row", C.c_void_p), ("short_pair", C.c_void_p),
     ]
 
 

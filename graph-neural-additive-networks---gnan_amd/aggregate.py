@@ -77,6 +77,8 @@ DEGREE_SORTED_COPY = True      # ... through a degree-sorted copy of the CSR (Ho
 XCD_CLASSED_HUBS = True        # wide forward rows of large graphs: hub slices of one column class each, a class per XCD (classed_hub_plan)
 CLASSED_MIN_ROW_BYTES = 128    # ... from operand rows of this many bytes (fp32 W >= 32, bf16 W >= 64)
 CLASSED_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs
+SHORT_ROW_TILES = True         # wide forward over a degree-sorted copy: rows of at most SHORT_ROW_LMAX pairs in tiles of many rows per wave
+SHORT_ROW_LMAX = 4             # (gnan_spmm_args.short_*; the library takes them where its kernel variant serves the call)
 
 
 def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -138,6 +140,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
     if not with_rest:
         s_total = None
     scatter = False
+    short = False
     n_hot = 0
     narrow = S.shape[1] * S.element_size() <= 8        # one or two lanes per row: see LONG_ROW_THRESHOLD_NARROW
     if (PB_NARROW and not g.is_dense and row_ids is None and S.dtype == torch.float32 and S.shape[1] in PB_WIDTHS and not per_row
@@ -174,6 +177,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         if DEGREE_SORTED_COPY and (by_col_table or (not per_row and not weight_by_col)) and g.n_rows >= DEGREE_SORTED_COPY_MIN_ROWS:
             g, row_ids, plan = g.degree_sorted_copy()   # walk a degree-sorted copy of the CSR, store rows at their own index
             scatter = 2
+            short = SHORT_ROW_TILES and not per_row and not weight_by_col
         else:
             row_ids, plan = g.degree_schedule()      # process rows by degree, store them in place
             scatter = True
@@ -192,6 +196,10 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         per_row = True
     a = _spmm_args(g, S, lut, use_cnt, s_total, out, row_ids, per_row, weight_by_col, minus_rest, plan,
                    reduce_cr=reduce_cr, scatter_out=scatter, s_by_code=s_by_code, packed=True, hot_rows=n_hot)
+    if short and a.packed_index:
+        # rows of the copy's shortest runs in tiles of many rows per wave: same bits as the row walk
+        runs = g.short_row_runs(SHORT_ROW_LMAX)
+        a.short_lmax, a.short_row, a.short_pair = runs.lmax, runs.row_ptr, runs.pair_ptr
     need = _lib.lib().gnan_spmm_fwd_workspace_bytes(a)
     ws = None
     if need:

@@ -61,6 +61,14 @@ struct Params {
   const int32_t* cls_slot_slice;
   int cls_n_slots;
   int n_slice_blocks;  // workgroups in front of the row blocks: n_slices, or 8 ceil(queue / 4) with the classed plan (a wave per slice)
+  // short-row tiles (gnan_spmm_args.short_*), set by launch() where the route serves the call: the n_tile_blocks workgroups behind
+  // the slice blocks take the runs of rows of L = 0 .. short_lmax pairs, a tile per wave (tile t of the launch is tile
+  // t - short_tile[L] of run L); the row blocks behind them start at row row_q0
+  int short_lmax;
+  int n_tile_blocks, n_tiles;
+  int64_t row_q0;
+  int64_t short_row[GNAN_SHORT_LMAX + 2], short_pair[GNAN_SHORT_LMAX + 1];
+  int short_tile[GNAN_SHORT_LMAX + 1];
 };
 
 __device__ __forceinline__ int64_t load_rowptr(const Params& p, int64_t i) {
@@ -301,7 +309,7 @@ __device__ __forceinline__ void rows_body(const Params& p, const int64_t block_i
   const int wave = threadIdx.x / kWave;
   const int sub = lane % LPR;
   const int slot = lane / LPR;
-  const int64_t q = (block_id * (blockDim.x / kWave) + wave) * G + slot;
+  const int64_t q = p.row_q0 + (block_id * (blockDim.x / kWave) + wave) * G + slot;
   if (q >= p.n_rows) return;
   const int64_t i = adj_row(p, q);
   int64_t lo, hi, code_base;
@@ -485,6 +493,146 @@ __device__ __forceinline__ void rows_body(const Params& p, const int64_t block_i
 }
 
 // ---------------------------------------------------------------------------------------------
+// short-row tiles: R rows of exactly L pairs per lane group, many rows per wave
+// ---------------------------------------------------------------------------------------------
+// A row of the degree-sorted copy with one to four pairs (82 % of the rows of a power-law graph) costs rows_body a wave's start,
+// a rowptr load and one round of gathers for four rows.  In a run of rows of one length L, row q's pairs start at
+// short_pair[L] + (q - short_row[L]) L: a tile needs no rowptr, loads the index entries of all its rows with one coalesced load
+// and has the gathers of R rows (R L of them, at most 8 per lane) in flight before the first is consumed.
+__host__ __device__ constexpr int short_rows_per_group(int L) { return L == 0 ? 8 : (8 / L > 0 ? 8 / L : 1); }
+
+// The kernel variants that take tiles: fp32 rows of 16-B chunks, 16 lanes or more per row (W in (32, 256]).  The others stay
+// within 8 waves/SIMD only without scratch: with the tile body the bf16 variants spilled 116-132 B, W = 32 (8 lanes) 8 B.
+__host__ __device__ constexpr bool short_tiles_serve(int vec, int lpr, bool smalld, bool packed, bool bycode) {
+  return vec == 4 && lpr >= 16 && smalld && packed && !bycode;
+}
+
+// Rows [qg, qg + R) (those below q_end) of run L, their first pair at e: per row exactly rows_body's arithmetic under SMALLD &&
+// PACKED with one pass over the columns (the launch guarantees LPR VEC >= W and LPR >= 8): the folded weights (w_d - w_rest),
+// fmaf over the row's pairs in order, fmaf(w_rest, tot, acc), then the fused read-out's channel sums and butterfly.
+template <int VEC, int LPR, int L>
+__device__ __forceinline__ void short_tile(const Params& p, int64_t qg, int64_t q_end, int64_t e) {
+  constexpr int R = short_rows_per_group(L);
+  constexpr int NP = R * L;                    // pairs of the group (<= 8 <= LPR: one index entry per lane)
+  constexpr int KW = (4 * R + LPR - 1) / LPR;  // weight registers per lane: (row r, code d) lives in lane (4 r + d) % LPR, register 4 r / LPR
+  static_assert(LPR >= 8 && LPR % 4 == 0 && NP <= LPR && R <= LPR, "one index entry and one output row per lane");
+  const int sub = (threadIdx.x & (kWave - 1)) % LPR;
+  const int nr = static_cast<int>(q_end - qg < R ? q_end - qg : R);
+  if (nr <= 0) return;  // (the whole group)
+  const int rest = p.D - 1;
+  const int cw = sub * VEC;
+  const bool col_ok = cw < p.W;
+  unsigned ent = 0u;
+  if constexpr (NP > 0) {
+    if (sub < nr * L) ent = static_cast<unsigned>(p.col[e + sub]);
+  }
+  int orow = 0;
+  if (sub < nr) orow = p.row_ids[qg + sub];
+  float wv[KW], wrv[KW];
+#pragma unroll
+  for (int k = 0; k < KW; ++k) {
+    const int idx = sub + k * LPR, r = idx >> 2, d = idx & 3;
+    float v = 0.f;
+    if (r < nr && d < p.D) {
+      v = p.lut[(qg + r) * p.lut_row_stride + d];
+      if (p.cnt) {
+        const int c = p.cnt[(qg + r) * p.cnt_stride + d];
+        v = v / static_cast<float>(c > 1 ? c : 1);
+      }
+    }
+    const float wr = __shfl(v, (sub & ~3) + rest, LPR);  // w_rest of this lane's row (before the fold)
+    wrv[k] = 0.f;
+    if (p.s_total) {
+      wrv[k] = wr;
+      v = d < rest ? v - wr : 0.f;
+    }
+    wv[k] = v;
+  }
+  Raw<VEC> s[NP > 0 ? NP : 1];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const unsigned en = static_cast<unsigned>(__shfl(static_cast<int>(ent), j, LPR));
+    s[j].zero();
+    if (j < nr * L && col_ok) s[j].load(p.S, static_cast<int64_t>(en & kPackMask), p.s_stride, cw);
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (r >= nr) break;
+    Vec<VEC> acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc.v[v] = 0.f;
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+      // the pair's weight: its code from the index entry (fetched again rather than held through the gathers: registers)
+      int d = static_cast<int>(static_cast<unsigned>(__shfl(static_cast<int>(ent), r * L + l, LPR)) >> kPackShift);
+      d = d < rest ? d : rest;
+      const float w = __shfl(wv[4 * r / LPR], (4 * r) % LPR + d, LPR);
+      const Vec<VEC> sv = s[r * L + l].widen();
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc.v[v] = fmaf(w, sv.v[v], acc.v[v]);
+    }
+    const float w_rest = __shfl(wrv[4 * r / LPR], (4 * r) % LPR, LPR);
+    const int64_t o = __shfl(orow, r, LPR);
+    float red[4] = {0.f, 0.f, 0.f, 0.f};
+    if (col_ok) {
+      if (p.s_total) {
+        const Vec<VEC> tot = load_vec<VEC>(p.s_total + cw);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc.v[v] = fmaf(w_rest, tot.v[v], acc.v[v]);
+      }
+      if (p.reduce_cr == 0) {
+        store_vec<VEC>(p.Y + o * p.y_stride + cw, acc);
+      } else {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          const int ch = (cw + v) & (p.reduce_cr - 1);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) red[c] += ch == c ? acc.v[v] : 0.f;
+        }
+      }
+    }
+    if (p.reduce_cr) {
+#pragma unroll
+      for (int off = 1; off < LPR; off <<= 1) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) red[c] += __shfl_xor(red[c], off);
+      }
+      if (sub == 0)
+        for (int c = 0; c < p.reduce_cr; ++c) p.Y[o * p.y_stride + c] = red[c];
+    }
+  }
+}
+
+// Tile t of the launch: find its run (static indices only: a dynamically indexed kernel argument would go to scratch).
+template <int VEC, int LPR>
+__device__ __forceinline__ void short_tiles(const Params& p, int t) {
+  if (t >= p.n_tiles) return;
+  int L = 0;
+  int64_t k = t, q0 = 0, q1 = p.short_row[1], e0 = p.short_pair[0];
+#pragma unroll
+  for (int l = 1; l <= GNAN_SHORT_LMAX; ++l) {
+    if (l <= p.short_lmax && t >= p.short_tile[l]) {
+      L = l; k = t - p.short_tile[l]; q0 = p.short_row[l]; q1 = p.short_row[l + 1]; e0 = p.short_pair[l];
+    }
+  }
+  constexpr int G = kWave / LPR;
+  const int slot = (threadIdx.x & (kWave - 1)) / LPR;
+#define GNAN_SHORT_CASE(LL)                                                                       \
+  case LL: {                                                                                      \
+    constexpr int R = short_rows_per_group(LL);                                              \
+    const int64_t qg = q0 + (k * G + slot) * R;                                                   \
+    short_tile<VEC, LPR, LL>(p, qg, q1, e0 + (qg - q0) * LL);                                     \
+    break;                                                                                        \
+  }
+  switch (L) {
+    GNAN_SHORT_CASE(0) GNAN_SHORT_CASE(1) GNAN_SHORT_CASE(2) GNAN_SHORT_CASE(3) GNAN_SHORT_CASE(4)
+    GNAN_SHORT_CASE(5) GNAN_SHORT_CASE(6) GNAN_SHORT_CASE(7) GNAN_SHORT_CASE(8)
+    default: break;
+  }
+#undef GNAN_SHORT_CASE
+}
+
+// ---------------------------------------------------------------------------------------------
 // long kernel: one 256-thread workgroup per slice of a hub row (classed hub plan: one wave per slice, one class per workgroup)
 // ---------------------------------------------------------------------------------------------
 template <int VEC, int LPR, bool SMALLD, bool DENSE, bool BYCODE, bool PACKED = false>
@@ -636,7 +784,13 @@ void spmm_kernel(const Params p) {
       slice_body<VEC, LPR, SMALLD, false, BYCODE, PACKED>(p, static_cast<int>(blockIdx.x));
       return;
     }
-    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED>(p, static_cast<int64_t>(blockIdx.x) - p.n_slice_blocks);
+    if constexpr (short_tiles_serve(VEC, LPR, SMALLD, PACKED, BYCODE)) {   // (launch() leaves n_tile_blocks 0 for every other variant)
+      if (static_cast<int>(blockIdx.x) < p.n_slice_blocks + p.n_tile_blocks) {
+        short_tiles<VEC, LPR>(p, (static_cast<int>(blockIdx.x) - p.n_slice_blocks) * (blockDim.x / kWave) + threadIdx.x / kWave);
+        return;
+      }
+    }
+    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED>(p, static_cast<int64_t>(blockIdx.x) - p.n_slice_blocks - p.n_tile_blocks);
   } else {
     if (p.n_slices > 0) {      // few rows, many neighbours: every row is cut into slices, there are no row blocks
       slice_body<VEC, LPR, SMALLD, true, false>(p, static_cast<int>(blockIdx.x));
@@ -1029,11 +1183,30 @@ int launch_shell_lpr(const Params& p, int lpr, bool dense, hipStream_t st) {
 // host-side dispatch
 // ---------------------------------------------------------------------------------------------
 template <int VEC, int LPR>
-int launch(const Params& p, bool dense, bool smalld, hipStream_t st) {
+int launch(const Params& p0, bool dense, bool smalld, hipStream_t st) {
   constexpr int G = kWave / LPR;
   const int rows_per_block = 4 * G;
+  Params p = p0;
+  // short-row tiles: the packed small-D forward over a degree-sorted copy, one pass of the lane group over the columns
+  if (short_tiles_serve(VEC, LPR, smalld, p.packed, p.s_by_code) && p.short_lmax > 0 && !dense && p.scatter_out == 2 &&
+      LPR * VEC >= p.W && p.nnz > 0) {
+    int64_t t = 0;
+    for (int L = 0; L <= p.short_lmax; ++L) {
+      p.short_tile[L] = static_cast<int>(t);
+      const int64_t per = static_cast<int64_t>(G) * short_rows_per_group(L);
+      t += (p.short_row[L + 1] - p.short_row[L] + per - 1) / per;
+    }
+    if (t > 0x7fffffffLL - 3) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many short-row tiles for one launch");
+    p.n_tiles = static_cast<int>(t);
+    p.n_tile_blocks = static_cast<int>((t + 3) / 4);
+    p.row_q0 = p.short_row[p.short_lmax + 1];
+  } else {
+    p.short_lmax = 0;
+  }
   const int n_slices = p.n_slices;
-  const int64_t blocks = dense && n_slices > 0 ? n_slices : (p.n_rows + rows_per_block - 1) / rows_per_block + p.n_slice_blocks;
+  const int64_t blocks = dense && n_slices > 0
+                             ? n_slices
+                             : (p.n_rows - p.row_q0 + rows_per_block - 1) / rows_per_block + p.n_slice_blocks + p.n_tile_blocks;
   if (blocks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many rows for one launch");
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
   if (p.s_by_code) {
@@ -1115,6 +1288,20 @@ int validate(const gnan_spmm_args* a) {
                         cr, a->W);
     GNAN_REQUIRE(a->y_stride >= cr, "spmm: y_stride smaller than reduce_cr");
   }
+  if (a->short_lmax != 0) {
+    const int lm = a->short_lmax;
+    GNAN_REQUIRE(lm > 0 && lm <= GNAN_SHORT_LMAX, "spmm: short_lmax must be in [0, %d] (got %d)", GNAN_SHORT_LMAX, lm);
+    GNAN_REQUIRE(a->short_row && a->short_pair, "spmm: short_lmax > 0 needs the short_row / short_pair host arrays");
+    GNAN_REQUIRE(a->rowptr != nullptr && a->scatter_out == 2 && a->short_row[0] == 0 && a->short_row[lm + 1] <= a->n_rows,
+                 "spmm: short-row runs need a degree-sorted copy (CSR, scatter_out 2) and runs from row 0 within n_rows");
+    for (int L = 0; L <= lm; ++L) {
+      const int64_t n = a->short_row[L + 1] - a->short_row[L];
+      const int64_t end = a->short_pair[L] + n * L;
+      GNAN_REQUIRE(n >= 0 && a->short_pair[L] >= 0 && (a->nnz <= 0 || end <= a->nnz) && (L == lm || end == a->short_pair[L + 1]),
+                   "spmm: short-row run %d is inconsistent (rows %lld, first pair %lld)", L, static_cast<long long>(n),
+                   static_cast<long long>(a->short_pair[L]));
+    }
+  }
   if (a->n_long > 0) {
     GNAN_REQUIRE(a->rowptr != nullptr || (a->n_long == a->n_rows && a->long_threshold == 0),
                  "spmm: a row plan for the dense layout must slice every row (n_long == n_rows, long_threshold == 0)");
@@ -1164,6 +1351,15 @@ Params make_params(const gnan_spmm_args* a) {
   p.cls_slice_start = a->cls_slice_start; p.cls_slice_row = a->cls_slice_row; p.cls_slot_slice = a->cls_slot_slice;
   p.cls_n_slots = a->cls_n_slots;
   p.n_slice_blocks = classed ? 8 * ((a->cls_n_slots / 8 + 3) / 4) : p.n_slices;
+  const bool runs = a->short_lmax > 0 && a->short_lmax <= GNAN_SHORT_LMAX && a->short_row && a->short_pair;  // (validate() checks them)
+  p.short_lmax = runs ? a->short_lmax : 0;
+  p.n_tile_blocks = p.n_tiles = 0;
+  p.row_q0 = 0;
+  for (int L = 0; L <= GNAN_SHORT_LMAX + 1; ++L) p.short_row[L] = L <= p.short_lmax + 1 && runs ? a->short_row[L] : 0;
+  for (int L = 0; L <= GNAN_SHORT_LMAX; ++L) {
+    p.short_pair[L] = L <= p.short_lmax && runs ? a->short_pair[L] : 0;
+    p.short_tile[L] = 0;
+  }
   return p;
 }
 

@@ -16,6 +16,7 @@ size of the rest bucket), i.e. the distinct values of ``normalization_matrix`` r
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
@@ -99,6 +100,15 @@ class ClassedHubPlan(LongRowPlan):
     n_slots: int = 0
 
 
+class ShortRowRuns:
+    """:meth:`HopGraph.short_row_runs`: run boundaries as the host arrays ``gnan_spmm_args.short_row / short_pair`` point to."""
+
+    def __init__(self, lmax: int, rows, pairs):
+        self.lmax, self.rows, self.pairs = lmax, list(rows), list(pairs)
+        self._c = ((ctypes.c_int64 * len(self.rows))(*self.rows), (ctypes.c_int64 * len(self.pairs))(*self.pairs))
+        self.row_ptr, self.pair_ptr = (ctypes.addressof(c) for c in self._c)    # (alive as long as this object)
+
+
 @dataclass
 class HopGraph:
     n_rows: int
@@ -116,6 +126,7 @@ class HopGraph:
     _dense_plans: dict = field(default_factory=dict, repr=False)
     _plans: dict = field(default_factory=dict, repr=False)          # hub-row plans by threshold (other than the default)
     _classed: dict = field(default_factory=dict, repr=False)        # classed_hub_plan(): (order, threshold, slice_edges) -> plan
+    _short_runs: dict = field(default_factory=dict, repr=False)     # short_row_runs(): lmax -> ShortRowRuns
     _sorted_copy: Optional["HopGraph"] = field(default=None, repr=False)
     _hot: Optional[tuple] = field(default=None, repr=False)           # hot_columns(): (ids or None,)
     _sorted_copy_hot: Optional["HopGraph"] = field(default=None, repr=False)
@@ -634,6 +645,19 @@ class HopGraph:
         if self._inv_rest is None:
             self._inv_rest = 1.0 / self.cnt[:, self.n_codes - 1:self.n_codes].clamp_min(1).float()
         return self._inv_rest
+
+    def short_row_runs(self, lmax: int) -> "ShortRowRuns":
+        """Runs of rows of exactly ``L = 0 .. lmax`` listed pairs of a degree-sorted copy (rows shortest first): row ``q`` in
+        ``[rows[L], rows[L + 1])`` lists ``L`` pairs from ``pairs[L] + (q - rows[L]) L`` on (``gnan_spmm_args.short_*``).
+        Host arrays, found by one search over the copy's row lengths; cached per ``lmax``."""
+        runs = self._short_runs.get(int(lmax))
+        if runs is None:
+            deg = self.rowptr[1:] - self.rowptr[:-1]
+            rows = torch.searchsorted(deg, torch.arange(lmax + 2, dtype=deg.dtype, device=deg.device))   # first row of >= L pairs
+            vals = torch.cat([rows, self.rowptr[rows[: lmax + 1]].long()]).tolist()
+            runs = ShortRowRuns(int(lmax), vals[: lmax + 2], vals[lmax + 2:])
+            self._short_runs[int(lmax)] = runs
+        return runs
 
     def degree_sorted_copy(self):
         """``(copy, order, plan)``: the CSR stored in the processing order of :meth:`degree_schedule` — row ``q`` of the

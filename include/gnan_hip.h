@@ -26,7 +26,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: exactly the functions declared in this header are exported */
 #pragma GCC visibility push(default)
 
-#define GNAN_ABI_VERSION 47
+#define GNAN_ABI_VERSION 48
 
 typedef void* gnan_stream_t; /* hipStream_t */
 
@@ -42,6 +42,7 @@ enum gnan_dtype { GNAN_F32 = 0, GNAN_BF16 = 1 };
 
 /* Largest number of hop codes (shells incl. the rest bucket) a uint8 code can address. */
 #define GNAN_MAX_CODES 256
+#define GNAN_SHORT_LMAX 8     /* longest run of gnan_spmm_args.short_row */
 
 int gnan_abi_version(void);
 const char* gnan_last_error(void);
@@ -497,6 +498,16 @@ typedef struct gnan_spmm_args {
   const int32_t* cls_slice_row;
   const int32_t* cls_slot_slice;
   int32_t cls_n_slots;
+  /* short-row runs (ABI 48; gnan_spmm_fwd only, optional): a degree-sorted copy (scatter_out == 2, rows shortest first) declares
+   * that row q in [short_row[L], short_row[L + 1]) lists exactly L pairs, L = 0 .. short_lmax, its first pair being
+   * short_pair[L] + (q - short_row[L]) L; short_row[0] must be 0.  Both are HOST arrays ([short_lmax + 2], [short_lmax + 1]),
+   * read when the call is enqueued.  The library then takes these rows in tiles of many rows per wave (no per-row rowptr load,
+   * the gathers of several rows in flight) where the route serves the call — packed index, small-D weights, fp32 or bf16 rows
+   * covered by one pass of the lane group — and walks them as ordinary rows otherwise.  Same output bits either way.
+   * short_lmax = 0 (the default): off */
+  int32_t short_lmax;            /* 0 .. GNAN_SHORT_LMAX */
+  const int64_t* short_row;
+  const int64_t* short_pair;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
