@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNAN_HIP_LIB: development aid for same-box A/B runs of two builds of the library (tools/ab_lib.sh)
 LIB_PATH = os.environ.get("GNAN_HIP_LIB") or os.path.join(_HERE, "libgnan_hip.so")
-ABI_VERSION = 48
+ABI_VERSION = 49
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # enum gnan_status
 
 GNAN_F32, GNAN_BF16 = 0, 1
@@ -128,6 +128,23 @@ class SpmmArgs(C.Structure):
         ("cls_n_slots", C.c_int32),
         ("short_lmax", C.c_int32), ("short_row", C.c_void_p), ("short_pair", C.c_void_p),
     ]
+
+
+SHORT_LMAX = 8                  # GNAN_SHORT_LMAX
+SPMM_KERNEL_NONE, SPMM_KERNEL_ROWS, SPMM_KERNEL_HOT = 0, 1, 2
+
+
+class SpmmLaunchInfo(C.Structure):
+    _fields_ = [
+        ("vec", C.c_int32), ("lpr", C.c_int32), ("smalld", C.c_int32), ("dense", C.c_int32), ("kernel", C.c_int32),
+        ("classed", C.c_int32), ("n_slice_blocks", C.c_int32), ("n_tile_blocks", C.c_int32), ("n_tiles", C.c_int32),
+        ("row_q0", C.c_int64), ("short_tile", C.c_int32 * (SHORT_LMAX + 1)),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["short_tile"] = list(self.short_tile)
+        return d
 
 
 class ClassedPlanArgs(C.Structure):
@@ -409,6 +426,7 @@ SYMBOLS = {
     "gnan_loss_step": (C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     "gnan_spmm_fwd_workspace_bytes": (C.c_size_t, [C.POINTER(SpmmArgs)]),
     "gnan_spmm_fwd": (C.c_int, [C.POINTER(SpmmArgs), C.c_void_p]),
+    "gnan_spmm_fwd_describe": (C.c_int, [C.POINTER(SpmmArgs), C.POINTER(SpmmLaunchInfo)]),
     "gnan_degree_sorted_csr_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnan_degree_sorted_csr": (C.c_int, [C.POINTER(SortedCsrArgs), C.c_void_p]),
     "gnan_long_row_plan_workspace_bytes": (C.c_size_t, [C.c_int64]),

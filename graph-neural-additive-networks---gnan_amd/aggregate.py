@@ -28,10 +28,15 @@ def _spmm_args(g: HopGraph, S, lut, use_cnt, s_total, out, row_ids, per_row_lut,
     # one index stream (col | code << 29) where the graph carries it and the kernel variant reads it (gnan_hip.h)
     packed = bool(packed and PACKED_INDEX and g.colp is not None and D <= 4 and Cw == 1 and not weight_by_col
                   and not minus_rest and not s_by_code)
+    col, code = (g.colp if packed else g.col), g.code
+    if g.rowptr is not None and col.numel() == 0:
+        # a CSR without a single listed pair: its empty index tensors have NULL pointers, which the library refuses beside a
+        # rowptr (gnan_hip.h) — every row is empty and nothing is read through this stand-in, so rowptr's own address serves
+        col = code = g.rowptr
     a = _lib.SpmmArgs(
         n_rows=out.shape[0], n_cols=g.n_cols,
         rowptr=_lib.ptr(g.rowptr), rowptr_is64=int(g.rowptr is not None and g.rowptr.dtype == torch.int64),
-        col=_lib.ptr(g.colp if packed else g.col), code=_lib.ptr(g.code), row_ids=_lib.ptr(row_ids),
+        col=_lib.ptr(col), code=_lib.ptr(code), row_ids=_lib.ptr(row_ids),
         S=_lib.ptr(S), s_dtype=_lib.GNAN_BF16 if S.dtype == torch.bfloat16 else _lib.GNAN_F32, W=S.shape[1],
         s_stride=S.stride(0),
         lut=_lib.ptr(lut), lut_row_stride=(D * Cw if per_row_lut else 0), D=D, Cw=Cw,
@@ -105,13 +110,16 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
                 row_ids: Optional[torch.Tensor] = None, weight_by_col: bool = False,
                 minus_rest: bool = False, s_total: Optional[torch.Tensor] = None, reduce_cr: int = 0,
                 s_by_code: bool = False, lut_of_counts=None, lut_channels: int = 1, room=None,
-                keep_shell: Optional[list] = None) -> torch.Tensor:
+                keep_shell: Optional[list] = None, describe: Optional[list] = None) -> torch.Tensor:
     """One ``gnan_spmm_fwd`` call (no autograd).  ``lut`` is ``[D, Cw]`` or ``[n_adj_rows, D, Cw]``.
     ``reduce_cr`` in FUSABLE_READOUT returns ``[n, reduce_cr]`` = per-channel sums over the operand columns.
     ``s_by_code``: ``S`` is ``[n_cols * D, W]`` and the pair with neighbour ``c`` and hop code ``d`` reads row ``c*D + d``.
     ``lut_of_counts`` (with ``lut=None``): a function ``cnt [n, D] -> [n, D, lut_channels]`` giving the per-row table of a
     graph from its shell counts (the pre-rho normalisation, :func:`pre_rho_aggregate`); it is called on the counts of the
-    graph that is actually walked, so a degree-sorted copy gets its table in its own row order and nothing is permuted."""
+    graph that is actually walked, so a degree-sorted copy gets its table in its own row order and nothing is permuted.
+    ``describe``: a list that receives the launch partition (``gnan_spmm_fwd_describe`` as a dict: kernel variant, slice / tile /
+    row blocks) of the ``gnan_spmm_fwd`` call about to be made; the propagation-blocked narrow route (csrc/spmm_pb.hip) makes no
+    such call and leaves the list as it was."""
     _lib.require_device(S, lut, g.code)
     whole = row_ids is None                              # (the walks below may bring row_ids of their own)
     S = S.detach()
@@ -213,6 +221,10 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         shell = torch.empty((n_out, lut_shape[0] - 1), dtype=torch.float32, device=S.device)
         a.shell_out = _lib.ptr(shell)
         keep_shell.append(shell)
+    if describe is not None:
+        info = _lib.SpmmLaunchInfo()
+        _lib.check(_lib.lib().gnan_spmm_fwd_describe(a, info), "gnan_spmm_fwd_describe")
+        describe.append(info.as_dict())
     _lib.check(_lib.lib().gnan_spmm_fwd(a, _lib.stream_of(S)), "gnan_spmm_fwd")
     return out
 
@@ -585,14 +597,15 @@ class _RhoAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, S, lut, g: HopGraph, use_cnt: bool, with_rest: bool, row_ids, s_total=None, reduce_cr=0,
-                total_rows=None, total_group=NOT_SHARED):
+                total_rows=None, total_group=NOT_SHARED, describe=None):
         ctx.g, ctx.use_cnt, ctx.with_rest, ctx.row_ids, ctx.reduce_cr = g, use_cnt, with_rest, row_ids, reduce_cr
         ctx.s_total = None if s_total is None else s_total.detach()
         ctx.total_rows, ctx.total_group = total_rows, total_group
         ctx.save_for_backward(S, lut)
         kept = [] if (S.shape[1] == 1 and all(ctx.needs_input_grad[:2]) and S.dtype == torch.float32) else None
+        ask = {} if describe is None else {"describe": describe}     # named only when asked for: a stand-in launch may not know it
         out = spmm_launch(g, S, lut, use_cnt, with_rest, row_ids, s_total=s_total, reduce_cr=reduce_cr,
-                          room=getattr(S, "gnan_room", None), keep_shell=kept)
+                          room=getattr(S, "gnan_room", None), keep_shell=kept, **ask)
         ctx.shell = kept[0] if kept else None
         return out
 
@@ -600,7 +613,7 @@ class _RhoAggregate(torch.autograd.Function):
     def backward(ctx, dY):
         S, lut = ctx.saved_tensors
         dS, dlut = _aggregate_backward(ctx, S, lut, dY, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return dS, dlut, None, None, None, None, None, None, None, None
+        return dS, dlut, None, None, None, None, None, None, None, None, None
 
 
 def _aggregate_backward(ctx, S, lut, dY, need_dS: bool, need_dlut: bool):
@@ -771,7 +784,7 @@ class _PreRhoAggregate(torch.autograd.Function):
     gradient of the table binned by the pieces of its arguments."""
 
     @staticmethod
-    def forward(ctx, S, g, with_rest, row_ids, s_total, total_rows, total_group, tables, u, L, H, C, *params):
+    def forward(ctx, S, g, with_rest, row_ids, s_total, total_rows, total_group, tables, u, L, H, C, describe, *params):
         ctx.g, ctx.use_cnt, ctx.with_rest, ctx.row_ids, ctx.reduce_cr = g, False, with_rest, row_ids, 0
         ctx.s_total = None if s_total is None else s_total.detach()
         ctx.total_rows, ctx.total_group = total_rows, total_group
@@ -779,7 +792,8 @@ class _PreRhoAggregate(torch.autograd.Function):
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(S, *[t for t in params if t is not None])
         return spmm_launch(g, S, None, False, with_rest, row_ids, s_total=s_total, room=getattr(S, "gnan_room", None),
-                           lut_of_counts=lambda cnt: Fn._rho_row_lut_launch(cnt, u, tables, C, False)[0], lut_channels=C)
+                           lut_of_counts=lambda cnt: Fn._rho_row_lut_launch(cnt, u, tables, C, False)[0], lut_channels=C,
+                           **({} if describe is None else {"describe": describe}))
 
     @staticmethod
     def backward(ctx, dY):
@@ -787,16 +801,16 @@ class _PreRhoAggregate(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         S = saved.pop(0)
         params = [saved.pop(0) if present else None for present in ctx.present]
-        need_rho = any(ctx.needs_input_grad[12:])
+        need_rho = any(ctx.needs_input_grad[13:])
         lut, arg = Fn._rho_row_lut_launch(ctx.g.cnt, ctx.u, ctx.tables, C, need_rho)
         dS, dlut = _aggregate_backward(ctx, S, lut, dY, ctx.needs_input_grad[0], need_rho)
         pg = Fn._rho_param_grads(arg, dlut, ctx.tables, params, ctx.present, L, H, C) if need_rho else (None,) * 6
-        return (dS,) + (None,) * 11 + tuple(pg)
+        return (dS,) + (None,) * 12 + tuple(pg)
 
 
 def pre_rho_aggregate(g: HopGraph, S: torch.Tensor, p: StackedMLP, u: torch.Tensor, with_rest: Optional[bool] = None,
                       row_ids: Optional[torch.Tensor] = None, s_total: Optional[torch.Tensor] = None,
-                      total_rows: Optional[int] = None, total_group=NOT_SHARED) -> torch.Tensor:
+                      total_rows: Optional[int] = None, total_group=NOT_SHARED, describe: Optional[list] = None) -> torch.Tensor:
     """The aggregation with the pre-rho normalisation of the stand-alone model file (GNAN.py:65-70):
     ``Y[q] = sum_j rho(u(i_q, j) / c(i_q, j)) (.) S[j]``; ``p`` = rho's layers as a one-feature :class:`StackedMLP`,
     ``u`` = the distinct values of ``node_distances`` (``graph.hop_inputs``).  Differentiable w.r.t. ``S`` and rho."""
@@ -807,9 +821,9 @@ def pre_rho_aggregate(g: HopGraph, S: torch.Tensor, p: StackedMLP, u: torch.Tens
     tables = Fn._rho_tables(p, g.n_rows * g.n_codes) if S.dtype == torch.float32 else None
     if tables is None:                      # small graphs / graph capture: the table through the shape-function kernels
         return rho_aggregate(g, S, Fn.rho_row_lut(g.cnt, u, p), False, with_rest, row_ids, s_total,
-                             total_rows=total_rows, total_group=total_group)
+                             total_rows=total_rows, total_group=total_group, describe=describe)
     return _PreRhoAggregate.apply(S, g, with_rest, row_ids, s_total, total_rows, total_group, tables, u.contiguous(),
-                                  p.L, p.H, p.C, *p[:6])
+                                  p.L, p.H, p.C, describe, *p[:6])
 
 
 REFERENCE_ORDER_KEEP_MAX_BYTES = 16 << 30   # the [N, F*C] rows of a reference-order forward are kept for its backward below this
@@ -916,7 +930,7 @@ def rest_total_term(g: HopGraph, lut: torch.Tensor, use_cnt: bool, total: torch.
 def rho_aggregate(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool,
                   with_rest: Optional[bool] = None, row_ids: Optional[torch.Tensor] = None,
                   s_total: Optional[torch.Tensor] = None, reduce_channels: int = 0,
-                  total_rows: Optional[int] = None, total_group=NOT_SHARED) -> torch.Tensor:
+                  total_rows: Optional[int] = None, total_group=NOT_SHARED, describe: Optional[list] = None) -> torch.Tensor:
     """``Y[q] = sum_j wt(i_q, hop(i_q, j)) * S[j]`` over the hop-coded adjacency ``g``.
 
     ``lut [D, Cw]`` (post-rho / un-normalised: ``rho`` at the D distinct distances) or
@@ -937,6 +951,7 @@ def rho_aggregate(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool
     if row_ids is not None:
         row_ids = row_ids.to(device=g.device, dtype=torch.int32).contiguous()
     if reduce_channels and reduce_channels not in FUSABLE_READOUT:
-        Y = _RhoAggregate.apply(S, lut, g, use_cnt, with_rest, row_ids, s_total, 0, total_rows, total_group)
+        Y = _RhoAggregate.apply(S, lut, g, use_cnt, with_rest, row_ids, s_total, 0, total_rows, total_group, describe)
         return Y.view(Y.shape[0], -1, reduce_channels).sum(dim=1)
-    return _RhoAggregate.apply(S, lut, g, use_cnt, with_rest, row_ids, s_total, reduce_channels, total_rows, total_group)
+    return _RhoAggregate.apply(S, lut, g, use_cnt, with_rest, row_ids, s_total, reduce_channels, total_rows, total_group,
+                               describe)

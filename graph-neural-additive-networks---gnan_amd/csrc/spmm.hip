@@ -1182,14 +1182,13 @@ int launch_shell_lpr(const Params& p, int lpr, bool dense, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------------------------
-template <int VEC, int LPR>
-int launch(const Params& p0, bool dense, bool smalld, hipStream_t st) {
-  constexpr int G = kWave / LPR;
-  const int rows_per_block = 4 * G;
-  Params p = p0;
+// The tile partition of a launch of the <vec, lpr> variant: which of the declared short-row runs the kernel takes in tiles, and where
+// each run's tiles start.  The launch and gnan_spmm_fwd_describe both call this (and nothing else decides it).
+int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld) {
+  const int G = kWave / lpr;
   // short-row tiles: the packed small-D forward over a degree-sorted copy, one pass of the lane group over the columns
-  if (short_tiles_serve(VEC, LPR, smalld, p.packed, p.s_by_code) && p.short_lmax > 0 && !dense && p.scatter_out == 2 &&
-      LPR * VEC >= p.W && p.nnz > 0) {
+  if (short_tiles_serve(vec, lpr, smalld, p.packed, p.s_by_code) && p.short_lmax > 0 && !dense && p.scatter_out == 2 &&
+      lpr * vec >= p.W && p.nnz > 0) {
     int64_t t = 0;
     for (int L = 0; L <= p.short_lmax; ++L) {
       p.short_tile[L] = static_cast<int>(t);
@@ -1203,6 +1202,15 @@ int launch(const Params& p0, bool dense, bool smalld, hipStream_t st) {
   } else {
     p.short_lmax = 0;
   }
+  return GNAN_OK;
+}
+
+template <int VEC, int LPR>
+int launch(const Params& p0, bool dense, bool smalld, hipStream_t st) {
+  constexpr int G = kWave / LPR;
+  const int rows_per_block = 4 * G;
+  Params p = p0;
+  if (int rc = plan_tiles(p, VEC, LPR, dense, smalld)) return rc;
   const int n_slices = p.n_slices;
   const int64_t blocks = dense && n_slices > 0
                              ? n_slices
@@ -2540,6 +2548,61 @@ extern "C" int gnan_spmm_shell_sums(const gnan_spmm_args* a, gnan_stream_t strea
   return vec == 4 ? launch_shell_lpr<4>(p, lpr, dense, st) : launch_shell_lpr<1>(p, lpr, dense, st);
 }
 
+namespace {
+
+// Which kernel variant serves a (validated) forward call: gnan_spmm_fwd launches what this picks, gnan_spmm_fwd_describe reports it.
+struct Route {
+  int vec, lpr;
+  bool dense, smalld, hot;
+};
+
+int pick_route(const gnan_spmm_args* a, Route* r) {
+  r->dense = a->rowptr == nullptr;
+  r->smalld = !r->dense && a->Cw == 1 && a->D <= 4 && !a->weight_by_col && !a->minus_rest;
+  r->hot = false;
+  if (a->reduce_cr) {
+    pick_tiling(a, static_cast<const float*>(a->S), a->s_stride, &r->vec, &r->lpr);  // narrow output: scalar stores
+  } else {
+    pick_tiling(a, a->Y, a->y_stride, &r->vec, &r->lpr);
+  }
+  if (a->s_dtype == GNAN_BF16) {       // (validate(): CSR layout only)
+    r->vec = 8;
+    r->lpr = 1;
+    while (r->lpr * 8 < a->W && r->lpr < kWave) r->lpr <<= 1;
+    return GNAN_OK;
+  }
+  if (a->shell_out != nullptr) {
+    const bool ok = r->smalld && a->W == 1 && a->n_slices == 0 && a->reduce_cr == 0 && !a->s_by_code && a->s_dtype == GNAN_F32 &&
+                    a->hot_rows == 0 && r->vec == 1 && r->lpr == 1;
+    if (!ok)
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: shell_out serves a one-column fp32 operand on the small-D CSR route without hub-row "
+                                              "slices, fused read-out or hot rows");
+  }
+  r->hot = r->smalld && hot_kernel_applies(a);   // narrow rows, hottest operand rows in LDS (persistent workgroups)
+  return GNAN_OK;
+}
+
+}  // namespace
+
+extern "C" int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_info* out) {
+  GNAN_REQUIRE(out != nullptr, "spmm describe: null output");
+  if (int rc = validate(a)) return rc;
+  *out = gnan_spmm_launch_info{};
+  if (a->n_rows == 0) return GNAN_OK;
+  Route r;
+  if (int rc = pick_route(a, &r)) return rc;
+  out->vec = r.vec; out->lpr = r.lpr; out->smalld = r.smalld; out->dense = r.dense;
+  out->kernel = r.hot ? GNAN_SPMM_KERNEL_HOT : GNAN_SPMM_KERNEL_ROWS;
+  if (r.hot) return GNAN_OK;
+  Params p = make_params(a);
+  if (int rc = plan_tiles(p, r.vec, r.lpr, r.dense, r.smalld)) return rc;
+  out->classed = p.cls_index != nullptr;
+  out->n_slice_blocks = p.n_slice_blocks; out->n_tile_blocks = p.n_tile_blocks; out->n_tiles = p.n_tiles;
+  out->row_q0 = p.row_q0;
+  for (int L = 0; L <= GNAN_SHORT_LMAX; ++L) out->short_tile[L] = p.short_tile[L];
+  return GNAN_OK;
+}
+
 extern "C" int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream) {
   if (int rc = validate(a)) return rc;
   if (a->n_rows == 0) return GNAN_OK;
@@ -2547,29 +2610,10 @@ extern "C" int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream) {
   if (need > 0 && (a->workspace == nullptr || a->workspace_bytes < need))
     return gnan::fail(GNAN_ERR_WORKSPACE, "spmm: workspace %zu B < required %zu B", a->workspace_bytes, need);
   const Params p = make_params(a);
-
-  const bool dense = a->rowptr == nullptr;
-  const bool smalld = !dense && a->Cw == 1 && a->D <= 4 && !a->weight_by_col && !a->minus_rest;
-  int vec, lpr;
-  if (a->reduce_cr) {
-    pick_tiling(a, static_cast<const float*>(a->S), a->s_stride, &vec, &lpr);  // narrow output: scalar stores
-  } else {
-    pick_tiling(a, a->Y, a->y_stride, &vec, &lpr);
-  }
+  Route r;
+  if (int rc = pick_route(a, &r)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (a->s_dtype == GNAN_BF16) {
-    lpr = 1;
-    while (lpr * 8 < a->W && lpr < kWave) lpr <<= 1;
-    return launch_lpr<8>(p, lpr, false, smalld, st);
-  }
-  if (a->shell_out != nullptr) {
-    const bool ok = smalld && a->W == 1 && a->n_slices == 0 && a->reduce_cr == 0 && !a->s_by_code && a->s_dtype == GNAN_F32 &&
-                    a->hot_rows == 0 && vec == 1 && lpr == 1;
-    if (!ok)
-      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: shell_out serves a one-column fp32 operand on the small-D CSR route without hub-row "
-                                              "slices, fused read-out or hot rows");
-  }
-  if (smalld && hot_kernel_applies(a))                // narrow rows, hottest operand rows in LDS (persistent workgroups)
-    return a->W == 1 ? launch_hot<1>(p, st) : (a->W == 2 ? launch_hot<2>(p, st) : launch_hot<4>(p, st));
-  return vec == 4 ? launch_lpr<4>(p, lpr, dense, smalld, st) : launch_lpr<1>(p, lpr, dense, smalld, st);
+  if (r.hot) return a->W == 1 ? launch_hot<1>(p, st) : (a->W == 2 ? launch_hot<2>(p, st) : launch_hot<4>(p, st));
+  if (r.vec == 8) return launch_lpr<8>(p, r.lpr, false, r.smalld, st);
+  return r.vec == 4 ? launch_lpr<4>(p, r.lpr, r.dense, r.smalld, st) : launch_lpr<1>(p, r.lpr, r.dense, r.smalld, st);
 }

@@ -26,7 +26,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: exactly the functions declared in this header are exported */
 #pragma GCC visibility push(default)
 
-#define GNAN_ABI_VERSION 48
+#define GNAN_ABI_VERSION 49
 
 typedef void* gnan_stream_t; /* hipStream_t */
 
@@ -410,7 +410,9 @@ int gnan_rho_row_lut(const gnan_rho_lut_args* a, gnan_stream_t stream);
  *   caller (`lut`), never per pair.
  *
  * Adjacency, two layouts:
- *   CSR   : rowptr (int32 or int64, n_rows+1), col int32, code uint8 (hop index < D-1)
+ *   CSR   : rowptr (int32 or int64, n_rows+1), col int32, code uint8 (hop index < D-1).  col and code
+ *           must be non-NULL even when no row lists a pair (nnz == 0: nothing is read through
+ *           them); a NULL col beside a non-NULL rowptr is an error, never the dense layout.
  *   dense : rowptr == col == NULL; code is [n_rows, n_cols] row-major, neighbour j of row i
  *           is column j; code D-1 marks "unreachable" pairs (they still count as listed).
  * row_ids (optional) selects / reorders output rows: output row q aggregates adjacency row
@@ -502,8 +504,9 @@ typedef struct gnan_spmm_args {
    * that row q in [short_row[L], short_row[L + 1]) lists exactly L pairs, L = 0 .. short_lmax, its first pair being
    * short_pair[L] + (q - short_row[L]) L; short_row[0] must be 0.  Both are HOST arrays ([short_lmax + 2], [short_lmax + 1]),
    * read when the call is enqueued.  The library then takes these rows in tiles of many rows per wave (no per-row rowptr load,
-   * the gathers of several rows in flight) where the route serves the call — packed index, small-D weights, fp32 or bf16 rows
-   * covered by one pass of the lane group — and walks them as ordinary rows otherwise.  Same output bits either way.
+   * the gathers of several rows in flight) where the route serves the call — packed index, small-D weights, fp32 rows read
+   * 16 B per lane and covered by one pass of a lane group of 16 lanes or more (W in (32, 256]; bf16 rows are declined) — and walks
+   * them as ordinary rows otherwise: gnan_spmm_fwd_describe says which.  Same output bits either way.
    * short_lmax = 0 (the default): off */
   int32_t short_lmax;            /* 0 .. GNAN_SHORT_LMAX */
   const int64_t* short_row;
@@ -512,6 +515,29 @@ typedef struct gnan_spmm_args {
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
 int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream);
+
+/* How gnan_spmm_fwd would partition the call (ABI 49).  Host only: no GPU work is started and no device memory is read; the
+ * arguments are validated as by gnan_spmm_fwd (the workspace aside) and the launch's own decisions are run — the library has one
+ * copy of them, which the launch and this query both call.  All fields are zero when n_rows == 0 (kernel NONE); the hot-row kernel
+ * has no block partition (the fields below `classed` stay zero). */
+#define GNAN_SPMM_KERNEL_NONE 0
+#define GNAN_SPMM_KERNEL_ROWS 1   /* spmm_kernel: slice blocks, then tile blocks, then row blocks */
+#define GNAN_SPMM_KERNEL_HOT 2    /* spmm_hot_kernel: persistent workgroups, hottest operand rows in LDS */
+typedef struct gnan_spmm_launch_info {
+  int32_t vec;                   /* floats (bf16: elements) a lane reads of an operand row at once: 1, 4 or 8 */
+  int32_t lpr;                   /* lanes per row */
+  int32_t smalld;                /* the small-D weight path (CSR, D <= 4, one weight channel, plain forward weights) */
+  int32_t dense;                 /* dense layout */
+  int32_t kernel;                /* GNAN_SPMM_KERNEL_* */
+  int32_t classed;               /* 1: the hub slices follow the classed hub plan */
+  int32_t n_slice_blocks;        /* workgroups of hub-row slices */
+  int32_t n_tile_blocks;         /* workgroups of short-row tiles (4 tiles each) */
+  int32_t n_tiles;               /* short-row tiles; 0: the declared runs are walked as ordinary rows */
+  int64_t row_q0;                /* first row the row blocks take (rows below it are tiled) */
+  int32_t short_tile[GNAN_SHORT_LMAX + 1];   /* first tile of run L, L = 0 .. short_lmax (when n_tiles > 0) */
+} gnan_spmm_launch_info;
+
+int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_info* out);
 
 /* The degree-sorted copy of a hop-coded CSR, the layout gnan_spmm_fwd walks with scatter_out = 2 (gnan_amd.graph.
  * HopGraph.degree_sorted_copy): order = the rows sorted by their number of listed pairs, ascending, ties by row id (a STABLE

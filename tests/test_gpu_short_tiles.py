@@ -1,6 +1,8 @@
 """Short-row tiles (aggregate.SHORT_ROW_TILES, gnan_spmm_args.short_*): the wide forward over a degree-sorted copy with the rows
 of at most SHORT_ROW_LMAX pairs taken in tiles gives the same bits as the plain row walk — self-only rows, rows without a self
-pair, empty rows, a run of every length up to the longest tiled one, hub rows behind them."""
+pair, empty rows, a run of every length up to the longest tiled one, hub rows behind them.  The launch query says which shapes
+take the tiles at all: fp32 rows of W = 64 and 128 do; W = 32 and bf16 rows are declined and compare the row walk with itself here
+(tests/test_gpu_wide_rows.py holds the per-row bounds and the list of declined shapes)."""
 import numpy as np
 import pytest
 import torch
@@ -38,11 +40,18 @@ def test_short_tiles_give_the_row_walks_bits(lmax, dtype, W, with_rest, reduce_c
     g = _graph(rowptr, col, code, n, 4)
     S = torch.from_numpy(rng.standard_normal((n, W)).astype(np.float32)).to(DEV).to(dtype)
     lut = torch.from_numpy(rng.standard_normal((4, 1)).astype(np.float32)).to(DEV)
-    out = {}
+    out, info = {}, {}
     for tiles in (True, False):
         monkeypatch.setattr(aggregate, "SHORT_ROW_TILES", tiles)
-        out[tiles] = aggregate.spmm_launch(g, S, lut, True, with_rest, reduce_cr=reduce_cr)
+        d = []
+        out[tiles] = aggregate.spmm_launch(g, S, lut, True, with_rest, reduce_cr=reduce_cr, describe=d)
+        info[tiles] = d[0]
     torch.cuda.synchronize()
+    if dtype == torch.float32 and W in (64, 128):
+        assert info[True]["n_tiles"] > 0 and info[True]["row_q0"] > 0
+    else:
+        assert info[True]["n_tiles"] == 0
+    assert info[False]["n_tiles"] == 0
     copy = g.degree_sorted_copy()[0]
     runs = copy.short_row_runs(lmax)
     assert all(runs.rows[L + 1] > runs.rows[L] for L in range(lmax + 1))        # every run is there
