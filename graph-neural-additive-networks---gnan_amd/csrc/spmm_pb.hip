@@ -16,7 +16,9 @@
 //            E[q] = S[col(q)] for the entries of its tiles: 2 B read + 4 W B written per pair, all of it streamed.
 //   phase 2  pb_reduce_kernel:  a workgroup owns ONE row bin: its entries are one contiguous range; every entry is added to
 //            its row's accumulator in LDS with a 64-bit INTEGER atomic (fixed point scaled from max |S|: order-independent,
-//            hence bit-reproducible, and exact to 2^-40 of max |S| — closer to the float64 sum than a float32 chain is);
+//            hence bit-reproducible; every entry truncated to a multiple of q = 2^(e + h - 62) = 2^(h - 61) of max |S| — 2^-40
+//            of it while no row has more than 2^21 entries — so a row's sum is off by at most L q, an ABSOLUTE term: closer to
+//            the float64 sum than a float32 chain where the operand is of one magnitude, and blind below q where it is not);
 //            the epilogue applies the row's weights  sum_d (wt(i,d) - wt(i,rest)) * T[i,d] + wt(i,rest) * total  and stores
 //            the output row: 2 + 4 W B read per pair.
 //

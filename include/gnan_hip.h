@@ -720,8 +720,13 @@ int gnan_pb_plan_fill(const gnan_pb_fill_args* a, gnan_stream_t stream);
  *
  * Y[i, :] = sum_d (wt(i,d) - wt(i,D-1)) * sum_{pairs of row i with code d} S[col, :]  +  wt(i,D-1) * s_total
  * (wt(i,d) = lut[d] / max(cnt[i,d], 1); without s_total the rest weight is zero), i.e. gnan_spmm_fwd's result with the
- * per-code sums exact to 2^-40 of max |S| (integer accumulation: order-independent, bit-reproducible) instead of a
- * float32 chain.  No listed pair costs a memory request of its own: see csrc/spmm_pb.hip.
+ * per-code sums in 64-bit fixed point (integer accumulation: order-independent, bit-reproducible) instead of a float32
+ * chain.  The precision contract: every operand entry is truncated toward zero to a multiple of q = 2^(e + h - 62), e the
+ * frexp exponent of max |S| over the WHOLE operand (listed or not), h = headroom_bits — that is 2^(h - 61) of max |S|, and
+ * 2^-40 of it only while no row receives more than 2^21 entries (h <= 21; h <= 40 is accepted).  The integer sums are exact,
+ * so a row's per-code sum is off by at most L q (L its entries of that code) whatever its own magnitude: the term is
+ * ABSOLUTE, and one outlier anywhere in the operand costs the rows of small values their digits (all of them once they
+ * fall below q).  No listed pair costs a memory request of its own: see csrc/spmm_pb.hip.
  * workspace: gnan_spmm_pb_workspace_bytes(a) bytes, 16-byte aligned (the expanded operand, n_entries * W floats).
  * A non-finite operand value yields NaN in every output row.
  * ------------------------------------------------------------------------------------------- */
@@ -781,7 +786,8 @@ int gnan_spmm_pb_fwd(const gnan_spmm_pb_args* a, gnan_stream_t stream);
  *   dS[j]    = lut[0] * V[0][self].x + lut[d1] * t1 - lut[D-1] * tr  (+ ds_add[0] * ds_add_scale[0])
  *   dlut[d1] = sum_j s_rows[j] * t1[j],  dlut[0] = sum_j s_rows[j] * V[0][self].x,
  *   dlut[D-1] = - sum_j s_rows[j] * tr[j] + rest_total[0] * rest_q[0]        (with_rest; other entries 0)
- * The sums over an operand node's entries are exact to 2^-40 of max |V| (integer accumulation); the table gradient adds
+ * The sums over an operand node's entries carry gnan_spmm_pb_fwd's fixed point (every entry of V[d1] truncated to a multiple
+ * of 2^(e + h - 62), e from max |V[d1]|: an absolute L q per sum; the integer accumulation is exact); the table gradient adds
  * float64 partials per bin in bin order: bit-reproducible.  workspace: gnan_spmm_pb_bwd_workspace_bytes(g), 16-byte aligned. */
 typedef struct gnan_spmm_pb_bwd_args {
   gnan_spmm_pb_args pb;
