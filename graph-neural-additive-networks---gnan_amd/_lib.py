@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNAN_HIP_LIB: development aid for same-box A/B runs of two builds of the library (tools/ab_lib.sh)
 LIB_PATH = os.environ.get("GNAN_HIP_LIB") or os.path.join(_HERE, "libgnan_hip.so")
-ABI_VERSION = 49
+ABI_VERSION = 50
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE = -1, -2, -3, -4      # enum gnan_status
 
 GNAN_F32, GNAN_BF16 = 0, 1
@@ -51,6 +51,7 @@ class FpwlArgs(C.Structure):
         ("sum_workspace", C.c_void_p), ("sum_workspace_bytes", C.c_size_t),
         ("sum_total", C.c_void_p), ("sum_total_workspace", C.c_void_p), ("sum_total_workspace_bytes", C.c_size_t),
         ("sum_total_arrive", C.c_void_p),
+        ("row_sum", C.c_void_p), ("row_keep", C.c_void_p),
     ]
 
 
@@ -127,6 +128,7 @@ class SpmmArgs(C.Structure):
         ("cls_index", C.c_void_p), ("cls_slice_start", C.c_void_p), ("cls_slice_row", C.c_void_p), ("cls_slot_slice", C.c_void_p),
         ("cls_n_slots", C.c_int32),
         ("short_lmax", C.c_int32), ("short_row", C.c_void_p), ("short_pair", C.c_void_p),
+        ("self_sum", C.c_void_p), ("self_parts", C.c_int32),
     ]
 
 
@@ -392,6 +394,7 @@ SYMBOLS = {
     "gnan_rho_row_lut": (C.c_int, [C.POINTER(RhoLutArgs), C.c_void_p]),
     "gnan_fpwl_total_workspace_bytes": (C.c_size_t, [C.POINTER(FpwlArgs)]),
     "gnan_fpwl_sum_workspace_bytes": (C.c_size_t, [C.POINTER(FpwlArgs)]),
+    "gnan_fpwl_row_sum_parts": (C.c_int, [C.POINTER(FpwlArgs)]),
     "gnan_fpwl_fwd": (C.c_int, [C.POINTER(FpwlArgs), C.c_void_p]),
     "gnan_fpwl_index_build": (C.c_int, [C.POINTER(FpwlIndexArgs), C.c_void_p]),
     "gnan_feature_range": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -110,7 +110,8 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
                 row_ids: Optional[torch.Tensor] = None, weight_by_col: bool = False,
                 minus_rest: bool = False, s_total: Optional[torch.Tensor] = None, reduce_cr: int = 0,
                 s_by_code: bool = False, lut_of_counts=None, lut_channels: int = 1, room=None,
-                keep_shell: Optional[list] = None, describe: Optional[list] = None) -> torch.Tensor:
+                keep_shell: Optional[list] = None, describe: Optional[list] = None,
+                self_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One ``gnan_spmm_fwd`` call (no autograd).  ``lut`` is ``[D, Cw]`` or ``[n_adj_rows, D, Cw]``.
     ``reduce_cr`` in FUSABLE_READOUT returns ``[n, reduce_cr]`` = per-channel sums over the operand columns.
     ``s_by_code``: ``S`` is ``[n_cols * D, W]`` and the pair with neighbour ``c`` and hop code ``d`` reads row ``c*D + d``.
@@ -119,7 +120,9 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
     graph that is actually walked, so a degree-sorted copy gets its table in its own row order and nothing is permuted.
     ``describe``: a list that receives the launch partition (``gnan_spmm_fwd_describe`` as a dict: kernel variant, slice / tile /
     row blocks) of the ``gnan_spmm_fwd`` call about to be made; the propagation-blocked narrow route (csrc/spmm_pb.hip) makes no
-    such call and leaves the list as it was."""
+    such call and leaves the list as it was.
+    ``self_sum [parts, n_rows]`` (``g`` lists no self pair; see ``gnan_spmm_args.self_sum``): the rows' self term, added in the
+    fused read-out's epilogue — the library refuses it off the packed degree-sorted route."""
     _lib.require_device(S, lut, g.code)
     whole = row_ids is None                              # (the walks below may bring row_ids of their own)
     S = S.detach()
@@ -208,6 +211,11 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         # rows of the copy's shortest runs in tiles of many rows per wave: same bits as the row walk
         runs = g.short_row_runs(SHORT_ROW_LMAX)
         a.short_lmax, a.short_row, a.short_pair = runs.lmax, runs.row_ptr, runs.pair_ptr
+    if self_sum is not None:
+        _lib.require_device(self_sum)
+        if self_sum.dtype != torch.float32 or self_sum.dim() != 2 or self_sum.shape[1] != n_out or not self_sum.is_contiguous():
+            raise ValueError("self_sum must be a contiguous float32 [parts, n_rows] tensor")
+        a.self_sum, a.self_parts = _lib.ptr(self_sum), int(self_sum.shape[0])
     need = _lib.lib().gnan_spmm_fwd_workspace_bytes(a)
     ws = None
     if need:
@@ -896,6 +904,61 @@ def reference_order_forward(g: HopGraph, x: torch.Tensor, p: StackedMLP, lut: to
     whose backward pass is the sum-first order's (see :class:`_ReferenceOrderAggregate`).  Check :func:`reference_order_applies`."""
     _lib.require_device(x, p.w_last, lut)
     return _ReferenceOrderAggregate.apply(x, lut, g, use_cnt, not g.is_dense, p.L, p.H, p.C, p.F, *p[:6])
+
+
+SELF_FROM_LOOKUP = True               # reference-order inference: the self pair's term from the look-up's row sums, no self gathers
+SELF_FROM_LOOKUP_SKIP_STORES = True   # ... and no store of the operand rows that only their own self pair would read
+SELF_FROM_LOOKUP_MIN_ROWS = DEGREE_SORTED_COPY_MIN_ROWS     # where the degree-sorted copy exists
+
+
+def reference_order_inference_applies(x: torch.Tensor, p: Optional[StackedMLP], lut: torch.Tensor, g: HopGraph,
+                                      operand_dtype=torch.float32) -> bool:
+    """Can :func:`reference_order_inference` take this call?  Inference (grad mode off, or nothing that requires grad) in the
+    reference order with one channel, an fp32 operand the direct-index look-up writes (whole 16-feature groups, aligned rows),
+    a width the short-row tiles serve, a global table, and a CSR large enough for its degree-sorted copy whose every row holds
+    its self pair once under code 0 (``HopGraph.self_free_plan(strict=False)``).  The plan is built by an eager forward: under stream
+    capture a missing plan means the old route."""
+    if not SELF_FROM_LOOKUP or p is None or operand_dtype != torch.float32 or g.is_dense or lut.dim() != 2 or lut.shape[1] != 1:
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or lut.requires_grad or any(t is not None and t.requires_grad for t in p[:6])):
+        return False
+    F = p.F
+    if not (p.C == 1 and p.L >= 2 and F % 16 == 0 and 32 < F <= 256 and x.dim() == 2 and x.shape[1] == F and x.dtype == torch.float32
+            and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and x.shape[0] == g.n_cols == g.n_rows
+            and g.n_rows >= SELF_FROM_LOOKUP_MIN_ROWS and g.n_rows >= DEGREE_SORTED_COPY_MIN_ROWS and g.n_codes <= 4
+            and DEGREE_SORTED_COPY and PACKED_INDEX and g.n_cols <= (1 << 29) and Fn.INDEX_LOOKUP and x.shape[0] >= Fn.INDEX_MIN_NODES):
+        return False
+    if Fn.FMLP_ALGO not in (_lib.FMLP_PWL, _lib.FMLP_AUTO) or (Fn.FMLP_ALGO == _lib.FMLP_AUTO and (
+            x.shape[0] * F < Fn.PWL_MIN_WORK or x.shape[0] < Fn.PWL_MIN_NODES)):
+        return False
+    if g._self_free is None and torch.cuda.is_current_stream_capturing():
+        return False
+    return g.self_free_plan(strict=False) is not None
+
+
+def reference_order_inference(g: HopGraph, x: torch.Tensor, p: StackedMLP, lut: torch.Tensor, use_cnt: bool,
+                              mark=None) -> torch.Tensor:
+    """``Y [N, 1]`` of the reference order at inference without a single self gather: the look-up stores the operand rows the
+    self-free twin of ``g`` lists, hands out every row's feature sum (4 bytes per feature group and node) and the column sums;
+    the aggregation walks the twin and adds ``(w(i, 0) - w_rest(i)) * a_i`` in its read-out's epilogue (``gnan_spmm_args.
+    self_sum``).  The ``[N, F]`` operand never leaves this function: its unlisted rows hold whatever was there and are never
+    read.  ``mark``: called between the two stages.  Check :func:`reference_order_inference_applies`."""
+    _lib.require_device(x, p.w_last, lut, g.code)
+    plan = g.self_free_plan(strict=False)
+    req = Fn.SelfRequest(plan.listed, SELF_FROM_LOOKUP_SKIP_STORES)
+    Fn._SELF_REQUEST = req
+    try:
+        with torch.no_grad():
+            fx, _, total = Fn._fmlp_forward(x, p, False, True)
+    finally:
+        Fn._SELF_REQUEST = None
+    if total is None:
+        total = Fn.column_sums(fx)
+    if mark is not None:
+        mark()
+    if req.row_sum is None:                 # another kernel served the look-up: complete rows, today's aggregation
+        return spmm_launch(g, fx, lut, use_cnt, True, None, s_total=total, reduce_cr=1)
+    return spmm_launch(plan.twin, fx, lut, use_cnt, True, None, s_total=total, reduce_cr=1, self_sum=req.row_sum)
 
 
 def add_rest_total_term(Y: torch.Tensor, g: HopGraph, lut: torch.Tensor, use_cnt: bool, total: torch.Tensor,

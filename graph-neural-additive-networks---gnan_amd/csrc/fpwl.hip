@@ -1522,6 +1522,8 @@ extern "C" int gnan_fpwl_fwd(const gnan_fpwl_args* a, gnan_stream_t stream) {
   }
   if (a->sum_total)
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl: sum_total is written by the group-split direct-index feature sum only");
+  if (a->row_sum || a->row_keep)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl: row_sum / row_keep are served by the direct-index look-up in per-feature rows mode only");
   const size_t lds = static_cast<size_t>(a->max_group_pieces) * (1 + 2 * static_cast<size_t>(table_stride(a->C))) * sizeof(float);
   Params p = base_params(a);
   auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) % 16) == 0; };

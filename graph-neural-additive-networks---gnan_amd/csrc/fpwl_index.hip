@@ -60,6 +60,8 @@ struct IndexParams {
   int64_t total_rows;
   uint8_t* piece_out;
   float* part;             // feature sum, split over the groups: [n_groups][n] partial sums (else NULL: the groups are walked inside the workgroup)
+  float* row_sum;          // SELF instances: [n_groups][n] the node's sum over the group's features (gnan_fpwl_args.row_sum), or NULL
+  const uint32_t* row_keep;  // SELF instances: a bit per node, clear = the node's row is not stored (gnan_fpwl_args.row_keep), or NULL
 };
 
 typedef __attribute__((address_space(3))) const float lds_cfloat;
@@ -77,6 +79,17 @@ __device__ __forceinline__ unsigned bf16_bits(float f) {      // round-to-neares
   const unsigned u = __float_as_uint(f);
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
+
+// v + (the value of lane ^ 1 / lane ^ 2 / the mirrored lane of the 8-lane half row) as DPP operands of the VALU: the row sums of the
+// SELF instances must stay off the LDS pipe, which bounds this kernel (__shfl_xor is a ds_bpermute_b32: three more LDS operations
+// per look-up of four).  After the steps 1 and 2 the four lanes of a quad hold the same bits, so the mirrored lane holds what lane
+// ^ 4 holds: the butterfly's association, bit for bit.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  const int o = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
+  return v + __int_as_float(o);
+}
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141;   // quad_perm:[1,0,3,2], quad_perm:[2,3,0,1], row_half_mirror
 
 using gnan_index::bucket_of;      // (csrc/fpwl_bucket.hpp: ONE definition for the look-up and for the builders)
 
@@ -135,8 +148,11 @@ __global__ __launch_bounds__(256) void index_build_kernel(const int32_t* __restr
 // (KF NaN pairs behind every feature, and NaN as the last piece's "next": the comparisons never see the next feature's
 // anchors) | [tot] (val, slope) pairs | s_off[FG + 1]
 // ---------------------------------------------------------------------------------------------
-template <int FG, bool SUM, bool OUT16, int LOGB, int BS>
+// SELF (per-feature fp32 rows only): the instance that serves gnan_fpwl_args.row_sum / row_keep.  A template parameter, not a
+// run-time branch: the plain rows instance sits at its copy pattern's ceiling and keeps its code, registers and occupancy.
+template <int FG, bool SUM, bool OUT16, int LOGB, int BS, bool SELF = false>
 __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
+  static_assert(!SELF || (!SUM && !OUT16), "row sums and kept rows: per-feature fp32 rows");
   constexpr int KF = 2;                             // NaN pairs behind every feature's run: what the comparisons may read
   static_assert(FG == 16 || FG == 32, "feature groups of 16 (half lines) or 32 (full lines)");
   constexpr int TPN = FG / FPT, B = 1 << LOGB, NODES = BS / TPN;
@@ -211,7 +227,7 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
     }
 
     float ps[FPT] = {0.f, 0.f, 0.f, 0.f};           // column sums of the output (per-feature mode)
-    auto look_up = [&](const int64_t n, const float4 t, const float before) {
+    auto look_up = [&](const int64_t n, const float4 t, const float before, const unsigned keep = 1u) {
       const float xv[FPT] = {t.x, t.y, t.z, t.w};
       int e[FPT];
 #pragma unroll
@@ -288,9 +304,18 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
           r = make_float4(__uint_as_float(b0 << 16), __uint_as_float(b1 << 16), __uint_as_float(b2 << 16),
                           __uint_as_float(b3 << 16));
         } else {
-          *reinterpret_cast<float4*>(p.out + n * p.out_stride + k0 + q * FPT) = r;
+          if (!SELF || keep) *reinterpret_cast<float4*>(p.out + n * p.out_stride + k0 + q * FPT) = r;
         }
         if (n < p.total_rows) { ps[0] += r.x; ps[1] += r.y; ps[2] += r.z; ps[3] += r.w; }
+        if constexpr (SELF) {
+          if (p.row_sum) {                          // (uniform) the SUM instance's association, for every node
+            float acc = ((y[0] + y[1]) + y[2]) + y[3];
+            acc = dpp_add<kDppXor1>(acc);
+            acc = dpp_add<kDppXor2>(acc);
+            if constexpr (TPN == 8) acc = dpp_add<kDppHalfMirror>(acc);
+            if (q == 0) p.row_sum[static_cast<int64_t>(g) * p.n + n] = acc;
+          }
+        }
       }
     };
     // U nodes per thread and round, the x rows of the NEXT round requested before this round's look-ups start: a look-up
@@ -351,17 +376,40 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
       // two-buffer form measured SLOWER here (tools/lookup_ab.py: rows 1.03 -> 1.07 ms, bf16 rows 0.875 -> 0.95 — twice the
       // code per iteration, nothing to gain from more loads in flight)
       float4 cur[U], nxt[U];
+      // SELF: a node's keep bit travels with its row — requested a round ahead, from a clamped address like the row (a load
+      // inside the look-up would wait for the next round's rows, which are requested before it).  No mask: every word reads as set
+      unsigned kcur[U], knxt[U];
+      const uint32_t* kw = SELF && p.row_keep ? p.row_keep : reinterpret_cast<const uint32_t*>(p.x);
+      const unsigned kall = SELF && p.row_keep ? 0u : ~0u;
+      auto keep_word = [&](const int64_t nn) {
+        const int64_t m = nn < n_hi ? nn : n_hi - 1;
+        return (kw[kall ? 0 : m >> 5] | kall) >> (m & 31) & 1u;
+      };
 #pragma unroll
-      for (int u = 0; u < U; ++u) cur[u] = row(xp + u * xstep);
+      for (int u = 0; u < U; ++u) {
+        cur[u] = row(xp + u * xstep);
+        if constexpr (SELF) kcur[u] = keep_word(n_lo + nl + u * NODES);
+      }
       for (int64_t n = n_lo + nl; n < n_hi; n += U * NODES) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) nxt[u] = row(xp + (U + u) * xstep);
+        for (int u = 0; u < U; ++u) {
+          nxt[u] = row(xp + (U + u) * xstep);
+          if constexpr (SELF) knxt[u] = keep_word(n + (U + u) * NODES);
+        }
         xp += U * xstep;
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (n + u * NODES < n_hi) look_up(n + u * NODES, cur[u], 0.f);
+        for (int u = 0; u < U; ++u) {
+          if constexpr (SELF) {
+            if (n + u * NODES < n_hi) look_up(n + u * NODES, cur[u], 0.f, kcur[u]);
+          } else {
+            if (n + u * NODES < n_hi) look_up(n + u * NODES, cur[u], 0.f);
+          }
+        }
 #pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        for (int u = 0; u < U; ++u) {
+          cur[u] = nxt[u];
+          if constexpr (SELF) kcur[u] = knxt[u];
+        }
       }
     }
     if constexpr (!SUM) {
@@ -537,6 +585,11 @@ int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st)
   if (!pl.ok) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_index: arguments outside what the direct-index kernel serves");
   // everything that can be refused is refused BEFORE the first launch (a caller that retries another kernel on an error code —
   // or a capture — must not find a look-up already queued)
+  const bool self = a->row_sum != nullptr || a->row_keep != nullptr;
+  if (self && (a->sum_features || a->out_dtype != GNAN_F32))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_index: row_sum / row_keep are served in per-feature rows mode with fp32 rows only");
+  if (self && ((a->row_sum && reinterpret_cast<uintptr_t>(a->row_sum) % 4 != 0) || (a->row_keep && reinterpret_cast<uintptr_t>(a->row_keep) % 4 != 0)))
+    return gnan::fail(GNAN_ERR_BAD_ARG, "fpwl_index: row_sum / row_keep must be 4-byte aligned");
   if (a->sum_total) {
     if (!pl.split)
       return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_index: sum_total is written by the group-split feature sum only (sum_workspace)");
@@ -561,6 +614,7 @@ int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st)
   p.total_rows = (a->total_rows > 0 && a->total_rows < a->n) ? a->total_rows : a->n;
   p.piece_out = a->piece_out;
   p.part = pl.split ? static_cast<float*>(a->sum_workspace) : nullptr;
+  p.row_sum = a->row_sum; p.row_keep = a->row_keep;
   size_t lds = pl.lds;
   if (col_partial && lds < static_cast<size_t>(pl.bs) * 4 * sizeof(float)) lds = static_cast<size_t>(pl.bs) * 4 * sizeof(float);
   const int64_t bx = (p.n + p.nodes_per_block - 1) / p.nodes_per_block;
@@ -578,6 +632,7 @@ int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st)
   auto by_mode = [&](auto fg_c, auto bs_c, auto lb_c) {
     constexpr int G = decltype(fg_c)::value, S = decltype(bs_c)::value, LB = decltype(lb_c)::value;
     if (a->out_dtype == GNAN_BF16) return go(fpwl_index_kernel<G, false, true, LB, S>);
+    if (self) return go(fpwl_index_kernel<G, false, false, LB, S, true>);
     return a->sum_features ? go(fpwl_index_kernel<G, true, false, LB, S>) : go(fpwl_index_kernel<G, false, false, LB, S>);
   };
   auto by_kf = [&](auto fg_c, auto bs_c) {
@@ -608,6 +663,13 @@ int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st)
     return gnan::check_launch("sum_total_final_kernel");
   }
   return GNAN_OK;
+}
+
+// rows of gnan_fpwl_args.row_sum: the feature groups of the instance that would serve the call (0: none would)
+extern "C" int gnan_fpwl_row_sum_parts(const gnan_fpwl_args* a) {
+  if (!a || a->sum_features || a->out_dtype != GNAN_F32 || a->features_per_group != 16) return 0;
+  const IndexPlan pl = index_plan(a);
+  return pl.ok ? a->F / pl.fg : 0;
 }
 
 // bytes of gnan_fpwl_args.sum_workspace this call would use (0: none): what index_plan's split needs

@@ -497,6 +497,8 @@ extern "C" int gnan_fpwl_rows_fwd(const gnan_fpwl_args* a, const int32_t* piece,
   if (a->n == 0) return GNAN_OK;
   GNAN_REQUIRE(a->val && a->slope && a->out, "fpwl_rows_fwd: null pointer");
   GNAN_REQUIRE(a->out_dtype == GNAN_F32, "fpwl_rows_fwd: fp32 output only");
+  if (a->row_sum || a->row_keep)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_rows_fwd: row_sum / row_keep are served by the direct-index look-up only");
   GNAN_REQUIRE(a->max_pieces >= 1, "fpwl_rows_fwd: max_pieces must be >= 1");
   if (static_cast<int64_t>(a->F) * a->max_pieces * a->C >= (1LL << 32))
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_rows_fwd: tables of F * max_pieces * C >= 2^32 floats");

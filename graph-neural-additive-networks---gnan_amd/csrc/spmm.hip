@@ -69,6 +69,9 @@ struct Params {
   int64_t row_q0;
   int64_t short_row[GNAN_SHORT_LMAX + 2], short_pair[GNAN_SHORT_LMAX + 1];
   int short_tile[GNAN_SHORT_LMAX + 1];
+  // the rows' self term from outside (gnan_spmm_args.self_sum): [self_parts][n_rows] by output row, added in the read-out's epilogue
+  const float* self_sum;
+  int self_parts;
 };
 
 __device__ __forceinline__ int64_t load_rowptr(const Params& p, int64_t i) {
@@ -86,6 +89,13 @@ __device__ __forceinline__ int64_t adj_row(const Params& p, int64_t q) {
 }
 __device__ __forceinline__ int64_t out_row(const Params& p, int64_t q, int64_t i) {
   return p.scatter_out == 2 ? static_cast<int64_t>(p.row_ids[q]) : (p.scatter_out ? i : q);
+}
+
+// a_i of gnan_spmm_args.self_sum for output row o: its parts in part order
+__device__ __forceinline__ float self_term(const Params& p, int64_t o) {
+  float a = p.self_sum[o];
+  for (int k = 1; k < p.self_parts; ++k) a += p.self_sum[k * p.n_rows + o];
+  return a;
 }
 
 template <int VEC>
@@ -295,7 +305,7 @@ __device__ __forceinline__ void load_index_run(const int32_t* col, const uint8_t
 // ---------------------------------------------------------------------------------------------
 // rows kernel: one LPR-lane group per output row
 // ---------------------------------------------------------------------------------------------
-template <int VEC, int LPR, bool DENSE, bool SMALLD, bool BYCODE, bool PACKED = false>
+template <int VEC, int LPR, bool DENSE, bool SMALLD, bool BYCODE, bool PACKED = false, bool SELF = false>
 __device__ __forceinline__ void rows_body(const Params& p, const int64_t block_id) {
   constexpr int G = kWave / LPR;     // groups (rows) per wave
   constexpr int TILE = LPR * VEC;    // operand columns one pass covers
@@ -487,8 +497,12 @@ __device__ __forceinline__ void rows_body(const Params& p, const int64_t block_i
 #pragma unroll
       for (int c = 0; c < 4; ++c) red[c] += __shfl_xor(red[c], off);
     }
-    if (sub == 0)
+    if (sub == 0) {
+      if constexpr (SELF) {   // (validate(): reduce_cr == 1) the self pair's term, its weight folded like a listed one
+        red[0] = fmaf(sw.w[0], self_term(p, out_row(p, q, i)), red[0]);
+      }
       for (int c = 0; c < p.reduce_cr; ++c) p.Y[out_row(p, q, i) * p.y_stride + c] = red[c];
+    }
   }
 }
 
@@ -510,7 +524,7 @@ __host__ __device__ constexpr bool short_tiles_serve(int vec, int lpr, bool smal
 // Rows [qg, qg + R) (those below q_end) of run L, their first pair at e: per row exactly rows_body's arithmetic under SMALLD &&
 // PACKED with one pass over the columns (the launch guarantees LPR VEC >= W and LPR >= 8): the folded weights (w_d - w_rest),
 // fmaf over the row's pairs in order, fmaf(w_rest, tot, acc), then the fused read-out's channel sums and butterfly.
-template <int VEC, int LPR, int L>
+template <int VEC, int LPR, int L, bool SELF>
 __device__ __forceinline__ void short_tile(const Params& p, int64_t qg, int64_t q_end, int64_t e) {
   constexpr int R = short_rows_per_group(L);
   constexpr int NP = R * L;                    // pairs of the group (<= 8 <= LPR: one index entry per lane)
@@ -597,14 +611,19 @@ __device__ __forceinline__ void short_tile(const Params& p, int64_t qg, int64_t 
 #pragma unroll
         for (int c = 0; c < 4; ++c) red[c] += __shfl_xor(red[c], off);
       }
-      if (sub == 0)
+      // the self pair's term (gnan_spmm_args.self_sum; validate(): reduce_cr == 1): row r's folded code-0 weight sits in lane 4 r
+      float w_self = 0.f;
+      if constexpr (SELF) w_self = __shfl(wv[4 * r / LPR], (4 * r) % LPR, LPR);
+      if (sub == 0) {
+        if constexpr (SELF) red[0] = fmaf(w_self, self_term(p, o), red[0]);
         for (int c = 0; c < p.reduce_cr; ++c) p.Y[o * p.y_stride + c] = red[c];
+      }
     }
   }
 }
 
 // Tile t of the launch: find its run (static indices only: a dynamically indexed kernel argument would go to scratch).
-template <int VEC, int LPR>
+template <int VEC, int LPR, bool SELF>
 __device__ __forceinline__ void short_tiles(const Params& p, int t) {
   if (t >= p.n_tiles) return;
   int L = 0;
@@ -621,7 +640,7 @@ __device__ __forceinline__ void short_tiles(const Params& p, int t) {
   case LL: {                                                                                      \
     constexpr int R = short_rows_per_group(LL);                                              \
     const int64_t qg = q0 + (k * G + slot) * R;                                                   \
-    short_tile<VEC, LPR, LL>(p, qg, q1, e0 + (qg - q0) * LL);                                     \
+    short_tile<VEC, LPR, LL, SELF>(p, qg, q1, e0 + (qg - q0) * LL);                                     \
     break;                                                                                        \
   }
   switch (L) {
@@ -776,9 +795,12 @@ __device__ __forceinline__ void slice_body(const Params& p, const int blk) {
 // so the long-latency slices overlap the bulk), the rest take 4*G ordinary rows each.
 // BYCODE (operand row = (neighbour, hop code), the narrow-operand backward) is a template parameter: as a run-time
 // flag its address arithmetic cost the W = 64 kernels 4 VGPRs and the bf16 variant 20 B of scratch (bf16 rows 2.85 -> 3.35 ms).
-template <int VEC, int LPR, bool DENSE, bool SMALLD, bool BYCODE = false, bool PACKED = false>
+// SELF (the route short_tiles_serve describes, reduce_cr == 1): the rows' self term from gnan_spmm_args.self_sum in the read-out's
+// epilogue.  A template parameter like BYCODE: as a run-time branch it cost the W = 32, 128 and 256 variants 12-20 B of scratch.
+template <int VEC, int LPR, bool DENSE, bool SMALLD, bool BYCODE = false, bool PACKED = false, bool SELF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SMALLD && LPR >= 8) ? 8 : 1)))
 void spmm_kernel(const Params p) {
+  static_assert(!SELF || short_tiles_serve(VEC, LPR, SMALLD, PACKED, BYCODE), "the self term: on the route the tiles serve");
   if constexpr (!DENSE) {
     if (static_cast<int>(blockIdx.x) < p.n_slice_blocks) {
       slice_body<VEC, LPR, SMALLD, false, BYCODE, PACKED>(p, static_cast<int>(blockIdx.x));
@@ -786,11 +808,11 @@ void spmm_kernel(const Params p) {
     }
     if constexpr (short_tiles_serve(VEC, LPR, SMALLD, PACKED, BYCODE)) {   // (launch() leaves n_tile_blocks 0 for every other variant)
       if (static_cast<int>(blockIdx.x) < p.n_slice_blocks + p.n_tile_blocks) {
-        short_tiles<VEC, LPR>(p, (static_cast<int>(blockIdx.x) - p.n_slice_blocks) * (blockDim.x / kWave) + threadIdx.x / kWave);
+        short_tiles<VEC, LPR, SELF>(p, (static_cast<int>(blockIdx.x) - p.n_slice_blocks) * (blockDim.x / kWave) + threadIdx.x / kWave);
         return;
       }
     }
-    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED>(p, static_cast<int64_t>(blockIdx.x) - p.n_slice_blocks - p.n_tile_blocks);
+    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED, SELF>(p, static_cast<int64_t>(blockIdx.x) - p.n_slice_blocks - p.n_tile_blocks);
   } else {
     if (p.n_slices > 0) {      // few rows, many neighbours: every row is cut into slices, there are no row blocks
       slice_body<VEC, LPR, SMALLD, true, false>(p, static_cast<int>(blockIdx.x));
@@ -1053,7 +1075,14 @@ __global__ __launch_bounds__(256) void spmm_long_fixup_kernel(const Params p) {
       chan += v;
     }
   }
-  if (p.reduce_cr && lane < p.reduce_cr) p.Y[out_row(p, q, i) * p.y_stride + lane] = chan;
+  if (p.reduce_cr && lane < p.reduce_cr) {
+    if (p.self_sum) {    // (validate(): reduce_cr == 1, one weight channel) the self pair's term, as the rows' epilogue adds it
+      float w = row_weights<1>(p, i, 0, 0).v[0];
+      if (p.s_total) w -= row_weights<1>(p, i, p.D - 1, 0).v[0];
+      chan = fmaf(w, self_term(p, out_row(p, q, i)), chan);
+    }
+    p.Y[out_row(p, q, i) * p.y_stride + lane] = chan;
+  }
 }
 
 constexpr int kHotLdsFloats = 16384;   // 64 KB of hot operand rows per workgroup (the default dynamic-LDS limit): two workgroups per CU
@@ -1230,7 +1259,13 @@ int launch(const Params& p0, bool dense, bool smalld, hipStream_t st) {
   } else if (dense) {
     hipLaunchKernelGGL((spmm_kernel<VEC, LPR, true, false>), grid, block, 0, st, p);
   } else if (smalld) {
-    if (p.packed) {
+    if (p.packed && p.self_sum != nullptr) {
+      if constexpr (short_tiles_serve(VEC, LPR, true, true, false)) {
+        hipLaunchKernelGGL((spmm_kernel<VEC, LPR, false, true, false, true, true>), grid, block, 0, st, p);
+      } else {
+        return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: self_sum is served for fp32 rows read 16 B per lane by 16 lanes or more");
+      }
+    } else if (p.packed) {
       hipLaunchKernelGGL((spmm_kernel<VEC, LPR, false, true, false, true>), grid, block, 0, st, p);
     } else {
       hipLaunchKernelGGL((spmm_kernel<VEC, LPR, false, true>), grid, block, 0, st, p);
@@ -1289,6 +1324,10 @@ int validate(const gnan_spmm_args* a) {
                           a->n_cols > static_cast<int64_t>(kPackMask) + 1))
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: packed index entries need the CSR layout, D <= 4, one weight channel, plain "
                       "forward weights and n_cols <= 2^29");
+  if (a->self_sum && !(a->packed_index && a->scatter_out == 2 && a->s_dtype == GNAN_F32 && a->reduce_cr == 1 && a->lut_row_stride == 0 &&
+                       a->self_parts >= 1 && a->hot_rows == 0 && a->shell_out == nullptr))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: self_sum is served over a packed degree-sorted copy (scatter_out 2) with a global "
+                      "small-D table, fp32 rows and reduce_cr == 1 (self_parts >= 1)");
   if (a->reduce_cr != 0) {
     const int cr = a->reduce_cr;
     if (!(cr == 1 || cr == 2 || cr == 4) || a->W % cr != 0)
@@ -1360,6 +1399,7 @@ Params make_params(const gnan_spmm_args* a) {
   p.cls_n_slots = a->cls_n_slots;
   p.n_slice_blocks = classed ? 8 * ((a->cls_n_slots / 8 + 3) / 4) : p.n_slices;
   const bool runs = a->short_lmax > 0 && a->short_lmax <= GNAN_SHORT_LMAX && a->short_row && a->short_pair;  // (validate() checks them)
+  p.self_sum = a->self_sum; p.self_parts = a->self_sum ? a->self_parts : 0;
   p.short_lmax = runs ? a->short_lmax : 0;
   p.n_tile_blocks = p.n_tiles = 0;
   p.row_q0 = 0;
@@ -2182,6 +2222,7 @@ extern "C" size_t gnan_spmm_lut_grad_workspace_bytes(const gnan_spmm_lut_grad_ar
 
 extern "C" int gnan_spmm_lut_grad(const gnan_spmm_lut_grad_args* g, gnan_stream_t stream) {
   GNAN_REQUIRE(g != nullptr, "lut_grad: null args");
+  GNAN_REQUIRE(g->spmm.self_sum == nullptr, "lut_grad: self_sum is read by gnan_spmm_fwd only");
   const gnan_spmm_args* a = &g->spmm;
   const float* dY = g->dY;
   const int64_t dy_stride = g->dy_stride;
@@ -2465,6 +2506,7 @@ extern "C" size_t gnan_spmm_bwd_narrow_workspace_bytes(const gnan_spmm_bwd_narro
 
 extern "C" int gnan_spmm_bwd_narrow(const gnan_spmm_bwd_narrow_args* g, gnan_stream_t stream) {
   GNAN_REQUIRE(g != nullptr, "bwd_narrow: null args");
+  GNAN_REQUIRE(g->spmm.self_sum == nullptr, "bwd_narrow: self_sum is read by gnan_spmm_fwd only");
   const gnan_spmm_args* a = &g->spmm;
   const float* s_rows = g->s_rows;
   const int64_t s_rows_stride = g->s_rows_stride, ds_stride = g->ds_stride;
@@ -2537,6 +2579,7 @@ extern "C" int gnan_spmm_shell_sums(const gnan_spmm_args* a, gnan_stream_t strea
   if (int rc = validate(a)) return rc;
   GNAN_REQUIRE(a->cls_index == nullptr, "shell_sums: the classed hub plan is read by gnan_spmm_fwd only");
   GNAN_REQUIRE(!a->packed_index, "shell_sums: packed index entries are read by gnan_spmm_fwd only");
+  GNAN_REQUIRE(a->self_sum == nullptr, "shell_sums: self_sum is read by gnan_spmm_fwd only");
   if (a->n_rows == 0) return GNAN_OK;
   GNAN_REQUIRE(!a->weight_by_col, "shell_sums: weight_by_col has no meaning here");
   if (a->s_dtype != GNAN_F32) return gnan::fail(GNAN_ERR_UNSUPPORTED, "shell_sums: fp32 operand rows only (no backward for bf16 storage)");
@@ -2578,6 +2621,9 @@ int pick_route(const gnan_spmm_args* a, Route* r) {
       return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: shell_out serves a one-column fp32 operand on the small-D CSR route without hub-row "
                                               "slices, fused read-out or hot rows");
   }
+  if (a->self_sum != nullptr && !(r->smalld && short_tiles_serve(r->vec, r->lpr, r->smalld, a->packed_index != 0, a->s_by_code != 0)))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: self_sum is served for fp32 rows read 16 B per lane by 16 lanes or more (W in (32, 256], "
+                                            "16-B aligned rows)");
   r->hot = r->smalld && hot_kernel_applies(a);   // narrow rows, hottest operand rows in LDS (persistent workgroups)
   return GNAN_OK;
 }

@@ -182,6 +182,15 @@ def _fpwl_index(a: "_lib.FpwlArgs", x: torch.Tensor, t, x_range: torch.Tensor) -
     return [table, key]
 
 
+class SelfRequest:
+    """What ``aggregate.reference_order_inference`` asks of the per-feature look-up: ``keep`` (in) the bit mask of the rows to
+    store, ``skip_stores`` (in) whether to apply it; ``row_sum`` (out) ``[parts, n]`` the rows' feature sums, or None when the
+    direct-index look-up did not serve the call (the rows are then complete)."""
+
+    def __init__(self, keep: torch.Tensor, skip_stores: bool):
+        self.keep, self.skip_stores, self.row_sum = keep, skip_stores, None
+
+
 LOCATED_KEEP_MAX_BYTES = 2 << 30   # (piece, dx) of a forward are kept for its backward pass while they stay below 2 GiB
 
 
@@ -235,6 +244,15 @@ def _fpwl_launch(x: torch.Tensor, t, sum_features: bool, want_total: bool = Fals
         a.index_table, a.index_key, a.index_buckets = _lib.ptr(index[0]), _lib.ptr(index[1]), int(index[0].shape[1])
     else:
         index_keep = _fpwl_index(a, x, t, x_range)      # noqa: F841  (alive until the look-up is queued)
+    req = _SELF_REQUEST
+    if req is not None and not sum_features and out_dtype == torch.float32 and a.index_table and n > 0:
+        # the reference-order inference route (aggregate.reference_order_inference): the rows' feature sums out of the same pass,
+        # and no store for the rows the self-free graph does not list (gnan_fpwl_args.row_sum / row_keep)
+        parts = int(_lib.lib().gnan_fpwl_row_sum_parts(a))
+        if parts > 0 and req.keep.numel() * 32 >= n:
+            req.row_sum = torch.empty((parts, n), dtype=torch.float32, device=x.device)
+            a.row_sum = _lib.ptr(req.row_sum)
+            a.row_keep = _lib.ptr(req.keep) if req.skip_stores else None
     sum_ws = None
     if sum_features and a.index_table:
         # a medium batch with several feature groups: a workgroup per (node block, group), partial sums added in group order
@@ -276,6 +294,7 @@ def _fpwl_launch(x: torch.Tensor, t, sum_features: bool, want_total: bool = Fals
     return (out, total) if want_total else out
 
 
+_SELF_REQUEST = None          # SelfRequest while aggregate.reference_order_inference runs its look-up
 _OUT_BUFFER = None            # feature_mlps(out=...): where the table look-up stores its result instead of a fresh tensor
 _ROOM_REQUEST = 0             # rows of room feature_mlps(room_rows=...) asks the table look-up to leave behind its [n, C] result
 _ROOM_RESULT = None           # (data_ptr of the result, the larger buffer it heads) of the last look-up that did

@@ -100,6 +100,14 @@ class ClassedHubPlan(LongRowPlan):
     n_slots: int = 0
 
 
+@dataclass
+class SelfFreePlan:
+    """:meth:`HopGraph.self_free_plan`: the graph without its rows' self pairs, and which nodes its remaining pairs list."""
+    twin: "HopGraph"              # same rows, the pair (i, i, code 0) removed from every row; ``cnt`` IS the graph's tensor
+    listed: torch.Tensor          # int32 [ceil(n_cols / 32)] holding uint32 words: bit j & 31 of word j >> 5 <=> a pair of twin lists j
+    strict: bool = True           # no row lists itself under another code (``self_free_plan(strict=True)`` gives the same plan)
+
+
 class ShortRowRuns:
     """:meth:`HopGraph.short_row_runs`: run boundaries as the host arrays ``gnan_spmm_args.short_row / short_pair`` point to."""
 
@@ -134,6 +142,7 @@ class HopGraph:
     _inv_rest: Optional[torch.Tensor] = field(default=None, repr=False)
     _pb_plans: dict = field(default_factory=dict, repr=False)       # pb_plan(): operand width -> PbPlan or None
     _cnt_by_col: bool = field(default=False, repr=False)     # transposed graphs: ``cnt`` rows belong to the neighbours
+    _self_free: Optional[tuple] = field(default=None, repr=False)     # self_free_plan(): (the lenient SelfFreePlan or None,)
 
     @property
     def is_dense(self) -> bool:
@@ -645,6 +654,49 @@ class HopGraph:
         if self._inv_rest is None:
             self._inv_rest = 1.0 / self.cnt[:, self.n_codes - 1:self.n_codes].clamp_min(1).float()
         return self._inv_rest
+
+    def self_free_plan(self, strict: bool = True) -> Optional["SelfFreePlan"]:
+        """The self-free twin of a hop-coded CSR and the mask of the nodes it lists, or ``None`` unless EVERY row ``i`` holds
+        exactly one pair with column ``i`` and that pair has code 0 (a row listing itself under another code, twice, or not at
+        all: ``None``).  ``twin`` is this graph with that pair removed from every row — same ``n_codes`` and the SAME ``cnt``
+        tensor, so shell sizes still count the self pair and every weight stays what it was; ``listed`` has a bit per node, set
+        iff some pair of ``twin`` has that column.  The reference-order inference route (``aggregate.reference_order_inference``)
+        takes the self pair's term from the look-up's row sums instead of gathering it, and never stores an operand row whose
+        bit is clear.  Pure index work wherever the tensors live; once per graph, cached.
+
+        ``strict=False`` asks for one pair ``(i, i, code 0)`` per row only: a row may list itself AGAIN under another code — an
+        edge list with self loops gives such rows (R-MAT draws a loop about once in 10^5 edges; ``synthetic.hop1_csr`` codes it
+        1 beside the row's own code-0 pair).  Those pairs stay in the twin as the ordinary pairs they are, node ``i`` counts as
+        listed, and nothing else differs.  The route asks this way: one such row would otherwise cost a whole graph its plan."""
+        if self._self_free is None:
+            self._self_free = (self._build_self_free_plan(),)
+        plan = self._self_free[0]                               # (one build serves both: the strict plan is the lenient one, or none)
+        return plan if (plan is None or not strict or plan.strict) else None
+
+    def _build_self_free_plan(self) -> Optional["SelfFreePlan"]:
+        n = self.n_rows
+        if self.is_dense or self._cnt_by_col or n > self.n_cols or n >= 2 ** 31 or self.nnz < n:
+            return None
+        dev = self.device
+        rp = self.rowptr.long()
+        row_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), rp[1:] - rp[:-1])
+        own = self.col == row_of                                # the pairs (i, i, any code)
+        at = torch.nonzero(own & (self.code == 0)).view(-1)     # ... under code 0, ascending: by row
+        if at.numel() != n or not torch.equal(row_of[at], torch.arange(n, dtype=torch.int32, device=dev)):
+            return None                                         # some row without its code-0 self pair, or with several
+        clean = int(own.sum()) == n                             # no row lists itself under another code
+        keep = torch.ones(self.nnz, dtype=torch.bool, device=dev)
+        keep[at] = False
+        del row_of
+        col_t, code_t = self.col[keep].contiguous(), self.code[keep].contiguous()
+        rowptr_t = (rp - torch.arange(n + 1, dtype=torch.int64, device=dev)).to(self.rowptr.dtype)
+        twin = HopGraph(n_rows=n, n_cols=self.n_cols, n_codes=self.n_codes, code=code_t, cnt=self.cnt, rowptr=rowptr_t, col=col_t)
+        words = (self.n_cols + 31) // 32
+        bits = torch.zeros(words * 32, dtype=torch.bool, device=dev)
+        bits[col_t.long()] = True
+        w = (bits.view(words, 32).long() << torch.arange(32, dtype=torch.int64, device=dev)).sum(1)
+        listed = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()      # (the uint32 words' bits)
+        return SelfFreePlan(twin, listed, clean)
 
     def short_row_runs(self, lmax: int) -> "ShortRowRuns":
         """Runs of rows of exactly ``L = 0 .. lmax`` listed pairs of a degree-sorted copy (rows shortest first): row ``q`` in

@@ -739,6 +739,13 @@ class TensorGNAN(_PathBase):
                 self._mark("fmlp")
                 self._mark("spmm")
                 return Y if not self.is_graph_task else graph_readout(Y)
+            from .aggregate import reference_order_inference, reference_order_inference_applies
+            if reference_order_inference_applies(x, stacked, lut, g, self.operand_dtype):
+                # inference at scale: the self pair's term from the look-up's row sums — no self gathers, no stores of rows
+                # that only their own self pair would read
+                Y = reference_order_inference(g, x, stacked, lut, use_cnt, mark=lambda: self._mark("fmlp"))
+                self._mark("spmm")
+                return Y if not self.is_graph_task else graph_readout(Y)
             fx, total = self._operand(x, "fs", self.fs, False, rest, pad_ok=True,
                                       out_dtype=self.operand_dtype)                   # [N, F*C] (+ zero columns when C == 1)
             self._mark("fmlp")

@@ -26,7 +26,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: exactly the functions declared in this header are exported */
 #pragma GCC visibility push(default)
 
-#define GNAN_ABI_VERSION 49
+#define GNAN_ABI_VERSION 50
 
 typedef void* gnan_stream_t; /* hipStream_t */
 
@@ -188,6 +188,13 @@ typedef struct gnan_fpwl_args {
   size_t sum_total_workspace_bytes; /* workgroup, fixed order) — the rest bucket's operand without a gnan_colsum over the result;   */
                                /* workspace: ceil(n / 256) * 8 bytes, 8-byte aligned                                              */
   uint32_t* sum_total_arrive;  /* optional arrival counter (see gnan_moment_scales_args): sum_total out of the group-sum launch      */
+  /* ABI 50, both optional and served by the direct-index look-up in per-feature rows mode only (!sum_features, fp32 out, C == 1):
+   * every other kernel or mode returns GNAN_ERR_UNSUPPORTED before its first launch when one of them is set */
+  float* row_sum;              /* [gnan_fpwl_row_sum_parts()][n]: row_sum[g][i] = the sum of node i's values over feature group g — per  */
+                               /* thread ((y0 + y1) + y2) + y3, then a butterfly over the node's lanes (offsets 1, 2, 4), the feature-sum */
+                               /* mode's association — for EVERY node, kept or not                                                        */
+  const uint32_t* row_keep;    /* [ceil(n / 32)] bit i & 31 of word i >> 5 clear: node i's row of `out` is NOT stored (its memory is left  */
+                               /* as it was); `total` and row_sum take the node all the same                                               */
 } gnan_fpwl_args;
 
 /* gnan_fpwl_args.flags (the library reads no environment variables: switches are the caller's, passed per call) */
@@ -201,6 +208,7 @@ enum gnan_fpwl_flags {
 size_t gnan_fpwl_total_workspace_bytes(const gnan_fpwl_args* a);
 size_t gnan_fpwl_sum_workspace_bytes(const gnan_fpwl_args* a);   /* 0: the call would not use one */
 int gnan_fpwl_fwd(const gnan_fpwl_args* a, gnan_stream_t stream);
+int gnan_fpwl_row_sum_parts(const gnan_fpwl_args* a);           /* F / (the group width the look-up picks): rows of row_sum; 0: not served */
 
 /* Direct-index acceleration of the one-channel look-up (csrc/fpwl_index.hip; no counterpart in the reference, whose
  * GNAN.py:57-62 evaluates the MLPs).  Per feature a uniform grid of `buckets` cells over [range[k][0], range[k][1]] —
@@ -511,6 +519,14 @@ typedef struct gnan_spmm_args {
   int32_t short_lmax;            /* 0 .. GNAN_SHORT_LMAX */
   const int64_t* short_row;
   const int64_t* short_pair;
+  /* the rows' self term from outside (ABI 50; gnan_spmm_fwd only, optional): the adjacency lists NO self pair, and output row i gets
+   *   Y[i] = fmaf(wt(i, 0) - wt(i, D-1), a_i, Y[i]),   a_i = (self_sum[0][i] + self_sum[1][i]) + ...  in part order
+   * after its fused read-out's butterfly (wt(i, D-1) counts as 0 without s_total) — what the pair (i, i, code 0) would have added
+   * when a_i is the sum of operand row i.  self_sum is [self_parts][n_rows], indexed by the row's OWN id (row_ids[q] under the sorted
+   * copy).  Served on one route: packed degree-sorted copy (scatter_out 2), small-D weights from a global table, fp32 rows,
+   * reduce_cr == 1; GNAN_ERR_UNSUPPORTED otherwise.  The launch partition does not depend on it */
+  const float* self_sum;
+  int32_t self_parts;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
