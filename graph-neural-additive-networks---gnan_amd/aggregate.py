@@ -1,12 +1,16 @@
 """The rho(distance)-weighted, shell-normalised neighbourhood sum (GNAN.py:65-73 / models.py:368-376) and its backward pass:
 launch wrappers of ``csrc/spmm.hip`` (``spmm_launch``, ``shell_sums_launch``, ``lut_grad_launch``, ``bwd_narrow_launch``,
 ``pack_bwd_rows``), the dispatch between them (thresholds below), and the autograd nodes ``rho_aggregate`` /
-``pre_rho_aggregate`` / ``reference_order_forward`` are built from.  Shape functions live in ``functional``; the two meet
-in ``modules``.
+``pre_rho_aggregate`` / ``reference_order_forward`` are built from.  A forward describes itself to the backward pass in one
+frozen record, :class:`AggregateCall` (the shell sums a one-column forward kept travel in it as :class:`KeptSums`, tagged
+with the route that wrote them); ``_aggregate_backward`` dispatches on it.  Shape functions live in ``functional``; the two
+meet in ``modules``.
 """
 from __future__ import annotations
 
-from typing import Optional
+import functools
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -60,10 +64,14 @@ def _spmm_args(g: HopGraph, S, lut, use_cnt, s_total, out, row_ids, per_row_lut,
         # 1.04 -> 0.91 ms; the 111M-node graph: 20.1 -> 20.7 ms, so not there)
         W = S.shape[1]
         head = min(int(hot_rows), HOT_LDS_FLOATS // max(W, 1))
-        share = (getattr(g, "_hot_head_share", None) or {}).get(head, 0.0)
-        if share >= HOT_LDS_MIN_SHARE:
+        if _hot_head_in_lds(g, head):
             a.hot_lo, a.hot_rows = g.n_cols - int(hot_rows), head
     return a
+
+
+def _hot_head_in_lds(g: HopGraph, head: int) -> bool:
+    """Do the first ``head`` rows of the appended hot copy receive enough of the pairs to be served from LDS?"""
+    return g.hot_head_share(head) >= HOT_LDS_MIN_SHARE
 
 
 FUSABLE_READOUT = (1, 2, 4)   # channel counts the aggregation kernel can sum over features in its epilogue
@@ -106,6 +114,24 @@ def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Op
     return ext
 
 
+def _rest_total(S: torch.Tensor, with_rest: bool, s_total: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The rest bucket's total a launch hands to the library: the caller's, else the column sums of ``S``; None without a rest bucket."""
+    if not with_rest:
+        return None
+    return Fn.column_sums(S) if s_total is None else s_total
+
+
+def _wide_walk(g: HopGraph, row_ids: Optional[torch.Tensor], W: int, sorted_copy: bool = True):
+    """``(graph to walk, processing order, hub-row plan, scatter_out)`` of a CSR aggregation that is not narrow: every row of a
+    wide operand (``W >= DEGREE_SCHEDULE_MIN_WIDTH``) by degree — through the degree-sorted copy where the caller's table allows
+    it (``sorted_copy``) and the graph is large enough, else through the degree schedule — and the natural order otherwise."""
+    if row_ids is None and W >= DEGREE_SCHEDULE_MIN_WIDTH and g.n_rows > 1:
+        if DEGREE_SORTED_COPY and sorted_copy and g.n_rows >= DEGREE_SORTED_COPY_MIN_ROWS:
+            return (*g.degree_sorted_copy(), 2)      # walk a degree-sorted copy of the CSR, store rows at their own index
+        return (g, *g.degree_schedule(), True)       # process rows by degree, store them in place
+    return g, row_ids, g.long_row_plan(row_ids), False
+
+
 def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_cnt: bool, with_rest: bool,
                 row_ids: Optional[torch.Tensor] = None, weight_by_col: bool = False,
                 minus_rest: bool = False, s_total: Optional[torch.Tensor] = None, reduce_cr: int = 0,
@@ -146,17 +172,14 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         raise ValueError("operand width must be a multiple of the weight-channel count")
     n_out = g.n_rows if row_ids is None else int(row_ids.numel())
     out = torch.empty((n_out, reduce_cr if reduce_cr else S.shape[1]), dtype=torch.float32, device=S.device)
-    if with_rest and s_total is None:
-        s_total = Fn.column_sums(S)
-    if not with_rest:
-        s_total = None
+    s_total = _rest_total(S, with_rest, s_total)
     scatter = False
     short = False
     n_hot = 0
     narrow = S.shape[1] * S.element_size() <= 8        # one or two lanes per row: see LONG_ROW_THRESHOLD_NARROW
-    if (PB_NARROW and not g.is_dense and row_ids is None and S.dtype == torch.float32 and S.shape[1] in PB_WIDTHS and not per_row
-            and not from_counts and lut_shape[1] == 1 and lut_shape[0] <= 4 and not weight_by_col and not minus_rest
-            and not s_by_code and reduce_cr == 0 and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ and not g._cnt_by_col):
+    if (_pb_takes(g, lut_shape[0]) and row_ids is None and S.dtype == torch.float32 and S.shape[1] in PB_WIDTHS and not per_row
+            and not from_counts and lut_shape[1] == 1 and not weight_by_col and not minus_rest and not s_by_code
+            and reduce_cr == 0 and not g._cnt_by_col):
         # narrow rows of a large graph: no per-pair gather at all — bucketed pairs, operand blocks and accumulators in LDS
         # (csrc/spmm_pb.hip; 10M-node R-MAT, W = 1: 0.87 ms of spmm_hot_kernel -> see DESIGN.md section 4.1c)
         pb = g.pb_plan(S.shape[1])
@@ -165,7 +188,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
             if keep_shell is not None and PB_BACKWARD_ONE_COLUMN and S.shape[1] == 1 and pb.n_acc == 1:
                 # a training forward keeps the rows' raw shell sums (4 bytes per row): its backward then needs no second column
                 shell = torch.empty(g.n_rows, dtype=torch.float32, device=S.device)
-                keep_shell.append(shell)
+                keep_shell.append(KeptSums("pb", shell))
             return pb_launch(g, pb, S, lut, use_cnt, s_total, out, shell_out=shell)
     if g.is_dense:
         # one lane group per row fills the chip only with >~ 16k rows; below that every row is sliced over workgroups
@@ -182,18 +205,13 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
             S = append_hot_rows(S, hot, g.n_codes if s_by_code else 1, room=room)
             n_hot = 0 if s_by_code else int(hot.numel())
         scatter = 2
-    elif row_ids is None and S.shape[1] >= DEGREE_SCHEDULE_MIN_WIDTH and g.n_rows > 1:
+    elif narrow and row_ids is None:
+        plan = g.narrow_row_plan()
+    else:
         # (a table indexed by COLUMN — the wide backward's per-node weights — does not care in which order the rows are walked)
         by_col_table = per_row and weight_by_col and not use_cnt
-        if DEGREE_SORTED_COPY and (by_col_table or (not per_row and not weight_by_col)) and g.n_rows >= DEGREE_SORTED_COPY_MIN_ROWS:
-            g, row_ids, plan = g.degree_sorted_copy()   # walk a degree-sorted copy of the CSR, store rows at their own index
-            scatter = 2
-            short = SHORT_ROW_TILES and not per_row and not weight_by_col
-        else:
-            row_ids, plan = g.degree_schedule()      # process rows by degree, store them in place
-            scatter = True
-    else:
-        plan = g.narrow_row_plan() if (narrow and row_ids is None) else g.long_row_plan(row_ids)
+        g, row_ids, plan, scatter = _wide_walk(g, row_ids, S.shape[1], by_col_table or (not per_row and not weight_by_col))
+        short = scatter == 2 and SHORT_ROW_TILES and not per_row and not weight_by_col
     if (XCD_CLASSED_HUBS and plan is not None and not g.is_dense and S.shape[1] * S.element_size() >= CLASSED_MIN_ROW_BYTES
             and g.nnz >= CLASSED_MIN_NNZ and not weight_by_col and not minus_rest and not s_by_code and not g._cnt_by_col
             and n_hot == 0):
@@ -228,7 +246,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         # over rows plus one gather of pre-weighted numbers (rows_bwd1_launch) instead of two numbers per row over the transposed pairs
         shell = torch.empty((n_out, lut_shape[0] - 1), dtype=torch.float32, device=S.device)
         a.shell_out = _lib.ptr(shell)
-        keep_shell.append(shell)
+        keep_shell.append(KeptSums("rows", shell))
     if describe is not None:
         info = _lib.SpmmLaunchInfo()
         _lib.check(_lib.lib().gnan_spmm_fwd_describe(a, info), "gnan_spmm_fwd_describe")
@@ -287,6 +305,22 @@ PB_MIN_NNZ = 1 << 23        # below, the row-parallel kernel's gathers stay in L
 PB_MAX_NNZ = 1 << 29        # above, building the bucketed copy (a sort of the pairs, ~80 B of temporaries per pair) is not attempted
 
 
+def _pb_takes(g: HopGraph, D: int) -> bool:
+    """Can the propagation-blocked kernels take this graph with a table of ``D`` codes?  (Each route adds its own conditions.)"""
+    return PB_NARROW and not g.is_dense and D <= 4 and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ
+
+
+def _pb_args(g: HopGraph, pb, **fields) -> _lib.SpmmPbArgs:
+    """``gnan_spmm_pb_args`` over the bucketed copy ``pb`` of ``g``: the plan's fields, and ``fields`` for what the call adds."""
+    return _lib.SpmmPbArgs(n_rows=g.n_rows, n_cols=g.n_cols, n_entries=pb.n_entries, src=_lib.ptr(pb.src), dst=_lib.ptr(pb.dst),
+                           cb_width=pb.cb_width, n_cblocks=pb.n_cblocks, chunk_q=_lib.ptr(pb.chunk_q),
+                           cb_chunk_ptr=_lib.ptr(pb.cb_chunk_ptr), n_bins=pb.n_bins, acc_per_bin=pb.acc_per_bin,
+                           bin_order=_lib.ptr(pb.bin_order), bin_entry_ptr=_lib.ptr(pb.bin_entry_ptr),
+                           bin_row_ptr=_lib.ptr(pb.bin_row_ptr), slot_ptr=_lib.ptr(pb.slot_ptr), n_acc=pb.n_acc,
+                           code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits,
+                           self_is_row=int(pb.self_is_row), **fields)
+
+
 def pb_launch(g: HopGraph, pb, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool, s_total: Optional[torch.Tensor],
               out: Optional[torch.Tensor] = None, shell_out: Optional[torch.Tensor] = None, S_self: Optional[torch.Tensor] = None,
               out_add=None) -> torch.Tensor:
@@ -300,14 +334,9 @@ def pb_launch(g: HopGraph, pb, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool
     lut = lut.detach().float().reshape(-1).contiguous()
     if out is None:
         out = torch.empty((g.n_rows, W), dtype=torch.float32, device=S.device)
-    a = _lib.SpmmPbArgs(n_rows=g.n_rows, n_cols=g.n_cols, S=_lib.ptr(S), s_stride=W, W=W, D=int(lut.numel()), lut=_lib.ptr(lut),
-                        cnt=_lib.ptr(g.cnt) if use_cnt else None, cnt_stride=g.cnt.stride(0), s_total=_lib.ptr(s_total),
-                        Y=_lib.ptr(out), y_stride=out.stride(0), n_entries=pb.n_entries, src=_lib.ptr(pb.src), dst=_lib.ptr(pb.dst),
-                        cb_width=pb.cb_width, n_cblocks=pb.n_cblocks, chunk_q=_lib.ptr(pb.chunk_q),
-                        cb_chunk_ptr=_lib.ptr(pb.cb_chunk_ptr), n_bins=pb.n_bins, acc_per_bin=pb.acc_per_bin,
-                        bin_order=_lib.ptr(pb.bin_order), bin_entry_ptr=_lib.ptr(pb.bin_entry_ptr),
-                        bin_row_ptr=_lib.ptr(pb.bin_row_ptr), slot_ptr=_lib.ptr(pb.slot_ptr), n_acc=pb.n_acc,
-                        code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits, self_is_row=int(pb.self_is_row))
+    a = _pb_args(g, pb, S=_lib.ptr(S), s_stride=W, W=W, D=int(lut.numel()), lut=_lib.ptr(lut),
+                 cnt=_lib.ptr(g.cnt) if use_cnt else None, cnt_stride=g.cnt.stride(0), s_total=_lib.ptr(s_total),
+                 Y=_lib.ptr(out), y_stride=out.stride(0))
     if shell_out is not None:
         a.shell_out = _lib.ptr(shell_out)
     if S_self is not None:
@@ -327,8 +356,7 @@ PB_BACKWARD_ONE_COLUMN = True   # the one-column backward from the forward's kep
 def pb_bwd1_applies(g: HopGraph, W: int, D: int, with_rest: bool, add_to_rows: bool, shell):
     """``(forward plan, transposed W = 1 plan)`` when the one-column backward can run WITHOUT the packed second column
     (``gnan_spmm_pb_pack1`` + ``gnan_spmm_pb_fwd`` over the transposed adjacency), else None."""
-    if not (PB_NARROW and PB_BACKWARD_ONE_COLUMN and shell is not None and W == 1 and not g.is_dense and D <= 4
-            and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ and (add_to_rows or not with_rest)):
+    if not (_pb_takes(g, D) and PB_BACKWARD_ONE_COLUMN and shell is not None and W == 1 and (add_to_rows or not with_rest)):
         return None
     fwd = g.pb_plan(1)
     if fwd is None or fwd.n_acc != 1 or fwd.code_base < 1:
@@ -372,7 +400,7 @@ def pb_bwd1_launch(g: HopGraph, plans, dY: torch.Tensor, S: torch.Tensor, shell:
 
 def pb_bwd_applies(g: HopGraph, W: int, D: int):
     """The transposed graph's bucketed copy when the ONE-column backward can take the propagation-blocked route, else None."""
-    if not (PB_NARROW and W == 1 and not g.is_dense and D <= 4 and PB_MIN_NNZ <= g.nnz <= PB_MAX_NNZ):
+    if not (_pb_takes(g, D) and W == 1):
         return None
     pb = g.transposed().pb_plan(2)
     return pb if (pb is not None and pb.n_acc == 1) else None
@@ -393,13 +421,7 @@ def pb_bwd_launch(gt: HopGraph, pb, V: torch.Tensor, S_rows: torch.Tensor, lut: 
     dS = torch.empty((gt.n_rows, 1), dtype=torch.float32, device=V.device)
     dlut = torch.empty(D, dtype=torch.float32, device=V.device)
     block = V[pb.code_base]
-    a = _lib.SpmmPbArgs(n_rows=gt.n_rows, n_cols=gt.n_cols, S=_lib.ptr(block), s_stride=2, W=2, D=D, lut=_lib.ptr(lut),
-                        cnt=None, cnt_stride=0, s_total=None, Y=None, y_stride=0, n_entries=pb.n_entries, src=_lib.ptr(pb.src),
-                        dst=_lib.ptr(pb.dst), cb_width=pb.cb_width, n_cblocks=pb.n_cblocks, chunk_q=_lib.ptr(pb.chunk_q),
-                        cb_chunk_ptr=_lib.ptr(pb.cb_chunk_ptr), n_bins=pb.n_bins, acc_per_bin=pb.acc_per_bin,
-                        bin_order=_lib.ptr(pb.bin_order), bin_entry_ptr=_lib.ptr(pb.bin_entry_ptr),
-                        bin_row_ptr=_lib.ptr(pb.bin_row_ptr), slot_ptr=_lib.ptr(pb.slot_ptr), n_acc=pb.n_acc,
-                        code_base=pb.code_base, self_col=_lib.ptr(pb.self_col), headroom_bits=pb.headroom_bits, self_is_row=int(pb.self_is_row))
+    a = _pb_args(gt, pb, S=_lib.ptr(block), s_stride=2, W=2, D=D, lut=_lib.ptr(lut))      # (no counts, total or Y: all NULL)
     ga = _lib.SpmmPbBwdArgs(pb=a, v_self=_lib.ptr(V[0]) if pb.code_base else None, s_rows=_lib.ptr(S_rows),
                             s_rows_stride=S_rows.stride(0), with_rest=int(with_rest), dS=_lib.ptr(dS), ds_stride=dS.stride(0),
                             dlut=_lib.ptr(dlut))
@@ -431,10 +453,7 @@ def shell_sums_launch(g: HopGraph, S: torch.Tensor, lut_like: torch.Tensor, with
     n_out = g.n_rows if row_ids is None else int(row_ids.numel())
     D = g.n_codes
     T = torch.zeros((n_out, D, S.shape[1]), dtype=torch.float32, device=S.device)
-    if with_rest and s_total is None:
-        s_total = Fn.column_sums(S)
-    if not with_rest:
-        s_total = None
+    s_total = _rest_total(S, with_rest, s_total)
     lut = lut_like.detach().float().contiguous()
     a = _spmm_args(g, S, lut, False, s_total, T.view(n_out, -1), row_ids, lut.dim() == 3)
     _lib.check(_lib.lib().gnan_spmm_shell_sums(a, _lib.stream_of(S)), "gnan_spmm_shell_sums")
@@ -449,22 +468,11 @@ def lut_grad_launch(g: HopGraph, S: torch.Tensor, dY: torch.Tensor, D: int, use_
     S = Fn._rows(S)
     dY = dY.detach().float().contiguous()
     n_out = g.n_rows if row_ids is None else int(row_ids.numel())
-    if with_rest and s_total is None:
-        s_total = Fn.column_sums(S)
-    if not with_rest:
-        s_total = None
-    scatter = False
+    s_total = _rest_total(S, with_rest, s_total)
     if g.is_dense:
-        plan = None                              # dense_lut_grad_kernel: one wave per row, no schedule, every output written
-    elif row_ids is None and S.shape[1] >= DEGREE_SCHEDULE_MIN_WIDTH and g.n_rows > 1:
-        if DEGREE_SORTED_COPY and not g.is_dense and g.n_rows >= DEGREE_SORTED_COPY_MIN_ROWS:
-            g, row_ids, plan = g.degree_sorted_copy()   # as the forward: adjacent index ranges for neighbouring lane groups
-            scatter = 2
-        else:
-            row_ids, plan = g.degree_schedule()
-            scatter = True
+        plan, scatter = None, False              # dense_lut_grad_kernel: one wave per row, no schedule, every output written
     else:
-        plan = g.long_row_plan(row_ids)
+        g, row_ids, plan, scatter = _wide_walk(g, row_ids, S.shape[1])   # as the forward: adjacent index ranges for neighbouring lane groups
     out = (torch.empty if g.is_dense else torch.zeros)((D,) if reduce_rows else (n_out, D), dtype=torch.float32, device=S.device)
     lut_like = torch.empty((D, 1), dtype=torch.float32, device=S.device)       # only its shape is read
     a = _spmm_args(g, S, lut_like, use_cnt, s_total, out.view(-1, 1), row_ids, False, plan=plan, scatter_out=scatter)
@@ -579,8 +587,7 @@ def bwd_narrow_launch(gt: HopGraph, V: torch.Tensor, S_rows: torch.Tensor, lut: 
         head = HOT_LDS_FLOATS // (2 * codes)
         head = 1 << (head.bit_length() - 1)           # the shares are known for 4096 / 8192 / 16384 rows
         head = min(int(hot.numel()), head)
-        share = (getattr(gt, "_hot_head_share", None) or {}).get(head, 0.0)
-        if share >= HOT_LDS_MIN_SHARE:
+        if _hot_head_in_lds(gt, head):
             a.hot_lo, a.hot_rows = gt.n_cols - int(hot.numel()), head
             na.spmm.hot_lo, na.spmm.hot_rows = a.hot_lo, a.hot_rows       # (the struct was copied into na)
             na.hot_code_lo, na.hot_codes = code_lo, codes
@@ -600,188 +607,219 @@ class _NotShared:
 NOT_SHARED = _NotShared()
 
 
+class KeptSums(NamedTuple):
+    """Raw shell sums a one-column training forward kept for its backward, and the route that wrote them: ``"rows"`` — the
+    row-parallel kernel's per-code sums ``[n, D - 1]``; ``"pb"`` — the propagation-blocked kernels' one sum per row ``[n]``."""
+    route: str
+    sums: torch.Tensor
+
+
+@dataclass(frozen=True)
+class AggregateCall:
+    """What a forward aggregation tells its backward pass (:func:`_aggregate_backward`): the arguments of :func:`rho_aggregate`
+    that shape the gradients, and ``kept``, the shell sums the forward's launch left behind (``spmm_launch(keep_shell=...)``)."""
+    g: HopGraph
+    use_cnt: bool
+    with_rest: bool
+    row_ids: Optional[torch.Tensor] = None
+    reduce_cr: int = 0
+    s_total: Optional[torch.Tensor] = None
+    total_rows: Optional[int] = None
+    total_group: object = NOT_SHARED        # (None would name the default process group and turn the all-reduce on)
+    kept: Optional[KeptSums] = None
+
+    def rest_total(self, S: torch.Tensor) -> torch.Tensor:
+        """The rest bucket's total as ``[W]`` floats: the one the forward was given, else the column sums of ``S``."""
+        return (self.s_total if self.s_total is not None else Fn.column_sums(S)).float().reshape(-1).contiguous()
+
+    @property
+    def shares_total(self) -> bool:
+        """Does the rest bucket's total reach beyond this call's own ``S``: summed over a process group, or over its first
+        ``total_rows`` rows only?  The rest total's term of ``dS`` is then added by :func:`_add_rest_total_grad`, not by a kernel."""
+        return self.with_rest and not (self.total_group is NOT_SHARED and self.total_rows is None)
+
+
 class _RhoAggregate(torch.autograd.Function):
     """Y = A_w(lut, cnt) @ S  with the rest-bucket term; gradients for S and the weight table."""
 
     @staticmethod
     def forward(ctx, S, lut, g: HopGraph, use_cnt: bool, with_rest: bool, row_ids, s_total=None, reduce_cr=0,
                 total_rows=None, total_group=NOT_SHARED, describe=None):
-        ctx.g, ctx.use_cnt, ctx.with_rest, ctx.row_ids, ctx.reduce_cr = g, use_cnt, with_rest, row_ids, reduce_cr
-        ctx.s_total = None if s_total is None else s_total.detach()
-        ctx.total_rows, ctx.total_group = total_rows, total_group
         ctx.save_for_backward(S, lut)
         kept = [] if (S.shape[1] == 1 and all(ctx.needs_input_grad[:2]) and S.dtype == torch.float32) else None
         ask = {} if describe is None else {"describe": describe}     # named only when asked for: a stand-in launch may not know it
         out = spmm_launch(g, S, lut, use_cnt, with_rest, row_ids, s_total=s_total, reduce_cr=reduce_cr,
                           room=getattr(S, "gnan_room", None), keep_shell=kept, **ask)
-        ctx.shell = kept[0] if kept else None
+        ctx.call = AggregateCall(g, use_cnt, with_rest, row_ids, reduce_cr, None if s_total is None else s_total.detach(),
+                                 total_rows, total_group, kept[0] if kept else None)
         return out
 
     @staticmethod
     def backward(ctx, dY):
         S, lut = ctx.saved_tensors
-        dS, dlut = _aggregate_backward(ctx, S, lut, dY, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        dS, dlut = _aggregate_backward(ctx.call, S, lut, dY, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return dS, dlut, None, None, None, None, None, None, None, None, None
 
 
-def _aggregate_backward(ctx, S, lut, dY, need_dS: bool, need_dlut: bool):
-    """Gradients of ``Y = A_w(lut, cnt) @ S`` (+ rest bucket) w.r.t. the operand and the weight table; ``ctx`` carries
-    ``g, use_cnt, with_rest, row_ids, reduce_cr, s_total, total_rows, total_group`` as :class:`_RhoAggregate` stores them."""
-    g, use_cnt, with_rest, row_ids = ctx.g, ctx.use_cnt, ctx.with_rest, ctx.row_ids
+def _aggregate_backward(call: AggregateCall, S, lut, dY, need_dS: bool, need_dlut: bool):
+    """Gradients of ``Y = A_w(lut, cnt) @ S`` (+ rest bucket) w.r.t. the operand and the weight table, for the forward that
+    ``call`` describes.  Both wanted of a narrow operand: :func:`_narrow_fused_backward`.  Else the operand gradient
+    (:func:`_operand_grad`) and the table gradient (:func:`_table_grad`) each by a pass of their own.  The rest total's term of
+    ``dS`` (:func:`_add_rest_total_grad`) follows wherever no kernel has added it."""
+    g = call.g
     dY = dY.contiguous().float()
     dY_out = dY                           # as the forward returned it: [n_out, W] or, with the fused sum, [n_out, cr]
     W = S.shape[1]
     D, Cw = lut.shape[-2], lut.shape[-1]
     per_row = lut.dim() == 3
     # truncated-hop graphs: the table gradient comes out of one pass over the listed pairs (gnan_spmm_lut_grad)
-    fused_lut_grad = (need_dlut and not g.is_dense and D <= 4 and Cw == 1
-                      and S.dtype == torch.float32)
+    listed_pass = not g.is_dense and D <= 4
     # dense layout (every pair listed, up to 256 shells), global table: one pass as well (dense_lut_grad_kernel) — the
-    # shell-sum route below goes through a [n, D, W] tensor and six framework launches
-    dense_lut_grad = (need_dlut and DENSE_LUT_GRAD and g.is_dense and Cw == 1 and D <= 256 and not per_row and not with_rest
-                      and S.dtype == torch.float32)
-    if ctx.reduce_cr and (need_dS or (need_dlut and not (fused_lut_grad or dense_lut_grad))):
-        dY = dY.repeat(1, W // ctx.reduce_cr)   # the fused feature sum broadcasts its gradient over the features
-    rows = None if row_ids is None else row_ids.long()
-    _inv = []
-
-    def inv_counts():                       # [n_out, D] 1 / shell size — three element-wise passes over N x D: only where needed
-        if not _inv:
-            cnt = g.cnt if rows is None else g.cnt[rows]
-            _inv.append(1.0 / cnt.clamp_min(1).float())
-        return _inv[0]
+    # shell-sum route goes through a [n, D, W] tensor and six framework launches
+    dense_pass = DENSE_LUT_GRAD and g.is_dense and D <= 256 and not per_row and not call.with_rest
+    one_pass_dlut = need_dlut and Cw == 1 and S.dtype == torch.float32 and (listed_pass or dense_pass)
+    if call.reduce_cr and (need_dS or (need_dlut and not one_pass_dlut)):
+        dY = dY.repeat(1, W // call.reduce_cr)   # the fused feature sum broadcasts its gradient over the features
+    rows = None if call.row_ids is None else call.row_ids.long()
+    # [n_out, D] 1 / shell size — three element-wise passes over N x D: only where needed, and once
+    inv_counts = functools.cache(lambda: 1.0 / (g.cnt if rows is None else g.cnt[rows]).clamp_min(1).float())
     dS = dlut = None
     rest_added = False
-    fused_bwd = (NARROW_FUSED_BACKWARD and need_dS and need_dlut and not g.is_dense
-                 and Cw == 1 and D <= 4 and not per_row and rows is None and not ctx.reduce_cr and W <= 16
-                 and S.dtype == torch.float32)
-    if fused_bwd:
-        # narrow operand, both gradients wanted: ONE pass over the transposed adjacency gathers, per pair, the packed row
-        # [dY_i / cnt(i, d) | dY_i / cnt(i, rest)] and yields the operand gradient AND the table gradient (the two-pass
-        # route below traverses the same pairs twice: 1.89 + 2.01 ms on the 10M-node graph)
-        half = 1 << max(0, (W - 1).bit_length())
-        shares_total = with_rest and not (ctx.total_group is NOT_SHARED and ctx.total_rows is None)
-        kept = getattr(ctx, "shell", None)
-        if kept is not None and kept.dim() == 2 and ROWS_BACKWARD_ONE_COLUMN and W == 1 and not shares_total:
-            # the row-parallel forward kept its per-code shell sums: a pass over the rows and one gather over the transposed pairs
-            total = None
-            if with_rest:
-                total = (ctx.s_total if ctx.s_total is not None else Fn.column_sums(S)).float().reshape(-1).contiguous()
-            dS, dl = rows_bwd1_launch(g, dY, kept, lut[:, 0], use_cnt, with_rest, total)
-            return dS, dl.view(D, 1)
-        plans = pb_bwd1_applies(g, W, D, with_rest, not shares_total, kept if (kept is not None and kept.dim() == 1) else None)
-        if plans is not None:
-            # one column, large graph, shell sums kept by the forward: a pass over the rows and ONE column through the buckets
-            total = None
-            if with_rest:
-                total = (ctx.s_total if ctx.s_total is not None else Fn.column_sums(S)).float().reshape(-1).contiguous()
-            dS, dl = pb_bwd1_launch(g, plans, dY, S, ctx.shell, lut[:, 0], use_cnt, with_rest, total)
-            rest_added = with_rest
-            return dS, dl.view(D, 1)
-        pb_t = pb_bwd_applies(g, W, D)                      # one column, large graph: no per-pair gather (csrc/spmm_pb.hip)
-        walk = (None, None, None) if pb_t is not None else narrow_walk(g.transposed())
-        q_sum = total = None
-        if with_rest and W == 1:                            # ... and their rest halves' column sum out of the same pass
-            V, q_sum = pack_bwd_rows(dY, g.cnt if use_cnt else None, D, with_rest, half, hot=walk[2], want_q_sum=True)
-        else:
-            V = pack_bwd_rows(dY, g.cnt if use_cnt else None, D, with_rest, half, hot=walk[2])  # [D, n (+ hot), 2 * half]
-        add_to_rows = False
-        if with_rest:
-            if q_sum is None:
-                q_sum = Fn.column_sums(V[0, :g.n_rows, half:half + W])                        # sum_i dY_i / cnt(i, rest)
-            # d/dS_j of  wt(i, rest) * total : the same vector rho(0) * q_sum for every j — added by the kernel's epilogue
-            add_to_rows = rest_added = ctx.total_group is NOT_SHARED and ctx.total_rows is None
-            # d/d lut[rest] of the same term: <total, q_sum> — added by the kernel's final pass
-            total = (ctx.s_total if ctx.s_total is not None else Fn.column_sums(S)).float().reshape(-1).contiguous()
-        if pb_t is not None:
-            dS, dl = pb_bwd_launch(g.transposed(), pb_t, V, S, lut[:, 0], with_rest, rest_q=q_sum, rest_total=total,
-                                   add_to_rows=add_to_rows)
-        else:
-            dS, dl = bwd_narrow_launch(g.transposed(), V.view(-1, 2 * half), S, lut[:, 0], with_rest, W, walk=walk,
-                                       rest_q=q_sum, rest_total=total, add_to_rows=add_to_rows)
-        dlut = dl.view(D, 1)
-
-    if need_dS and not fused_bwd:
-        dY_full = dY
-        if rows is not None:
-            dY_full = torch.zeros((g.n_rows, W), dtype=torch.float32, device=dY.device)
-            dY_full.index_add_(0, rows, dY)
-        if not g.is_dense and Cw == 1 and W * D <= NARROW_DS_MAX_WIDTH:
-            # narrow operand: fold the per-pair weight into a pre-weighted operand with one row per (node, hop code),
-            # Z[i, d] = (wt(i, d) - wt(i, rest)) dY[i], and gather it over the transposed adjacency with unit weights —
-            # one random request per listed pair instead of the operand row plus the neighbour's table row
-            wt = (lut[..., 0] if per_row else lut[:, 0].unsqueeze(0)).float()                 # [N or 1, D]
-            if use_cnt:
-                wt = wt / g.cnt.clamp_min(1).float()
-            if with_rest:
-                wt = wt - wt[:, D - 1:D]
-            Z = (wt.unsqueeze(-1) * dY_full.unsqueeze(1)).reshape(g.n_rows * D, W)
-            dS = spmm_launch(g.transposed(), Z, torch.ones((D, 1), device=Z.device), False, False, None,
-                             s_by_code=True)
-        elif g.n_rows * D * Cw * 4 <= WEIGHT_TABLE_MAX_BYTES and not (g.is_dense and g.n_rows <= SMALL_DENSE_ROWS and not per_row):
-            # wide operand: the weight of a pair belongs to the NEIGHBOUR's row there.  Read from (lut, cnt) that is two
-            # random count reads, two divisions and a subtraction per pair; a per-node table wt(i, d) - wt(i, rest)
-            # built once per backward pass makes it one 4-byte read (arxiv-shaped W = 40: 0.55 -> 0.28 ms)
-            if not per_row and lut.is_cuda and g.cnt.dtype == torch.int32:
-                wt = Fn.weight_table(lut, g.cnt if use_cnt else None, g.n_rows, with_rest)    # one launch (four framework ones before)
-            else:
-                wt = (lut if per_row else lut.unsqueeze(0)).float()                           # [N or 1, D, Cw]
-                if use_cnt:
-                    wt = wt / g.cnt.clamp_min(1).float().unsqueeze(-1)
-                if with_rest:
-                    wt = wt - wt[:, D - 1:D]
-                wt = wt.expand(g.n_rows, D, Cw).contiguous()
-            dS = spmm_launch(g.transposed(), dY_full, wt, False, False, None, weight_by_col=True)
-        else:
-            dS = spmm_launch(g.transposed(), dY_full, lut, use_cnt, False, None,
-                             weight_by_col=True, minus_rest=with_rest)
-    if need_dS:
-        if with_rest and not rest_added:
-            # d/dS_j of  wt(i, rest) * total  : the same vector for every j
-            if (not per_row and rows is None and Cw == 1 and use_cnt and dY.is_cuda and g.cnt.dtype == torch.int32
-                    and dY.shape[0] == g.n_rows):
-                # rho(0) sum_i dY[i, :] / cnt(i, rest) in one weighted column sum (eight framework launches before)
-                v = Fn.column_sums_weighted(dY, g.cnt[:, D - 1], lut[D - 1]).view(1, W)
-            else:
-                l_rest = (lut[rows, D - 1] if rows is not None else lut[:, D - 1]) if per_row else lut[D - 1].unsqueeze(0)
-                w_rest = l_rest * inv_counts()[:, D - 1:D] if use_cnt else l_rest   # [n_out or 1, Cw]
-                w_rest = w_rest.expand(dY.shape[0], Cw).repeat(1, W // Cw)
-                v = (w_rest * dY).sum(0, keepdim=True)
-            if ctx.total_group is not NOT_SHARED:
-                # the total was summed over the ranks of a group: every rank's output rows pull on every rank's
-                # summed operand rows, so the ranks add their vectors (W floats) before handing them down
-                import torch.distributed as dist
-                dist.all_reduce(v, op=dist.ReduceOp.SUM, group=ctx.total_group)
-            if ctx.total_rows is None:
-                dS.add_(v)
-            else:                          # only the first rows of S went into the total (owned rows ahead of halo rows)
-                dS[: ctx.total_rows] += v
-
-    if fused_bwd:
-        pass                                  # both gradients came out of the one transposed pass above
-    elif need_dlut and (dense_lut_grad or (fused_lut_grad and not per_row)):
-        dlut = lut_grad_launch(g, S, dY_out, D, use_cnt, with_rest, row_ids, ctx.s_total, True)       # [D, 1]
-    elif need_dlut:
-        if fused_lut_grad:
-            dwt = lut_grad_launch(g, S, dY_out, D, use_cnt, with_rest, row_ids, ctx.s_total, False)   # [n_out, D, 1]
-        else:
-            T = shell_sums_launch(g, S, lut, with_rest, row_ids, ctx.s_total)  # [n_out, D, W]
-            dwt = (T.view(T.shape[0], D, W // Cw, Cw) * dY.view(dY.shape[0], 1, W // Cw, Cw)).sum(2)
-            if use_cnt:
-                dwt = dwt * inv_counts().unsqueeze(-1)                        # [n_out, D, Cw]
-        if per_row:
-            if rows is None:
-                dlut = dwt
-            else:
-                dlut = torch.zeros_like(lut)
-                dlut.index_add_(0, rows, dwt)
-        else:
-            dlut = dwt.sum(0)
+    fused = (NARROW_FUSED_BACKWARD and need_dS and need_dlut and not g.is_dense
+             and Cw == 1 and D <= 4 and not per_row and rows is None and not call.reduce_cr and W <= 16
+             and S.dtype == torch.float32)
+    if fused:
+        dS, dlut, rest_added = _narrow_fused_backward(call, S, lut, dY)
+    elif need_dS:
+        dS = _operand_grad(call, lut, dY, rows)
+    if need_dS and call.with_rest and not rest_added:
+        _add_rest_total_grad(call, dS, lut, dY, rows, inv_counts)
+    if need_dlut and not fused:
+        dlut = _table_grad(call, S, lut, dY, dY_out, rows, inv_counts, one_pass_dlut)
     return dS, dlut
 
 
-class _Bag:
-    pass
+def _narrow_fused_backward(call: AggregateCall, S, lut, dY):
+    """``(dS, dlut, rest_added)`` of a narrow operand, both gradients wanted: ONE pass over the transposed adjacency gathers, per
+    pair, the packed row [dY_i / cnt(i, d) | dY_i / cnt(i, rest)] and yields the operand gradient AND the table gradient (the
+    two-pass route traverses the same pairs twice: 1.89 + 2.01 ms on the 10M-node graph).  The first route that applies, in
+    this order: ``rows_bwd1_launch`` and ``pb_bwd1_launch`` (one column, from the shell sums the forward kept on its route),
+    ``pb_bwd_launch`` (one column, large graph), ``bwd_narrow_launch``.  ``rest_added``: the rest total's term is in ``dS``."""
+    g, use_cnt, with_rest = call.g, call.use_cnt, call.with_rest
+    W, D = S.shape[1], lut.shape[0]
+    own_total = not call.shares_total
+    route, sums = call.kept or (None, None)
+    if route == "rows" and ROWS_BACKWARD_ONE_COLUMN and W == 1 and own_total:
+        # the row-parallel forward kept its per-code shell sums: a pass over the rows and one gather over the transposed pairs
+        dS, dl = rows_bwd1_launch(g, dY, sums, lut[:, 0], use_cnt, with_rest, call.rest_total(S) if with_rest else None)
+        return dS, dl.view(D, 1), True
+    plans = pb_bwd1_applies(g, W, D, with_rest, own_total, sums if route == "pb" else None)
+    if plans is not None:
+        # one column, large graph, shell sums kept by the forward: a pass over the rows and ONE column through the buckets
+        dS, dl = pb_bwd1_launch(g, plans, dY, S, sums, lut[:, 0], use_cnt, with_rest, call.rest_total(S) if with_rest else None)
+        return dS, dl.view(D, 1), True
+    half = 1 << max(0, (W - 1).bit_length())
+    pb_t = pb_bwd_applies(g, W, D)                      # one column, large graph: no per-pair gather (csrc/spmm_pb.hip)
+    walk = (None, None, None) if pb_t is not None else narrow_walk(g.transposed())
+    q_sum = total = None
+    if with_rest and W == 1:                            # ... and their rest halves' column sum out of the same pass
+        V, q_sum = pack_bwd_rows(dY, g.cnt if use_cnt else None, D, with_rest, half, hot=walk[2], want_q_sum=True)
+    else:
+        V = pack_bwd_rows(dY, g.cnt if use_cnt else None, D, with_rest, half, hot=walk[2])  # [D, n (+ hot), 2 * half]
+    # d/dS_j of  wt(i, rest) * total : the same vector rho(0) * q_sum for every j — added by the kernel's epilogue
+    add_to_rows = with_rest and own_total
+    if with_rest:
+        if q_sum is None:
+            q_sum = Fn.column_sums(V[0, :g.n_rows, half:half + W])                        # sum_i dY_i / cnt(i, rest)
+        # d/d lut[rest] of the same term: <total, q_sum> — added by the kernel's final pass
+        total = call.rest_total(S)
+    if pb_t is not None:
+        dS, dl = pb_bwd_launch(g.transposed(), pb_t, V, S, lut[:, 0], with_rest, rest_q=q_sum, rest_total=total, add_to_rows=add_to_rows)
+    else:
+        dS, dl = bwd_narrow_launch(g.transposed(), V.view(-1, 2 * half), S, lut[:, 0], with_rest, W, walk=walk,
+                                   rest_q=q_sum, rest_total=total, add_to_rows=add_to_rows)
+    return dS, dl.view(D, 1), add_to_rows
+
+
+def _operand_grad(call: AggregateCall, lut, dY, rows):
+    """``dS`` without the rest total's term: the forward kernel over the transposed adjacency, ``dY [n_out, W]`` as its operand."""
+    g, use_cnt, with_rest = call.g, call.use_cnt, call.with_rest
+    W = dY.shape[1]
+    D, Cw = lut.shape[-2], lut.shape[-1]
+    per_row = lut.dim() == 3
+    dY_full = dY if rows is None else torch.zeros((g.n_rows, W), dtype=torch.float32, device=dY.device).index_add_(0, rows, dY)
+    if not g.is_dense and Cw == 1 and W * D <= NARROW_DS_MAX_WIDTH:
+        # narrow operand: fold the per-pair weight into a pre-weighted operand with one row per (node, hop code),
+        # Z[i, d] = (wt(i, d) - wt(i, rest)) dY[i], and gather it over the transposed adjacency with unit weights —
+        # one random request per listed pair instead of the operand row plus the neighbour's table row
+        wt = (lut[..., 0] if per_row else lut[:, 0].unsqueeze(0)).float()                 # [N or 1, D]
+        if use_cnt:
+            wt = wt / g.cnt.clamp_min(1).float()
+        if with_rest:
+            wt = wt - wt[:, D - 1:D]
+        Z = (wt.unsqueeze(-1) * dY_full.unsqueeze(1)).reshape(g.n_rows * D, W)
+        return spmm_launch(g.transposed(), Z, torch.ones((D, 1), device=Z.device), False, False, None, s_by_code=True)
+    if g.n_rows * D * Cw * 4 <= WEIGHT_TABLE_MAX_BYTES and not (g.is_dense and g.n_rows <= SMALL_DENSE_ROWS and not per_row):
+        # wide operand: the weight of a pair belongs to the NEIGHBOUR's row there.  Read from (lut, cnt) that is two
+        # random count reads, two divisions and a subtraction per pair; a per-node table wt(i, d) - wt(i, rest)
+        # built once per backward pass makes it one 4-byte read (arxiv-shaped W = 40: 0.55 -> 0.28 ms)
+        if not per_row and lut.is_cuda and g.cnt.dtype == torch.int32:
+            wt = Fn.weight_table(lut, g.cnt if use_cnt else None, g.n_rows, with_rest)    # one launch (four framework ones before)
+        else:
+            wt = (lut if per_row else lut.unsqueeze(0)).float()                           # [N or 1, D, Cw]
+            if use_cnt:
+                wt = wt / g.cnt.clamp_min(1).float().unsqueeze(-1)
+            if with_rest:
+                wt = wt - wt[:, D - 1:D]
+            wt = wt.expand(g.n_rows, D, Cw).contiguous()
+        return spmm_launch(g.transposed(), dY_full, wt, False, False, None, weight_by_col=True)
+    return spmm_launch(g.transposed(), dY_full, lut, use_cnt, False, None, weight_by_col=True, minus_rest=with_rest)
+
+
+def _add_rest_total_grad(call: AggregateCall, dS, lut, dY, rows, inv_counts):
+    """``dS += d/dS_j of  wt(i, rest) * total`` in place: the same vector for every j of the rows that went into the total."""
+    g, use_cnt = call.g, call.use_cnt
+    W = dY.shape[1]
+    D, Cw = lut.shape[-2], lut.shape[-1]
+    per_row = lut.dim() == 3
+    if not per_row and rows is None and Cw == 1 and use_cnt and dY.is_cuda and g.cnt.dtype == torch.int32 and dY.shape[0] == g.n_rows:
+        # rho(0) sum_i dY[i, :] / cnt(i, rest) in one weighted column sum (eight framework launches before)
+        v = Fn.column_sums_weighted(dY, g.cnt[:, D - 1], lut[D - 1]).view(1, W)
+    else:
+        l_rest = (lut[rows, D - 1] if rows is not None else lut[:, D - 1]) if per_row else lut[D - 1].unsqueeze(0)
+        w_rest = l_rest * inv_counts()[:, D - 1:D] if use_cnt else l_rest   # [n_out or 1, Cw]
+        w_rest = w_rest.expand(dY.shape[0], Cw).repeat(1, W // Cw)
+        v = (w_rest * dY).sum(0, keepdim=True)
+    if call.total_group is not NOT_SHARED:
+        # the total was summed over the ranks of a group: every rank's output rows pull on every rank's
+        # summed operand rows, so the ranks add their vectors (W floats) before handing them down
+        import torch.distributed as dist
+        dist.all_reduce(v, op=dist.ReduceOp.SUM, group=call.total_group)
+    if call.total_rows is None:
+        dS.add_(v)
+    else:                          # only the first rows of S went into the total (owned rows ahead of halo rows)
+        dS[: call.total_rows] += v
+
+
+def _table_grad(call: AggregateCall, S, lut, dY, dY_out, rows, inv_counts, one_pass: bool):
+    """``dlut``, shaped as ``lut``: out of one pass over the pairs (``lut_grad_launch`` on ``dY_out``, the gradient as the forward's
+    output is shaped) where ``one_pass``, else contracted from the rows' shell sums."""
+    g, use_cnt, with_rest, row_ids = call.g, call.use_cnt, call.with_rest, call.row_ids
+    W = S.shape[1]
+    D, Cw = lut.shape[-2], lut.shape[-1]
+    per_row = lut.dim() == 3
+    if one_pass and not per_row:
+        return lut_grad_launch(g, S, dY_out, D, use_cnt, with_rest, row_ids, call.s_total, True)      # [D, 1]
+    if one_pass:
+        dwt = lut_grad_launch(g, S, dY_out, D, use_cnt, with_rest, row_ids, call.s_total, False)      # [n_out, D, 1]
+    else:
+        T = shell_sums_launch(g, S, lut, with_rest, row_ids, call.s_total)  # [n_out, D, W]
+        dwt = (T.view(T.shape[0], D, W // Cw, Cw) * dY.view(dY.shape[0], 1, W // Cw, Cw)).sum(2)
+        if use_cnt:
+            dwt = dwt * inv_counts().unsqueeze(-1)                        # [n_out, D, Cw]
+    if not per_row:
+        return dwt.sum(0)
+    return dwt if rows is None else torch.zeros_like(lut).index_add_(0, rows, dwt)
 
 
 class _PreRhoAggregate(torch.autograd.Function):
@@ -793,9 +831,8 @@ class _PreRhoAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, S, g, with_rest, row_ids, s_total, total_rows, total_group, tables, u, L, H, C, describe, *params):
-        ctx.g, ctx.use_cnt, ctx.with_rest, ctx.row_ids, ctx.reduce_cr = g, False, with_rest, row_ids, 0
-        ctx.s_total = None if s_total is None else s_total.detach()
-        ctx.total_rows, ctx.total_group = total_rows, total_group
+        ctx.call = AggregateCall(g, False, with_rest, row_ids, 0, None if s_total is None else s_total.detach(),
+                                 total_rows, total_group)
         ctx.tables, ctx.u, ctx.meta = tables, u, (L, H, C)
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(S, *[t for t in params if t is not None])
@@ -810,8 +847,8 @@ class _PreRhoAggregate(torch.autograd.Function):
         S = saved.pop(0)
         params = [saved.pop(0) if present else None for present in ctx.present]
         need_rho = any(ctx.needs_input_grad[13:])
-        lut, arg = Fn._rho_row_lut_launch(ctx.g.cnt, ctx.u, ctx.tables, C, need_rho)
-        dS, dlut = _aggregate_backward(ctx, S, lut, dY, ctx.needs_input_grad[0], need_rho)
+        lut, arg = Fn._rho_row_lut_launch(ctx.call.g.cnt, ctx.u, ctx.tables, C, need_rho)
+        dS, dlut = _aggregate_backward(ctx.call, S, lut, dY, ctx.needs_input_grad[0], need_rho)
         pg = Fn._rho_param_grads(arg, dlut, ctx.tables, params, ctx.present, L, H, C) if need_rho else (None,) * 6
         return (dS,) + (None,) * 12 + tuple(pg)
 
@@ -853,12 +890,10 @@ class _ReferenceOrderAggregate(torch.autograd.Function):
     def forward(ctx, x, lut, g, use_cnt, with_rest, L, H, C, F, *params):
         p = StackedMLP(*params, L, H, C, F)
         needs_grad = any(ctx.needs_input_grad[9:])
-        located = None
-        fx, tables, total = Fn._fmlp_forward(x, p, False, with_rest, needs_grad, torch.float32, None, located=located)
+        fx, tables, total = Fn._fmlp_forward(x, p, False, with_rest, needs_grad, torch.float32, None)
         if with_rest and total is None:
             total = Fn.column_sums(fx)
-        ctx.g, ctx.use_cnt, ctx.with_rest, ctx.row_ids, ctx.reduce_cr = g, use_cnt, with_rest, None, 0
-        ctx.total_rows, ctx.total_group = None, NOT_SHARED
+        ctx.call = AggregateCall(g, use_cnt, with_rest, s_total=None)     # (the backward's operand is the rows' feature sum: its own total)
         ctx.tables, ctx.meta = tables, (L, H, C, F)
         ctx.present = [t is not None for t in params]
         keep = fx if (fx.numel() * 4 <= REFERENCE_ORDER_KEEP_MAX_BYTES or tables is None) else None
@@ -880,8 +915,7 @@ class _ReferenceOrderAggregate(torch.autograd.Function):
             S1 = Fn.feature_sum(fx, C)
         else:                                                       # rows too large to keep: the feature sum is looked up again
             S1 = Fn._fpwl_launch(x, ctx.tables, True)
-        ctx.s_total = None
-        dS1, dlut = _aggregate_backward(ctx, S1, lut, dY, True, ctx.needs_input_grad[1])
+        dS1, dlut = _aggregate_backward(ctx.call, S1, lut, dY, True, ctx.needs_input_grad[1])
         pg = (None,) * 6
         if any(ctx.needs_input_grad[9:]):
             # every feature's rows have the gradient dS1: the shape functions' gradients are those of the feature-SUM mode

@@ -287,10 +287,8 @@ class _BatchedGraphs(torch.autograd.Function):
                                     "channels or too large a workspace): no other route reads the slots' sizes from the device")
         dY = d_out.index_select(0, blocks.batch_vector()) if ctx.graph_sum else d_out      # every node gets its graph's gradient
         from . import aggregate
-        bag = aggregate._Bag()
-        bag.g, bag.use_cnt, bag.with_rest, bag.row_ids, bag.reduce_cr = blocks.csr(), False, False, None, 0
-        bag.s_total, bag.total_rows, bag.total_group = None, None, aggregate.NOT_SHARED
-        dS, dlut = aggregate._aggregate_backward(bag, S, lut[0].contiguous(), dY.contiguous(), need_f, need_r)
+        call = aggregate.AggregateCall(blocks.csr(), use_cnt=False, with_rest=False)
+        dS, dlut = aggregate._aggregate_backward(call, S, lut[0].contiguous(), dY.contiguous(), need_f, need_r)
         pg_f = pg_r = [None] * 6
         if need_f:
             _, pg_f = Fn._shape_function_grads(x, params[:6], ctx.present[:6], None, dS, True, Lf, Hf, Cf, F, dests=ctx.dests[:6])

@@ -814,6 +814,10 @@ class HopGraph:
             self._hot = (ids,)
         return self._hot[0]
 
+    def hot_head_share(self, head: int) -> float:
+        """Share of the pairs that list the first ``head`` hot neighbours (:meth:`hot_columns`); 0.0 where none is known."""
+        return (self._hot_head_share or {}).get(head, 0.0)
+
     def _packed_index(self) -> Optional[torch.Tensor]:
         """``col | code << 29`` as int32, one 4-byte index stream for the aggregation kernel instead of two (its index
         loads are L2 requests like its gathers); ``None`` when ids or codes do not fit."""
