@@ -1,6 +1,6 @@
 """The rho(distance)-weighted, shell-normalised neighbourhood sum (GNAN.py:65-73 / models.py:368-376) and its backward pass:
-launch wrappers of ``csrc/spmm.hip`` (``spmm_launch``, ``shell_sums_launch``, ``lut_grad_launch``, ``bwd_narrow_launch``,
-``pack_bwd_rows``), the dispatch between them (thresholds below), and the autograd nodes ``rho_aggregate`` /
+launch wrappers of ``csrc/spmm.hip`` (``spmm_launch``, ``shell_sums_launch``), ``csrc/spmm_grad.hip`` (``lut_grad_launch``,
+``bwd_narrow_launch``) and ``csrc/pack_bwd_rows.hip`` (``pack_bwd_rows``), the dispatch between them (thresholds below), and the autograd nodes ``rho_aggregate`` /
 ``pre_rho_aggregate`` / ``reference_order_forward`` are built from.  A forward describes itself to the backward pass in one
 frozen record, :class:`AggregateCall` (the shell sums a one-column forward kept travel in it as :class:`KeptSums`, tagged
 with the route that wrote them); ``_aggregate_backward`` dispatches on it.  Shape functions live in ``functional``; the two

@@ -198,7 +198,7 @@ def tile_partition(deg, lpr, lmax):
 
 
 # =====================================================================================================================================
-# The narrow aggregation (W in {1, 2, 4}): csrc/spmm_pb.hip and the narrow row walks of csrc/spmm.hip
+# The narrow aggregation (W in {1, 2, 4}): csrc/spmm_pb.hip and the narrow row walks of csrc/spmm.hip (spmm_hot_kernel) and csrc/spmm_fwd_body.hpp
 # =====================================================================================================================================
 # Propagation-blocked forward (pb_expand_kernel + pb_reduce_kernel).  Every operand entry is truncated toward zero to a multiple of
 #     q = 2^(e + h - 62),    e = the frexp exponent of the float32 max |S| over ALL rows of S,    h = plan.headroom_bits,

@@ -24,7 +24,7 @@ def _fma32(a, b, c):
 
 
 def _kernel_order_f32(rowptr, col, code, S, lut, cnt, s_total, reduce_cr=0):
-    """The small-D rows' arithmetic of csrc/spmm.hip (rows_body / short_tile) in float32, rows of any length walked as one chain."""
+    """The small-D rows' arithmetic of csrc/spmm_fwd_body.hpp (rows_body / short_tile) in float32, rows of any length walked as one chain."""
     n, D = len(rowptr) - 1, lut.shape[0]
     rest = D - 1
     w = np.broadcast_to(lut.reshape(1, D).astype(np.float32), (n, D)).copy()
