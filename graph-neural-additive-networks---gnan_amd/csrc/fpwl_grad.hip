@@ -13,7 +13,14 @@
 // One workgroup per feature walks its pieces (empty ones are skipped), float64 throughout, every gradient element
 // owned by one thread: no atomics, bit-reproducible.  It replaces ~110 tiny framework launches of the torch
 // restatement of the same sum (gnan_amd/pwl.py:parameter_grads_from_moments, two probe points per piece through the
-// batched MLP in float64 — still the route for L >= 4 and the reference this kernel is tested against).
+// batched MLP in float64 — still the route for L >= 5 and the reference this kernel is tested against).
+//
+// L == 4 (fpwl_grad4_kernel) is the same derivation with one more layer: D3 the third mask,
+//     h3a = D3 (W3 h2a + b3),  h3' = D3 W3 h2'
+//     dW4 = M0 (x) h3a + M1 (x) h3'        db4 = M0
+//     e0 = D3 W4^T M0,  e1 = D3 W4^T M1    dW3 = e0 (x) h2a + e1 (x) h2'     db3 = e0
+//     r0 = D2 W3^T e0,  r1 = D2 W3^T e1    dW2 = r0 (x) h1a + r1 (x) h1'     db2 = r0
+//     q0 = D1 W2^T r0,  q1 = D1 W2^T r1    dw1 = q0 a + q1                   db1 = q0
 //
 // gnan_fpwl_moment_scales: the two power-of-two scales of the fixed-point moments, from max|grad| and max|x - anchor|,
 // in one pass + one single-thread kernel instead of ~20 framework launches.
@@ -34,15 +41,15 @@ struct GradParams {
   const double* scales;   // [2] (with Mi)
   const float* w1;
   const float* b1;
-  const float* W2;
-  const float* b2;
+  const float* W2;        // [L - 2, F, H, H]
+  const float* b2;        // [L - 2, F, H]
   const float* Wl;
   const float* bl;
   int F, L, H, C;
   float* d_w1;
   float* d_b1;
-  float* d_W2;
-  float* d_b2;
+  float* d_W2;            // [L - 2, F, H, H]
+  float* d_b2;            // [L - 2, F, H]
   float* d_Wl;
   float* d_bl;
 };
@@ -297,6 +304,253 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
     }
   }
   if (lt < C && p.d_bl) p.d_bl[static_cast<int64_t>(k) * C + lt] = static_cast<float>(db3);
+}
+
+// ---- L == 4, H <= 64: fpwl_grad3_kernel's mapping with one more layer.  Thread (j, ib) of a group of 256 = (unit, quarter of
+// the units of the layer below); per piece the three hidden layers go forward (value at the inner point for the masks, value and
+// x-derivative at the anchor) and the two reverse passes come back through W4, W3, W2, with a barrier between layers.  A thread
+// owns the quarter rows dW2[j][.] and dW3[j][.] (2 x 16 float64 accumulators = 64 VGPRs) next to its CQ channel accumulators:
+// TWO groups (512 threads, 256 VGPRs per lane) for every channel count — four would leave 128 and spill.  W2 and W3 sit in
+// padded LDS copies (row stride H + 1: conflict-free row and column reads).  The sweep kernel's prefix sums are not carried
+// over: their monotone-mask argument holds for the first layer only.
+template <int kNG, int CQ>
+__global__ __launch_bounds__(256 * kNG) void fpwl_grad4_kernel(const GradParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int H = p.H, C = p.C, HS = H + 1;
+  float* w1 = reinterpret_cast<float*>(smem_raw);
+  float* b1 = w1 + H;
+  float* b2 = b1 + H;
+  float* b3 = b2 + H;
+  float* W2s = b3 + H;                 // [H][HS]: W2[j][i], padded rows
+  float* W3s = W2s + H * HS;           // [H][HS]: W3[j][i]
+  float* Wl = W3s + H * HS;            // [C][H]
+  double* vec = reinterpret_cast<double*>(smem_raw + (((4 * H + 2 * H * HS + C * H) * sizeof(float) + 7) & ~size_t(7)));
+  const int tid = threadIdx.x, k = blockIdx.x;
+  const int grp = tid >> 8, lt = tid & 255;
+  double* h1i = vec + grp * (10 * H + 2 * C);     // per group: h1i | h1a | h1p | h2i | h2a | h2p | e0 | e1 | r0 | r1 | Mv[2C]
+  double* h1a = h1i + H;
+  double* h1p = h1a + H;
+  double* h2i = h1p + H;
+  double* h2a = h2i + H;
+  double* h2p = h2a + H;
+  double* e0 = h2p + H;
+  double* e1 = e0 + H;
+  double* r0 = e1 + H;
+  double* r1 = r0 + H;
+  double* Mv = r1 + H;
+  double* red = vec + kNG * (10 * H + 2 * C);     // [kNG - 1][256]
+  int* live = reinterpret_cast<int*>(red + (kNG - 1) * 256);   // [P]: the pieces that hold at least one node, ascending
+  __shared__ int n_live;
+  __shared__ int wave_live[4 * kNG];
+  const int j = lt >> 2, ib = lt & 3;
+  const int BI = (H + 3) >> 2;
+  const int64_t kH = static_cast<int64_t>(k) * H;
+  const int64_t FH = static_cast<int64_t>(p.F) * H;            // second mid layer: + FH (biases), + FH * H (weights)
+
+  for (int i = tid; i < H; i += 256 * kNG) {
+    w1[i] = p.w1[kH + i];
+    b1[i] = p.b1 ? p.b1[kH + i] : 0.f;
+    b2[i] = p.b2 ? p.b2[kH + i] : 0.f;
+    b3[i] = p.b2 ? p.b2[FH + kH + i] : 0.f;
+  }
+  for (int i = tid; i < H * H; i += 256 * kNG) {
+    W2s[(i / H) * HS + i % H] = p.W2[kH * H + i];
+    W3s[(i / H) * HS + i % H] = p.W2[(FH + kH) * H + i];
+  }
+  for (int i = tid; i < C * H; i += 256 * kNG) Wl[i] = p.Wl[kH * C + i];
+  double dW2[kBI], dW3[kBI], dW4[CQ];
+#pragma unroll
+  for (int r = 0; r < kBI; ++r) dW2[r] = dW3[r] = 0.0;
+#pragma unroll
+  for (int r = 0; r < CQ; ++r) dW4[r] = 0.0;
+  double db3 = 0.0, db2 = 0.0, dw1 = 0.0, db1 = 0.0, db4 = 0.0;
+  const int base = p.off[k], P = p.off[k + 1] - base;
+  const double inv0 = p.Mi ? 1.0 / p.scales[0] : 1.0, inv1 = p.Mi ? 1.0 / p.scales[1] : 1.0;
+  list_live_pieces<256 * kNG>(p, base, P, inv0, inv1, live, wave_live, &n_live);
+  __syncthreads();
+  const int nl = n_live;
+  double mval = 0.0;                                // this thread's moment of the group's NEXT piece, requested a round ahead
+  double a_next = 0.0, xi_next = 0.0;
+  if (grp < nl) {
+    if (lt < 2 * C) piece_moment(p, base + live[grp], lt, inv0, inv1, &mval);
+    piece_points(p.anchor + base, live[grp], P, &a_next, &xi_next);
+  }
+
+  for (int l0 = 0; l0 < nl; l0 += kNG) {
+    const int at = l0 + grp;                        // this group's piece of the round (a group beyond the list: zeros)
+    const int li = at < nl ? live[at] : -1;
+    __syncthreads();                                // the previous round's readers of the LDS vectors are done
+    const double a = a_next, xi = xi_next;
+    if (lt < 2 * C) Mv[lt] = li >= 0 ? mval : 0.0;
+    mval = 0.0;
+    if (at + kNG < nl) {
+      const int ln = live[at + kNG];
+      if (lt < 2 * C) piece_moment(p, base + ln, lt, inv0, inv1, &mval);
+      piece_points(p.anchor + base, ln, P, &a_next, &xi_next);
+    }
+    if (lt < H) {
+      const double wv = static_cast<double>(w1[lt]), bv = static_cast<double>(b1[lt]);
+      const double z = fma(wv, xi, bv);
+      const bool on = z > 0.0;
+      h1i[lt] = on ? z : 0.0;
+      h1a[lt] = on ? fma(wv, a, bv) : 0.0;
+      h1p[lt] = on ? wv : 0.0;
+    }
+    __syncthreads();
+    bool on2 = false;
+    if (j < H) {                        // second layer forward: unit j, the quad splits the first-layer units
+      double si = 0.0, sa = 0.0, sp = 0.0;
+#pragma unroll
+      for (int r = 0; r < kBI; ++r) {
+        const int i = ib * BI + r;
+        if (r < BI && i < H) {
+          const double w = static_cast<double>(W2s[j * HS + i]);
+          si = fma(w, h1i[i], si);
+          sa = fma(w, h1a[i], sa);
+          sp = fma(w, h1p[i], sp);
+        }
+      }
+      si = quad_sum(si); sa = quad_sum(sa); sp = quad_sum(sp);
+      const double bj = static_cast<double>(b2[j]);
+      on2 = si + bj > 0.0;
+      if (ib == 0) {
+        h2i[j] = on2 ? si + bj : 0.0;
+        h2a[j] = on2 ? sa + bj : 0.0;
+        h2p[j] = on2 ? sp : 0.0;
+      }
+    }
+    __syncthreads();
+    if (j < H) {                        // third layer forward, last layer backward, dW3
+      double si = 0.0, sa = 0.0, sp = 0.0;
+#pragma unroll
+      for (int r = 0; r < kBI; ++r) {
+        const int i = ib * BI + r;
+        if (r < BI && i < H) {
+          const double w = static_cast<double>(W3s[j * HS + i]);
+          si = fma(w, h2i[i], si);
+          sa = fma(w, h2a[i], sa);
+          sp = fma(w, h2p[i], sp);
+        }
+      }
+      si = quad_sum(si); sa = quad_sum(sa); sp = quad_sum(sp);
+      const double bj = static_cast<double>(b3[j]);
+      const bool on3 = si + bj > 0.0;
+      const double h3a = on3 ? sa + bj : 0.0, h3p = on3 ? sp : 0.0;
+      double p0 = 0.0, p1 = 0.0;
+      for (int c = ib; c < C; c += 4) {
+        const double wl = static_cast<double>(Wl[c * H + j]);
+        p0 = fma(wl, Mv[c], p0);
+        p1 = fma(wl, Mv[C + c], p1);
+      }
+      p0 = quad_sum(p0); p1 = quad_sum(p1);
+      const double e0v = on3 ? p0 : 0.0, e1v = on3 ? p1 : 0.0;
+#pragma unroll
+      for (int r = 0; r < kBI; ++r) {
+        const int i = ib * BI + r;
+        if (r < BI && i < H) dW3[r] = fma(e0v, h2a[i], fma(e1v, h2p[i], dW3[r]));
+      }
+#pragma unroll
+      for (int r = 0; r < CQ; ++r) {
+        const int c = ib + 4 * r;
+        if (c < C) dW4[r] = fma(Mv[c], h3a, fma(Mv[C + c], h3p, dW4[r]));
+      }
+      if (ib == 0) {
+        db3 += e0v;
+        e0[j] = e0v;
+        e1[j] = e1v;
+      }
+    }
+    if (lt < C) db4 += Mv[lt];
+    __syncthreads();
+    if (j < H) {                        // back through W3: column j (its mask D2 is this quad's on2), then dW2's row j
+      double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int r = 0; r < kBI; ++r) {
+        const int jj = ib * BI + r;
+        if (r < BI && jj < H) {
+          const double w = static_cast<double>(W3s[jj * HS + j]);
+          s0 = fma(w, e0[jj], s0);
+          s1 = fma(w, e1[jj], s1);
+        }
+      }
+      s0 = quad_sum(s0); s1 = quad_sum(s1);
+      const double r0v = on2 ? s0 : 0.0, r1v = on2 ? s1 : 0.0;
+#pragma unroll
+      for (int r = 0; r < kBI; ++r) {
+        const int i = ib * BI + r;
+        if (r < BI && i < H) dW2[r] = fma(r0v, h1a[i], fma(r1v, h1p[i], dW2[r]));
+      }
+      if (ib == 0) {
+        db2 += r0v;
+        r0[j] = r0v;
+        r1[j] = r1v;
+      }
+    }
+    __syncthreads();
+    if (j < H) {                        // back through W2: column i = j
+      const int i = j;
+      double q0 = 0.0, q1 = 0.0;
+#pragma unroll
+      for (int r = 0; r < kBI; ++r) {
+        const int jj = ib * BI + r;
+        if (r < BI && jj < H) {
+          const double w = static_cast<double>(W2s[jj * HS + i]);
+          q0 = fma(w, r0[jj], q0);
+          q1 = fma(w, r1[jj], q1);
+        }
+      }
+      q0 = quad_sum(q0); q1 = quad_sum(q1);
+      if (ib == 0 && fma(static_cast<double>(w1[i]), xi, static_cast<double>(b1[i])) > 0.0) {
+        dw1 += fma(q0, a, q1);
+        db1 += q0;
+      }
+    }
+    // the next round's first barrier separates these reads of r0 / r1 from their next writes
+  }
+
+  // groups 1 .. NG-1 hand their accumulators to group 0, one value per thread at a time; group 0 adds them in group order
+  auto gather = [&](double& v) {
+    __syncthreads();
+    if (grp > 0) red[(grp - 1) * 256 + lt] = v;
+    __syncthreads();
+    if (grp == 0) {
+#pragma unroll
+      for (int g = 1; g < kNG; ++g) v += red[(g - 1) * 256 + lt];
+    }
+  };
+#pragma unroll
+  for (int r = 0; r < kBI; ++r)
+    if (r < BI) { gather(dW2[r]); gather(dW3[r]); }
+#pragma unroll
+  for (int r = 0; r < CQ; ++r)
+    if (r * 4 < C) gather(dW4[r]);
+  gather(db3); gather(db2); gather(dw1); gather(db1); gather(db4);
+  if (grp != 0) return;
+
+  if (j < H) {
+#pragma unroll
+    for (int r = 0; r < kBI; ++r) {
+      const int i = ib * BI + r;
+      if (r < BI && i < H) {
+        p.d_W2[(kH + j) * H + i] = static_cast<float>(dW2[r]);
+        p.d_W2[(FH + kH + j) * H + i] = static_cast<float>(dW3[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < CQ; ++r) {
+      const int c = ib + 4 * r;
+      if (c < C) p.d_Wl[(static_cast<int64_t>(k) * C + c) * H + j] = static_cast<float>(dW4[r]);
+    }
+    if (ib == 0) {
+      if (p.d_b2) {
+        p.d_b2[kH + j] = static_cast<float>(db2);
+        p.d_b2[FH + kH + j] = static_cast<float>(db3);
+      }
+      p.d_w1[kH + j] = static_cast<float>(dw1);
+      if (p.d_b1) p.d_b1[kH + j] = static_cast<float>(db1);
+    }
+  }
+  if (lt < C && p.d_bl) p.d_bl[static_cast<int64_t>(k) * C + lt] = static_cast<float>(db4);
 }
 
 // ---- L == 3, H <= 64, C <= 4, at most 1024 pieces per feature: the same sums in O(live pieces x H + H^2) ------------------
@@ -711,14 +965,14 @@ __global__ __launch_bounds__(256) void scales_kernel(const unsigned* blk, int n_
 extern "C" int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fpwl_param_grads: null args");
   GNAN_REQUIRE(a->F >= 1 && a->H >= 1 && a->C >= 1, "fpwl_param_grads: bad sizes");
-  if (a->L != 2 && a->L != 3) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: kernel covers L in {2, 3} (got %d)", a->L);
-  if (a->C > 64 || a->H > (a->L == 3 ? 64 : 128))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: H <= %d and C <= 64 (got H=%d, C=%d)", a->L == 3 ? 64 : 128, a->H, a->C);
+  if (a->L < 2 || a->L > 4) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: kernel covers L in {2, 3, 4} (got %d)", a->L);
+  if (a->C > 64 || a->H > (a->L >= 3 ? 64 : 128))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: H <= %d and C <= 64 (got H=%d, C=%d)", a->L >= 3 ? 64 : 128, a->H, a->C);
   GNAN_REQUIRE(a->off && a->anchor && a->w_first && a->w_last && a->d_w_first && a->d_w_last, "fpwl_param_grads: null pointer");
   GNAN_REQUIRE(a->max_pieces >= 1 && a->max_pieces <= 8192, "fpwl_param_grads: max_pieces must be in [1, 8192] (got %d)", a->max_pieces);
   GNAN_REQUIRE((a->moments != nullptr) != (a->moments_fixed != nullptr), "fpwl_param_grads: exactly one of moments / moments_fixed");
   GNAN_REQUIRE(a->moments_fixed == nullptr || a->scales != nullptr, "fpwl_param_grads: moments_fixed needs scales");
-  if (a->L == 3) GNAN_REQUIRE(a->w_mid && a->d_w_mid, "fpwl_param_grads: L == 3 needs w_mid / d_w_mid");
+  if (a->L >= 3) GNAN_REQUIRE(a->w_mid && a->d_w_mid, "fpwl_param_grads: L >= 3 needs w_mid / d_w_mid");
   GNAN_REQUIRE((a->b_first == nullptr) == (a->d_b_first == nullptr) && (a->b_last == nullptr) == (a->d_b_last == nullptr) &&
                (a->L == 2 || (a->b_mid == nullptr) == (a->d_b_mid == nullptr)),
                "fpwl_param_grads: d_b_* must be NULL exactly where the bias is NULL");
@@ -729,6 +983,26 @@ extern "C" int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t
   p.d_w1 = a->d_w_first; p.d_b1 = a->d_b_first; p.d_W2 = a->d_w_mid; p.d_b2 = a->d_b_mid;
   p.d_Wl = a->d_w_last; p.d_bl = a->d_b_last;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (a->L == 4) {
+    const size_t H = a->H, C = a->C;
+    constexpr int ng = 2;
+    const size_t lds = (((4 * H + 2 * H * (H + 1) + C * H) * sizeof(float) + 7) & ~size_t(7)) +
+                       (ng * (10 * H + 2 * C) + (ng - 1) * 256) * sizeof(double) + (static_cast<size_t>(a->max_pieces) + 8) * sizeof(int);
+    const void* fn = C <= 4 ? reinterpret_cast<const void*>(fpwl_grad4_kernel<ng, 1>)
+                     : C <= 8 ? reinterpret_cast<const void*>(fpwl_grad4_kernel<ng, 2>)
+                     : C <= 16 ? reinterpret_cast<const void*>(fpwl_grad4_kernel<ng, 4>)
+                               : reinterpret_cast<const void*>(fpwl_grad4_kernel<ng, 16>);
+    if (lds > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+      if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_param_grads: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    }
+    const dim3 grid(a->F), block(256 * ng);
+    if (C <= 4) hipLaunchKernelGGL((fpwl_grad4_kernel<ng, 1>), grid, block, lds, st, p);
+    else if (C <= 8) hipLaunchKernelGGL((fpwl_grad4_kernel<ng, 2>), grid, block, lds, st, p);
+    else if (C <= 16) hipLaunchKernelGGL((fpwl_grad4_kernel<ng, 4>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((fpwl_grad4_kernel<ng, 16>), grid, block, lds, st, p);
+    return gnan::check_launch("fpwl_grad4_kernel");
+  }
   if (a->L == 3) {
     const size_t H = a->H, C = a->C;
     size_t lds = ((3 * H + H * (H + 1) + C * H) * sizeof(float) + 7) & ~size_t(7);

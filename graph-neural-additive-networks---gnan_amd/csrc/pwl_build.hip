@@ -4,12 +4,14 @@
 // tabulates it for gnan_fpwl_fwd, once per forward, from the current weights.  One workgroup per feature,
 // everything in LDS, float64 arithmetic:
 //   1. kinks of the first layer  t_j = -b1_j / w1_j, bitonic-sorted;
-//   2. (L = 3) between consecutive kinks every second-layer pre-activation z_j(x) is affine: threads walk the
-//      sample points, detect sign changes, append the roots, sort again;
+//   2. (L >= 3) between consecutive kinks every second-layer pre-activation z_j(x) is affine: threads walk the
+//      sample points, detect sign changes, append the roots, sort again; (L = 4) once more for the third layer, whose
+//      pre-activations are affine between consecutive breakpoints of layers 1 and 2;
 //   3. the network itself is evaluated at the float32-rounded kinks (+ one point beyond each end) and turned
 //      into (anchor, value, slope) per piece.
 // It replaces ~150 tiny framework launches of the torch restatement of the same procedure
-// (gnan_amd/pwl.py:_build_padded, which remains the reference implementation and the L >= 4 path).
+// (gnan_amd/pwl.py:_build_padded, which remains the reference implementation and the path of L >= 5 and of L = 4, H > 64:
+// two H x H matrices, three breakpoint arrays and the node tiles fit the 160 KB of LDS up to H = 64).
 //
 // L = 3, H <= 64 ("affine" route): between two consecutive FIRST-layer kinks every second-layer pre-activation is affine in x,
 // z_j(x) = A[s][j] x + B[s][j], and crossing the kink of unit k changes (A, B) by W2[j, k] (w1_k, b1_k).  The (H + 1) x H forms
@@ -35,8 +37,8 @@ constexpr int kBT = 1024;         // threads of the build workgroup: one workgro
 struct BuildParams {
   const float* w_first;  // [F, H]
   const float* b_first;  // [F, H] or null
-  const float* w_mid;    // [F, H, H] (L == 3) or null
-  const float* b_mid;    // [F, H] or null
+  const float* w_mid;    // [L - 2, F, H, H] (L >= 3) or null
+  const float* b_mid;    // [L - 2, F, H] or null
   const float* w_last;   // [F, C, H]
   const float* b_last;   // [F, C] or null
   int F, L, H, C;
@@ -81,34 +83,23 @@ __device__ __forceinline__ void rank_merge(const double* a, int na, const double
   }
 }
 
-// Second-layer pre-activations of a run of nodes (L == 3):  zt[ni, j] = b2_j + sum_k W2[j, k] relu(w1_k x_ni + b1_k).
-// The first-layer activations of a node are the same for all H units, so they are computed ONCE per node into h1
-// (float64, LDS) and every unit's dot product reads them back: one fma and two LDS reads per term instead of two
-// fmas, three float->double conversions and a select (the kernel is bound by float64 issue: 25 + 45 us of its 87 us
-// were these dot products).  Same operations in the same order per value as evaluating each unit on its own.
-// W2 sits TRANSPOSED in LDS (W2t[k*H + j]): lanes holding consecutive units read consecutive banks, the h1 reads
-// are broadcasts.  Ends with a barrier; h1 holds relu(layer 1) and zt the pre-activations of layer 2.
-template <typename NodeFn>
-__device__ __forceinline__ void eval_nodes(NodeFn node, int n0, int nn, int H, bool three, const float* w1, const float* b1,
-                                           const float* b2, const float* W2t, double* h1, double* zt, int tid) {
-  for (int it = tid; it < nn * H; it += kBT) {
-    const int ni = it / H, kk = it % H;
-    const double h = fma(static_cast<double>(w1[kk]), node(n0 + ni), static_cast<double>(b1[kk]));
-    h1[it] = h > 0.0 ? h : 0.0;
-  }
-  __syncthreads();
-  if (three && H % 2 == 0) {
-    // thread = (two nodes, two units): one 8-byte read of W2t and two broadcast reads of h1 feed four fma chains —
+// Pre-activations of the next hidden layer for a run of nodes:  zout[ni, j] = bias_j + sum_k W[j, k] hin[ni, k]  (hin = relu of
+// the layer before, float64, LDS).  W sits TRANSPOSED in LDS (Wt[k*H + j]): lanes holding consecutive units read consecutive
+// banks, the hin reads are broadcasts.  Ends with a barrier; zout must not alias hin.
+__device__ __forceinline__ void dense_layer(int nn, int H, const float* bias, const float* Wt, const double* hin, double* zout,
+                                            int tid) {
+  if (H % 2 == 0) {
+    // thread = (two nodes, two units): one 8-byte read of Wt and two broadcast reads of hin feed four fma chains —
     // 3 LDS instructions per 4 terms instead of 8 (the dot products are bound by the LDS issue rate), and the four
     // independent chains hide the float64 latency.  Each value still sees the same operations in the same order.
     const int H2 = H / 2, nn2 = (nn + 1) / 2;
     for (int it = tid; it < nn2 * H2; it += kBT) {
       const int np = it / H2, jp = it % H2;
       const int na = 2 * np, nb = 2 * np + 1 < nn ? 2 * np + 1 : na;
-      const double* ha = h1 + na * H;
-      const double* hb = h1 + nb * H;
-      const float2* wc = reinterpret_cast<const float2*>(W2t + 2 * jp);   // 8-byte aligned: H is even
-      double z00 = b2[2 * jp], z01 = b2[2 * jp + 1], z10 = z00, z11 = z01;
+      const double* ha = hin + na * H;
+      const double* hb = hin + nb * H;
+      const float2* wc = reinterpret_cast<const float2*>(Wt + 2 * jp);   // 8-byte aligned: H is even
+      double z00 = bias[2 * jp], z01 = bias[2 * jp + 1], z10 = z00, z11 = z01;
 #pragma unroll 8
       for (int kk = 0; kk < H; ++kk) {
         const float2 w = wc[kk * H2];
@@ -118,28 +109,57 @@ __device__ __forceinline__ void eval_nodes(NodeFn node, int n0, int nn, int H, b
         z10 = fma(static_cast<double>(w.x), b, z10);
         z11 = fma(static_cast<double>(w.y), b, z11);
       }
-      zt[na * H + 2 * jp] = z00;
-      zt[na * H + 2 * jp + 1] = z01;
+      zout[na * H + 2 * jp] = z00;
+      zout[na * H + 2 * jp + 1] = z01;
       if (nb != na) {
-        zt[nb * H + 2 * jp] = z10;
-        zt[nb * H + 2 * jp + 1] = z11;
+        zout[nb * H + 2 * jp] = z10;
+        zout[nb * H + 2 * jp + 1] = z11;
       }
     }
-    __syncthreads();
-  } else if (three) {
+  } else {
     for (int it = tid; it < nn * H; it += kBT) {
       const int ni = it / H, j = it % H;
-      const double* hrow = h1 + ni * H;
-      const float* wcol = W2t + j;
-      double z = b2[j];
+      const double* hrow = hin + ni * H;
+      const float* wcol = Wt + j;
+      double z = bias[j];
 #pragma unroll 8
       for (int kk = 0; kk < H; ++kk) z = fma(static_cast<double>(wcol[kk * H]), hrow[kk], z);
-      zt[it] = z;
+      zout[it] = z;
     }
-    __syncthreads();
   }
+  __syncthreads();
 }
 
+// Second-layer pre-activations of a run of nodes (L >= 3):  zt[ni, j] = b2_j + sum_k W2[j, k] relu(w1_k x_ni + b1_k).
+// The first-layer activations of a node are the same for all H units, so they are computed ONCE per node into h1
+// (float64, LDS) and every unit's dot product reads them back: one fma and two LDS reads per term instead of two
+// fmas, three float->double conversions and a select (the kernel is bound by float64 issue: 25 + 45 us of its 87 us
+// were these dot products).  Same operations in the same order per value as evaluating each unit on its own.
+// Ends with a barrier; h1 holds relu(layer 1) and zt the pre-activations of layer 2.
+template <typename NodeFn>
+__device__ __forceinline__ void eval_nodes(NodeFn node, int n0, int nn, int H, bool three, const float* w1, const float* b1,
+                                           const float* b2, const float* W2t, double* h1, double* zt, int tid) {
+  for (int it = tid; it < nn * H; it += kBT) {
+    const int ni = it / H, kk = it % H;
+    const double h = fma(static_cast<double>(w1[kk]), node(n0 + ni), static_cast<double>(b1[kk]));
+    h1[it] = h > 0.0 ? h : 0.0;
+  }
+  __syncthreads();
+  if (three) dense_layer(nn, H, b2, W2t, h1, zt, tid);
+}
+
+// relu in place over a tile of nn x H values; ends with a barrier
+__device__ __forceinline__ void relu_tile(double* z, int n, int tid) {
+  for (int it = tid; it < n; it += kBT) z[it] = z[it] > 0.0 ? z[it] : 0.0;
+  __syncthreads();
+}
+
+// DEEP: L == 4 (H <= 64).  The procedure with one more level — the third layer's pre-activations are affine between consecutive
+// breakpoints of layers 1 and 2, their sign changes on the merged breakpoints are the third layer's kinks — all by the dot
+// products of dense_layer (the interval forms of L == 3 are not carried over).  An instance of its own: everything it adds is
+// under `DEEP`, so the L in {2, 3} instance keeps its barriers and its arithmetic, operation for operation (eval_nodes now goes
+// through dense_layer, the same loops under another name).
+template <bool DEEP>
 __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* bp = reinterpret_cast<double*>(smem_raw);        // [kCap]
@@ -149,8 +169,15 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
   float* b1 = w1 + p.H;                                     // [H]
   float* b2 = b1 + p.H;                                     // [H]
   float* wl = b2 + p.H;                                     // [4 * H + 4] last layer's rows and biases of up to four channels
-  float* W2 = wl + 4 * p.H + 4;                             // [H*H] (L == 3), transposed: W2[k * H + j]
+  float* W2 = wl + 4 * p.H + 4;                             // [H*H] (L >= 3), transposed: W2[k * H + j]
   float* wl_wide = W2 + (p.L == 3 ? p.H * p.H : 0);        // [C][H + 1] + [C] (5..64 channels: p.wl_wide): rows padded against bank conflicts
+  float* W3 = nullptr;                                      // [H*H] (L == 4), transposed
+  float* b3 = nullptr;                                      // [H] (L == 4)
+  if constexpr (DEEP) {
+    W3 = W2 + p.H * p.H;
+    b3 = W3 + p.H * p.H;
+    wl_wide = b3 + p.H;
+  }
   double* h1 = reinterpret_cast<double*>(smem_raw + p.hid_offset);    // [chunk, H] relu(layer 1)
   double* zt = h1 + p.chunk * p.H;                                     // [chunk, H] layer-2 pre-activations
   // the affine route's use of the same region
@@ -170,7 +197,8 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
   for (int i = tid; i < H; i += kBT) {
     w1[i] = p.w_first[k * H + i];
     b1[i] = p.b_first ? p.b_first[k * H + i] : 0.f;
-    b2[i] = (p.L == 3 && p.b_mid) ? p.b_mid[k * H + i] : 0.f;
+    b2[i] = (p.L >= 3 && p.b_mid) ? p.b_mid[k * H + i] : 0.f;
+    if constexpr (DEEP) b3[i] = p.b_mid ? p.b_mid[(static_cast<int64_t>(p.F) + k) * H + i] : 0.f;
   }
   if (p.wl_wide) {
     for (int i = tid; i < C * H; i += kBT) wl_wide[(i / H) * (H + 1) + i % H] = p.w_last[static_cast<int64_t>(k) * C * H + i];
@@ -181,15 +209,19 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
     if (tid < C) wl[4 * H + tid] = p.b_last ? p.b_last[k * C + tid] : 0.f;
   }
   // W2 (16 KB at H = 64, one cold read per workgroup) is requested now and stored behind step 1, which needs only w1 and b1
-  const bool w2_ahead = p.L == 3 && H * H <= 4 * kBT;
+  const bool w2_ahead = !DEEP && p.L == 3 && H * H <= 4 * kBT;
   float w2r[4] = {0.f, 0.f, 0.f, 0.f};
   if (w2_ahead) {
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (tid + q * kBT < H * H) w2r[q] = p.w_mid[static_cast<int64_t>(k) * H * H + tid + q * kBT];
-  } else if (p.L == 3) {
+  } else if (p.L >= 3) {
     for (int i = tid; i < H * H; i += kBT)       // coalesced read of W[j][kk], transposed write
       W2[(i % H) * H + i / H] = p.w_mid[static_cast<int64_t>(k) * H * H + i];
+    if constexpr (DEEP) {
+      for (int i = tid; i < H * H; i += kBT)
+        W3[(i % H) * H + i / H] = p.w_mid[(static_cast<int64_t>(p.F) + k) * H * H + i];
+    }
   }
   if (tid == 0) { n_cand = 0; over = 0; n_bp = 0; }
   __syncthreads();
@@ -224,9 +256,12 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
   __syncthreads();
   const int P1 = n_bp;                                       // first-layer kinks (finite ones)
 
-  // ---- 2. second-layer kinks ------------------------------------------------------------------
-  if (p.L == 3) {
-    const int P = P1;
+  // ---- 2. second-layer kinks (DEEP: then the third layer's, on the merged breakpoints) ----------------------------------
+  const int levels = DEEP ? 2 : (p.L == 3 ? 1 : 0);
+  for (int level = 1; level <= levels; ++level) {
+    const int P = DEEP ? n_bp : P1;
+    // the torch route's cap per layer: of the cap breakpoints the first two layers may take two thirds
+    const int level_cap = (DEEP && level == 1) ? p.cap * 2 / 3 : p.cap;
     const double t_first = P ? bp[0] : 0.0, t_last = P ? bp[P - 1] : 0.0;
     const int n_nodes = P + 4;
     auto node = [&](int i) -> double {
@@ -253,7 +288,7 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
         if (dl != 0.0 && z_prev / dl > 0.0) push(e_prev - z_prev / dl * (e - e_prev));
       }
     };
-    if (p.affine) {
+    if (!DEEP && p.affine) {
       // the interval forms: z_j(x) = A[s][j] x + B[s][j] for x between first-layer kinks s - 1 and s.  Left of all kinks the
       // units with w1 < 0 are active (and the constant ones with b1 > 0); crossing the kink of unit k switches it on (w1 > 0)
       // or off.  float x float products are exact in float64: every step is one rounding per form.
@@ -338,20 +373,30 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
       for (int c0 = 0; c0 < n_nodes - 1; c0 += p.chunk - 1) {
         const int nn = n_nodes - c0 < p.chunk ? n_nodes - c0 : p.chunk;                    // nodes of this pass
         eval_nodes(node, c0, nn, H, true, w1, b1, b2, W2, h1, zt, tid);
+        const double* zl = zt;                                // this level's pre-activations
+        if (DEEP && level == 2) {
+          relu_tile(zt, nn * H, tid);
+          dense_layer(nn, H, b3, W3, zt, h1, tid);
+          zl = h1;
+        }
         for (int it = tid; it < (nn - 1) * H; it += kBT) {
           const int li = it / H + 1, j = it % H, i = c0 + li;                              // interval (i - 1, i)
-          roots(i, node(i - 1), node(i), zt[(li - 1) * H + j], zt[li * H + j]);
+          roots(i, node(i - 1), node(i), zl[(li - 1) * H + j], zl[li * H + j]);
         }
         __syncthreads();                                      // the tiles are rewritten by the next chunk
       }
     }
     __syncthreads();
     const int nc = n_cand < kCap ? n_cand : kCap;
-    if (P + nc > p.cap) { if (tid == 0) over = 1; }
+    if (P + nc > level_cap) { if (tid == 0) over = 1; }
     const int total = P + nc < kCap ? P + nc : kCap;
     rank_merge(bp, P, cand, total - P, tmp, tid);
     { double* t = bp; bp = tmp; tmp = t; }                  // (nothing reads bp beyond its n_bp entries from here on)
-    if (tid == 0) n_bp = total < p.cap ? total : p.cap;
+    if constexpr (DEEP) __syncthreads();                    // every thread has read this level's n_cand
+    if (tid == 0) {
+      n_bp = total < level_cap ? total : level_cap;
+      if constexpr (DEEP) n_cand = 0;
+    }
     __syncthreads();
   }
 
@@ -395,7 +440,7 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
     // take the output dot products
     // affine route, C <= 4: one pass, a thread per node keeps the output sums in registers; more channels: relu(z) goes to the
     // tile chunk by chunk and (node, channel) pairs take the dot products as below
-    const bool inline_out = p.affine && C <= 4;
+    const bool inline_out = !DEEP && p.affine && C <= 4;
     const int step = inline_out ? Pn + 2 : p.chunk;
     for (int n0 = 0; n0 < Pn + 2; n0 += step) {
       const int nn = Pn + 2 - n0 < step ? Pn + 2 - n0 : step;
@@ -446,7 +491,7 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
         __syncthreads();
         continue;
       }
-      if (p.affine) {
+      if (!DEEP && p.affine) {
         for (int ni = wave; ni < nn; ni += kBT / 64) {      // wave = node, lane = unit: relu(z) into the tile
           const int g = n0 + ni;
           const double x = tnode(g);
@@ -462,25 +507,36 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
         }
         __syncthreads();
       } else {
-        eval_nodes(tnode, n0, nn, H, p.L == 3, w1, b1, b2, W2, h1, zt, tid);
+        eval_nodes(tnode, n0, nn, H, p.L >= 3, w1, b1, b2, W2, h1, zt, tid);
         if (mark) {
           for (int it = tid; it < nn * H; it += kBT) {
             const int g = n0 + it / H, j = it % H;
             if (g < 1 || g > P) continue;
             bool zero = w1[j] != 0.f && fma(static_cast<double>(w1[j]), bp[g - 1], static_cast<double>(b1[j])) == 0.0;
-            if (p.L == 3) zero |= zt[it] == 0.0;
+            if (p.L >= 3) zero |= zt[it] == 0.0;
             if (zero) on_kink[g - 1] = 1;
           }
         }
       }
       const double* hid = h1;                               // L == 2: relu(layer 1) is the last hidden layer
-      if (p.L == 3) {
-        if (!p.affine) {
+      if (p.L >= 3) {
+        if (DEEP || !p.affine) {
           if (mark) __syncthreads();
-          for (int it = tid; it < nn * H; it += kBT) zt[it] = zt[it] > 0.0 ? zt[it] : 0.0;
-          __syncthreads();
+          relu_tile(zt, nn * H, tid);
         }
         hid = zt;
+      }
+      if constexpr (DEEP) {                                  // the third hidden layer, into the tile of the first
+        dense_layer(nn, H, b3, W3, zt, h1, tid);
+        if (mark) {
+          for (int it = tid; it < nn * H; it += kBT) {
+            const int g = n0 + it / H;
+            if (g >= 1 && g <= P && h1[it] == 0.0) on_kink[g - 1] = 1;
+          }
+          __syncthreads();
+        }
+        relu_tile(h1, nn * H, tid);
+        hid = h1;
       }
       if (p.wl_wide) {                                     // (uniform) the last layer's rows from LDS
         for (int it = tid; it < nn * C; it += kBT) {
@@ -629,12 +685,14 @@ extern "C" size_t gnan_pwl_build_scratch_bytes(int32_t F, int32_t C, int32_t cap
 extern "C" int gnan_pwl_build(const gnan_pwl_build_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "pwl_build: null args");
   GNAN_REQUIRE(a->F >= 1 && a->C >= 1 && a->H >= 1, "pwl_build: bad sizes");
-  if (a->L != 2 && a->L != 3) return gnan::fail(GNAN_ERR_UNSUPPORTED, "pwl_build: kernel covers L in {2, 3} (got %d)", a->L);
+  if (a->L < 2 || a->L > 4) return gnan::fail(GNAN_ERR_UNSUPPORTED, "pwl_build: kernel covers L in {2, 3, 4} (got %d)", a->L);
   if (a->H > 128) return gnan::fail(GNAN_ERR_UNSUPPORTED, "pwl_build: hidden width %d > 128", a->H);
+  // L == 4: two hidden matrices and the node tiles next to the breakpoints fit the 160 KB of LDS up to H = 64 only
+  if (a->L == 4 && a->H > 64) return gnan::fail(GNAN_ERR_UNSUPPORTED, "pwl_build: L == 4 covers hidden width <= 64 (got %d)", a->H);
   GNAN_REQUIRE(a->cap >= 1 && a->cap <= kCap, "pwl_build: cap must be in [1, %d]", kCap);
   GNAN_REQUIRE(a->w_first && a->w_last && a->anchor && a->val && a->slope && a->off && a->overflow && a->scratch,
                "pwl_build: null pointer");
-  if (a->L == 3) GNAN_REQUIRE(a->w_mid != nullptr, "pwl_build: L == 3 needs w_mid");
+  if (a->L >= 3) GNAN_REQUIRE(a->w_mid != nullptr, "pwl_build: L >= 3 needs w_mid");
   GNAN_REQUIRE((a->index_table == nullptr && a->index_key == nullptr && a->index_range == nullptr) ||
                    (a->index_table && a->index_key && a->index_range &&
                     (a->index_buckets == 256 || a->index_buckets == 512 || a->index_buckets == 1024 || a->index_buckets == 2048)),
@@ -652,7 +710,9 @@ extern "C" int gnan_pwl_build(const gnan_pwl_build_args* a, gnan_stream_t stream
   p.val = p.anchor + static_cast<size_t>(a->F) * (a->cap + 1);
   p.slope = p.val + static_cast<size_t>(a->F) * (a->cap + 1) * a->C;
   p.pieces = reinterpret_cast<int32_t*>(p.slope + static_cast<size_t>(a->F) * (a->cap + 1) * a->C);
-  size_t lds = 3 * kCap * sizeof(double) + (7 * static_cast<size_t>(a->H) + 4 + (a->L == 3 ? static_cast<size_t>(a->H) * a->H : 0)) * sizeof(float);
+  const bool deep = a->L == 4;                            // W2 | W3 | b3 behind the small vectors
+  size_t lds = 3 * kCap * sizeof(double) + (7 * static_cast<size_t>(a->H) + 4 + (a->L == 3 ? static_cast<size_t>(a->H) * a->H : 0) +
+                                            (deep ? 2 * static_cast<size_t>(a->H) * a->H + a->H : 0)) * sizeof(float);
   // 5..64 channels: the last layer's rows (padded) behind W2, if everything still fits 160 KB
   const size_t wide_floats = static_cast<size_t>(a->C) * (a->H + 1) + a->C;
   const size_t tiles_guess = (a->L == 3 && a->H <= 64)
@@ -668,12 +728,14 @@ extern "C" int gnan_pwl_build(const gnan_pwl_build_args* a, gnan_stream_t stream
   if (p.affine) lds += (2 * (H_ + 1) * (H_ + 1) + p.chunk * H_ + H_) * sizeof(double) + H_ * sizeof(int);
   else lds += 2 * static_cast<size_t>(p.chunk) * a->H * sizeof(double);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pwl_build_kernel),
+    hipError_t e = hipFuncSetAttribute(deep ? reinterpret_cast<const void*>(pwl_build_kernel<true>)
+                                            : reinterpret_cast<const void*>(pwl_build_kernel<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "pwl_build: hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(pwl_build_kernel, dim3(a->F), dim3(kBT), lds, st, p);
+  if (deep) hipLaunchKernelGGL(pwl_build_kernel<true>, dim3(a->F), dim3(kBT), lds, st, p);
+  else hipLaunchKernelGGL(pwl_build_kernel<false>, dim3(a->F), dim3(kBT), lds, st, p);
   if (int rc = gnan::check_launch("pwl_build_kernel")) return rc;
   CompactParams c;
   c.anchor_p = p.anchor; c.val_p = p.val; c.slope_p = p.slope; c.pieces = p.pieces;

@@ -584,7 +584,7 @@ HIP_TABLE_GRADS = True   # table path: parameter gradients by gnan_fpwl_param_gr
 
 
 def _table_grads_applies(L: int, H: int, C: int) -> bool:
-    return HIP_TABLE_GRADS and C <= 4096 and ((L == 3 and H <= 64) or (L == 2 and H <= 128))
+    return HIP_TABLE_GRADS and C <= 4096 and ((L in (3, 4) and H <= 64) or (L == 2 and H <= 128))
 
 
 def _grad_outputs(keep, dests):
@@ -636,10 +636,10 @@ def _fpwl_param_grads_launch(params, t, moments, L, H, C, F, dests=None):
         off=_lib.ptr(t.off), anchor=_lib.ptr(t.anchor), moments=_lib.ptr(M),
         moments_fixed=_lib.ptr(moments[0]) if fixed else None, scales=_lib.ptr(moments[1]) if fixed else None,
         w_first=_lib.ptr(keep[0]), b_first=_lib.ptr(keep[1]),
-        w_mid=None if keep[2] is None else _lib.ptr(keep[2][0]), b_mid=None if keep[3] is None else _lib.ptr(keep[3][0]),
+        w_mid=_lib.ptr(keep[2]), b_mid=_lib.ptr(keep[3]),                  # the whole stacks: [L-2, F, H, H] / [L-2, F, H]
         w_last=_lib.ptr(keep[4]), b_last=_lib.ptr(keep[5]), F=F, L=L, H=H, C=C, max_pieces=int(t.max_pieces),
         d_w_first=_lib.ptr(outs[0]), d_b_first=_lib.ptr(outs[1]),
-        d_w_mid=None if outs[2] is None else _lib.ptr(outs[2][0]), d_b_mid=None if outs[3] is None else _lib.ptr(outs[3][0]),
+        d_w_mid=_lib.ptr(outs[2]), d_b_mid=_lib.ptr(outs[3]),
         d_w_last=_lib.ptr(outs[4]), d_b_last=_lib.ptr(outs[5]))
     _lib.check(_lib.lib().gnan_fpwl_param_grads(a, _lib.stream_of(t.anchor)), "gnan_fpwl_param_grads")
     return outs

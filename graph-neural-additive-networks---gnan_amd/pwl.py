@@ -298,7 +298,8 @@ INDEX_IN_BUILD = True        # the look-up's direct-index tables out of the buil
 def _build_tables_hip(p, lazy: bool = False, pinned_slot: int = 0, buffers=None, index_request=None):
     """Tables by TWO kernel launches (``gnan_pwl_build``: a workgroup per feature finds the kinks and tabulates the
     network in float64, LDS-resident; a second tiny kernel packs the features back to back) and one
-    device->host copy of the F+1 offsets.  Covers L in {2, 3}, H <= 128; same result as :func:`_build_padded`."""
+    device->host copy of the F+1 offsets.  Covers L in {2, 3} with H <= 128 and L == 4 with H <= 64
+    (:func:`hip_build_applies`); same result as :func:`_build_padded`."""
     from . import _lib
     dev = p.w_last.device
     F, C = p.F, p.C
@@ -307,10 +308,9 @@ def _build_tables_hip(p, lazy: bool = False, pinned_slot: int = 0, buffers=None,
         buffers = table_buffers(p)                                    # (off[F+1] | overflow: every entry is written by the build)
     anchor, val, slope, meta, scratch = buffers
     keepalive = [t if t is None else t.detach().float().contiguous() for t in p[:6]]
-    w_mid = keepalive[2][0] if keepalive[2] is not None else None      # [1, F, H, H] -> [F, H, H]
-    b_mid = keepalive[3][0] if keepalive[3] is not None else None
-    a = _lib.PwlBuildArgs(w_first=_lib.ptr(keepalive[0]), b_first=_lib.ptr(keepalive[1]), w_mid=_lib.ptr(w_mid),
-                          b_mid=_lib.ptr(b_mid), w_last=_lib.ptr(keepalive[4]), b_last=_lib.ptr(keepalive[5]),
+    # (the mid layers travel as the whole stacks, [L-2, F, H, H] / [L-2, F, H])
+    a = _lib.PwlBuildArgs(w_first=_lib.ptr(keepalive[0]), b_first=_lib.ptr(keepalive[1]), w_mid=_lib.ptr(keepalive[2]),
+                          b_mid=_lib.ptr(keepalive[3]), w_last=_lib.ptr(keepalive[4]), b_last=_lib.ptr(keepalive[5]),
                           F=F, L=p.L, H=p.H, C=C, cap=cap, anchor=_lib.ptr(anchor), val=_lib.ptr(val),
                           slope=_lib.ptr(slope), off=_lib.ptr(meta), overflow=meta[F + 1:].data_ptr(),
                           scratch=_lib.ptr(scratch), scratch_bytes=scratch.numel() * 8)
@@ -408,11 +408,11 @@ def covers(spec: PwlTables, exact: PwlTables) -> bool:
     return spec.features_per_group * exact.max_pieces <= spec.max_group_pieces
 
 
-BUILD_BACKEND = "auto"       # "auto": HIP kernel where it applies, else the (graph-replayed) torch restatement; "torch"
+BUILD_BACKEND = "auto"       # "auto": HIP kernel where it applies (L in {2, 3}; L == 4 up to H = 64), else the (graph-replayed) torch restatement; "torch"
 
 
 def hip_build_applies(p) -> bool:
-    return BUILD_BACKEND == "auto" and p.w_last.is_cuda and p.L in (2, 3) and 1 <= p.H <= 128
+    return BUILD_BACKEND == "auto" and p.w_last.is_cuda and ((p.L in (2, 3) and 1 <= p.H <= 128) or (p.L == 4 and 1 <= p.H <= 64))
 
 
 @torch.no_grad()

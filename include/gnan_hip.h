@@ -26,7 +26,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: exactly the functions declared in this header are exported */
 #pragma GCC visibility push(default)
 
-#define GNAN_ABI_VERSION 50
+#define GNAN_ABI_VERSION 51
 
 typedef void* gnan_stream_t; /* hipStream_t */
 
@@ -312,8 +312,9 @@ int gnan_fpwl_moment_scales(const gnan_moment_scales_args* a, gnan_stream_t stre
  * d/dtheta ( <M0, f(anchor)> + <M1, slope> ): one reverse pass for the value and one for the slope per piece, float64,
  * one workgroup per feature, no atomics (bit-reproducible).  Moments as gnan_fpwl_moments wrote them (`moments`) or in
  * fixed point (`moments_fixed` + the `scales` they were accumulated with); tables as gnan_pwl_build wrote them (only
- * off / anchor are read).  Weight and gradient layouts as gnan_fmlp_bwd_args.  Covers L in {2, 3}, H <= 64 (L == 3) /
- * 128 (L == 2), C <= 64. */
+ * off / anchor are read).  Weight and gradient layouts as gnan_fmlp_bwd_args, the mid layers stacked as in gnan_fmlp_args:
+ * w_mid / d_w_mid [L-2, F, H, H], b_mid / d_b_mid [L-2, F, H].  Covers L == 2 with H <= 128 and L in {3, 4} with H <= 64 (L == 4:
+ * ABI 51), C <= 64; anything else is GNAN_ERR_UNSUPPORTED before a launch. */
 typedef struct gnan_fpwl_grad_args {
   const int32_t* off;           /* [F+1] */
   const float* anchor;          /* [T] */
@@ -322,16 +323,16 @@ typedef struct gnan_fpwl_grad_args {
   const double* scales;         /* [2], device memory (with moments_fixed) */
   const float* w_first;         /* [F, H] */
   const float* b_first;         /* [F, H] or NULL */
-  const float* w_mid;           /* [F, H, H] (L == 3) */
-  const float* b_mid;           /* [F, H] or NULL */
+  const float* w_mid;           /* [L-2, F, H, H] (L >= 3) */
+  const float* b_mid;           /* [L-2, F, H] or NULL */
   const float* w_last;          /* [F, C, H] */
   const float* b_last;          /* [F, C] or NULL */
   int32_t F, L, H, C;
   int32_t max_pieces;           /* >= max_k (off[k+1] - off[k]); sizes the list of non-empty pieces in LDS */
   float* d_w_first;
   float* d_b_first;
-  float* d_w_mid;
-  float* d_b_mid;
+  float* d_w_mid;               /* [L-2, F, H, H] */
+  float* d_b_mid;               /* [L-2, F, H]; NULL exactly where b_mid is */
   float* d_w_last;
   float* d_b_last;
 } gnan_fpwl_grad_args;
@@ -339,15 +340,17 @@ typedef struct gnan_fpwl_grad_args {
 int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t stream);
 
 /* Build the look-up tables on the device: one workgroup per feature finds the kinks of f_k (zero crossings
- * of its hidden pre-activations, float64) and tabulates the network at them.  Covers L in {2, 3}, H <= 128.
+ * of its hidden pre-activations, float64) and tabulates the network at them.  Covers L in {2, 3} with H <= 128 and
+ * L == 4 with H <= 64 (ABI 51; two hidden matrices next to the breakpoints do not fit LDS beyond that: GNAN_ERR_UNSUPPORTED).
+ * L == 4: of the `cap` breakpoints the first two layers may take cap * 2 / 3 (the per-layer cap of the torch restatement).
  * Outputs are the compact tables gnan_fpwl_fwd reads (features back to back, off[k] = first piece of feature
  * k, capacity F*(cap+1) pieces); *overflow is set if a feature has more than `cap` kinks (the caller then
  * falls back).  Weight layout as gnan_fmlp_args. */
 typedef struct gnan_pwl_build_args {
   const float* w_first;   /* [F, H] */
   const float* b_first;   /* [F, H] or NULL */
-  const float* w_mid;     /* [F, H, H] when L == 3 */
-  const float* b_mid;     /* [F, H] or NULL */
+  const float* w_mid;     /* [L-2, F, H, H] when L >= 3 */
+  const float* b_mid;     /* [L-2, F, H] or NULL */
   const float* w_last;    /* [F, C, H] */
   const float* b_last;    /* [F, C] or NULL */
   int32_t F, L, H, C;
