@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from . import functional as Fn
 from .functional import StackedMLP
-from .graph import HopGraph
+from .graph import LONG_ROW_THRESHOLD, HopGraph
 
 DENSE_SLICE_MAX_ROWS = 16384  # dense layout: slice every row over workgroups while row blocks alone would not fill the GPU
 DENSE_SLICE_MIN_COLS = 512
@@ -92,6 +92,9 @@ CLASSED_MIN_ROW_BYTES = 128    # ... from operand rows of this many bytes (fp32 
 CLASSED_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs
 SHORT_ROW_TILES = True         # wide forward over a degree-sorted copy: rows of at most SHORT_ROW_LMAX pairs in tiles of many rows per wave
 SHORT_ROW_LMAX = 4             # (gnan_spmm_args.short_*; the library takes them where its kernel variant serves the call)
+CLASSED_ROWS = True            # reference-order inference (self_sum): the row walk's longer rows a lane group per (row, column class)
+CLASSED_ROWS_MIN_NNZ = 1 << 24     # ... on graphs of at least this many pairs (its own gate: not CLASSED_MIN_NNZ)
+CLASSED_ROWS_MIN_PAIRS = 33        # ... rows of this many pairs up to the hub threshold (HopGraph.classed_row_plan); swept on C4: DESIGN.md 4.1
 
 
 def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -234,6 +237,14 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         if self_sum.dtype != torch.float32 or self_sum.dim() != 2 or self_sum.shape[1] != n_out or not self_sum.is_contiguous():
             raise ValueError("self_sum must be a contiguous float32 [parts, n_rows] tensor")
         a.self_sum, a.self_parts = _lib.ptr(self_sum), int(self_sum.shape[0])
+        if (CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
+                and s_total is not None and S.dtype == torch.float32 and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
+            # the rows between the tiles and the hubs in segments of one column class each, a class per XCD
+            rows = g.classed_row_plan(max(CLASSED_ROWS_MIN_PAIRS, SHORT_ROW_LMAX + 1))
+            if rows is not None:
+                a.seg_index, a.seg_start, a.seg_row = _lib.ptr(rows.index), _lib.ptr(rows.seg_start), _lib.ptr(rows.seg_row)
+                a.cls_seg_ptr, a.seg_mask = _lib.ptr(rows.cls_seg_ptr), _lib.ptr(rows.mask)
+                a.seg_q_lo, a.seg_q_hi, a.n_seg, a.seg_max_per_class = rows.q_lo, rows.q_hi, rows.n_seg, rows.max_per_class
     need = _lib.lib().gnan_spmm_fwd_workspace_bytes(a)
     ws = None
     if need:

@@ -15,7 +15,8 @@
 //                   the slices in a fixed order (bit-reproducible, no float atomics).
 // HBM-bound: per edge 4 B col + 1 B code + W*4 B gathered row; per row rowptr + W*4 B store.
 //
-// This file: the forward's entry points and routing, the persistent narrow kernel, the hub rows' fix-up and the shell sums.
+// This file: the forward's entry points and routing, the persistent narrow kernel, the hub rows' fix-up, the classed rows' combine pass
+// and the shell sums.
 // spmm_kernel itself is csrc/spmm_fwd_body.hpp (an object per VEC), the gradients are csrc/spmm_grad.hip, what they share is
 // csrc/spmm_common.hpp.
 #include "spmm_common.hpp"
@@ -285,6 +286,42 @@ int launch_fixup(const Params& p, hipStream_t st) {
   return gnan::check_launch("spmm_long_fixup_kernel");
 }
 
+// combine: the classed rows' segments (seg_body, csrc/spmm_fwd_body.hpp) -> the rows' read-out.  One thread per classed row:
+//   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))))
+// p_c the row's partial of class c where the mask says it exists (else 0: the workspace is never cleared), T the sum of s_total in
+// float64 rounded once (a float32 chain over W columns would put more roundings on the rest term than a 5-pair row's bound counts),
+// a_i as the other epilogues read it.  One fixed shape per row: bit-reproducible.
+__global__ __launch_bounds__(256) void spmm_seg_combine_kernel(const Params p) {
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= p.seg_q_hi - p.seg_q_lo) return;
+  const int64_t q = p.seg_q_lo + r;
+  const int64_t o = out_row(p, q, q);
+  const unsigned mask = p.seg_mask[r];
+  const float4 a = *reinterpret_cast<const float4*>(p.seg_partial + r * 8);
+  const float4 b = *reinterpret_cast<const float4*>(p.seg_partial + r * 8 + 4);
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  float c[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) c[k] = (mask >> k) & 1u ? v[k] : 0.f;
+  float y = ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
+  double T = 0.0;
+  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
+  const int rest = p.D - 1;
+  const SmallW sw = small_weights(p, q);
+  const float w_rest = sw.pick(rest);
+  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
+  y = fmaf(w_rest, static_cast<float>(T), y);
+  y = fmaf(w_self, self_term(p, o), y);
+  p.Y[o * p.y_stride] = y;
+}
+
+int launch_seg_combine(const Params& p, hipStream_t st) {
+  if (p.seg_index == nullptr) return GNAN_OK;
+  const int64_t n = p.seg_q_hi - p.seg_q_lo;
+  hipLaunchKernelGGL(spmm_seg_combine_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, p);
+  return gnan::check_launch("spmm_seg_combine_kernel");
+}
+
 // can the persistent hot-row kernel take this call?  (what the host wrapper sets up: functional.spmm_launch, narrow walk)
 bool hot_kernel_applies(const gnan_spmm_args* a) {
   const int W = a->W;
@@ -425,8 +462,10 @@ int pick_route(const gnan_spmm_args* a, Route* r) {
 }  // namespace
 
 extern "C" size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a) {
-  if (!a || a->n_long <= 0) return 0;
-  return static_cast<size_t>(a->n_slices) * 2 * static_cast<size_t>(a->W) * sizeof(float);
+  if (!a) return 0;
+  size_t floats = seg_partial_offset(a);
+  if (a->seg_index && a->seg_q_hi > a->seg_q_lo) floats += static_cast<size_t>(a->seg_q_hi - a->seg_q_lo) * 8;   // the classed rows' partials
+  return floats * sizeof(float);
 }
 
 extern "C" int gnan_spmm_shell_sums(const gnan_spmm_args* a, gnan_stream_t stream) {
@@ -455,7 +494,8 @@ extern "C" int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_
   out->kernel = r.hot ? GNAN_SPMM_KERNEL_HOT : GNAN_SPMM_KERNEL_ROWS;
   if (r.hot) return GNAN_OK;
   Params p = make_params(a);
-  if (int rc = plan_tiles(p, r.vec, r.lpr, r.dense, r.smalld)) return rc;
+  if (int rc = plan_tiles(p, r.vec, r.lpr, r.dense, r.smalld, a->seg_max_per_class)) return rc;
+  out->n_seg_blocks = p.n_seg_blocks; out->n_segs = p.n_seg_blocks > 0 ? a->n_seg : 0;
   out->classed = p.cls_index != nullptr;
   out->n_slice_blocks = p.n_slice_blocks; out->n_tile_blocks = p.n_tile_blocks; out->n_tiles = p.n_tiles;
   out->row_q0 = p.row_q0;
@@ -478,5 +518,7 @@ extern "C" int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream) {
   if (r.hot) return a->W == 1 ? launch_hot<1>(p, st) : (a->W == 2 ? launch_hot<2>(p, st) : launch_hot<4>(p, st));
   const int rc = r.vec == 8 ? gnan::launch_lpr<8>(a, r.lpr, r.dense, r.smalld, st)
                             : (r.vec == 4 ? gnan::launch_lpr<4>(a, r.lpr, r.dense, r.smalld, st) : gnan::launch_lpr<1>(a, r.lpr, r.dense, r.smalld, st));
-  return rc ? rc : launch_fixup(p, st);
+  if (rc) return rc;
+  if (int rc2 = launch_fixup(p, st)) return rc2;
+  return launch_seg_combine(p, st);
 }

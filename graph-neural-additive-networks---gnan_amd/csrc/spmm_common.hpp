@@ -62,6 +62,17 @@ struct Params {
   // the rows' self term from outside (gnan_spmm_args.self_sum): [self_parts][n_rows] by output row, added in the read-out's epilogue
   const float* self_sum;
   int self_parts;
+  // classed row segments (gnan_spmm_args.seg_*; the SELF instance alone reads them): rows [seg_q_lo, seg_q_hi) of the sorted copy are
+  // taken a (row, column class) segment per lane group by the n_seg_blocks workgroups behind the slice blocks — workgroup b of that
+  // range takes class b & 7 — and the row blocks skip them; a segment's float goes to seg_partial[(q - seg_q_lo) * 8 + class]
+  const int32_t* seg_index;
+  const int64_t* seg_start;
+  const int32_t* seg_row;
+  const int32_t* cls_seg_ptr;
+  const uint8_t* seg_mask;
+  float* seg_partial;
+  int64_t seg_q_lo, seg_q_hi;
+  int n_seg_blocks;
 };
 
 __device__ __forceinline__ int64_t load_rowptr(const Params& p, int64_t i) {
@@ -378,6 +389,16 @@ inline int validate(const gnan_spmm_args* a) {
                    static_cast<long long>(a->short_pair[L]));
     }
   }
+  if (a->seg_index) {
+    // (one pair of requirements: the fields are read by the self_sum instance alone, over a well-formed plan)
+    if (!(a->self_sum && a->s_total && a->short_lmax > 0))
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: classed row segments are served on the self_sum route (short-row runs declared, "
+                        "s_total set) only");
+    GNAN_REQUIRE(a->seg_start && a->seg_row && a->cls_seg_ptr && a->seg_mask && a->n_seg > 0 && a->seg_max_per_class > 0 &&
+                 a->seg_max_per_class <= a->n_seg && a->seg_q_lo >= a->short_row[a->short_lmax + 1] && a->seg_q_lo < a->seg_q_hi &&
+                 a->seg_q_hi <= a->n_rows && a->D <= 8,
+                 "spmm: incomplete classed row plan (segments, a class table, a mask, rows behind the tiled runs within n_rows)");
+  }
   if (a->n_long > 0) {
     GNAN_REQUIRE(a->rowptr != nullptr || (a->n_long == a->n_rows && a->long_threshold == 0),
                  "spmm: a row plan for the dense layout must slice every row (n_long == n_rows, long_threshold == 0)");
@@ -390,6 +411,11 @@ inline int validate(const gnan_spmm_args* a) {
     }
   }
   return GNAN_OK;
+}
+
+// floats of the hub slices' partials at the head of the forward's workspace; the classed rows' [seg_q_hi - seg_q_lo, 8] floats follow
+inline size_t seg_partial_offset(const gnan_spmm_args* a) {
+  return a->n_long > 0 ? static_cast<size_t>(a->n_slices) * 2 * static_cast<size_t>(a->W) : 0;
 }
 
 inline Params make_params(const gnan_spmm_args* a) {
@@ -421,6 +447,15 @@ inline Params make_params(const gnan_spmm_args* a) {
   const bool runs = a->short_lmax > 0 && a->short_lmax <= GNAN_SHORT_LMAX && a->short_row && a->short_pair;  // (validate() checks them)
   p.self_sum = a->self_sum; p.self_parts = a->self_sum ? a->self_parts : 0;
   p.short_lmax = runs ? a->short_lmax : 0;
+  p.seg_index = a->seg_index; p.seg_start = a->seg_start; p.seg_row = a->seg_row; p.cls_seg_ptr = a->cls_seg_ptr;
+  p.seg_mask = a->seg_mask;
+  p.seg_q_lo = p.seg_q_hi = 0;
+  p.n_seg_blocks = 0;
+  p.seg_partial = nullptr;
+  if (a->seg_index) {   // (behind the hub slices' [n_slices, 2, W] partials: seg_partial_offset)
+    p.seg_q_lo = a->seg_q_lo; p.seg_q_hi = a->seg_q_hi;
+    p.seg_partial = static_cast<float*>(a->workspace) + seg_partial_offset(a);
+  }
   p.n_tile_blocks = p.n_tiles = 0;
   p.row_q0 = 0;
   for (int L = 0; L <= GNAN_SHORT_LMAX + 1; ++L) p.short_row[L] = L <= p.short_lmax + 1 && runs ? a->short_row[L] : 0;
@@ -443,7 +478,7 @@ inline void pick_tiling(const gnan_spmm_args* a, const float* out, int64_t out_s
 
 // The tile partition of a launch of the <vec, lpr> variant: which of the declared short-row runs the kernel takes in tiles, and where
 // each run's tiles start.  The launch and gnan_spmm_fwd_describe both call this (and nothing else decides it).
-inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld) {
+inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld, int seg_max = 0) {
   const int G = kWave / lpr;
   // short-row tiles: the packed small-D forward over a degree-sorted copy, one pass of the lane group over the columns
   if (short_tiles_serve(vec, lpr, smalld, p.packed, p.s_by_code) && p.short_lmax > 0 && !dense && p.scatter_out == 2 &&
@@ -460,6 +495,16 @@ inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld) {
     p.row_q0 = p.short_row[p.short_lmax + 1];
   } else {
     p.short_lmax = 0;
+  }
+  if (p.seg_index) {
+    // classed row segments: the route validate() admits runs the tiled SELF instance; G segments per wave, 4 waves per workgroup,
+    // as many workgroups per class as the longest class needs, interleaved so that blockIdx & 7 is the class
+    if (!(p.short_lmax > 0 && p.self_sum && p.seg_q_lo >= p.row_q0))
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: classed row segments need the tiled self_sum variant (fp32 rows of 16 lanes or more)");
+    const int64_t per = 4 * static_cast<int64_t>(G);
+    const int64_t nb = 8 * ((static_cast<int64_t>(seg_max) + per - 1) / per);
+    if (nb > 0x3fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many row segments for one launch");
+    p.n_seg_blocks = static_cast<int>(nb);
   }
   return GNAN_OK;
 }

@@ -1,4 +1,4 @@
-// The wide forward's kernel and its launch: row blocks, short-row tiles and hub-row slices of spmm_kernel<VEC, LPR, ...>
+// The wide forward's kernel and its launch: row blocks, short-row tiles, classed row segments and hub-row slices of spmm_kernel<VEC, LPR, ...>
 // (the mapping: csrc/spmm.hip).  Compiled once per VEC — csrc/spmm_fwd_v1.hip, _v4 and _v8 instantiate gnan::launch_lpr<VEC>
 // over this body — so that the 100 instances build as three objects side by side.
 #pragma once
@@ -23,7 +23,10 @@ __device__ __forceinline__ void rows_body(const Params& p, const int64_t block_i
   const int wave = threadIdx.x / kWave;
   const int sub = lane % LPR;
   const int slot = lane / LPR;
-  const int64_t q = p.row_q0 + (block_id * (blockDim.x / kWave) + wave) * G + slot;
+  int64_t q = p.row_q0 + (block_id * (blockDim.x / kWave) + wave) * G + slot;
+  if constexpr (SELF) {   // rows [seg_q_lo, seg_q_hi) are taken in segments (seg_body); both are 0 without a classed row plan
+    if (q >= p.seg_q_lo) q += p.seg_q_hi - p.seg_q_lo;
+  }
   if (q >= p.n_rows) return;
   const int64_t i = adj_row(p, q);
   int64_t lo, hi, code_base;
@@ -348,6 +351,90 @@ __device__ __forceinline__ void short_tiles(const Params& p, int t) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// classed row segments: one lane group per (row, column class) of the rows the classed row plan names
+// ---------------------------------------------------------------------------------------------
+// The row walk spreads every often-listed operand row over all eight L2s (a workgroup's XCD is blockIdx & 7, its rows list any
+// column).  Here the pairs of row q whose column falls in class c = col & 7 are one segment, the segments of class c are taken by the
+// workgroups with blockIdx & 7 == c, and so each XCD's L2 holds one eighth of the hot rows.  The read-out is fused on this route
+// (reduce_cr == 1), so a segment's result is ONE float — the lane group's share of the row's feature sum — stored at
+// seg_partial[(q - seg_q_lo) * 8 + c]; the combine pass (spmm_seg_combine_kernel, csrc/spmm.hip) adds a row's classes, the rest term
+// and the self term.  Weights as rows_body folds them under SMALLD; 16 index entries per round, four gathers in flight,
+// no branch around a gather: a slot past the segment's end reads the segment's last row again (an L1 hit) and is dropped by a select.
+// No LDS, no barrier, no atomics; the lane butterfly's first four steps are DPP row operations.
+template <int CTRL>
+__device__ __forceinline__ float dpp_row(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+template <int VEC, int LPR>
+__device__ __forceinline__ void seg_body(const Params& p, const int blk) {
+  static_assert(LPR >= 16 && VEC == 4, "a DPP row per lane group, one index entry per lane and round");
+  constexpr int G = kWave / LPR;
+  constexpr int IW = 16;    // index entries per round
+  constexpr int FLY = 4;    // gathers in flight per lane: 8 spills 8 B of scratch at 8 waves/SIMD (64 VGPRs), 4 fits (63)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int sub = lane % LPR;
+  const int slot = lane / LPR;
+  const int cls = blk & 7;
+  const int s = p.cls_seg_ptr[cls] + ((blk >> 3) * 4 + wave) * G + slot;
+  if (s >= p.cls_seg_ptr[cls + 1]) return;   // (the whole group)
+  const int64_t q = p.seg_row[s];
+  const int64_t lo = p.seg_start[s];
+  const int n = static_cast<int>(p.seg_start[s + 1] - lo);     // (a row of at most long_threshold pairs)
+  const int32_t* idx = p.seg_index + lo;
+  const int rest = p.D - 1;
+  SmallW sw = small_weights(p, q);           // (scatter_out 2: slot q reads adjacency row q)
+  {
+    const float w_rest = sw.pick(rest);      // (validate(): s_total is set)
+#pragma unroll
+    for (int d = 0; d < 4; ++d) sw.w[d] = d < rest ? sw.w[d] - w_rest : 0.f;
+  }
+  const bool col_ok = sub * VEC < p.W;
+  const float* Sl = static_cast<const float*>(p.S) + (col_ok ? sub * VEC : 0);   // (a lane past the columns reads column 0, dropped below)
+  Vec<VEC> acc;
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) acc.v[v] = 0.f;
+  for (int base = 0; base < n; base += IW) {
+    const int m = n - base < IW ? n - base : IW;
+    int ent = 0;
+    if (sub < m) ent = idx[base + sub];
+#pragma unroll
+    for (int j0 = 0; j0 < IW; j0 += FLY) {
+      if (j0 >= m) break;
+      Vec<VEC> sv[FLY];
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) {
+        const int j = j0 + u < m ? j0 + u : m - 1;
+        const unsigned en = static_cast<unsigned>(__shfl(ent, j, LPR));
+        sv[u] = load_vec<VEC>(Sl + static_cast<int64_t>(en & kPackMask) * p.s_stride);
+      }
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) {
+        const bool ok = j0 + u < m;
+        const int j = ok ? j0 + u : m - 1;
+        int d = static_cast<int>(static_cast<unsigned>(__shfl(ent, j, LPR)) >> kPackShift);
+        d = d < rest ? d : rest;
+        const float w = ok ? sw.pick(d) : 0.f;     // (a slot past the end: weight 0 would still turn an inf into a NaN, hence the select)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc.v[v] = ok ? fmaf(w, sv[u].v[v], acc.v[v]) : acc.v[v];
+      }
+    }
+  }
+  float r = 0.f;
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) r += acc.v[v];
+  r = col_ok ? r : 0.f;
+  r += dpp_row<0xB1>(r);    // quad_perm [1, 0, 3, 2]: lane ^ 1
+  r += dpp_row<0x4E>(r);    // quad_perm [2, 3, 0, 1]: lane ^ 2
+  r += dpp_row<0x141>(r);   // row_half_mirror: the other quad of the eight (its four lanes hold one value)
+  r += dpp_row<0x140>(r);   // row_mirror: the other half of the sixteen
+#pragma unroll
+  for (int off = 16; off < LPR; off <<= 1) r += __shfl_xor(r, off);
+  if (sub == 0) p.seg_partial[(q - p.seg_q_lo) * 8 + cls] = r;
+}
+
+// ---------------------------------------------------------------------------------------------
 // long kernel: one 256-thread workgroup per slice of a hub row (classed hub plan: one wave per slice, one class per workgroup)
 // ---------------------------------------------------------------------------------------------
 template <int VEC, int LPR, bool SMALLD, bool DENSE, bool BYCODE, bool PACKED = false>
@@ -478,7 +565,7 @@ __device__ __forceinline__ void slice_body(const Params& p, const int blk) {
 }
 
 // One launch covers everything: workgroups [0, n_slices) take the hub-row slices (they start first,
-// so the long-latency slices overlap the bulk), the rest take 4*G ordinary rows each.
+// so the long-latency slices overlap the bulk), then (SELF) the classed rows' segments, then the tiles; the rest take 4*G ordinary rows each.
 // BYCODE (operand row = (neighbour, hop code), the narrow-operand backward) is a template parameter: as a run-time
 // flag its address arithmetic cost the W = 64 kernels 4 VGPRs and the bf16 variant 20 B of scratch (bf16 rows 2.85 -> 3.35 ms).
 // SELF (the route short_tiles_serve describes, reduce_cr == 1): the rows' self term from gnan_spmm_args.self_sum in the read-out's
@@ -492,13 +579,21 @@ void spmm_kernel(const Params p) {
       slice_body<VEC, LPR, SMALLD, false, BYCODE, PACKED>(p, static_cast<int>(blockIdx.x));
       return;
     }
+    int front = p.n_slice_blocks;       // workgroups ahead of the tile blocks
+    if constexpr (SELF) {               // (plan_tiles() leaves n_seg_blocks 0 without a classed row plan)
+      if (static_cast<int>(blockIdx.x) < front + p.n_seg_blocks) {
+        seg_body<VEC, LPR>(p, static_cast<int>(blockIdx.x) - front);
+        return;
+      }
+      front += p.n_seg_blocks;
+    }
     if constexpr (short_tiles_serve(VEC, LPR, SMALLD, PACKED, BYCODE)) {   // (launch() leaves n_tile_blocks 0 for every other variant)
-      if (static_cast<int>(blockIdx.x) < p.n_slice_blocks + p.n_tile_blocks) {
-        short_tiles<VEC, LPR, SELF>(p, (static_cast<int>(blockIdx.x) - p.n_slice_blocks) * (blockDim.x / kWave) + threadIdx.x / kWave);
+      if (static_cast<int>(blockIdx.x) < front + p.n_tile_blocks) {
+        short_tiles<VEC, LPR, SELF>(p, (static_cast<int>(blockIdx.x) - front) * (blockDim.x / kWave) + threadIdx.x / kWave);
         return;
       }
     }
-    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED, SELF>(p, static_cast<int64_t>(blockIdx.x) - p.n_slice_blocks - p.n_tile_blocks);
+    rows_body<VEC, LPR, false, SMALLD, BYCODE, PACKED, SELF>(p, static_cast<int64_t>(blockIdx.x) - front - p.n_tile_blocks);
   } else {
     if (p.n_slices > 0) {      // few rows, many neighbours: every row is cut into slices, there are no row blocks
       slice_body<VEC, LPR, SMALLD, true, false>(p, static_cast<int>(blockIdx.x));
@@ -513,11 +608,12 @@ int launch(const gnan_spmm_args* a, bool dense, bool smalld, hipStream_t st) {
   constexpr int G = kWave / LPR;
   const int rows_per_block = 4 * G;
   Params p = make_params(a);
-  if (int rc = plan_tiles(p, VEC, LPR, dense, smalld)) return rc;
+  if (int rc = plan_tiles(p, VEC, LPR, dense, smalld, a->seg_max_per_class)) return rc;
   const int n_slices = p.n_slices;
+  const int64_t walked = p.n_rows - p.row_q0 - (p.seg_q_hi - p.seg_q_lo);   // (the classed rows are taken in segments)
   const int64_t blocks = dense && n_slices > 0
                              ? n_slices
-                             : (p.n_rows - p.row_q0 + rows_per_block - 1) / rows_per_block + p.n_slice_blocks + p.n_tile_blocks;
+                             : (walked + rows_per_block - 1) / rows_per_block + p.n_slice_blocks + p.n_seg_blocks + p.n_tile_blocks;
   if (blocks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many rows for one launch");
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
   if (p.s_by_code) {

@@ -101,6 +101,25 @@ class ClassedHubPlan(LongRowPlan):
 
 
 @dataclass
+class ClassedRowPlan:
+    """:meth:`HopGraph.classed_row_plan`: the pairs of rows ``[q_lo, q_hi)`` of a degree-sorted copy as SEGMENTS, one per (row,
+    column class ``col & 7``) that holds a pair (``gnan_spmm_args.seg_*``).  ``index`` (``col | code << 29``) is class-major, within
+    a class in row order, within a segment in the row's own pair order; segment ``s`` covers ``index[seg_start[s], seg_start[s + 1])``
+    of row ``seg_row[s]``; class ``c`` owns segments ``[cls_seg_ptr[c], cls_seg_ptr[c + 1])``; bit ``c`` of ``mask[q - q_lo]`` says
+    whether row ``q`` has a segment of class ``c``."""
+    q_lo: int
+    q_hi: int
+    min_pairs: int
+    n_seg: int
+    max_per_class: int            # segments of the largest class (sizes the launch)
+    index: torch.Tensor           # int32 [pairs of the classed rows]
+    seg_start: torch.Tensor       # int64 [n_seg + 1]
+    seg_row: torch.Tensor         # int32 [n_seg]
+    cls_seg_ptr: torch.Tensor     # int32 [9]
+    mask: torch.Tensor            # uint8 [q_hi - q_lo]
+
+
+@dataclass
 class SelfFreePlan:
     """:meth:`HopGraph.self_free_plan`: the graph without its rows' self pairs, and which nodes its remaining pairs list."""
     twin: "HopGraph"              # same rows, the pair (i, i, code 0) removed from every row; ``cnt`` IS the graph's tensor
@@ -135,6 +154,7 @@ class HopGraph:
     _plans: dict = field(default_factory=dict, repr=False)          # hub-row plans by threshold (other than the default)
     _classed: dict = field(default_factory=dict, repr=False)        # classed_hub_plan(): (order, threshold, slice_edges) -> plan
     _short_runs: dict = field(default_factory=dict, repr=False)     # short_row_runs(): lmax -> ShortRowRuns
+    _classed_rows: dict = field(default_factory=dict, repr=False)   # classed_row_plan(): (min_pairs, max_pairs) -> plan or None
     _sorted_copy: Optional["HopGraph"] = field(default=None, repr=False)
     _hot: Optional[tuple] = field(default=None, repr=False)           # hot_columns(): (ids or None,)
     _sorted_copy_hot: Optional["HopGraph"] = field(default=None, repr=False)
@@ -422,6 +442,51 @@ class HopGraph:
         return ClassedHubPlan(base.rows, slice_ptr, R, n_slices, threshold=base.threshold, slice_edges=SE, index=index,
                               slice_start=slice_start, slice_row=(t // K).to(torch.int32), slot_slice=slot_slice,
                               n_slots=K * longest)
+
+    def classed_row_plan(self, min_pairs: int, max_pairs: int = LONG_ROW_THRESHOLD) -> Optional[ClassedRowPlan]:
+        """The rows of ``min_pairs .. max_pairs`` listed pairs of a DEGREE-SORTED copy (rows shortest first: they are one range
+        ``[q_lo, q_hi)``, and so are their pairs) cut into one segment per (row, column class): :class:`ClassedRowPlan`.  ``None``
+        where no row qualifies or the packed entries cannot hold the graph.  Framework ops on the graph's device (a stable sort of
+        the range's pairs by (class, row)); cached per graph."""
+        key = (int(min_pairs), int(max_pairs))
+        if key in self._classed_rows:
+            return self._classed_rows[key]
+        plan = None
+        if not self.is_dense and self.n_cols <= (1 << PACK_SHIFT) and self.n_codes <= 8 and self.n_rows > 0 and self.nnz < 2 ** 31:
+            plan = self._classed_row_plan_torch(*key)
+        self._classed_rows[key] = plan
+        return plan
+
+    def _classed_row_plan_torch(self, min_pairs: int, max_pairs: int) -> Optional[ClassedRowPlan]:
+        dev, K = self.device, HUB_CLASSES
+        rp = self.rowptr.long()
+        deg = rp[1:] - rp[:-1]
+        if bool((deg[1:] < deg[:-1]).any()):
+            raise ValueError("classed_row_plan needs a degree-sorted copy (rows shortest first)")
+        q_lo, q_hi = (int(v) for v in torch.searchsorted(deg, torch.tensor([min_pairs, max_pairs + 1], device=dev)).tolist())
+        R = q_hi - q_lo
+        if R <= 0:
+            return None
+        e0, e1 = int(rp[q_lo]), int(rp[q_hi])
+        if self.colp is not None:
+            v = self.colp[e0:e1]
+        else:
+            w = self.col[e0:e1].long() | (self.code[e0:e1].long() << PACK_SHIFT)
+            v = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        row = torch.repeat_interleave(torch.arange(R, device=dev), deg[q_lo:q_hi])
+        key = (self.col[e0:e1].long() & (K - 1)) * R + row                    # class-major, then row; the sort keeps a row's order
+        index = v[torch.argsort(key, stable=True)].contiguous()
+        cnt = torch.bincount(key, minlength=K * R)
+        del key, row
+        seg = torch.nonzero(cnt).flatten()                                   # (class, row) of every segment, in plan order
+        n_seg = int(seg.numel())
+        seg_start = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+        seg_start[1:] = torch.cumsum(cnt[seg], 0)
+        cls_ptr = torch.searchsorted(seg, torch.arange(K + 1, device=dev) * R)
+        has = (cnt.view(K, R) > 0).long()
+        mask = (has << torch.arange(K, device=dev).view(K, 1)).sum(0).to(torch.uint8)
+        return ClassedRowPlan(q_lo, q_hi, int(min_pairs), n_seg, int((cls_ptr[1:] - cls_ptr[:-1]).max()), index, seg_start,
+                              (seg % R + q_lo).to(torch.int32), cls_ptr.to(torch.int32), mask.contiguous())
 
     def narrow_row_plan(self) -> LongRowPlan:
         """Hub-row plan for operand rows of one or two lanes: the low threshold while only a FEW rows exceed it (the tail

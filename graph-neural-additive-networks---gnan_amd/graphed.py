@@ -23,6 +23,8 @@ Dropout in training mode is stochastic per call and is never captured (``Graphed
 from __future__ import annotations
 
 import atexit
+import contextlib
+import gc
 import weakref
 from typing import Callable, List, Optional
 
@@ -58,6 +60,22 @@ def _release_graphs_at_exit():
 atexit.register(_release_graphs_at_exit)
 
 
+@contextlib.contextmanager
+def collector_held_off():
+    """Around a stream capture: dead reference cycles are collected BEFORE it and the cyclic collector stays off while it runs.  A
+    model that went out of scope keeps its captured steps in a cycle until the collector finds it; on ROCm the finaliser of a
+    ``torch.cuda.CUDAGraph`` synchronises the device, which a capture in progress does not survive (the process aborts), and when
+    the collector runs is a matter of allocation counts.  ``torch.cuda.graph`` itself stopped collecting at its entry."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 class GraphedCallable:
     """``fn()`` — no arguments, closes over static tensors — captured into a hipGraph after ``warmup`` eager runs."""
 
@@ -88,7 +106,7 @@ class GraphedCallable:
         import torch.distributed as dist
         mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"
         try:
-            with torch.cuda.graph(self.graph, capture_error_mode=mode):
+            with collector_held_off(), torch.cuda.graph(self.graph, capture_error_mode=mode):
                 self.out = fn()
             # a captured hipMemsetAsync replays correctly only once on this ROCm (csrc/graph_fix.hip); the framework's
             # multi-block reductions (a loss's mean, a column sum) zero their semaphores with one: swap the nodes for kernels

@@ -243,7 +243,8 @@ class _GraphedBuild:
                 _build_padded(sp)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        from .graphed import collector_held_off      # (no dead cycle's captured graph is finalised under this capture)
+        with collector_held_off(), torch.cuda.graph(self.graph):
             self.static_out = _build_padded(sp)
 
     def __call__(self, p):

@@ -530,6 +530,24 @@ typedef struct gnan_spmm_args {
    * reduce_cr == 1; GNAN_ERR_UNSUPPORTED otherwise.  The launch partition does not depend on it */
   const float* self_sum;
   int32_t self_parts;
+  /* classed row segments (the struct grew at its end; gnan_spmm_fwd only, optional, on the self_sum route alone: GNAN_ERR_UNSUPPORTED on any other).
+   * Rows [seg_q_lo, seg_q_hi) of the degree-sorted copy (min_pairs .. long_threshold pairs each; seg_q_lo at or behind the tiled rows)
+   * are not walked as rows: the pairs of row q that fall in column class c = column & 7 form one SEGMENT, listed class-major (within a
+   * class in row order, within a segment in the row's own pair order).  Segment s reads the packed entries
+   * seg_index[seg_start[s], seg_start[s + 1]) and belongs to row seg_row[s]; class c owns segments [cls_seg_ptr[c], cls_seg_ptr[c + 1])
+   * (a DEVICE array of 9); seg_max_per_class is the longest class's segment count (it sizes the launch: workgroup b of the segment
+   * range takes class b & 7).  A lane group takes a segment and stores ONE float, its share of the row's fused read-out, at
+   * partial[(q - seg_q_lo) * 8 + c] behind the hub slices' partials in `workspace`; seg_mask[q - seg_q_lo] bit c says which exist.
+   * A combine pass adds a row's partials in a fixed tree over the classes, the rest term fmaf(wt(i, D-1), T, .) with T = the float64
+   * sum of s_total rounded once, and the self term.  s_total must be set.  NULL seg_index (the default): off */
+  const int32_t* seg_index;
+  const int64_t* seg_start;
+  const int32_t* seg_row;
+  const int32_t* cls_seg_ptr;
+  const uint8_t* seg_mask;
+  int64_t seg_q_lo, seg_q_hi;
+  int32_t n_seg;
+  int32_t seg_max_per_class;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
@@ -540,7 +558,7 @@ int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream);
  * copy of them, which the launch and this query both call.  All fields are zero when n_rows == 0 (kernel NONE); the hot-row kernel
  * has no block partition (the fields below `classed` stay zero). */
 #define GNAN_SPMM_KERNEL_NONE 0
-#define GNAN_SPMM_KERNEL_ROWS 1   /* spmm_kernel: slice blocks, then tile blocks, then row blocks */
+#define GNAN_SPMM_KERNEL_ROWS 1   /* spmm_kernel: slice blocks, then segment blocks, then tile blocks, then row blocks */
 #define GNAN_SPMM_KERNEL_HOT 2    /* spmm_hot_kernel: persistent workgroups, hottest operand rows in LDS */
 typedef struct gnan_spmm_launch_info {
   int32_t vec;                   /* floats (bf16: elements) a lane reads of an operand row at once: 1, 4 or 8 */
@@ -554,6 +572,8 @@ typedef struct gnan_spmm_launch_info {
   int32_t n_tiles;               /* short-row tiles; 0: the declared runs are walked as ordinary rows */
   int64_t row_q0;                /* first row the row blocks take (rows below it are tiled) */
   int32_t short_tile[GNAN_SHORT_LMAX + 1];   /* first tile of run L, L = 0 .. short_lmax (when n_tiles > 0) */
+  int32_t n_seg_blocks;          /* workgroups of classed row segments (a multiple of 8); 0: no row is taken in segments */
+  int32_t n_segs;                /* classed row segments */
 } gnan_spmm_launch_info;
 
 int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_info* out);
