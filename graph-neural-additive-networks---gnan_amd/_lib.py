@@ -63,6 +63,20 @@ class FpwlIndexArgs(C.Structure):
 
 
 FPWL_MOMENTS_GENERAL, FPWL_INDEX_HALF_LINES, FPWL_INDEX_BS512, FPWL_INDEX_BS1024 = 1, 4, 8, 16   # gnan_fpwl_args.flags
+# gnan_fpwl_moments_info.kernel (GNAN_FPWL_MOMENTS_*)
+(MOMENTS_NONE, MOMENTS_C1_SEARCH, MOMENTS_C1_KEPT, MOMENTS_C1_SAVED, MOMENTS_C1_RAGGED, MOMENTS_FAST, MOMENTS_GENERAL_FIXED,
+ MOMENTS_GENERAL_FLOAT, MOMENTS_ROWS, MOMENTS_ROWS_PAIRS) = range(10)
+
+
+class FpwlMomentsInfo(C.Structure):
+    _fields_ = [
+        ("kernel", C.c_int32), ("nstep", C.c_int32), ("nodes_per_block", C.c_int32), ("nodes_per_round", C.c_int32),
+        ("block_size", C.c_int32), ("pieces_kept", C.c_int32), ("channel_chunk", C.c_int32), ("n_chunks", C.c_int32),
+        ("cp2", C.c_int32), ("lds_bytes", C.c_int32), ("n_blocks", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class PwlBuildArgs(C.Structure):
@@ -405,6 +419,8 @@ SYMBOLS = {
     "gnan_fpwl_moments": (C.c_int, [C.POINTER(FpwlArgs), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gnan_fpwl_moments_fixed": (C.c_int, [C.POINTER(FpwlArgs), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "gnan_fpwl_moments_describe": (C.c_int, [C.POINTER(FpwlArgs), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(FpwlMomentsInfo)]),
+    "gnan_fpwl_rows_moments_describe": (C.c_int, [C.POINTER(FpwlArgs), C.c_int64, C.POINTER(FpwlMomentsInfo)]),
     "gnan_fpwl_locate_bytes": (C.c_size_t, [C.POINTER(FpwlArgs)]),
     "gnan_fpwl_locate": (C.c_int, [C.POINTER(FpwlArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnan_fpwl_rows_fwd": (C.c_int, [C.POINTER(FpwlArgs), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -961,8 +961,18 @@ __global__ __launch_bounds__(BS) void fpwl_moments_c1_kernel(const MomentParams 
   }
 }
 
+// What a moment launcher tells gnan_fpwl_moments_describe: every launcher takes `probe` and, when it is set, fills it where it would
+// otherwise set the kernel's attributes and launch (so the query reports the launch's own decisions, the LDS fall-backs included).
+void fill_probe(gnan_fpwl_moments_info* probe, int kernel, int nstep, const Params& p, int nodes, int bs, bool kept, size_t lds) {
+  *probe = gnan_fpwl_moments_info{};
+  probe->kernel = kernel; probe->nstep = nstep; probe->nodes_per_block = p.nodes_per_block; probe->nodes_per_round = nodes;
+  probe->block_size = bs; probe->pieces_kept = kept; probe->channel_chunk = p.C; probe->n_chunks = 1;
+  probe->lds_bytes = static_cast<int32_t>(lds);
+  probe->n_blocks = (p.n + p.nodes_per_block - 1) / p.nodes_per_block;
+}
+
 template <int FG, int NSTEP, int BS, bool RAGGED = false>
-int launch_moments_c1(MomentParams mp, hipStream_t st) {
+int launch_moments_c1(MomentParams mp, hipStream_t st, gnan_fpwl_moments_info* probe) {
   Params& p = mp.f;
   const size_t pieces = static_cast<size_t>(p.max_group_pieces);
   size_t lds = ((static_cast<size_t>(FG) << NSTEP) + (FG / 4) * kTreeSkew) * sizeof(float) + pieces * 2 * sizeof(unsigned long long);
@@ -972,13 +982,21 @@ int launch_moments_c1(MomentParams mp, hipStream_t st) {
   p.soff_offset = static_cast<int>(lds / sizeof(float));
   lds += (FG + 1) * sizeof(int);
   if (lds > 150 * 1024) return -1;                       // caller falls back to the general kernels
+  p.nodes_per_block = tuned_moment_block(p.n, p.n_groups, lds, BS);
+  if (probe) {                                           // (the branches of the kernel, by the conditions it tests)
+    const bool saved = p.piece_in != nullptr;
+    const int kernel = RAGGED ? GNAN_FPWL_MOMENTS_C1_RAGGED
+                              : (!saved ? GNAN_FPWL_MOMENTS_C1_SEARCH
+                                        : ((p.sum_features || mp.vec_g) ? GNAN_FPWL_MOMENTS_C1_KEPT : GNAN_FPWL_MOMENTS_C1_SAVED));
+    fill_probe(probe, kernel, NSTEP, p, BS / (FG / 4), BS, saved, lds);
+    return GNAN_OK;
+  }
   const void* fn = p.sum_features ? reinterpret_cast<const void*>(&fpwl_moments_c1_kernel<FG, NSTEP, BS, true, RAGGED>)
                                   : reinterpret_cast<const void*>(&fpwl_moments_c1_kernel<FG, NSTEP, BS, false, RAGGED>);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl: hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
-  p.nodes_per_block = tuned_moment_block(p.n, p.n_groups, lds, BS);
   const int64_t bx = ((p.n + p.nodes_per_block - 1) / p.nodes_per_block + 7) / 8 * 8;   // whole rounds of the 8 XCDs
   if (bx * p.n_groups > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl: too many nodes for one launch");
   const dim3 grid(static_cast<unsigned>(bx * p.n_groups));
@@ -991,7 +1009,7 @@ int launch_moments_c1(MomentParams mp, hipStream_t st) {
 }
 
 template <int FG, int NSTEP, int BS>
-int launch_moments_fast(MomentParams mp, hipStream_t st) {
+int launch_moments_fast(MomentParams mp, hipStream_t st, gnan_fpwl_moments_info* probe) {
   Params& p = mp.f;
   const size_t pieces = static_cast<size_t>(p.max_group_pieces);
   size_t lds = ((static_cast<size_t>(FG) << NSTEP) + (FG / 4) * kTreeSkew) * sizeof(float) +
@@ -999,6 +1017,10 @@ int launch_moments_fast(MomentParams mp, hipStream_t st) {
   p.soff_offset = static_cast<int>(lds / sizeof(float));
   lds += (FG + 1) * sizeof(int);
   if (lds > 150 * 1024) return -1;                       // caller falls back to the plain kernel
+  if (probe) {
+    fill_probe(probe, GNAN_FPWL_MOMENTS_FAST, NSTEP, p, BS / (FG / 4), BS, false, lds);
+    return GNAN_OK;
+  }
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fpwl_moments_fast_kernel<FG, NSTEP, BS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
@@ -1012,7 +1034,7 @@ int launch_moments_fast(MomentParams mp, hipStream_t st) {
 }
 
 template <int FG, int BS>
-int launch_moments(const MomentParams& mp_in, size_t lds, hipStream_t st) {
+int launch_moments(const MomentParams& mp_in, size_t lds, hipStream_t st, gnan_fpwl_moments_info* probe) {
   MomentParams mp = mp_in;
   if (mp.f.max_pieces > 256) mp.f.piece_in = nullptr;      // one byte per look-up: searched again instead
   const bool fixed = mp.Mi != nullptr;
@@ -1024,11 +1046,11 @@ int launch_moments(const MomentParams& mp_in, size_t lds, hipStream_t st) {
       int rc = -1;
       if (!mp.general_only) {
         switch (nstep) {
-          case 6: rc = launch_moments_c1<FG, 6, BS, true>(mp, st); break;
-          case 7: rc = launch_moments_c1<FG, 7, BS, true>(mp, st); break;
-          case 8: rc = launch_moments_c1<FG, 8, BS, true>(mp, st); break;
-          case 9: rc = launch_moments_c1<FG, 9, BS, true>(mp, st); break;
-          case 10: rc = launch_moments_c1<FG, 10, BS, true>(mp, st); break;
+          case 6: rc = launch_moments_c1<FG, 6, BS, true>(mp, st, probe); break;
+          case 7: rc = launch_moments_c1<FG, 7, BS, true>(mp, st, probe); break;
+          case 8: rc = launch_moments_c1<FG, 8, BS, true>(mp, st, probe); break;
+          case 9: rc = launch_moments_c1<FG, 9, BS, true>(mp, st, probe); break;
+          case 10: rc = launch_moments_c1<FG, 10, BS, true>(mp, st, probe); break;
           default: break;
         }
         if (rc != -1) return rc;
@@ -1042,26 +1064,31 @@ int launch_moments(const MomentParams& mp_in, size_t lds, hipStream_t st) {
         if (!mp.general_only) {                              // (GNAN_FPWL_MOMENTS_GENERAL: A/B aid, tests)
           // 512 threads = three workgroups (24 waves) per CU; 640 (30 waves): +13 %/+6 %, 1024 (32 waves): +-0 on C4
           switch (nstep) {
-            case 6: rc = launch_moments_c1<FG, 6, BS>(mp, st); break;
-            case 7: rc = launch_moments_c1<FG, 7, BS>(mp, st); break;
-            case 8: rc = launch_moments_c1<FG, 8, BS>(mp, st); break;
-            case 9: rc = launch_moments_c1<FG, 9, BS>(mp, st); break;
-            case 10: rc = launch_moments_c1<FG, 10, BS>(mp, st); break;
+            case 6: rc = launch_moments_c1<FG, 6, BS>(mp, st, probe); break;
+            case 7: rc = launch_moments_c1<FG, 7, BS>(mp, st, probe); break;
+            case 8: rc = launch_moments_c1<FG, 8, BS>(mp, st, probe); break;
+            case 9: rc = launch_moments_c1<FG, 9, BS>(mp, st, probe); break;
+            case 10: rc = launch_moments_c1<FG, 10, BS>(mp, st, probe); break;
             default: break;
           }
           if (rc != -1) return rc;
         }
       }
       switch (nstep) {
-        case 6: rc = launch_moments_fast<FG, 6, BS>(mp, st); break;
-        case 7: rc = launch_moments_fast<FG, 7, BS>(mp, st); break;
-        case 8: rc = launch_moments_fast<FG, 8, BS>(mp, st); break;
-        case 9: rc = launch_moments_fast<FG, 9, BS>(mp, st); break;
-        case 10: rc = launch_moments_fast<FG, 10, BS>(mp, st); break;
+        case 6: rc = launch_moments_fast<FG, 6, BS>(mp, st, probe); break;
+        case 7: rc = launch_moments_fast<FG, 7, BS>(mp, st, probe); break;
+        case 8: rc = launch_moments_fast<FG, 8, BS>(mp, st, probe); break;
+        case 9: rc = launch_moments_fast<FG, 9, BS>(mp, st, probe); break;
+        case 10: rc = launch_moments_fast<FG, 10, BS>(mp, st, probe); break;
         default: break;
       }
       if (rc != -1) return rc;
     }
+  }
+  if (probe) {
+    fill_probe(probe, fixed ? GNAN_FPWL_MOMENTS_GENERAL_FIXED : GNAN_FPWL_MOMENTS_GENERAL_FLOAT, 0, mp.f, Map<FG, BS>::NODES, BS,
+               false, lds);
+    return GNAN_OK;
   }
   const void* fn = fixed ? reinterpret_cast<const void*>(&fpwl_moments_kernel<FG, BS, true>)
                          : reinterpret_cast<const void*>(&fpwl_moments_kernel<FG, BS, false>);
@@ -1445,8 +1472,9 @@ int gnan_locate_tree(const gnan_fpwl_args* a, int32_t* piece, float* dx, hipStre
 
 namespace {
 int moments_common(const gnan_fpwl_args* a, const float* grad, int64_t grad_stride, float* moments,
-                   const double* scales, int64_t* moments_fixed, gnan_stream_t stream) {
+                   const double* scales, int64_t* moments_fixed, gnan_stream_t stream, gnan_fpwl_moments_info* probe = nullptr) {
   if (int rc = common_checks(a)) return rc;
+  if (probe) *probe = gnan_fpwl_moments_info{};
   if (a->n == 0) return GNAN_OK;
   const int64_t gw = a->sum_features ? a->C : static_cast<int64_t>(a->F) * a->C;
   GNAN_REQUIRE(grad_stride >= gw, "fpwl_moments: grad row stride smaller than its width");
@@ -1468,11 +1496,11 @@ int moments_common(const gnan_fpwl_args* a, const float* grad, int64_t grad_stri
   // waves on a CU (arxiv-shaped, C = 40: 91 KB of bins per feature -> one workgroup per CU)
   const bool wide = lds > 40 * 1024;
   switch (a->features_per_group) {
-    case 1: return wide ? launch_moments<1, 1024>(mp, lds, st) : launch_moments<1, 256>(mp, lds, st);
-    case 2: return wide ? launch_moments<2, 1024>(mp, lds, st) : launch_moments<2, 256>(mp, lds, st);
-    case 4: return wide ? launch_moments<4, 1024>(mp, lds, st) : launch_moments<4, 256>(mp, lds, st);
-    case 8: return launch_moments<8, 512>(mp, lds, st);
-    default: return launch_moments<16, 512>(mp, lds, st);
+    case 1: return wide ? launch_moments<1, 1024>(mp, lds, st, probe) : launch_moments<1, 256>(mp, lds, st, probe);
+    case 2: return wide ? launch_moments<2, 1024>(mp, lds, st, probe) : launch_moments<2, 256>(mp, lds, st, probe);
+    case 4: return wide ? launch_moments<4, 1024>(mp, lds, st, probe) : launch_moments<4, 256>(mp, lds, st, probe);
+    case 8: return launch_moments<8, 512>(mp, lds, st, probe);
+    default: return launch_moments<16, 512>(mp, lds, st, probe);
   }
 }
 }  // namespace
@@ -1487,6 +1515,14 @@ extern "C" int gnan_fpwl_moments_fixed(const gnan_fpwl_args* a, const float* gra
                                        const double* scales, int64_t* moments, gnan_stream_t stream) {
   GNAN_REQUIRE(a == nullptr || a->n == 0 || (grad && moments && scales), "fpwl_moments_fixed: null grad / scales / moments");
   return moments_common(a, grad, grad_stride, nullptr, scales, moments, stream);
+}
+
+extern "C" int gnan_fpwl_moments_describe(const gnan_fpwl_args* a, const float* grad, int64_t grad_stride, int32_t fixed,
+                                          gnan_fpwl_moments_info* out) {
+  GNAN_REQUIRE(out != nullptr, "fpwl_moments describe: null output");
+  // (the launchers tell the fixed-point call from the float one by its accumulator pointer: any non-null address, never read)
+  static int64_t fixed_mark;
+  return moments_common(a, grad, grad_stride, nullptr, nullptr, fixed ? &fixed_mark : nullptr, nullptr, out);
 }
 
 // csrc/fpwl_index.hip: the direct-index look-up (one channel, whole 16-feature groups, aligned rows)

@@ -408,13 +408,20 @@ int cp2_of(int C) {
   return cp2;
 }
 
-int rows_checks(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, const char* who) {
+// the sizes of a two-phase call (what a route query validates too) ...
+int rows_size_checks(const gnan_fpwl_args* a, const char* who) {
   GNAN_REQUIRE(a != nullptr, "%s: null args", who);
   GNAN_REQUIRE(a->n >= 0 && a->F >= 1 && a->C >= 1, "%s: bad sizes", who);
   if (a->C > 4096) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: at most 4096 output channels (got %d)", who, a->C);
+  GNAN_REQUIRE(a->n * static_cast<int64_t>(a->F) < (1LL << 40), "%s: n * F too large", who);
+  return GNAN_OK;
+}
+
+// ... and the pointers a launch reads
+int rows_checks(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, const char* who) {
+  if (int rc = rows_size_checks(a, who)) return rc;
   if (a->n == 0) return GNAN_OK;
   GNAN_REQUIRE(piece && dx && a->off, "%s: null pointer", who);
-  GNAN_REQUIRE(a->n * static_cast<int64_t>(a->F) < (1LL << 40), "%s: n * F too large", who);
   return GNAN_OK;
 }
 
@@ -519,12 +526,15 @@ extern "C" int gnan_fpwl_rows_fwd(const gnan_fpwl_args* a, const int32_t* piece,
   }
 }
 
-extern "C" int gnan_fpwl_rows_moments_fixed(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, const float* grad,
-                                            int64_t grad_stride, const double* scales, int64_t* moments,
-                                            gnan_stream_t stream) {
-  if (int rc = rows_checks(a, piece, dx, "fpwl_rows_moments")) return rc;
+namespace {
+// gnan_fpwl_rows_moments_fixed, and with `probe` set gnan_fpwl_rows_moments_describe: the same function up to the launch
+int rows_moments(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, const float* grad, int64_t grad_stride,
+                 const double* scales, int64_t* moments, gnan_stream_t stream, gnan_fpwl_moments_info* probe) {
+  if (probe) *probe = gnan_fpwl_moments_info{};
+  // (a query reads no pointer of the call: the sizes are checked as for a launch, the pointers not)
+  if (int rc = probe ? rows_size_checks(a, "fpwl_rows_moments") : rows_checks(a, piece, dx, "fpwl_rows_moments")) return rc;
   if (a->n == 0) return GNAN_OK;
-  GNAN_REQUIRE(grad && scales && moments, "fpwl_rows_moments: null grad / scales / moments");
+  GNAN_REQUIRE(probe || (grad && scales && moments), "fpwl_rows_moments: null grad / scales / moments");
   const int64_t gw = a->sum_features ? a->C : static_cast<int64_t>(a->F) * a->C;
   GNAN_REQUIRE(grad_stride >= gw, "fpwl_rows_moments: grad row stride smaller than its width");
   GNAN_REQUIRE(a->max_pieces >= 1, "fpwl_rows_moments: max_pieces must be >= 1");
@@ -555,7 +565,16 @@ extern "C" int gnan_fpwl_rows_moments_fixed(const gnan_fpwl_args* a, const int32
   if (p.wgs_per_chunk * n_chunks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_rows_moments: too many nodes for one launch");
   const dim3 grid(static_cast<unsigned>(p.wgs_per_chunk * n_chunks));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (cc > 32 && 3 * ((cc + 1) / 2) <= kWave) {
+  const bool pairs = cc > 32 && 3 * ((cc + 1) / 2) <= kWave;
+  if (probe) {
+    probe->kernel = pairs ? GNAN_FPWL_MOMENTS_ROWS_PAIRS : GNAN_FPWL_MOMENTS_ROWS;
+    probe->nodes_per_block = p.nodes_per_block; probe->nodes_per_round = 16 * kWave; probe->block_size = 1024;
+    probe->channel_chunk = cc; probe->n_chunks = n_chunks; probe->cp2 = pairs ? 0 : cp2_of(cc);
+    probe->lds_bytes = static_cast<int32_t>(lds);
+    probe->n_blocks = (a->n + npb - 1) / npb;
+    return GNAN_OK;
+  }
+  if (pairs) {
     // 33..42 channels: a pair of channels per lane, three nodes per step (see fpwl_rows_moments_pairs_kernel)
     if (lds > 64 * 1024) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fpwl_rows_moments_pairs_kernel),
@@ -571,4 +590,16 @@ extern "C" int gnan_fpwl_rows_moments_fixed(const gnan_fpwl_args* a, const int32
     case 32: return launch_rows_moments<32>(p, lds, grid, st);
     default: return launch_rows_moments<64>(p, lds, grid, st);
   }
+}
+}  // namespace
+
+extern "C" int gnan_fpwl_rows_moments_fixed(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, const float* grad,
+                                            int64_t grad_stride, const double* scales, int64_t* moments,
+                                            gnan_stream_t stream) {
+  return rows_moments(a, piece, dx, grad, grad_stride, scales, moments, stream, nullptr);
+}
+
+extern "C" int gnan_fpwl_rows_moments_describe(const gnan_fpwl_args* a, int64_t grad_stride, gnan_fpwl_moments_info* out) {
+  GNAN_REQUIRE(out != nullptr, "fpwl_rows_moments describe: null output");
+  return rows_moments(a, nullptr, nullptr, nullptr, grad_stride, nullptr, nullptr, nullptr, out);
 }

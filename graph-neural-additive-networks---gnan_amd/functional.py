@@ -346,7 +346,7 @@ def _abs_max_cached(x: torch.Tensor) -> torch.Tensor:
 
 
 def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
-                  x_abs_max: Optional[torch.Tensor] = None, raw: bool = False, located=None):
+                  x_abs_max: Optional[torch.Tensor] = None, raw: bool = False, located=None, describe: Optional[list] = None):
     """Per-piece moments of the upstream gradient (``gnan_fpwl_moments[_fixed]``) -> ``[T, 2, C]`` float32; with ``raw``
     the fixed-point route returns ``(moments int64 [T, 2, C], scales float64 [2])`` undivided (``gnan_fpwl_param_grads``
     takes them as they are).
@@ -354,7 +354,11 @@ def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
     Fixed-point route (default where the 64-bit bins fit LDS): every term is added as ``round(v * 2^e)`` with ``e``
     chosen on the device from ``max |grad|`` and ``max |x - anchor|`` such that n terms cannot overflow 62 bits —
     per-term resolution 2^-(61 - log2 n) of the largest term, i.e. far below fp32 — and the sums do not depend on
-    the order of the atomics."""
+    the order of the atomics.
+
+    ``describe``: a list that receives the route of the launch (``gnan_fpwl_moments_describe`` /
+    ``gnan_fpwl_rows_moments_describe`` as a dict: kernel, tree depth, node blocks), asked of the library with the very
+    arguments of the launch."""
     x = x.detach().float()
     x = _rows(x)
     grad = grad.detach().float()
@@ -388,6 +392,13 @@ def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
         scales = scales[:2]
         if located and len(located) == 1 and not rows:          # one channel: the forward's pieces, one byte per look-up
             a.piece_in = _lib.ptr(located[0])
+        if describe is not None:
+            info = _lib.FpwlMomentsInfo()
+            if rows:
+                _lib.check(_lib.lib().gnan_fpwl_rows_moments_describe(a, grad.stride(0), info), "gnan_fpwl_rows_moments_describe")
+            else:
+                _lib.check(_lib.lib().gnan_fpwl_moments_describe(a, _lib.ptr(grad), grad.stride(0), 1, info), "gnan_fpwl_moments_describe")
+            describe.append(info.as_dict())
         if rows:
             piece, dx = located if (located and len(located) == 2) else _fpwl_locate(x, t, a)    # kept by the forward pass, or located again
             _lib.check(_lib.lib().gnan_fpwl_rows_moments_fixed(a, _lib.ptr(piece), _lib.ptr(dx), _lib.ptr(grad), grad.stride(0),
@@ -399,6 +410,10 @@ def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
         if raw:
             return Mi, scales
         return (Mi.double() / scales.view(1, 2, 1)).float()
+    if describe is not None:
+        info = _lib.FpwlMomentsInfo()
+        _lib.check(_lib.lib().gnan_fpwl_moments_describe(a, _lib.ptr(grad), grad.stride(0), 0, info), "gnan_fpwl_moments_describe")
+        describe.append(info.as_dict())
     M = torch.zeros((T, 2, C), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().gnan_fpwl_moments(a, _lib.ptr(grad), grad.stride(0), _lib.ptr(M), _lib.stream_of(x)),
                "gnan_fpwl_moments")

@@ -251,6 +251,40 @@ int gnan_fpwl_moments(const gnan_fpwl_args* a, const float* grad, int64_t grad_s
 int gnan_fpwl_moments_fixed(const gnan_fpwl_args* a, const float* grad, int64_t grad_stride, const double* scales,
                             int64_t* moments, gnan_stream_t stream);
 
+/* Which kernel gnan_fpwl_moments[_fixed] / gnan_fpwl_rows_moments_fixed would launch for a call, and how it cuts the nodes (added under ABI 51: two new
+ * functions, no struct changed, the number did not move).  Host only: no kernel is launched and no device memory is read; the arguments are validated as by the launch and the launch's own
+ * routing functions are run — the library has one copy of them, which stop short of the launch when asked by a query.  `grad` is
+ * looked at for its ADDRESS only (16-byte readable rows are one of the routing conditions) and may be any pointer of the same
+ * alignment; `fixed` != 0 asks for gnan_fpwl_moments_fixed, 0 for gnan_fpwl_moments.  All fields are zero when n == 0.
+ * From 16 384 nodes the one-channel kernels size their node blocks by the compute units of the current device
+ * (hipGetDevice / hipDeviceGetAttribute: the query then initialises the HIP runtime as the launch would; 256 units are assumed when
+ * there is no device), so nodes_per_block is a property of the device the launch would run on. */
+#define GNAN_FPWL_MOMENTS_NONE 0
+#define GNAN_FPWL_MOMENTS_C1_SEARCH 1     /* fpwl_moments_c1_kernel: tree search, float32 product g * (x - anchor) */
+#define GNAN_FPWL_MOMENTS_C1_KEPT 2       /* ... over the forward's kept pieces, piece-major bins, sum g x - anchor sum g */
+#define GNAN_FPWL_MOMENTS_C1_SAVED 3      /* ... kept pieces, anchors staged in LDS (gradient rows not 16-byte readable) */
+#define GNAN_FPWL_MOMENTS_C1_RAGGED 4     /* ... partial last feature group / unaligned x rows */
+#define GNAN_FPWL_MOMENTS_FAST 5          /* fpwl_moments_fast_kernel */
+#define GNAN_FPWL_MOMENTS_GENERAL_FIXED 6 /* fpwl_moments_kernel<FIXED = true> */
+#define GNAN_FPWL_MOMENTS_GENERAL_FLOAT 7 /* fpwl_moments_kernel<FIXED = false> */
+#define GNAN_FPWL_MOMENTS_ROWS 8          /* fpwl_rows_moments_kernel<cp2> */
+#define GNAN_FPWL_MOMENTS_ROWS_PAIRS 9    /* fpwl_rows_moments_pairs_kernel */
+typedef struct gnan_fpwl_moments_info {
+  int32_t kernel;            /* GNAN_FPWL_MOMENTS_* */
+  int32_t nstep;             /* tree depth of the c1 / fast kernels (2^nstep >= max_pieces); 0 elsewhere */
+  int32_t nodes_per_block;   /* nodes of one workgroup */
+  int32_t nodes_per_round;   /* nodes a workgroup takes per pass of its loop (NODES; rows kernels: 16 waves x 64) */
+  int32_t block_size;        /* threads per workgroup */
+  int32_t pieces_kept;       /* 1: piece_in is read (0 above 256 pieces per feature and on the kernels that ignore it) */
+  int32_t channel_chunk;     /* rows kernels: channels per workgroup; else C */
+  int32_t n_chunks;          /* rows kernels: channel chunks; else 1 */
+  int32_t cp2;               /* rows kernel: lanes per node (channel_chunk rounded up to 8, 16, 32 or 64); else 0 */
+  int32_t lds_bytes;         /* dynamic LDS of the launch */
+  int64_t n_blocks;          /* node blocks that hold a node: ceil(n / nodes_per_block) */
+} gnan_fpwl_moments_info;
+int gnan_fpwl_moments_describe(const gnan_fpwl_args* a, const float* grad, int64_t grad_stride, int32_t fixed,
+                               gnan_fpwl_moments_info* out);
+
 /* ---------------------------------------------------------------------------------------------
  * Table look-up with SEVERAL output channels in two phases (csrc/fpwl_rows.hip; node classification: C = classes).
  * The piece a value falls into does not depend on the channel, so it is found once per (node, feature) and the
@@ -270,6 +304,8 @@ int gnan_fpwl_locate(const gnan_fpwl_args* a, int32_t* piece, float* dx, gnan_st
 int gnan_fpwl_rows_fwd(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, gnan_stream_t stream);
 int gnan_fpwl_rows_moments_fixed(const gnan_fpwl_args* a, const int32_t* piece, const float* dx, const float* grad,
                                  int64_t grad_stride, const double* scales, int64_t* moments, gnan_stream_t stream);
+/* ... and the query for it (see gnan_fpwl_moments_describe; no pointer of the call is needed: its route depends on sizes only) */
+int gnan_fpwl_rows_moments_describe(const gnan_fpwl_args* a, int64_t grad_stride, gnan_fpwl_moments_info* out);
 
 /* The two scales of gnan_fpwl_moments_fixed, computed on the device:
  *   scales[0] = 2^floor(bits - log2(max|grad|)),  scales[1] = 2^floor(bits - log2(max|grad| * (x_abs_max + max|anchor|)))

@@ -84,7 +84,8 @@ def test_struct_layout_matches_header():
                         ("gnan_small_batch_args", _lib.SmallBatchArgs), ("gnan_fpwl_index_args", _lib.FpwlIndexArgs),
                         ("gnan_small_graph_nam_args", _lib.SmallGraphNamArgs),
                         ("gnan_small_graph_nam_bwd_args", _lib.SmallGraphNamBwdArgs),
-                        ("gnan_small_batch_bwd_args", _lib.SmallBatchBwdArgs)):
+                        ("gnan_small_batch_bwd_args", _lib.SmallBatchBwdArgs),
+                        ("gnan_fpwl_moments_info", _lib.FpwlMomentsInfo)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
