@@ -146,6 +146,9 @@ class SpmmArgs(C.Structure):
         ("seg_index", C.c_void_p), ("seg_start", C.c_void_p), ("seg_row", C.c_void_p), ("cls_seg_ptr", C.c_void_p),
         ("seg_mask", C.c_void_p), ("seg_q_lo", C.c_int64), ("seg_q_hi", C.c_int64), ("n_seg", C.c_int32),
         ("seg_max_per_class", C.c_int32),
+        ("hub_index", C.c_void_p), ("hub_seg_start", C.c_void_p), ("hub_seg_row", C.c_void_p), ("hub_seg_slot", C.c_void_p),
+        ("hub_row_slot_ptr", C.c_void_p), ("hub_cls_seg_ptr", C.c_void_p), ("hub_q_lo", C.c_int64), ("n_hub", C.c_int32),
+        ("n_hub_seg", C.c_int32), ("hub_seg_max_per_class", C.c_int32),
     ]
 
 
@@ -158,7 +161,7 @@ class SpmmLaunchInfo(C.Structure):
         ("vec", C.c_int32), ("lpr", C.c_int32), ("smalld", C.c_int32), ("dense", C.c_int32), ("kernel", C.c_int32),
         ("classed", C.c_int32), ("n_slice_blocks", C.c_int32), ("n_tile_blocks", C.c_int32), ("n_tiles", C.c_int32),
         ("row_q0", C.c_int64), ("short_tile", C.c_int32 * (SHORT_LMAX + 1)),
-        ("n_seg_blocks", C.c_int32), ("n_segs", C.c_int32),
+        ("n_seg_blocks", C.c_int32), ("n_segs", C.c_int32), ("n_hub_seg_blocks", C.c_int32), ("n_hub_segs", C.c_int32),
     ]
 
     def as_dict(self) -> dict:

@@ -95,6 +95,11 @@ SHORT_ROW_LMAX = 4             # (gnan_spmm_args.short_*; the library takes them
 CLASSED_ROWS = True            # reference-order inference (self_sum): the row walk's longer rows a lane group per (row, column class)
 CLASSED_ROWS_MIN_NNZ = 1 << 24     # ... on graphs of at least this many pairs (its own gate: not CLASSED_MIN_NNZ)
 CLASSED_ROWS_MIN_PAIRS = 33        # ... rows of this many pairs up to the hub threshold (HopGraph.classed_row_plan); swept on C4: DESIGN.md 4.1
+BLOCKED_HUBS = True            # ... and the hub rows in segments by (row, column class, popularity block), a class's queue block-major
+BLOCKED_HUBS_MIN_NNZ = 1 << 24     # ... on graphs of at least this many pairs (its own gate, as CLASSED_ROWS_MIN_NNZ is)
+BLOCKED_HUB_BLOCK_BYTES = 4 << 20  # ... operand rows of one (class, block): one XCD's L2 (HopGraph.blocked_hub_plan); swept on C4 with the
+BLOCKED_HUB_BLOCKS = 4             # ... ranked blocks per class (the columns behind them share one more) and with the
+BLOCKED_HUB_SEG_PAIRS = 256        # ... pairs a lane group carries at most (a longer run is cut into pieces): DESIGN.md 4.1
 
 
 def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -245,6 +250,19 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
                 a.seg_index, a.seg_start, a.seg_row = _lib.ptr(rows.index), _lib.ptr(rows.seg_start), _lib.ptr(rows.seg_row)
                 a.cls_seg_ptr, a.seg_mask = _lib.ptr(rows.cls_seg_ptr), _lib.ptr(rows.mask)
                 a.seg_q_lo, a.seg_q_hi, a.n_seg, a.seg_max_per_class = rows.q_lo, rows.q_hi, rows.n_seg, rows.max_per_class
+        if (BLOCKED_HUBS and g.nnz >= BLOCKED_HUBS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
+                and s_total is not None and S.dtype == torch.float32 and plan is not None and plan.n_long > 0
+                and plan.threshold == LONG_ROW_THRESHOLD):
+            # the hub rows in segments of one (column class, popularity block) each, every XCD walking its class's blocks most listed
+            # first: they leave the slice plan — no slice blocks, no fix-up launch
+            hubs = g.blocked_hub_plan(max(1, BLOCKED_HUB_BLOCK_BYTES // (S.shape[1] * 4)), BLOCKED_HUB_BLOCKS, BLOCKED_HUB_SEG_PAIRS)
+            if hubs is not None:
+                a.long_rows = a.long_slice_ptr = a.cls_index = a.cls_slice_start = a.cls_slice_row = a.cls_slot_slice = None
+                a.n_long = a.n_slices = a.cls_n_slots = 0                 # (long_threshold stays: the row blocks leave the hub rows out by it)
+                a.hub_index, a.hub_seg_start, a.hub_seg_row = _lib.ptr(hubs.index), _lib.ptr(hubs.seg_start), _lib.ptr(hubs.seg_row)
+                a.hub_seg_slot, a.hub_row_slot_ptr = _lib.ptr(hubs.seg_slot), _lib.ptr(hubs.row_slot_ptr)
+                a.hub_cls_seg_ptr, a.hub_q_lo, a.n_hub = _lib.ptr(hubs.cls_seg_ptr), hubs.q_lo, hubs.n_hub
+                a.n_hub_seg, a.hub_seg_max_per_class = hubs.n_seg, hubs.max_per_class
     need = _lib.lib().gnan_spmm_fwd_workspace_bytes(a)
     ws = None
     if need:

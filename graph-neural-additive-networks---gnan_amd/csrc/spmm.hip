@@ -15,8 +15,8 @@
 //                   the slices in a fixed order (bit-reproducible, no float atomics).
 // HBM-bound: per edge 4 B col + 1 B code + W*4 B gathered row; per row rowptr + W*4 B store.
 //
-// This file: the forward's entry points and routing, the persistent narrow kernel, the hub rows' fix-up, the classed rows' combine pass
-// and the shell sums.
+// This file: the forward's entry points and routing, the persistent narrow kernel, the hub rows' fix-up, the combine passes of the
+// classed rows and of the blocked hub segments, and the shell sums.
 // spmm_kernel itself is csrc/spmm_fwd_body.hpp (an object per VEC), the gradients are csrc/spmm_grad.hip, what they share is
 // csrc/spmm_common.hpp.
 #include "spmm_common.hpp"
@@ -322,6 +322,40 @@ int launch_seg_combine(const Params& p, hipStream_t st) {
   return gnan::check_launch("spmm_seg_combine_kernel");
 }
 
+// combine of the blocked hub segments (seg_body<.., HUB>): one WAVE per hub row r, four rows per workgroup, no barrier.  Lane l adds the
+// row's slots hub_row_slot_ptr[r] + l, + l + 64, ... in turn (a serial chain), the 64 lane sums meet in a fixed xor butterfly, then
+//   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, sum))
+// with T, the weights and a_i exactly as spmm_seg_combine_kernel reads them.  The slots are the ROW-major enumeration of the row's
+// segments, so the order of the adds depends on the plan alone, not on the queues: bit-reproducible, no atomics.
+__global__ __launch_bounds__(256) void spmm_hub_combine_kernel(const Params p) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int r = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+  if (r >= p.n_hub) return;
+  const int s0 = p.hub_row_slot_ptr[r], s1 = p.hub_row_slot_ptr[r + 1];
+  float y = 0.f;
+  for (int s = s0 + lane; s < s1; s += kWave) y += p.hub_partial[s];
+#pragma unroll
+  for (int off = kWave / 2; off >= 1; off >>= 1) y += __shfl_xor(y, off);
+  if (lane != 0) return;
+  const int64_t q = p.hub_q_lo + r;
+  const int64_t o = out_row(p, q, q);
+  double T = 0.0;
+  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
+  const int rest = p.D - 1;
+  const SmallW sw = small_weights(p, q);
+  const float w_rest = sw.pick(rest);
+  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
+  y = fmaf(w_rest, static_cast<float>(T), y);
+  y = fmaf(w_self, self_term(p, o), y);
+  p.Y[o * p.y_stride] = y;
+}
+
+int launch_hub_combine(const Params& p, hipStream_t st) {
+  if (p.hub_index == nullptr) return GNAN_OK;
+  hipLaunchKernelGGL(spmm_hub_combine_kernel, dim3(static_cast<unsigned>((p.n_hub + 3) / 4)), dim3(256), 0, st, p);
+  return gnan::check_launch("spmm_hub_combine_kernel");
+}
+
 // can the persistent hot-row kernel take this call?  (what the host wrapper sets up: functional.spmm_launch, narrow walk)
 bool hot_kernel_applies(const gnan_spmm_args* a) {
   const int W = a->W;
@@ -463,8 +497,8 @@ int pick_route(const gnan_spmm_args* a, Route* r) {
 
 extern "C" size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a) {
   if (!a) return 0;
-  size_t floats = seg_partial_offset(a);
-  if (a->seg_index && a->seg_q_hi > a->seg_q_lo) floats += static_cast<size_t>(a->seg_q_hi - a->seg_q_lo) * 8;   // the classed rows' partials
+  size_t floats = hub_partial_offset(a);                               // the hub slices' partials, then the classed rows'
+  if (a->hub_index && a->n_hub_seg > 0) floats += static_cast<size_t>(a->n_hub_seg);   // ... then the blocked hub segments'
   return floats * sizeof(float);
 }
 
@@ -494,8 +528,9 @@ extern "C" int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_
   out->kernel = r.hot ? GNAN_SPMM_KERNEL_HOT : GNAN_SPMM_KERNEL_ROWS;
   if (r.hot) return GNAN_OK;
   Params p = make_params(a);
-  if (int rc = plan_tiles(p, r.vec, r.lpr, r.dense, r.smalld, a->seg_max_per_class)) return rc;
+  if (int rc = plan_tiles(p, r.vec, r.lpr, r.dense, r.smalld, a->seg_max_per_class, a->hub_seg_max_per_class)) return rc;
   out->n_seg_blocks = p.n_seg_blocks; out->n_segs = p.n_seg_blocks > 0 ? a->n_seg : 0;
+  out->n_hub_seg_blocks = p.n_hub_blocks; out->n_hub_segs = p.n_hub_blocks > 0 ? a->n_hub_seg : 0;
   out->classed = p.cls_index != nullptr;
   out->n_slice_blocks = p.n_slice_blocks; out->n_tile_blocks = p.n_tile_blocks; out->n_tiles = p.n_tiles;
   out->row_q0 = p.row_q0;
@@ -520,5 +555,6 @@ extern "C" int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream) {
                             : (r.vec == 4 ? gnan::launch_lpr<4>(a, r.lpr, r.dense, r.smalld, st) : gnan::launch_lpr<1>(a, r.lpr, r.dense, r.smalld, st));
   if (rc) return rc;
   if (int rc2 = launch_fixup(p, st)) return rc2;
+  if (int rc2 = launch_hub_combine(p, st)) return rc2;
   return launch_seg_combine(p, st);
 }

@@ -73,6 +73,18 @@ struct Params {
   float* seg_partial;
   int64_t seg_q_lo, seg_q_hi;
   int n_seg_blocks;
+  // blocked hub segments (gnan_spmm_args.hub_*; the SELF instance alone reads them): rows [hub_q_lo, n_rows) are taken a (row, column
+  // class, popularity block) segment per lane group by the n_hub_blocks workgroups at the launch's head — workgroup b takes class b & 7,
+  // a class's queue is block-major — and neither sliced nor walked; a segment's float goes to hub_partial[hub_seg_slot[s]]
+  const int32_t* hub_index;
+  const int64_t* hub_seg_start;
+  const int32_t* hub_seg_row;
+  const int32_t* hub_seg_slot;
+  const int32_t* hub_row_slot_ptr;
+  const int32_t* hub_cls_seg_ptr;
+  float* hub_partial;
+  int64_t hub_q_lo;
+  int n_hub, n_hub_blocks;
 };
 
 __device__ __forceinline__ int64_t load_rowptr(const Params& p, int64_t i) {
@@ -399,6 +411,18 @@ inline int validate(const gnan_spmm_args* a) {
                  a->seg_q_hi <= a->n_rows && a->D <= 8,
                  "spmm: incomplete classed row plan (segments, a class table, a mask, rows behind the tiled runs within n_rows)");
   }
+  if (a->hub_index) {
+    // (read by the self_sum instance alone, in place of a hub-row plan)
+    if (!(a->self_sum && a->s_total && a->short_lmax > 0 && a->n_long == 0 && a->cls_index == nullptr))
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: blocked hub segments are served on the self_sum route (short-row runs declared, "
+                        "s_total set) without a hub-row plan only");
+    GNAN_REQUIRE(a->hub_seg_start && a->hub_seg_row && a->hub_seg_slot && a->hub_row_slot_ptr && a->hub_cls_seg_ptr && a->n_hub > 0 &&
+                 a->n_hub_seg > 0 && a->hub_seg_max_per_class > 0 && a->hub_seg_max_per_class <= a->n_hub_seg && a->long_threshold > 0 &&
+                 a->hub_q_lo >= a->short_row[a->short_lmax + 1] && a->hub_q_lo + a->n_hub == a->n_rows &&
+                 (a->seg_index == nullptr || a->seg_q_hi <= a->hub_q_lo) && a->D <= 8,
+                 "spmm: incomplete blocked hub plan (segments, slots, a class table, the hub rows the last n_hub of n_rows behind the "
+                 "tiled and the classed rows, long_threshold set)");
+  }
   if (a->n_long > 0) {
     GNAN_REQUIRE(a->rowptr != nullptr || (a->n_long == a->n_rows && a->long_threshold == 0),
                  "spmm: a row plan for the dense layout must slice every row (n_long == n_rows, long_threshold == 0)");
@@ -413,9 +437,15 @@ inline int validate(const gnan_spmm_args* a) {
   return GNAN_OK;
 }
 
-// floats of the hub slices' partials at the head of the forward's workspace; the classed rows' [seg_q_hi - seg_q_lo, 8] floats follow
+// floats of the hub slices' partials at the head of the forward's workspace; the classed rows' [seg_q_hi - seg_q_lo, 8] floats follow,
+// the blocked hub segments' [n_hub_seg] floats come last
 inline size_t seg_partial_offset(const gnan_spmm_args* a) {
   return a->n_long > 0 ? static_cast<size_t>(a->n_slices) * 2 * static_cast<size_t>(a->W) : 0;
+}
+inline size_t hub_partial_offset(const gnan_spmm_args* a) {
+  size_t floats = seg_partial_offset(a);
+  if (a->seg_index && a->seg_q_hi > a->seg_q_lo) floats += static_cast<size_t>(a->seg_q_hi - a->seg_q_lo) * 8;
+  return floats;
 }
 
 inline Params make_params(const gnan_spmm_args* a) {
@@ -456,6 +486,16 @@ inline Params make_params(const gnan_spmm_args* a) {
     p.seg_q_lo = a->seg_q_lo; p.seg_q_hi = a->seg_q_hi;
     p.seg_partial = static_cast<float*>(a->workspace) + seg_partial_offset(a);
   }
+  p.hub_index = a->hub_index; p.hub_seg_start = a->hub_seg_start; p.hub_seg_row = a->hub_seg_row; p.hub_seg_slot = a->hub_seg_slot;
+  p.hub_row_slot_ptr = a->hub_row_slot_ptr; p.hub_cls_seg_ptr = a->hub_cls_seg_ptr;
+  p.hub_partial = nullptr;
+  p.hub_q_lo = a->n_rows;
+  p.n_hub = p.n_hub_blocks = 0;
+  if (a->hub_index) {   // (validate(): no hub-row plan beside it; the row blocks still leave the hub rows out by their length)
+    p.hub_q_lo = a->hub_q_lo; p.n_hub = a->n_hub;
+    p.hub_partial = static_cast<float*>(a->workspace) + hub_partial_offset(a);
+    p.long_threshold = a->long_threshold;
+  }
   p.n_tile_blocks = p.n_tiles = 0;
   p.row_q0 = 0;
   for (int L = 0; L <= GNAN_SHORT_LMAX + 1; ++L) p.short_row[L] = L <= p.short_lmax + 1 && runs ? a->short_row[L] : 0;
@@ -478,7 +518,7 @@ inline void pick_tiling(const gnan_spmm_args* a, const float* out, int64_t out_s
 
 // The tile partition of a launch of the <vec, lpr> variant: which of the declared short-row runs the kernel takes in tiles, and where
 // each run's tiles start.  The launch and gnan_spmm_fwd_describe both call this (and nothing else decides it).
-inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld, int seg_max = 0) {
+inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld, int seg_max = 0, int hub_seg_max = 0) {
   const int G = kWave / lpr;
   // short-row tiles: the packed small-D forward over a degree-sorted copy, one pass of the lane group over the columns
   if (short_tiles_serve(vec, lpr, smalld, p.packed, p.s_by_code) && p.short_lmax > 0 && !dense && p.scatter_out == 2 &&
@@ -505,6 +545,14 @@ inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld, int 
     const int64_t nb = 8 * ((static_cast<int64_t>(seg_max) + per - 1) / per);
     if (nb > 0x3fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many row segments for one launch");
     p.n_seg_blocks = static_cast<int>(nb);
+  }
+  if (p.hub_index) {   // blocked hub segments: the same partition, their workgroups at the launch's head
+    if (!(p.short_lmax > 0 && p.self_sum && p.hub_q_lo >= p.row_q0))
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: blocked hub segments need the tiled self_sum variant (fp32 rows of 16 lanes or more)");
+    const int64_t per = 4 * static_cast<int64_t>(G);
+    const int64_t nb = 8 * ((static_cast<int64_t>(hub_seg_max) + per - 1) / per);
+    if (nb > 0x3fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many hub segments for one launch");
+    p.n_hub_blocks = static_cast<int>(nb);
   }
   return GNAN_OK;
 }
@@ -540,6 +588,7 @@ inline int forward_only_self_sum(const gnan_spmm_args* a, const char* who) {
 }
 inline int forward_only_index(const gnan_spmm_args* a, const char* who, bool reads_packed = false) {
   GNAN_REQUIRE(a->cls_index == nullptr, "%s: the classed hub plan is read by gnan_spmm_fwd only", who);
+  GNAN_REQUIRE(a->hub_index == nullptr, "%s: blocked hub segments are read by gnan_spmm_fwd only", who);
   GNAN_REQUIRE(reads_packed || !a->packed_index, "%s: packed index entries are read by gnan_spmm_fwd only", who);
   return GNAN_OK;
 }

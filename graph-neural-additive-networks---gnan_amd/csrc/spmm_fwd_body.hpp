@@ -366,7 +366,9 @@ __device__ __forceinline__ float dpp_row(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
-template <int VEC, int LPR>
+// HUB: the blocked hub segments (gnan_spmm_args.hub_*) — the same body over the hub plan's arrays; the float goes to the segment's slot
+// of the row-major enumeration, hub_partial[hub_seg_slot[s]] (spmm_hub_combine_kernel, csrc/spmm.hip, adds a row's slots).
+template <int VEC, int LPR, bool HUB = false>
 __device__ __forceinline__ void seg_body(const Params& p, const int blk) {
   static_assert(LPR >= 16 && VEC == 4, "a DPP row per lane group, one index entry per lane and round");
   constexpr int G = kWave / LPR;
@@ -377,12 +379,14 @@ __device__ __forceinline__ void seg_body(const Params& p, const int blk) {
   const int sub = lane % LPR;
   const int slot = lane / LPR;
   const int cls = blk & 7;
-  const int s = p.cls_seg_ptr[cls] + ((blk >> 3) * 4 + wave) * G + slot;
-  if (s >= p.cls_seg_ptr[cls + 1]) return;   // (the whole group)
-  const int64_t q = p.seg_row[s];
-  const int64_t lo = p.seg_start[s];
-  const int n = static_cast<int>(p.seg_start[s + 1] - lo);     // (a row of at most long_threshold pairs)
-  const int32_t* idx = p.seg_index + lo;
+  const int32_t* cls_ptr = HUB ? p.hub_cls_seg_ptr : p.cls_seg_ptr;
+  const int64_t* start = HUB ? p.hub_seg_start : p.seg_start;
+  const int s = cls_ptr[cls] + ((blk >> 3) * 4 + wave) * G + slot;
+  if (s >= cls_ptr[cls + 1]) return;   // (the whole group)
+  const int64_t q = (HUB ? p.hub_seg_row : p.seg_row)[s];
+  const int64_t lo = start[s];
+  const int n = static_cast<int>(start[s + 1] - lo);     // (a row of at most long_threshold pairs; a hub segment of at most the plan's cap)
+  const int32_t* idx = (HUB ? p.hub_index : p.seg_index) + lo;
   const int rest = p.D - 1;
   SmallW sw = small_weights(p, q);           // (scatter_out 2: slot q reads adjacency row q)
   {
@@ -431,7 +435,11 @@ __device__ __forceinline__ void seg_body(const Params& p, const int blk) {
   r += dpp_row<0x140>(r);   // row_mirror: the other half of the sixteen
 #pragma unroll
   for (int off = 16; off < LPR; off <<= 1) r += __shfl_xor(r, off);
-  if (sub == 0) p.seg_partial[(q - p.seg_q_lo) * 8 + cls] = r;
+  if constexpr (HUB) {
+    if (sub == 0) p.hub_partial[p.hub_seg_slot[s]] = r;
+  } else {
+    if (sub == 0) p.seg_partial[(q - p.seg_q_lo) * 8 + cls] = r;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -565,7 +573,8 @@ __device__ __forceinline__ void slice_body(const Params& p, const int blk) {
 }
 
 // One launch covers everything: workgroups [0, n_slices) take the hub-row slices (they start first,
-// so the long-latency slices overlap the bulk), then (SELF) the classed rows' segments, then the tiles; the rest take 4*G ordinary rows each.
+// so the long-latency slices overlap the bulk) — or (SELF) the blocked hub segments, a class's queue in popularity-block order — then
+// (SELF) the classed rows' segments, then the tiles; the rest take 4*G ordinary rows each.
 // BYCODE (operand row = (neighbour, hop code), the narrow-operand backward) is a template parameter: as a run-time
 // flag its address arithmetic cost the W = 64 kernels 4 VGPRs and the bf16 variant 20 B of scratch (bf16 rows 2.85 -> 3.35 ms).
 // SELF (the route short_tiles_serve describes, reduce_cr == 1): the rows' self term from gnan_spmm_args.self_sum in the read-out's
@@ -580,7 +589,12 @@ void spmm_kernel(const Params p) {
       return;
     }
     int front = p.n_slice_blocks;       // workgroups ahead of the tile blocks
-    if constexpr (SELF) {               // (plan_tiles() leaves n_seg_blocks 0 without a classed row plan)
+    if constexpr (SELF) {               // (plan_tiles() leaves n_hub_blocks / n_seg_blocks 0 without a blocked hub / classed row plan)
+      if (static_cast<int>(blockIdx.x) < front + p.n_hub_blocks) {   // (validate(): no slice blocks then — these are the launch's first)
+        seg_body<VEC, LPR, true>(p, static_cast<int>(blockIdx.x) - front);
+        return;
+      }
+      front += p.n_hub_blocks;
       if (static_cast<int>(blockIdx.x) < front + p.n_seg_blocks) {
         seg_body<VEC, LPR>(p, static_cast<int>(blockIdx.x) - front);
         return;
@@ -608,12 +622,14 @@ int launch(const gnan_spmm_args* a, bool dense, bool smalld, hipStream_t st) {
   constexpr int G = kWave / LPR;
   const int rows_per_block = 4 * G;
   Params p = make_params(a);
-  if (int rc = plan_tiles(p, VEC, LPR, dense, smalld, a->seg_max_per_class)) return rc;
+  if (int rc = plan_tiles(p, VEC, LPR, dense, smalld, a->seg_max_per_class, a->hub_seg_max_per_class)) return rc;
   const int n_slices = p.n_slices;
-  const int64_t walked = p.n_rows - p.row_q0 - (p.seg_q_hi - p.seg_q_lo);   // (the classed rows are taken in segments)
+  // (the classed rows are taken in segments; so are the rows from hub_q_lo on, n_rows without a blocked hub plan)
+  const int64_t walked = p.hub_q_lo - p.row_q0 - (p.seg_q_hi - p.seg_q_lo);
   const int64_t blocks = dense && n_slices > 0
                              ? n_slices
-                             : (walked + rows_per_block - 1) / rows_per_block + p.n_slice_blocks + p.n_seg_blocks + p.n_tile_blocks;
+                             : (walked + rows_per_block - 1) / rows_per_block + p.n_slice_blocks + p.n_hub_blocks + p.n_seg_blocks +
+                                   p.n_tile_blocks;
   if (blocks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many rows for one launch");
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
   if (p.s_by_code) {

@@ -120,6 +120,36 @@ class ClassedRowPlan:
 
 
 @dataclass
+class BlockedHubPlan:
+    """:meth:`HopGraph.blocked_hub_plan`: the pairs of the hub rows ``[q_lo, n_rows)`` of a degree-sorted copy as SEGMENTS of at most
+    ``seg_pairs`` pairs of one (row, column class ``col & 7``, popularity block) each (``gnan_spmm_args.hub_*``).  ``index``
+    (``col | code << 29``) and the segments are in QUEUE order: class-major, within a class block-major, then by row, then by piece; a
+    segment keeps the row's own pair order.  Segment ``s`` covers ``index[seg_start[s], seg_start[s + 1])`` of row ``seg_row[s]``; class
+    ``c`` owns segments ``[cls_seg_ptr[c], cls_seg_ptr[c + 1])``; ``seg_slot[s]`` is the segment's place in the ROW-major enumeration
+    (row, class, block, piece), and row ``q_lo + r`` owns the slots ``[row_slot_ptr[r], row_slot_ptr[r + 1])``."""
+    q_lo: int
+    n_hub: int
+    block_rows: int
+    n_blocks: int                 # ranked blocks; block ``n_blocks`` is the cold remainder
+    seg_pairs: int
+    n_seg: int
+    max_per_class: int            # segments of the largest class (sizes the launch)
+    index: torch.Tensor           # int32 [pairs of the hub rows]
+    seg_start: torch.Tensor       # int64 [n_seg + 1]
+    seg_row: torch.Tensor         # int32 [n_seg]
+    seg_slot: torch.Tensor        # int32 [n_seg]
+    row_slot_ptr: torch.Tensor    # int32 [n_hub + 1]
+    cls_seg_ptr: torch.Tensor     # int32 [9]
+    block_pairs: list             # pairs per block, 0 .. n_blocks (for the record)
+    block_segs: list              # segments per block
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.index, self.seg_start, self.seg_row, self.seg_slot, self.row_slot_ptr,
+                                                           self.cls_seg_ptr))
+
+
+@dataclass
 class SelfFreePlan:
     """:meth:`HopGraph.self_free_plan`: the graph without its rows' self pairs, and which nodes its remaining pairs list."""
     twin: "HopGraph"              # same rows, the pair (i, i, code 0) removed from every row; ``cnt`` IS the graph's tensor
@@ -155,6 +185,7 @@ class HopGraph:
     _classed: dict = field(default_factory=dict, repr=False)        # classed_hub_plan(): (order, threshold, slice_edges) -> plan
     _short_runs: dict = field(default_factory=dict, repr=False)     # short_row_runs(): lmax -> ShortRowRuns
     _classed_rows: dict = field(default_factory=dict, repr=False)   # classed_row_plan(): (min_pairs, max_pairs) -> plan or None
+    _blocked_hubs: dict = field(default_factory=dict, repr=False)   # blocked_hub_plan(): its parameters -> plan or None
     _sorted_copy: Optional["HopGraph"] = field(default=None, repr=False)
     _hot: Optional[tuple] = field(default=None, repr=False)           # hot_columns(): (ids or None,)
     _sorted_copy_hot: Optional["HopGraph"] = field(default=None, repr=False)
@@ -487,6 +518,81 @@ class HopGraph:
         mask = (has << torch.arange(K, device=dev).view(K, 1)).sum(0).to(torch.uint8)
         return ClassedRowPlan(q_lo, q_hi, int(min_pairs), n_seg, int((cls_ptr[1:] - cls_ptr[:-1]).max()), index, seg_start,
                               (seg % R + q_lo).to(torch.int32), cls_ptr.to(torch.int32), mask.contiguous())
+
+    def column_blocks(self, block_rows: int, n_blocks: int) -> torch.Tensor:
+        """Popularity block of every column (int64 ``[n_cols]``): the columns of one class ``col & 7`` ranked by how often the graph's
+        pairs list them — most listed first, ties by column id — ``block_rows`` to a block; ranks from ``block_rows * n_blocks`` on
+        share block ``n_blocks``, the cold remainder."""
+        dev, K = self.device, HUB_CLASSES
+        listed = torch.bincount(self.col.long(), minlength=self.n_cols)
+        by_count = torch.argsort(listed, descending=True, stable=True)              # ties keep the ascending column id
+        order = by_count[torch.argsort(by_count & (K - 1), stable=True)]             # class-major, a class's columns by rank
+        cls_first = torch.cumsum(torch.bincount(order & (K - 1), minlength=K), 0)
+        cls_first = torch.cat([cls_first.new_zeros(1), cls_first[:-1]])
+        rank = torch.empty(self.n_cols, dtype=torch.int64, device=dev)
+        rank[order] = torch.arange(self.n_cols, device=dev) - cls_first[order & (K - 1)]
+        return torch.clamp(rank // int(block_rows), max=int(n_blocks))
+
+    def blocked_hub_plan(self, block_rows: int, n_blocks: int, seg_pairs: int,
+                         threshold: int = LONG_ROW_THRESHOLD) -> Optional[BlockedHubPlan]:
+        """The rows of more than ``threshold`` listed pairs of a DEGREE-SORTED copy (its last rows) cut into segments by (row, column
+        class, popularity block of :meth:`column_blocks`), a run of more than ``seg_pairs`` pairs into pieces: :class:`BlockedHubPlan`.
+        ``None`` without such a row or where the packed entries cannot hold the graph.  Framework ops on the graph's device (stable
+        sorts of the hub rows' pairs and of the columns' counts); cached per graph and parameter set."""
+        key = (int(block_rows), int(n_blocks), int(seg_pairs), int(threshold))
+        if key in self._blocked_hubs:
+            return self._blocked_hubs[key]
+        plan = None
+        if (not self.is_dense and self.n_cols <= (1 << PACK_SHIFT) and self.n_codes <= 8 and self.n_rows > 0 and self.nnz < 2 ** 31
+                and min(key[:3]) >= 1):
+            plan = self._blocked_hub_plan_torch(*key)
+        self._blocked_hubs[key] = plan
+        return plan
+
+    def _blocked_hub_plan_torch(self, block_rows: int, n_blocks: int, cap: int, threshold: int) -> Optional[BlockedHubPlan]:
+        dev, K, NB = self.device, HUB_CLASSES, n_blocks + 1
+        rp = self.rowptr.long()
+        deg = rp[1:] - rp[:-1]
+        if bool((deg[1:] < deg[:-1]).any()):
+            raise ValueError("blocked_hub_plan needs a degree-sorted copy (rows shortest first)")
+        q_lo = int(torch.searchsorted(deg, torch.tensor([threshold + 1], device=dev)))
+        R = self.n_rows - q_lo
+        if R <= 0:
+            return None
+        e0 = int(rp[q_lo])
+        c = self.col[e0:].long()
+        if self.colp is not None:
+            v = self.colp[e0:]
+        else:
+            w = c | (self.code[e0:].long() << PACK_SHIFT)
+            v = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        blk = self.column_blocks(block_rows, n_blocks)[c]
+        row = torch.repeat_interleave(torch.arange(R, device=dev), deg[q_lo:])
+        key = (((c & (K - 1)) * NB + blk) * R + row)                       # class, block, row; the sort keeps a row's pair order
+        block_pairs = torch.bincount(blk, minlength=NB).tolist()
+        del c, blk, row
+        index = v[torch.argsort(key, stable=True)].contiguous()
+        cnt = torch.bincount(key, minlength=K * NB * R)
+        del key
+        run = torch.nonzero(cnt).flatten()                                 # (class, block, row) of every run, in queue order
+        pieces = (cnt[run] + cap - 1) // cap
+        pair_off = torch.cumsum(cnt[run], 0) - cnt[run]
+        n_seg = int(pieces.sum())
+        t = torch.repeat_interleave(torch.arange(int(run.numel()), device=dev), pieces)      # the run of every segment
+        j = torch.arange(n_seg, device=dev) - (torch.cumsum(pieces, 0) - pieces)[t]          # ... and which piece of it
+        seg_start = torch.cat([pair_off[t] + j * cap, cnt.sum().view(1)])
+        seg_key = run[t]
+        seg_r, seg_cb = seg_key % R, seg_key // R
+        cls_ptr = torch.searchsorted(seg_key, torch.arange(K + 1, device=dev) * (NB * R))
+        # the row-major enumeration (row, class, block, piece): a stable sort of the queue order by (row, class, block) keeps the pieces
+        by_row = torch.argsort(seg_r * (K * NB) + seg_cb, stable=True)
+        seg_slot = torch.empty(n_seg, dtype=torch.int64, device=dev)
+        seg_slot[by_row] = torch.arange(n_seg, device=dev)
+        row_slot_ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        row_slot_ptr[1:] = torch.cumsum(torch.bincount(seg_r, minlength=R), 0)
+        return BlockedHubPlan(q_lo, R, int(block_rows), int(n_blocks), int(cap), n_seg, int((cls_ptr[1:] - cls_ptr[:-1]).max()), index,
+                              seg_start, (seg_r + q_lo).to(torch.int32), seg_slot.to(torch.int32), row_slot_ptr.to(torch.int32),
+                              cls_ptr.to(torch.int32), block_pairs, torch.bincount(seg_cb % NB, minlength=NB).tolist())
 
     def narrow_row_plan(self) -> LongRowPlan:
         """Hub-row plan for operand rows of one or two lanes: the low threshold while only a FEW rows exceed it (the tail

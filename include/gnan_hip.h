@@ -584,6 +584,29 @@ typedef struct gnan_spmm_args {
   int64_t seg_q_lo, seg_q_hi;
   int32_t n_seg;
   int32_t seg_max_per_class;
+  /* blocked hub segments (the struct grew at its end again; gnan_spmm_fwd only, optional, on the self_sum route alone and instead of a
+   * hub-row plan: n_long must be 0, long_threshold stays the hub threshold; GNAN_ERR_UNSUPPORTED anywhere else).  The hub rows of the
+   * degree-sorted copy — rows [hub_q_lo, n_rows), every row of more than long_threshold pairs — are neither sliced nor walked: the
+   * pairs of hub row q whose column falls in class c = column & 7 and in popularity block b (the columns of a class ranked by how often
+   * they are listed, block_rows of them per block, the rest in the last one) form a run, cut into SEGMENTS of at most a fixed number of
+   * pairs.  Class c's queue, segments [hub_cls_seg_ptr[c], hub_cls_seg_ptr[c + 1]) (a DEVICE array of 9), is sorted block-major, then
+   * by row, then by piece; workgroup b of the hub range — the first workgroups of the launch — takes class b & 7, so every XCD walks
+   * its class's blocks in popularity order.  Segment s reads hub_index[hub_seg_start[s], hub_seg_start[s + 1]) (packed entries, the
+   * row's own pair order) for row hub_seg_row[s] and stores ONE float at partial[hub_seg_slot[s]] behind the classed rows' partials
+   * in `workspace`; hub_seg_slot is the segment's place in a ROW-major enumeration, so that row hub_q_lo + r owns
+   * partial[hub_row_slot_ptr[r] .. hub_row_slot_ptr[r + 1]) whatever the queues' order.  A combine pass adds a row's partials in a
+   * fixed order (a wave per row: lane l the slots l, l + 64, ... in turn, then a fixed butterfly), then the rest and self terms as
+   * the classed rows' combine does.  No atomics.  NULL hub_index (the default): off */
+  const int32_t* hub_index;
+  const int64_t* hub_seg_start;      /* [n_hub_seg + 1] */
+  const int32_t* hub_seg_row;        /* [n_hub_seg] rows of the sorted copy */
+  const int32_t* hub_seg_slot;       /* [n_hub_seg] a permutation */
+  const int32_t* hub_row_slot_ptr;   /* [n_hub + 1] */
+  const int32_t* hub_cls_seg_ptr;    /* [9] */
+  int64_t hub_q_lo;
+  int32_t n_hub;                     /* n_rows - hub_q_lo */
+  int32_t n_hub_seg;
+  int32_t hub_seg_max_per_class;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
@@ -594,7 +617,7 @@ int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream);
  * copy of them, which the launch and this query both call.  All fields are zero when n_rows == 0 (kernel NONE); the hot-row kernel
  * has no block partition (the fields below `classed` stay zero). */
 #define GNAN_SPMM_KERNEL_NONE 0
-#define GNAN_SPMM_KERNEL_ROWS 1   /* spmm_kernel: slice blocks, then segment blocks, then tile blocks, then row blocks */
+#define GNAN_SPMM_KERNEL_ROWS 1   /* spmm_kernel: slice blocks (or blocked hub segment blocks), then segment blocks, tile blocks, row blocks */
 #define GNAN_SPMM_KERNEL_HOT 2    /* spmm_hot_kernel: persistent workgroups, hottest operand rows in LDS */
 typedef struct gnan_spmm_launch_info {
   int32_t vec;                   /* floats (bf16: elements) a lane reads of an operand row at once: 1, 4 or 8 */
@@ -610,6 +633,8 @@ typedef struct gnan_spmm_launch_info {
   int32_t short_tile[GNAN_SHORT_LMAX + 1];   /* first tile of run L, L = 0 .. short_lmax (when n_tiles > 0) */
   int32_t n_seg_blocks;          /* workgroups of classed row segments (a multiple of 8); 0: no row is taken in segments */
   int32_t n_segs;                /* classed row segments */
+  int32_t n_hub_seg_blocks;      /* workgroups of blocked hub segments (a multiple of 8, the launch's first); then n_slice_blocks == 0 */
+  int32_t n_hub_segs;            /* blocked hub segments */
 } gnan_spmm_launch_info;
 
 int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_info* out);
