@@ -116,6 +116,34 @@ class FpwlGradArgs(C.Structure):
     ]
 
 
+class PwlDfdxArgs(C.Structure):
+    _fields_ = [
+        ("off", C.c_void_p), ("anchor", C.c_void_p), ("T", C.c_int64),
+        ("w_first", C.c_void_p), ("b_first", C.c_void_p), ("w_mid", C.c_void_p), ("b_mid", C.c_void_p), ("w_last", C.c_void_p),
+        ("F", C.c_int32), ("L", C.c_int32), ("H", C.c_int32), ("C", C.c_int32), ("dfdx", C.c_void_p),
+    ]
+
+
+class FpwlInputGradArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("n", C.c_int64), ("x_stride", C.c_int64), ("F", C.c_int32), ("C", C.c_int32),
+        ("off", C.c_void_p), ("anchor", C.c_void_p), ("dfdx", C.c_void_p),
+        ("max_pieces", C.c_int32), ("features_per_group", C.c_int32), ("max_group_pieces", C.c_int32),
+        ("sum_features", C.c_int32), ("grad", C.c_void_p), ("grad_stride", C.c_int64), ("gx", C.c_void_p),
+        ("gx_stride", C.c_int64),
+    ]
+
+
+class FpwlInputGradInfo(C.Structure):
+    _fields_ = [
+        ("block_size", C.c_int32), ("nodes_per_block", C.c_int32), ("features_per_group", C.c_int32), ("lds_bytes", C.c_int32),
+        ("vec", C.c_int32), ("n_groups", C.c_int32), ("n_blocks", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class RhoLutArgs(C.Structure):
     _fields_ = [
         ("cnt", C.c_void_p), ("cnt_stride", C.c_int64), ("n_rows", C.c_int64), ("D", C.c_int32), ("C", C.c_int32),
@@ -431,6 +459,9 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p]),
     "gnan_fpwl_moment_scales": (C.c_int, [C.POINTER(MomentScalesArgs), C.c_void_p]),
     "gnan_fpwl_param_grads": (C.c_int, [C.POINTER(FpwlGradArgs), C.c_void_p]),
+    "gnan_pwl_piece_dfdx": (C.c_int, [C.POINTER(PwlDfdxArgs), C.c_void_p]),
+    "gnan_fpwl_input_grad": (C.c_int, [C.POINTER(FpwlInputGradArgs), C.c_void_p]),
+    "gnan_fpwl_input_grad_describe": (C.c_int, [C.POINTER(FpwlInputGradArgs), C.POINTER(FpwlInputGradInfo)]),
     "gnan_graph_replace_memsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "gnan_graph_node_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gnan_small_graph_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -918,7 +918,7 @@ class _ReferenceOrderAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, lut, g, use_cnt, with_rest, L, H, C, F, *params):
         p = StackedMLP(*params, L, H, C, F)
-        needs_grad = any(ctx.needs_input_grad[9:])
+        needs_grad = any(ctx.needs_input_grad[9:]) or ctx.needs_input_grad[0]
         fx, tables, total = Fn._fmlp_forward(x, p, False, with_rest, needs_grad, torch.float32, None)
         if with_rest and total is None:
             total = Fn.column_sums(fx)
@@ -945,18 +945,23 @@ class _ReferenceOrderAggregate(torch.autograd.Function):
         else:                                                       # rows too large to keep: the feature sum is looked up again
             S1 = Fn._fpwl_launch(x, ctx.tables, True)
         dS1, dlut = _aggregate_backward(ctx.call, S1, lut, dY, True, ctx.needs_input_grad[1])
-        pg = (None,) * 6
-        if any(ctx.needs_input_grad[9:]):
-            # every feature's rows have the gradient dS1: the shape functions' gradients are those of the feature-SUM mode
-            _, pg = Fn._shape_function_grads(x, params, ctx.present, ctx.tables, dS1, True, L, H, C, F, ctx.x_abs_max)
-        return (None, dlut, None, None, None, None, None, None, None, *pg)
+        gx, pg = None, (None,) * 6
+        if any(ctx.needs_input_grad[9:]) or ctx.needs_input_grad[0]:
+            # every feature's rows have the gradient dS1: the shape functions' gradients — x.grad among them, the same look-up of
+            # the per-piece derivatives — are those of the feature-SUM mode
+            gx, pg = Fn._shape_function_grads(x, params, ctx.present, ctx.tables, dS1, True, L, H, C, F, ctx.x_abs_max,
+                                              want_x_grad=ctx.needs_input_grad[0],
+                                              want_param_grads=any(ctx.needs_input_grad[9:]))
+        return (gx, dlut, None, None, None, None, None, None, None, *pg)
 
 
 def reference_order_applies(x: torch.Tensor, p: StackedMLP, lut: torch.Tensor, g: HopGraph) -> bool:
     """Can :func:`reference_order_forward` take this call?  Training through the table path (what AUTO picks from 2^18
-    look-ups), a global weight table, a read-out width the aggregation kernel fuses, features without a gradient."""
+    look-ups), a global weight table, a read-out width the aggregation kernel fuses, and features without a gradient or with
+    one the tables serve (``functional._table_grads_applies``: ``x.grad`` is then a look-up in the backward pass)."""
     grads = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in p[:6])
-    return (grads and not x.requires_grad and lut.dim() == 2 and p.C in FUSABLE_READOUT and p.L >= 2 and not g.is_dense
+    x_ok = not x.requires_grad or (x.is_cuda and Fn._table_grads_applies(p.L, p.H, p.C))
+    return (grads and x_ok and lut.dim() == 2 and p.C in FUSABLE_READOUT and p.L >= 2 and not g.is_dense
             and (Fn.FMLP_ALGO == _lib.FMLP_PWL or (Fn.FMLP_ALGO == _lib.FMLP_AUTO and x.shape[0] * p.F >= Fn.PWL_MIN_WORK_GRAD))
             and not torch.cuda.is_current_stream_capturing() and not (Fn.PAD_FEATURES and p.F % Fn.PAD_FEATURES and p.C == 1
                                                                       and x.shape[0] * p.F >= Fn.PAD_MIN_WORK))

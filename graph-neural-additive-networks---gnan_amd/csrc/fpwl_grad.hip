@@ -25,6 +25,7 @@
 // gnan_fpwl_moment_scales: the two power-of-two scales of the fixed-point moments, from max|grad| and max|x - anchor|,
 // in one pass + one single-thread kernel instead of ~20 framework launches.
 #include "common.hpp"
+#include "piece_points.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -73,19 +74,7 @@ __device__ __forceinline__ bool piece_moment(const GradParams& p, int64_t t, int
   return v != 0.f;
 }
 
-// anchor of piece li (of P) and a point strictly inside it: piece 0 is the ray left of the first kink (anchored at that
-// kink), the last piece the ray right of the last kink; a zero-width piece (coinciding kinks) holds no node
-// A piece one float32 step wide, [a, nextafter(a)), holds the nodes with x == a and nothing else (the table builder puts one
-// behind every anchor on which a hidden unit's pre-activation is exactly zero, pwl_build.hip): its masks are taken AT a,
-// strictly (z > 0), which is torch's relu'(0) = 0 — with zero biases (GNAN.py:49-53) and one-hot features that is every
-// unit of most nodes, and the masks of the piece to the right would hand their bias gradients to the wrong units.
-__device__ __forceinline__ void piece_points(const float* A, int li, int P, double* a, double* xi) {
-  *a = static_cast<double>(A[li]);
-  if (li == 0) *xi = *a - 1.0;
-  else if (li == P - 1) *xi = *a + 1.0;
-  else if (A[li + 1] <= nextafterf(A[li], INFINITY)) *xi = *a;
-  else *xi = 0.5 * (*a + static_cast<double>(A[li + 1]));
-}
+using gnan::piece_points;   // anchor of a piece and the point its masks are taken at (csrc/piece_points.hpp)
 
 // live[0 .. *n_live) = the pieces of [base, base + P) that hold at least one node (a non-zero moment), ascending: one parallel
 // pass over the moments and an ordered compaction by ballots (a single thread walking P flags in LDS cost ~5 us of the 64 the

@@ -660,6 +660,55 @@ def _fpwl_param_grads_launch(params, t, moments, L, H, C, F, dests=None):
     return outs
 
 
+def _input_grad_applies(tables, L: int, H: int, C: int, x: torch.Tensor) -> bool:
+    """``x.grad`` of the table path comes from the tables (:func:`_fpwl_input_grad`) for the shapes whose parameter gradients
+    do (:func:`_table_grads_applies`), on tables the thread-per-node look-up holds in LDS."""
+    if tables is None or not x.is_cuda or not _table_grads_applies(L, H, C):
+        return False
+    from .pwl import oversize
+    return not oversize(tables)
+
+
+def _piece_dfdx_launch(params, t, L, H, C, F) -> torch.Tensor:
+    """``gnan_pwl_piece_dfdx``: ``dfdx [T, C]`` float32, the input derivative of every piece of the stacked tables ``t`` at the
+    point the parameter gradients take its masks at (``pwl.piece_derivatives_reference`` restates it)."""
+    keep = [None if q is None else q.detach().float().contiguous() for q in params]
+    T = t.anchor.numel()
+    dfdx = torch.empty((T, C), dtype=torch.float32, device=t.anchor.device)
+    a = _lib.PwlDfdxArgs(off=_lib.ptr(t.off), anchor=_lib.ptr(t.anchor), T=T, w_first=_lib.ptr(keep[0]), b_first=_lib.ptr(keep[1]),
+                         w_mid=_lib.ptr(keep[2]), b_mid=_lib.ptr(keep[3]), w_last=_lib.ptr(keep[4]), F=F, L=L, H=H, C=C,
+                         dfdx=_lib.ptr(dfdx))
+    _lib.check(_lib.lib().gnan_pwl_piece_dfdx(a, _lib.stream_of(dfdx)), "gnan_pwl_piece_dfdx")
+    return dfdx
+
+
+def _fpwl_input_grad(x: torch.Tensor, t, dfdx: torch.Tensor, grad: torch.Tensor, sum_features: bool,
+                     describe: Optional[list] = None) -> torch.Tensor:
+    """``gx[n, k] = sum_c g[n, k, c] dfdx[piece of x[n, k], c]`` (``gnan_fpwl_input_grad``): ``[n, F]`` float32.  ``describe``: a
+    list that receives the launch's plan (``gnan_fpwl_input_grad_describe`` as a dict), asked with the very arguments."""
+    x = _rows(x.detach().float())
+    grad = _rows(grad.detach().float())
+    n, F = x.shape
+    gx = torch.empty((n, F), dtype=torch.float32, device=x.device)
+    a = _lib.FpwlInputGradArgs(x=_lib.ptr(x), n=n, x_stride=x.stride(0), F=F, C=dfdx.shape[1], off=_lib.ptr(t.off),
+                               anchor=_lib.ptr(t.anchor), dfdx=_lib.ptr(dfdx), max_pieces=int(t.max_pieces),
+                               features_per_group=int(t.features_per_group), max_group_pieces=int(t.max_group_pieces),
+                               sum_features=int(sum_features), grad=_lib.ptr(grad), grad_stride=grad.stride(0),
+                               gx=_lib.ptr(gx), gx_stride=gx.stride(0))
+    if describe is not None:
+        info = _lib.FpwlInputGradInfo()
+        _lib.check(_lib.lib().gnan_fpwl_input_grad_describe(a, info), "gnan_fpwl_input_grad_describe")
+        describe.append(info.as_dict())
+    _lib.check(_lib.lib().gnan_fpwl_input_grad(a, _lib.stream_of(x)), "gnan_fpwl_input_grad")
+    return gx
+
+
+def _table_input_grad(x, params, t, grad_out, sum_features, L, H, C, F) -> torch.Tensor:
+    """``d x`` of ``sum_n <grad_out[n], f(x[n])>`` from the tables: two launches, one streaming pass over ``x``."""
+    gx = _fpwl_input_grad(x, t, _piece_dfdx_launch(params, t, L, H, C, F), grad_out, sum_features)
+    return gx if gx.dtype == x.dtype else gx.to(x.dtype)
+
+
 HIP_SMALL_BACKWARD = True
 # gnan_fmlp_bwd recomputes the activations of every (node, feature) pair (3 H^2 fmas each, fp32 vector units): beyond a few
 # million pairs the batched GEMMs of the torch route (matrix cores) catch up; AUTO sends such sizes to the table route anyway
@@ -834,9 +883,11 @@ class _FeatureMLPs(torch.autograd.Function):
         ctx.present = [t is not None for t in params]
         ctx.grad_dests = _grad_dests_of(params)
         ctx.set_materialize_grads(False)      # (the non-differentiable column sums would get a zero-filled gradient: a launch)
-        needs_grad = any(ctx.needs_input_grad[9:]) and not ctx.needs_input_grad[0]
-        if needs_grad and out_dtype != torch.float32:
+        if any(ctx.needs_input_grad[9:]) and not ctx.needs_input_grad[0] and out_dtype != torch.float32:
             raise _lib.GnanHipError("bf16 operand storage is an inference format: no backward pass")
+        # parameters or x need a gradient: the training thresholds, and the pieces are kept for the backward pass — x.grad is
+        # a look-up in the same tables (_shape_function_grads)
+        needs_grad = (any(ctx.needs_input_grad[9:]) or ctx.needs_input_grad[0]) and out_dtype == torch.float32
         if total_rows is not None and not 0 <= total_rows <= x.shape[0]:
             raise ValueError(f"total_rows={total_rows} outside [0, {x.shape[0]}]")
         fused_total = want_total and total_rows != 0           # 0 rows: the kernel reads that as "all", sum nothing instead
@@ -865,7 +916,8 @@ class _FeatureMLPs(torch.autograd.Function):
         if grad_out is None:                  # nothing downstream used the values
             return (None,) * (9 + len(params))
         gx, pg = _shape_function_grads(x, params, ctx.present, ctx.tables, grad_out, sum_features, L, H, C, F, ctx.x_abs_max,
-                                       located, ctx.needs_input_grad[0], dests=ctx.grad_dests)
+                                       located, ctx.needs_input_grad[0], dests=ctx.grad_dests,
+                                       want_param_grads=any(ctx.needs_input_grad[9:]))
         return (gx, None, None, None, None, None, None, None, None, *pg)
 
 
@@ -875,9 +927,19 @@ def _grad_dests_of(params):
 
 
 def _shape_function_grads(x, params, present, tables, grad_out, sum_features, L, H, C, F, x_abs_max=None, located=None,
-                          want_x_grad=False, dests=None):
+                          want_x_grad=False, dests=None, want_param_grads=True):
     """``(d x or None, [gradients of the six stacked parameter tensors, None where absent])`` of
-    ``sum_n <grad_out[n], f(x[n])>`` — autograd through GNAN.py:57-62 (``sum_features``: through GNAN.py:157 as well)."""
+    ``sum_n <grad_out[n], f(x[n])>`` — autograd through GNAN.py:57-62 (``sum_features``: through GNAN.py:157 as well).
+    ``want_param_grads=False`` (frozen parameters, ``x`` needs a gradient) skips the parameter gradients where ``x.grad`` has a
+    route of its own."""
+    if want_x_grad and _input_grad_applies(tables, L, H, C, x):
+        # table path with x.grad: the parameter gradients exactly as when x needs none (moments + gnan_fpwl_param_grads), and
+        # x.grad by a look-up of the per-piece derivatives — f is piecewise linear in every x[n, k]
+        pg = [None] * len(params)
+        if want_param_grads:
+            M = _fpwl_moments(x, tables, grad_out, sum_features, x_abs_max, raw=True, located=located)
+            pg = _fpwl_param_grads_launch(params, tables, M, L, H, C, F, dests=dests)
+        return _table_input_grad(x, params, tables, grad_out, sum_features, L, H, C, F), pg
     leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
     p = StackedMLP(*leaves, L, H, C, F)
     live = [t for t in leaves if t is not None]

@@ -489,6 +489,71 @@ def piece_probe_points(t: PwlTables):
     return torch.where(point, a, a + h), torch.where(point, a, a + 2.0 * h), h
 
 
+def piece_derivative_points(t: PwlTables) -> torch.Tensor:
+    """The point every piece is differentiated at, ``[T]`` float64 (``csrc/piece_points.hpp``): the anchor of a point
+    piece, anchor -/+ 1 on the first / last piece of a feature, else the midpoint.  Rows behind ``off[F]`` get 0."""
+    off = t.off.tolist()
+    xi = torch.zeros(t.anchor.numel(), dtype=torch.float64, device=t.anchor.device)
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=t.anchor.device)
+    for k in range(len(off) - 1):
+        A = t.anchor[off[k]:off[k + 1]]
+        a = A.double()
+        u = a.clone()
+        if A.numel() > 2:
+            point = A[2:] <= torch.nextafter(A[1:-1], inf)
+            u[1:-1] = torch.where(point, a[1:-1], 0.5 * (a[1:-1] + a[2:]))
+        u[-1] = a[-1] + 1.0
+        u[0] = a[0] - 1.0
+        xi[off[k]:off[k + 1]] = u
+    return xi
+
+
+def piece_derivatives_reference(p, t: PwlTables) -> torch.Tensor:
+    """Plain-torch restatement of ``gnan_pwl_piece_dfdx`` (tests; no product path comes here): ``dfdx [T, C]`` in float64,
+    ``d f_k / dx`` of every piece at :func:`piece_derivative_points` — forward mode through the hidden layers with the strict
+    masks ``z > 0`` (torch's ``relu'(0) = 0``).  NOT ``t.slope``: on the point piece behind a kink the slope is the divided
+    difference to the kink's right, this is the derivative autograd takes AT the kink.  Rows behind ``off[F]`` are zero."""
+    f64 = torch.float64
+    off = t.off.tolist()
+    xi = piece_derivative_points(t)
+    out = torch.zeros(t.anchor.numel(), p.C, dtype=f64, device=t.anchor.device)
+    for k in range(len(off) - 1):
+        u = xi[off[k]:off[k + 1]]
+        if p.L == 1:
+            out[off[k]:off[k + 1]] = p.w_last[k].to(f64).unsqueeze(0)
+            continue
+        w = p.w_first[k].to(f64)
+        z = u.unsqueeze(1) * w
+        if p.b_first is not None:
+            z = z + p.b_first[k].to(f64)
+        on = z > 0
+        h, d = torch.where(on, z, torch.zeros_like(z)), on.to(f64) * w
+        for l in range(p.L - 2):
+            W = p.w_mid[l][k].to(f64)
+            z, dz = h @ W.t(), d @ W.t()
+            if p.b_mid is not None:
+                z = z + p.b_mid[l][k].to(f64)
+            on = z > 0
+            h, d = torch.where(on, z, torch.zeros_like(z)), torch.where(on, dz, torch.zeros_like(dz))
+        out[off[k]:off[k + 1]] = d @ p.w_last[k].to(f64).t()
+    return out
+
+
+def input_grad_reference(x: torch.Tensor, g: torch.Tensor, t: PwlTables, dfdx: torch.Tensor, sum_features: bool) -> torch.Tensor:
+    """Plain-torch restatement of ``gnan_fpwl_input_grad`` (tests): ``gx [n, F]`` float64, ``gx[n, k] = sum_c g[n, k, c]
+    dfdx[off[k] + i, c]`` with ``i = #{anchors[1:] <= x[n, k]}``, the piece :func:`evaluate_reference` puts the node on."""
+    n, F = x.shape
+    C = dfdx.shape[1]
+    off = t.off.tolist()
+    gx = torch.zeros(n, F, dtype=torch.float64, device=x.device)
+    for k in range(F):
+        a = t.anchor[off[k]:off[k + 1]]
+        i = torch.searchsorted(a[1:].contiguous(), x[:, k].contiguous(), right=True)
+        gk = (g if sum_features else g[:, k * C:(k + 1) * C]).double()
+        gx[:, k] = (gk * dfdx[off[k]:off[k + 1]].double()[i]).sum(dim=1)
+    return gx
+
+
 def moments_reference(x: torch.Tensor, g: torch.Tensor, t: PwlTables, sum_features: bool) -> torch.Tensor:
     """Plain-torch restatement of ``gnan_fpwl_moments`` (CPU tests): ``M [T, 2, C]``."""
     n, F = x.shape

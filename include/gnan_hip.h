@@ -375,6 +375,74 @@ typedef struct gnan_fpwl_grad_args {
 
 int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Input gradients of the table path (autograd through GNAN.py:57-62 w.r.t. x; csrc/fpwl_input_grad.hip).  Added under
+ * ABI 51: new functions and new structs, no existing struct changed, the number did not move.
+ *
+ * gnan_pwl_piece_dfdx: dfdx[t, c] = d f_k[c] / dx on piece t of the stacked tables, evaluated at the point the parameter
+ * gradients take the piece's activation masks at (a point piece: its anchor; the first / last piece of a feature:
+ * anchor -/+ 1; else the midpoint) — forward mode in float64 through the L - 1 hidden layers with strict masks z > 0
+ * (torch's relu'(0) = 0), rounded once.  NOT the table's `slope`: on a point piece [a, nextafter(a)) the slope is the
+ * divided difference to the right of a kink, the derivative autograd takes is the one AT the kink.  One workgroup per
+ * feature, piece counts read from `off` on the device; rows [off[F], T) (tables in a buffer of full capacity) are
+ * written as zeros.  Weight layout as gnan_fmlp_args.  Covers L == 2 with H <= 128 and L in {3, 4} with H <= 64,
+ * C <= 4096; anything else is GNAN_ERR_UNSUPPORTED before a launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_pwl_dfdx_args {
+  const int32_t* off;     /* [F + 1] */
+  const float* anchor;    /* [T] */
+  int64_t T;              /* rows of anchor / dfdx (>= off[F]) */
+  const float* w_first;   /* [F, H] */
+  const float* b_first;   /* [F, H] or NULL */
+  const float* w_mid;     /* [L-2, F, H, H] when L >= 3 */
+  const float* b_mid;     /* [L-2, F, H] or NULL */
+  const float* w_last;    /* [F, C, H] */
+  int32_t F, L, H, C;
+  float* dfdx;            /* [T, C] out */
+} gnan_pwl_dfdx_args;
+int gnan_pwl_piece_dfdx(const gnan_pwl_dfdx_args* a, gnan_stream_t stream);
+
+/* gnan_fpwl_input_grad: the look-up of the backward pass,
+ *   gx[n, k] = sum_c g[n, k, c] * dfdx[off[k] + i, c],   i = #{ breakpoints of f_k <= x[n, k] }   (the forward's piece)
+ * with g[n, k, c] = grad[n, c] when sum_features, grad[n, k * C + c] otherwise; the channel sum is a chain of fused
+ * multiply-adds in channel order starting from 0.  gx[n, k] depends on x[n, k] and row n of grad alone.  A workgroup
+ * takes a block of nodes and one feature group of the table plan (max_pieces / features_per_group / max_group_pieces as
+ * in gnan_fpwl_args) whose anchors and dfdx rows it stages in LDS; the search is fused, nothing of size [n, F] but gx is
+ * written.  Any F (a partial last group), any row strides >= the row widths; 16-byte requests for x and gx where F, the
+ * strides and the addresses are multiples of 4 floats.  n == 0 is a no-op.  Tables whose largest group exceeds the LDS
+ * image of gnan_fpwl_fwd (max_group_pieces * (1 + 2 * (C > 1 ? C | 1 : 1)) * 4 > 150 KiB) are GNAN_ERR_UNSUPPORTED. */
+typedef struct gnan_fpwl_input_grad_args {
+  const float* x;              /* [n, F], row stride x_stride */
+  int64_t n;
+  int64_t x_stride;
+  int32_t F, C;
+  const int32_t* off;          /* [F + 1] */
+  const float* anchor;         /* [T] */
+  const float* dfdx;           /* [T, C] (gnan_pwl_piece_dfdx) */
+  int32_t max_pieces;
+  int32_t features_per_group;  /* 1, 2, 4, 8 or 16 */
+  int32_t max_group_pieces;
+  int32_t sum_features;
+  const float* grad;           /* [n, C] (sum_features) or [n, F * C], row stride grad_stride */
+  int64_t grad_stride;
+  float* gx;                   /* [n, F] out, row stride gx_stride */
+  int64_t gx_stride;
+} gnan_fpwl_input_grad_args;
+int gnan_fpwl_input_grad(const gnan_fpwl_input_grad_args* a, gnan_stream_t stream);
+
+/* How gnan_fpwl_input_grad would run a call (host only: nothing is launched, no device memory is read; the arguments are
+ * validated as by the launch, whose own plan this is).  All fields are zero when n == 0. */
+typedef struct gnan_fpwl_input_grad_info {
+  int32_t block_size;          /* threads per workgroup */
+  int32_t nodes_per_block;     /* nodes of one workgroup */
+  int32_t features_per_group;  /* features of one workgroup */
+  int32_t lds_bytes;           /* dynamic LDS of the launch: max_group_pieces * (1 + (C > 1 ? C | 1 : 1)) * 4 */
+  int32_t vec;                 /* 1: x and gx move as 16-byte requests */
+  int32_t n_groups;            /* feature groups: ceil(F / features_per_group) */
+  int64_t n_blocks;            /* node blocks that hold a node: ceil(n / nodes_per_block) */
+} gnan_fpwl_input_grad_info;
+int gnan_fpwl_input_grad_describe(const gnan_fpwl_input_grad_args* a, gnan_fpwl_input_grad_info* out);
+
 /* Build the look-up tables on the device: one workgroup per feature finds the kinks of f_k (zero crossings
  * of its hidden pre-activations, float64) and tabulates the network at them.  Covers L in {2, 3} with H <= 128 and
  * L == 4 with H <= 64 (ABI 51; two hidden matrices next to the breakpoints do not fit LDS beyond that: GNAN_ERR_UNSUPPORTED).
