@@ -277,8 +277,12 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
       }
     };
     // interval (i - 1, i) of the nodes, unit j, with the pre-activations at its two ends
+    // Signs are compared, not multiplied: the product of two pre-activations below ~1e-162 underflows to -0.  A root EXACTLY on
+    // one of the four added nodes is no breakpoint yet and no strict test sees it; the two nodes of a ray lie on one affine
+    // piece, so the pre-activation vanishes at exactly one of them iff its root is that node (both zero: zero on the whole
+    // ray, no kink).  Exclusive with the ray's own root, whose z / d is 0 or -1 there (pwl.py:_build_padded, same rule).
     auto roots = [&](int i, double e_prev, double e, double z_prev, double z) {
-      if (z_prev * z < 0.0) push(e_prev + (e - e_prev) * (z_prev / (z_prev - z)));
+      if ((z_prev < 0.0 && z > 0.0) || (z_prev > 0.0 && z < 0.0)) push(e_prev + (e - e_prev) * (z_prev / (z_prev - z)));
       if (i == n_nodes - 1) {                               // right ray: extrapolate the outermost affine piece
         const double dr = z - z_prev;
         if (dr != 0.0 && z / dr < 0.0) push(e - z / dr * (e - e_prev));
@@ -286,6 +290,10 @@ __global__ __launch_bounds__(kBT) void pwl_build_kernel(const BuildParams p) {
       if (i == 1) {                                         // left ray
         const double dl = z - z_prev;
         if (dl != 0.0 && z_prev / dl > 0.0) push(e_prev - z_prev / dl * (e - e_prev));
+      }
+      if (i == 1 || i == n_nodes - 1) {
+        if (z == 0.0 && (z_prev < 0.0 || z_prev > 0.0)) push(e);
+        if (z_prev == 0.0 && (z < 0.0 || z > 0.0)) push(e_prev);
       }
     };
     if (!DEEP && p.affine) {

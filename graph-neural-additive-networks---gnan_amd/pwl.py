@@ -134,6 +134,22 @@ def _with_point_pieces(bp32: torch.Tensor, p, w, b) -> torch.Tensor:
     return torch.sort(torch.cat([bp32, extra], dim=1), dim=1)[0]
 
 
+def _sign_change(z0: torch.Tensor, z1: torch.Tensor) -> torch.Tensor:
+    """Do the pre-activations at the two ends of an interval differ in sign?  By the signs themselves: the product of two
+    pre-activations below ~1e-162 underflows to -0 and would hide the root."""
+    return ((z0 < 0) & (z1 > 0)) | ((z0 > 0) & (z1 < 0))
+
+
+def _lone_zero(za: torch.Tensor, zb: torch.Tensor, ea: torch.Tensor, eb: torch.Tensor) -> torch.Tensor:
+    """A root EXACTLY on one of the four added sample nodes (``t_first - 2``, ``t_first - 1``, ``t_last + 1``, ``t_last + 2``) is
+    no breakpoint yet, and no strict test sees it.  The two nodes ``ea < eb`` of a ray lie on ONE affine piece (the ray reaches
+    to the outermost breakpoint), so the pre-activation vanishes at exactly one of them iff its root is that node; zero at
+    both is a unit that is zero on the whole ray: no kink.  Exclusive with the ray's own root, whose ``z / d`` is 0 or -1 here.
+    Returns the node, +inf where there is none (a NaN pre-activation is neither zero nor non-zero)."""
+    return torch.where((za == 0) & ((zb < 0) | (zb > 0)), ea,
+                       torch.where((zb == 0) & ((za < 0) | (za > 0)), eb, torch.full_like(ea, float("inf"))))
+
+
 def _build_padded(p):
     """Device part of the build — static shapes only, no host round trip (so it can live in a hipGraph):
     returns ``(off [F+1] int64, overflow [] bool, anchor [F, P+1], val [F, P+1, C], slope [F, P+1, C], keep [F, P+1])``
@@ -169,7 +185,7 @@ def _build_padded(p):
             z = _prefix(nodes, p, depth, w, b)                                                    # [F, P + 4, H]
             e0, e1 = nodes[:, :-1].unsqueeze(-1), nodes[:, 1:].unsqueeze(-1)
             z0, z1 = z[:, :-1], z[:, 1:]
-            inside = (z0 * z1) < 0                                   # sign change strictly inside (e0, e1)
+            inside = _sign_change(z0, z1)                            # strictly inside (e0, e1)
             root = e0 + (e1 - e0) * (z0 / (z0 - z1))
             new_in = torch.where(inside, root, torch.full_like(root, INF))
             # rays: extrapolate the affine piece beyond the outermost sample points
@@ -179,8 +195,9 @@ def _build_padded(p):
             dr = z[:, -1] - z[:, -2]
             rr = nodes[:, -1:] - z[:, -1] / dr * (nodes[:, -1:] - nodes[:, -2:-1])
             ok_r = (dr != 0) & (z[:, -1] / dr < 0)
-            new = torch.cat([new_in.reshape(F, -1), torch.where(ok_l, rl, torch.full_like(rl, INF)),
-                             torch.where(ok_r, rr, torch.full_like(rr, INF))], dim=1)
+            on_l = _lone_zero(z[:, 0], z[:, 1], nodes[:, :1], nodes[:, 1:2])       # a root ON an added node shares the
+            on_r = _lone_zero(z[:, -2], z[:, -1], nodes[:, -2:-1], nodes[:, -1:])   # ray's column: static shapes
+            new = torch.cat([new_in.reshape(F, -1), torch.where(ok_l, rl, on_l), torch.where(ok_r, rr, on_r)], dim=1)
         new = torch.where(torch.isfinite(new), new, torch.full_like(new, INF))       # NaN / -inf -> dropped
         bp, _ = torch.sort(torch.cat([bp, new], dim=1), dim=1)
         # keep a fixed number of columns per layer (no host round trip); an overflow is detected at the end
