@@ -350,6 +350,35 @@ class SmallGraphBwdArgs(C.Structure):
     ]
 
 
+class MidGraphArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("x_stride", C.c_int64), ("n", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
+        ("code", C.c_void_p), ("D", C.c_int32), ("reserved", C.c_int32), ("cnt", C.c_void_p), ("cnt_stride", C.c_int64),
+        ("S", C.c_void_p), ("lut", C.c_void_p), ("Y", C.c_void_p), ("Ysum", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MidGraphBwdArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("x_stride", C.c_int64), ("n", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
+        ("code", C.c_void_p), ("D", C.c_int32), ("reserved", C.c_int32), ("cnt", C.c_void_p), ("cnt_stride", C.c_int64),
+        ("S", C.c_void_p), ("lut", C.c_void_p), ("dY", C.c_void_p), ("dYsum", C.c_void_p), ("df", SmallMlpGrads),
+        ("drho", SmallMlpGrads), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class MidGraphInfo(C.Structure):
+    _fields_ = [
+        ("row_tiles", C.c_int32), ("rho_groups", C.c_int32), ("fwd_grid", C.c_int32), ("bwd_grid", C.c_int32),
+        ("fwd_lds_bytes", C.c_int32), ("bwd_lds_bytes", C.c_int32), ("fwd_workspace_bytes", C.c_int64),
+        ("bwd_workspace_bytes", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SmallGraphNamArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x_stride", C.c_int64), ("n", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
@@ -468,6 +497,11 @@ SYMBOLS = {
     "gnan_small_graph_fwd": (C.c_int, [C.POINTER(SmallGraphArgs), C.c_void_p]),
     "gnan_small_graph_bwd": (C.c_int, [C.POINTER(SmallGraphBwdArgs), C.c_void_p]),
     "gnan_small_graph_bwd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gnan_mid_graph_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "gnan_mid_graph_bwd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gnan_mid_graph_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MidGraphInfo)]),
+    "gnan_mid_graph_fwd": (C.c_int, [C.POINTER(MidGraphArgs), C.c_void_p]),
+    "gnan_mid_graph_bwd": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.c_void_p]),
     "gnan_small_graph_nam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gnan_small_graph_nam_fwd": (C.c_int, [C.POINTER(SmallGraphNamArgs), C.c_void_p]),
     "gnan_small_graph_nam_bwd": (C.c_int, [C.POINTER(SmallGraphNamBwdArgs), C.c_void_p]),

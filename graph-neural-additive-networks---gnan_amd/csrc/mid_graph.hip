@@ -1,0 +1,502 @@
+// One-launch forward and one-launch backward of a dense-coded graph of up to 448 nodes (csrc/small_graph.hip stops at 128: its
+// last workgroup stages the whole [n][n] hop-code block in LDS — 174 KB at the 417 nodes of the largest Mutagenicity graph — and
+// its backward keeps [D][n | 1] bins per wave).  The same model, the same arithmetic and the same orders as there; the graph is
+// walked in TILES OF 64 ROWS, so that a [64][n] block of hop codes and a [64][64] block of row weights is all of the graph a
+// workgroup holds at a time.  Post-rho shell normalisation (or none), a one-channel rho, D <= 64 shells, C <= 8.
+//
+// Forward
+//   workgroup k < F : f_k on all nodes, in node blocks of 64 (small_graph_body.hpp's mlp_block), into part[k, node, :].
+//   workgroup F     : lut[d] = rho(u_d).
+//   the LAST workgroup to arrive adds the features in order (S, written out), then takes the row tiles in order: hop codes and
+//   shell sizes of tile t + 1 are requested (into registers) before tile t is consumed from LDS; one thread per (row, channel)
+//   walks the neighbours in ascending order; the read-out sum in row order; the counter goes back to zero.
+// Backward
+//   workgroup k < F : dS[j, c] = sum_i lut[code(i, j)] / max(cnt(i, code), 1) * dY[i, c] over the row tiles in ascending order
+//                     (every feature workgroup forms it itself: nobody waits for anybody), then fmlp_bwd_body.hpp's feature_grads.
+//   workgroup F + g : the table gradient of rows 32 g .. 32 g + 31 — a row per wave at a time, the neighbours' dot products
+//                     binned by hop code in lane-private LDS columns ([D][65]), float64 across rows — left as float64 partials
+//                     dlut[g][64] in the workspace; the last rho group to arrive adds the partials in group order and runs
+//                     feature_grads on rho's D arguments.
+// No workgroup waits for another: the only joins are "the last to arrive continues, everyone else returns".
+#include <cstdint>
+
+#include "small_graph_body.hpp"
+
+namespace {
+
+using namespace gnan_small;
+
+constexpr int kMidNodes = 448;                       // 7 row tiles
+constexpr int kTile = 64;                            // rows per tile
+constexpr int kMidBlocks = kMidNodes / kTile;
+constexpr int kMidD = kWave;                         // shells (lane = shell in the table steps)
+constexpr int kRhoRows = 32;                         // rows per rho group of the backward: 14 groups at 448 nodes
+constexpr int kRhoGroupsMid = kMidNodes / kRhoRows;
+constexpr int kThreads = kWaves * kWave;
+constexpr int kBinCols = kWave + 1;                  // odd stride of the lane-private bin columns
+
+// ---- LDS plans (floats unless said otherwise): one size per kernel, the largest admitted shape --------------------------------
+// forward, last workgroup: S [n, C] | Y [n, C] | lut [64] | row weights [64][64] | hop codes [64][row bytes]; the MLP phases use
+// the first 2 * 64 * 64 floats as activation columns
+constexpr int kFwdS = 0, kFwdY = kMidNodes * kMaxC, kFwdLut = 2 * kMidNodes * kMaxC, kFwdW = kFwdLut + kWave,
+              kFwdCode = kFwdW + kTile * kWave;
+constexpr int kCodeRowMax = 4 * ((kMidNodes / 4) | 1);                               // padded row of the forward's tile (below)
+constexpr size_t kFwdDynBytes = static_cast<size_t>(kFwdCode) * 4 + static_cast<size_t>(kTile) * kCodeRowMax;
+constexpr size_t kFwdStaticBytes = kWeightFloats * 4 + 16;                           // weight image + the arrival slot
+static_assert(kFwdCode >= 2 * kMaxH * kWave, "the activation columns fit in front of the code tile");
+// backward, feature workgroup: dY [n, C] | dS [n, C] | row weights [64][64] | hop codes [64][n] bytes
+constexpr int kBwdDY = 0, kBwdG = kMidNodes * kMaxC, kBwdU = 2 * kMidNodes * kMaxC, kBwdCode = kBwdU + kTile * kWave;
+constexpr size_t kBwdDynBytes = static_cast<size_t>(kBwdCode) * 4 + static_cast<size_t>(kTile) * kMidNodes;
+// backward, rho group: S [n, C] | dY of the group's rows [32, C] | hop codes [32][n] bytes | bins [waves][D][65]
+constexpr int kRhoS = 0, kRhoDY = kMidNodes * kMaxC, kRhoCode = kRhoDY + kRhoRows * kMaxC,
+              kRhoBins = kRhoCode + kRhoRows * kMidNodes / 4;
+constexpr int kRhoBinFloats = static_cast<int>(kBwdDynBytes / 4) - kRhoBins;
+static_assert(kRhoBinFloats >= 2 * kMidD * kBinCols, "two waves' bins fit at 64 shells");
+constexpr size_t kBwdStaticBytes = sizeof(gnan_bwd::RedBuffer) + kWaves * kWave * sizeof(double) + 2 * kWave * 4 + 16;
+
+// A tile's hop codes and shell sizes on their way from memory to LDS: ROWS rows of n codes are ROWS * n consecutive bytes that start
+// on a 4-byte boundary (ROWS is a multiple of 4), fetched as words; shell sizes as [ROWS][64].
+template <int ROWS>
+struct TileRegs {
+  static constexpr int kWords = ROWS * kMidNodes / 4 / kThreads;
+  static constexpr int kCnt = ROWS * kWave / kThreads;
+  uint32_t w[kWords];
+  int q[kCnt];
+};
+
+template <int ROWS>
+__device__ __forceinline__ void tile_fetch(TileRegs<ROWS>& r, const uint8_t* code, const int32_t* cnt, int64_t cnt_stride, int n, int D,
+                                           int i0) {
+  const int rows = n - i0 < ROWS ? n - i0 : ROWS;
+  const int words = rows * n / 4;
+  const uint32_t* cw = reinterpret_cast<const uint32_t*>(code + static_cast<int64_t>(i0) * n);
+#pragma unroll
+  for (int u = 0; u < TileRegs<ROWS>::kWords; ++u) {
+    const int i = static_cast<int>(threadIdx.x) + u * kThreads;
+    r.w[u] = i < words ? cw[i] : 0u;
+  }
+#pragma unroll
+  for (int u = 0; u < TileRegs<ROWS>::kCnt; ++u) {
+    const int e = static_cast<int>(threadIdx.x) + u * kThreads;
+    const int rr = e / kWave, d = e % kWave;
+    r.q[u] = (cnt && rr < rows && d < D) ? cnt[(i0 + rr) * cnt_stride + d] : 1;
+  }
+}
+
+// ... into LDS.  PAD: rows of n % 4 == 0 codes start `row_bytes` = 4 * (n / 4 | 1) apart (the forward's threads walk a row each:
+// with rows 448 bytes apart sixteen of them would share a bank); every other n keeps the rows back to back (row_bytes = n).
+template <int ROWS, bool PAD>
+__device__ __forceinline__ void tile_store_codes(const TileRegs<ROWS>& r, const uint8_t* code, int n, int i0, uint8_t* s_code) {
+  const int rows = n - i0 < ROWS ? n - i0 : ROWS;
+  const int bytes = rows * n, words = bytes / 4;
+  uint32_t* dw = reinterpret_cast<uint32_t*>(s_code);
+  const bool pad = PAD && (n & 3) == 0;
+  const int row_words = n / 4, pad_words = row_words | 1;
+#pragma unroll
+  for (int u = 0; u < TileRegs<ROWS>::kWords; ++u) {
+    const int i = static_cast<int>(threadIdx.x) + u * kThreads;
+    if (i < words) dw[pad ? (i / row_words) * pad_words + i % row_words : i] = r.w[u];
+  }
+  // (n * rows not a multiple of 4: the last one to three codes of the graph's last tile)
+  for (int i = words * 4 + static_cast<int>(threadIdx.x); i < bytes; i += kThreads) s_code[i] = code[static_cast<int64_t>(i0) * n + i];
+}
+
+// row weights lut[d] / max(cnt[i, d], 1) of the tile's rows, [ROWS][64]
+template <int ROWS>
+__device__ __forceinline__ void tile_store_weights(const TileRegs<ROWS>& r, const float* s_lut, bool with_cnt, int D, float* s_w) {
+#pragma unroll
+  for (int u = 0; u < TileRegs<ROWS>::kCnt; ++u) {
+    const int e = static_cast<int>(threadIdx.x) + u * kThreads;
+    const int d = e % kWave;
+    if (d < D) {
+      const float l = s_lut[d];
+      s_w[e] = with_cnt ? l / static_cast<float>(r.q[u] > 1 ? r.q[u] : 1) : l;
+    }
+  }
+}
+
+struct MidParams {
+  const float* x;
+  int64_t x_stride;
+  int n, F;
+  Mlp f, r;
+  const uint8_t* code;
+  int D;
+  const int32_t* cnt;
+  int64_t cnt_stride;
+  float* S;
+  float* lut;
+  float* Y;
+  float* Ysum;
+  float* part;          // [F, n, C]
+  unsigned* counter;    // zero before the first launch; the last workgroup zeroes it again
+};
+
+__global__ __launch_bounds__(kThreads) void mid_graph_kernel(const MidParams p) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  __shared__ __attribute__((aligned(16))) float weights[kWeightFloats];
+  __shared__ unsigned s_last;
+  float* col_a = dyn;
+  float* col_b = dyn + kMaxH * kWave;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int k = blockIdx.x, n = p.n, C = p.f.C;
+  const int blocks = (n + kTile - 1) / kTile;
+  float out[kMaxC];
+  const MlpLds wl = carve(weights);
+  // the first tile's codes and shell sizes are requested now, by every workgroup (any may be the last): they fly during the MLPs
+  TileRegs<kTile> regs;
+  tile_fetch<kTile>(regs, p.code, p.cnt, p.cnt_stride, n, p.D, 0);
+  if (k < p.F) {
+    stage_weights(p.f, k, wl);
+    float xv[kMidBlocks];
+#pragma unroll
+    for (int b = 0; b < kMidBlocks; ++b) {            // (all node blocks' inputs requested before the first MLP)
+      const int j = b * kWave + lane;
+      xv[b] = j < n ? p.x[static_cast<int64_t>(j) * p.x_stride + k] : 0.f;
+    }
+#pragma unroll
+    for (int b = 0; b < kMidBlocks; ++b) {
+      const int j = b * kWave + lane;
+      if (b < blocks) {                               // (uniform)
+        mlp_block(p.f, wl, xv[b], col_a, col_b, lane, wave, out);
+        if (wave == 0 && j < n)
+          for (int c = 0; c < C; ++c) p.part[(static_cast<int64_t>(k) * n + j) * C + c] = out[c];
+      }
+    }
+  } else {
+    stage_weights(p.r, 0, wl);
+    const float u = lane < p.D - 1 ? 1.0f / (static_cast<float>(lane) + 1.0f) : 0.f;     // graph.hop_inputs
+    mlp_block(p.r, wl, u, col_a, col_b, lane, wave, out);
+    if (wave == 0 && lane < p.D) p.lut[lane] = out[0];
+  }
+  // ---- join: the last workgroup to arrive finishes the graph -----------------------------------------------------------------
+  if (!last_to_arrive(p.counter, gridDim.x, &s_last)) return;
+  float* s_S = dyn + kFwdS;
+  float* s_Y = dyn + kFwdY;
+  float* s_lut = dyn + kFwdLut;
+  float* s_w = dyn + kFwdW;
+  uint8_t* s_code = reinterpret_cast<uint8_t*>(dyn + kFwdCode);
+  const int nc = n * C;
+  if (threadIdx.x < kWave) s_lut[threadIdx.x] = static_cast<int>(threadIdx.x) < p.D ? p.lut[threadIdx.x] : 0.f;
+  // node sums: a thread per (node, channel) adds the features in order, eight terms in flight at a time
+  for (int e = threadIdx.x; e < nc; e += kThreads) {
+    float sum = 0.f;
+    for (int k0 = 0; k0 < p.F; k0 += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = k0 + u < p.F ? p.part[static_cast<int64_t>(k0 + u) * nc + e] : 0.f;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (k0 + u < p.F) sum += v[u];
+    }
+    s_S[e] = sum;
+    p.S[e] = sum;
+  }
+  const int row_bytes = (n & 3) == 0 ? 4 * ((n / 4) | 1) : n;
+  for (int t = 0; t < blocks; ++t) {
+    const int i0 = t * kTile;
+    const int rows = n - i0 < kTile ? n - i0 : kTile;
+    __syncthreads();                                  // (the tile before is consumed; first round: S and the table are in place)
+    tile_store_codes<kTile, true>(regs, p.code, n, i0, s_code);
+    tile_store_weights<kTile>(regs, s_lut, p.cnt != nullptr, p.D, s_w);
+    if (t + 1 < blocks) tile_fetch<kTile>(regs, p.code, p.cnt, p.cnt_stride, n, p.D, i0 + kTile);
+    __syncthreads();
+    // one thread per (row, channel), neighbours in ascending order
+    for (int e = threadIdx.x; e < rows * C; e += kThreads) {
+      const int r = e / C, c = e % C;
+      const uint8_t* codes = s_code + r * row_bytes;
+      const float* wrow = s_w + r * kWave;
+      float acc = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < n; ++j) {                   // (unrolled: the code -> weight reads of eight neighbours overlap)
+        int d = codes[j];
+        d = d < p.D - 1 ? d : p.D - 1;
+        acc = fmaf(wrow[d], s_S[j * C + c], acc);
+      }
+      s_Y[i0 * C + e] = acc;
+      if (p.Y) p.Y[i0 * C + e] = acc;
+    }
+  }
+  __syncthreads();
+  if (p.Ysum && static_cast<int>(threadIdx.x) < C) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int i = 0; i < n; ++i) s += s_Y[i * C + threadIdx.x];
+    p.Ysum[threadIdx.x] = s;
+  }
+  if (threadIdx.x == 0) *p.counter = 0u;
+}
+
+struct MidBwdParams {
+  const float* x;
+  int64_t x_stride;
+  int n, F;
+  gnan_bwd::Weights f, r;
+  int f_mid, r_mid;          // L == 3
+  const uint8_t* code;
+  int D;
+  const int32_t* cnt;
+  int64_t cnt_stride;
+  const float* S;
+  const float* lut;
+  const float* dY;
+  const float* dYsum;
+  int rho_groups;
+  double* part;              // [rho_groups][64] partial table gradients
+  unsigned* counter;         // arrivals of the rho groups
+};
+
+template <int C>
+__global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdParams p) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  __shared__ gnan_bwd::RedBuffer red;
+  __shared__ double s_part[kWaves][kWave];
+  __shared__ float s_lut[kWave];
+  __shared__ float s_dl[kWave];
+  __shared__ unsigned s_last;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int k = blockIdx.x, n = p.n, nc = p.n * C;
+  const gnan_bwd::Drop nodrop{0u, 1.f, 0ull};
+  if (k < p.F) {
+    // ---- operand gradient of every node over the row tiles, then this feature's parameter gradients --------------------------
+    float* s_dY = dyn + kBwdDY;
+    float* s_g = dyn + kBwdG;
+    float* s_u = dyn + kBwdU;
+    uint8_t* s_code = reinterpret_cast<uint8_t*>(dyn + kBwdCode);
+    const int blocks = (n + kTile - 1) / kTile;
+    TileRegs<kTile> regs;
+    tile_fetch<kTile>(regs, p.code, p.cnt, p.cnt_stride, n, p.D, 0);
+    if (threadIdx.x < kWave) s_lut[threadIdx.x] = static_cast<int>(threadIdx.x) < p.D ? p.lut[threadIdx.x] : 0.f;
+    for (int e = threadIdx.x; e < nc; e += kThreads) {
+      s_dY[e] = p.dY ? p.dY[e] : p.dYsum[e % C];
+      s_g[e] = 0.f;
+    }
+    for (int t = 0; t < blocks; ++t) {
+      const int i0 = t * kTile;
+      const int rows = n - i0 < kTile ? n - i0 : kTile;
+      __syncthreads();
+      tile_store_codes<kTile, false>(regs, p.code, n, i0, s_code);
+      tile_store_weights<kTile>(regs, s_lut, p.cnt != nullptr, p.D, s_u);
+      if (t + 1 < blocks) tile_fetch<kTile>(regs, p.code, p.cnt, p.cnt_stride, n, p.D, i0 + kTile);
+      __syncthreads();
+      for (int e = threadIdx.x; e < nc; e += kThreads) {          // thread (column j, channel): the tile's rows in ascending order
+        const int j = e / C, c = e % C;
+        float acc = s_g[e];
+#pragma unroll 8
+        for (int r = 0; r < rows; ++r) {
+          int d = s_code[r * n + j];
+          d = d < p.D - 1 ? d : p.D - 1;
+          acc = fmaf(s_u[r * kWave + d], s_dY[(i0 + r) * C + c], acc);
+        }
+        s_g[e] = acc;
+      }
+    }
+    __syncthreads();
+    auto x_of = [&](int64_t node) { return p.x[node * p.x_stride + k]; };
+    auto g_of = [&](int64_t node, int c) { return s_g[node * C + c]; };
+    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, 0, n, 0, nodrop, x_of, g_of, red);
+    else gnan_bwd::feature_grads<C, false>(p.f, k, 0, n, 0, nodrop, x_of, g_of, red);
+    return;
+  }
+  // ---- table gradient of this group's rows -------------------------------------------------------------------------------------
+  const int grp = k - p.F;
+  const int i_lo = grp * kRhoRows;
+  const int i_hi = i_lo + kRhoRows < n ? i_lo + kRhoRows : n;
+  float* s_S = dyn + kRhoS;
+  float* s_dY = dyn + kRhoDY;
+  uint8_t* s_code = reinterpret_cast<uint8_t*>(dyn + kRhoCode);
+  {
+    TileRegs<kRhoRows> regs;
+    tile_fetch<kRhoRows>(regs, p.code, nullptr, 0, n, p.D, i_lo);
+    for (int e = threadIdx.x; e < nc; e += kThreads) s_S[e] = p.S[e];
+    for (int e = threadIdx.x; e < (i_hi - i_lo) * C; e += kThreads) s_dY[e] = p.dY ? p.dY[i_lo * C + e] : p.dYsum[e % C];
+    tile_store_codes<kRhoRows, false>(regs, p.code, n, i_lo, s_code);
+  }
+  const int nw = kWaves * p.D * kBinCols <= kRhoBinFloats ? kWaves : 2;      // waves that bin: as many as have room for [D][65]
+  float* bins = dyn + kRhoBins + wave * p.D * kBinCols;
+  double acc = 0.0;                                                        // lane d: dlut[d] over this wave's rows
+  __syncthreads();
+  for (int rr = 0; i_lo + nw * rr < i_hi; ++rr) {
+    const int i = i_lo + nw * rr + wave;
+    const bool live = wave < nw && i < i_hi;
+    if (live) {
+      for (int d = 0; d < p.D; ++d) bins[d * kBinCols + lane] = 0.f;
+      float gy[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) gy[c] = s_dY[(i - i_lo) * C + c];
+      const uint8_t* codes = s_code + (i - i_lo) * n;
+      for (int j = lane; j < n; j += kWave) {          // (a lane owns its column of the bins: no other lane writes it)
+        int d = codes[j];
+        d = d < p.D - 1 ? d : p.D - 1;
+        float v = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) v = fmaf(gy[c], s_S[j * C + c], v);
+        bins[d * kBinCols + lane] += v;
+      }
+    }
+    __syncthreads();
+    if (live && lane < p.D) {
+      float sum = 0.f;
+#pragma unroll 8
+      for (int l = 0; l < kWave; ++l) sum += bins[lane * kBinCols + l];
+      if (p.cnt) {
+        const int q = p.cnt[i * p.cnt_stride + lane];
+        sum *= 1.f / static_cast<float>(q > 1 ? q : 1);
+      }
+      acc += static_cast<double>(sum);
+    }
+    __syncthreads();
+  }
+  s_part[wave][lane] = (wave < nw && lane < p.D) ? acc : 0.0;
+  __syncthreads();
+  if (wave == 0) p.part[grp * kWave + lane] = ((s_part[0][lane] + s_part[1][lane]) + s_part[2][lane]) + s_part[3][lane];
+  // ---- join of the rho groups: the last to arrive adds the partials in group order, then rho's parameter gradients ------------
+  if (!last_to_arrive(p.counter, static_cast<unsigned>(p.rho_groups), &s_last)) return;
+  if (wave == 0) {
+    double v[kRhoGroupsMid];
+#pragma unroll
+    for (int g = 0; g < kRhoGroupsMid; ++g) v[g] = g < p.rho_groups ? p.part[g * kWave + lane] : 0.0;
+    double sum = 0.0;
+#pragma unroll
+    for (int g = 0; g < kRhoGroupsMid; ++g)
+      if (g < p.rho_groups) sum += v[g];
+    s_dl[lane] = static_cast<float>(sum);
+  }
+  if (threadIdx.x == 0) *p.counter = 0u;
+  __syncthreads();
+  auto u_of = [&](int64_t d) { return d < p.D - 1 ? 1.0f / (static_cast<float>(d) + 1.0f) : 0.f; };
+  auto gl_of = [&](int64_t d, int) { return s_dl[d]; };
+  if (p.r_mid) gnan_bwd::feature_grads<1, true>(p.r, 0, 0, p.D, 0, nodrop, u_of, gl_of, red);
+  else gnan_bwd::feature_grads<1, false>(p.r, 0, 0, p.D, 0, nodrop, u_of, gl_of, red);
+}
+
+template <int C>
+int launch_mid_bwd(const MidBwdParams& p, hipStream_t st) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_graph_bwd_kernel<C>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kBwdDynBytes));
+  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "mid_graph_bwd: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+  hipLaunchKernelGGL((mid_graph_bwd_kernel<C>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(kThreads), kBwdDynBytes, st, p);
+  return gnan::check_launch("mid_graph_bwd_kernel");
+}
+
+// what both entry points refuse: sizes and MLP shapes outside the kernels' cover, each named
+int mid_shape_ok(const char* who, int n, int F, int D, const gnan_small_mlp* f, const gnan_small_mlp* rho) {
+  GNAN_REQUIRE(n >= 1 && F >= 1 && D >= 1, "%s: bad sizes n=%d F=%d D=%d", who, n, F, D);
+  if (n > kMidNodes) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers n <= %d nodes (got n=%d)", who, kMidNodes, n);
+  if (D > kMidD) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers D <= %d shells (got D=%d)", who, kMidD, D);
+  if (f && (f->C < 1 || f->C > kMaxC))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= C <= %d output channels (got C=%d)", who, kMaxC, f->C);
+  if (rho && rho->C != 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers a one-channel rho (got rho.C=%d)", who, rho->C);
+  const gnan_small_mlp* m[2] = {f, rho};
+  for (int t = 0; t < 2; ++t) {
+    if (m[t] == nullptr) continue;
+    if (m[t]->L != 2 && m[t]->L != 3)
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers L in {2, 3} (got L=%d for %s)", who, m[t]->L, t ? "rho" : "f");
+    if (m[t]->H < 1 || m[t]->H > kMaxH)
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= H <= %d (got H=%d for %s)", who, kMaxH, m[t]->H, t ? "rho" : "f");
+  }
+  return GNAN_OK;
+}
+
+bool mlp_ptrs_ok(const gnan_small_mlp* m) { return m->w_first && m->w_last && (m->L == 2 || m->w_mid); }
+
+}  // namespace
+
+extern "C" size_t gnan_mid_graph_workspace_bytes(int32_t n, int32_t F, int32_t C) {
+  return 16 + static_cast<size_t>(F) * n * C * sizeof(float);      // counter (own 16 bytes) | part [F, n, C]
+}
+
+extern "C" size_t gnan_mid_graph_bwd_workspace_bytes(int32_t n, int32_t D) {
+  (void)D;
+  return 16 + static_cast<size_t>((n + kRhoRows - 1) / kRhoRows) * kWave * sizeof(double);      // counter | dlut partials [groups][64]
+}
+
+extern "C" int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t C, gnan_mid_graph_info* out) {
+  GNAN_REQUIRE(out != nullptr, "mid_graph_describe: null out");
+  gnan_small_mlp f{};
+  f.L = 3; f.H = 1; f.C = C;
+  const int rc = mid_shape_ok("mid_graph_describe", n, F, D, &f, nullptr);
+  if (rc != GNAN_OK) return rc;
+  out->row_tiles = (n + kTile - 1) / kTile;
+  out->rho_groups = (n + kRhoRows - 1) / kRhoRows;
+  out->fwd_grid = F + 1;
+  out->bwd_grid = F + out->rho_groups;
+  out->fwd_lds_bytes = static_cast<int32_t>(kFwdDynBytes + kFwdStaticBytes);
+  out->bwd_lds_bytes = static_cast<int32_t>(kBwdDynBytes + kBwdStaticBytes);
+  out->fwd_workspace_bytes = static_cast<int64_t>(gnan_mid_graph_workspace_bytes(n, F, C));
+  out->bwd_workspace_bytes = static_cast<int64_t>(gnan_mid_graph_bwd_workspace_bytes(n, D));
+  return GNAN_OK;
+}
+
+extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
+  const int rc = mid_shape_ok("mid_graph", a->n, a->F, a->D, &a->f, &a->rho);
+  if (rc != GNAN_OK) return rc;
+  GNAN_REQUIRE(a->x != nullptr, "mid_graph: null x");
+  GNAN_REQUIRE(a->code != nullptr, "mid_graph: null code");
+  GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->code) % 4 == 0, "mid_graph: code must be 4-byte aligned (got %p)",
+               static_cast<const void*>(a->code));
+  GNAN_REQUIRE(a->S && a->lut && (a->Y || a->Ysum), "mid_graph: null S / lut / outputs");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "mid_graph: null weights");
+  GNAN_REQUIRE(a->x_stride >= a->F, "mid_graph: row stride x_stride=%lld smaller than F=%d", static_cast<long long>(a->x_stride), a->F);
+  GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "mid_graph: row stride cnt_stride=%lld smaller than D=%d",
+               static_cast<long long>(a->cnt_stride), a->D);
+  const size_t need = gnan_mid_graph_workspace_bytes(a->n, a->F, a->f.C);
+  if (a->workspace == nullptr || a->workspace_bytes < need)
+    return gnan::fail(GNAN_ERR_WORKSPACE, "mid_graph: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  MidParams p;
+  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
+  p.f = to_mlp(&a->f); p.r = to_mlp(&a->rho);
+  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  p.S = a->S; p.lut = a->lut; p.Y = a->Y; p.Ysum = a->Ysum;
+  p.counter = static_cast<unsigned*>(a->workspace);
+  p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 16);
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_graph_kernel),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFwdDynBytes));
+  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "mid_graph: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+  hipLaunchKernelGGL(mid_graph_kernel, dim3(static_cast<unsigned>(a->F) + 1u), dim3(kThreads), kFwdDynBytes,
+                     static_cast<hipStream_t>(stream), p);
+  return gnan::check_launch("mid_graph_kernel");
+}
+
+extern "C" int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
+  const int rc = mid_shape_ok("mid_graph_bwd", a->n, a->F, a->D, &a->f, &a->rho);
+  if (rc != GNAN_OK) return rc;
+  GNAN_REQUIRE(a->x != nullptr, "mid_graph_bwd: null x");
+  GNAN_REQUIRE(a->code != nullptr, "mid_graph_bwd: null code");
+  GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->code) % 4 == 0, "mid_graph_bwd: code must be 4-byte aligned (got %p)",
+               static_cast<const void*>(a->code));
+  GNAN_REQUIRE(a->S && a->lut && (a->dY || a->dYsum), "mid_graph_bwd: null S / lut / output gradient");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "mid_graph_bwd: null weights");
+  GNAN_REQUIRE(a->x_stride >= a->F, "mid_graph_bwd: row stride x_stride=%lld smaller than F=%d", static_cast<long long>(a->x_stride),
+               a->F);
+  GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "mid_graph_bwd: row stride cnt_stride=%lld smaller than D=%d",
+               static_cast<long long>(a->cnt_stride), a->D);
+  GNAN_REQUIRE(grads_ok(&a->f, &a->df) && grads_ok(&a->rho, &a->drho),
+               "mid_graph_bwd: a gradient pointer for every weight, and for a bias exactly where there is one");
+  const size_t need = gnan_mid_graph_bwd_workspace_bytes(a->n, a->D);
+  if (a->workspace == nullptr || a->workspace_bytes < need)
+    return gnan::fail(GNAN_ERR_WORKSPACE, "mid_graph_bwd: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->workspace) % 8 == 0, "mid_graph_bwd: workspace must be 8-byte aligned (got %p)", a->workspace);
+  MidBwdParams p;
+  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
+  p.f = to_weights(&a->f, &a->df); p.r = to_weights(&a->rho, &a->drho);
+  p.f_mid = a->f.L == 3; p.r_mid = a->rho.L == 3;
+  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  p.S = a->S; p.lut = a->lut; p.dY = a->dY; p.dYsum = a->dYsum;
+  p.rho_groups = (a->n + kRhoRows - 1) / kRhoRows;
+  p.counter = static_cast<unsigned*>(a->workspace);
+  p.part = reinterpret_cast<double*>(static_cast<char*>(a->workspace) + 16);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (a->f.C) {
+    case 1: return launch_mid_bwd<1>(p, st);
+    case 2: return launch_mid_bwd<2>(p, st);
+    case 3: return launch_mid_bwd<3>(p, st);
+    case 4: return launch_mid_bwd<4>(p, st);
+    case 5: return launch_mid_bwd<5>(p, st);
+    case 6: return launch_mid_bwd<6>(p, st);
+    case 7: return launch_mid_bwd<7>(p, st);
+    default: return launch_mid_bwd<8>(p, st);
+  }
+}

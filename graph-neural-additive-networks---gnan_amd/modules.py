@@ -461,8 +461,8 @@ class _PathBase(nn.Module):
         """The whole forward by one launch where ``gnan_small_graph_fwd`` applies (a small dense-coded graph, features summed
         per node: what a graph-level task feeds per step; ``use_cnt``: False, True = post-rho normalisation, "pre" =
         GNAN.py:65-67), else None."""
-        from .small_graph import (SMALL_GRAPH_MAX_NODES, SlotGraph, slot_graph_applies, slot_graph_forward, small_graph_applies,
-                                  small_graph_forward)
+        from .small_graph import (MID_GRAPH_MAX_NODES, SMALL_GRAPH_MAX_NODES, SlotGraph, mid_graph_applies, mid_graph_forward,
+                                  slot_graph_applies, slot_graph_forward, small_graph_applies, small_graph_forward)
         if isinstance(g, SlotGraph):
             # a captured step of a batch-size-1 loop: the graph sits in slots, its size is the device's to know
             f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
@@ -470,12 +470,17 @@ class _PathBase(nn.Module):
                 raise _lib.GnanHipError("graph slots serve graph-level read-outs with post-rho (or no) normalisation, a one-channel "
                                         "rho and at most 8 output channels")
             return slot_graph_forward(g, f, rho, bool(use_cnt))
-        if not g.is_dense or x.shape[0] > SMALL_GRAPH_MAX_NODES:
+        if not g.is_dense or x.shape[0] > MID_GRAPH_MAX_NODES:
             return None
         f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
-        if not small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre"):
+        if x.shape[0] > SMALL_GRAPH_MAX_NODES:          # 129 to 448 nodes: the same by tiles of 64 rows (gnan_mid_graph_fwd)
+            if not mid_graph_applies(x, g, f, rho, use_cnt):
+                return None
+            out = mid_graph_forward(x, g, f, rho, use_cnt, graph_sum)
+        elif not small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre"):
             return None
-        out = small_graph_forward(x, g, f, rho, use_cnt, graph_sum)
+        else:
+            out = small_graph_forward(x, g, f, rho, use_cnt, graph_sum)
         for name in ("lut", "fmlp", "spmm"):
             self._mark(name)
         return out

@@ -4,7 +4,8 @@ graph-level task feeds per step (trainer.py:23-86 with ``batch_size = 1``; SURVE
 * :func:`small_graph_forward` — features summed per node, rho on the distinct distances (or, ``use_cnt="pre"``, on the n x D
   normalised distances of GNAN.py:65-67), the normalised aggregation and the graph read-out: GNAN.py:55-79 / 146-172,
   models.py:358-384 with ``readout_n_layers == 0``;
-* :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381).
+* :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381);
+* :func:`mid_graph_forward` — the first of the three for graphs of 129 to 448 nodes, over tiles of 64 rows (``csrc/mid_graph.hip``).
 
 Both are autograd nodes whose backward pass is one launch as well.  The general kernels (``functional``) take everything these
 do not cover; the ``*_applies`` predicates say which is which.
@@ -97,12 +98,11 @@ class _SmallGraph(torch.autograd.Function):
         x, S, lut = saved[:3]
         rest = saved[3:]
         params = [rest.pop(0) if pr else None for pr in ctx.present]
-        fp, rp = params[:6], params[6:]
         Lf, Hf, Cf, F = ctx.fm
         Lr, Hr, Cr = ctx.rm
         n = x.shape[0]
         need_f, need_r = any(ctx.needs_input_grad[6:12]), any(ctx.needs_input_grad[12:])
-        pre_rho = ctx.use_cnt == "pre"           # (small_graph_applies admitted it only where the one launch below covers it)
+        pre_rho = ctx.use_cnt == "pre"          # (small_graph_applies admitted it only where the one launch below covers it)
         if ((SMALL_GRAPH_BACKWARD and Cr == 1 and ctx.g.n_codes <= 64 and d_out.dtype == torch.float32
                 and all(t is None or t.dtype == torch.float32 for t in params)) and ((need_f and need_r) or pre_rho)):
             # one launch: every workgroup forms the operand (or table) gradient it needs itself, then the small-batch MLP backward
@@ -132,17 +132,26 @@ class _SmallGraph(torch.autograd.Function):
         if pre_rho:
             raise RuntimeError("the one-launch small-graph forward with pre-rho normalisation was taken where its backward "
                                "does not apply (float32 parameters and output gradient expected)")
-        dY = d_out.reshape(1, Cf).expand(n, Cf).contiguous() if ctx.graph_sum else d_out.contiguous()
-        call = aggregate.AggregateCall(ctx.g, ctx.use_cnt, with_rest=False)
-        dS, dlut = aggregate._aggregate_backward(call, S, lut, dY, need_f, need_r)
-        pg_f = pg_r = [None] * 6
-        if need_f:
-            _, pg_f = Fn._shape_function_grads(x, fp, ctx.present[:6], None, dS, True, Lf, Hf, Cf, F, dests=ctx.dests[:6])
-        if need_r:
-            u = hop_inputs(ctx.g.n_codes, x.device).view(-1, 1)
-            _, pg_r = Fn._shape_function_grads(u, rp, ctx.present[6:], None, dlut.reshape(-1, Cr), False, Lr, Hr, Cr, 1,
-                                            dests=ctx.dests[6:])
-        return (None, None, None, None, None, None, *pg_f, *pg_r)
+        return _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r)
+
+
+def _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r):
+    """The backward of a one-launch forward by the general path's kernels on the node sums and the rho table it saved."""
+    fp, rp = params[:6], params[6:]
+    Lf, Hf, Cf, F = ctx.fm
+    Lr, Hr, Cr = ctx.rm
+    n = x.shape[0]
+    dY = d_out.reshape(1, Cf).expand(n, Cf).contiguous() if ctx.graph_sum else d_out.contiguous()
+    call = aggregate.AggregateCall(ctx.g, ctx.use_cnt, with_rest=False)
+    dS, dlut = aggregate._aggregate_backward(call, S, lut, dY, need_f, need_r)
+    pg_f = pg_r = [None] * 6
+    if need_f:
+        _, pg_f = Fn._shape_function_grads(x, fp, ctx.present[:6], None, dS, True, Lf, Hf, Cf, F, dests=ctx.dests[:6])
+    if need_r:
+        u = hop_inputs(ctx.g.n_codes, x.device).view(-1, 1)
+        _, pg_r = Fn._shape_function_grads(u, rp, ctx.present[6:], None, dlut.reshape(-1, Cr), False, Lr, Hr, Cr, 1,
+                                        dests=ctx.dests[6:])
+    return (None, None, None, None, None, None, *pg_f, *pg_r)
 
 
 def small_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool):
@@ -152,6 +161,97 @@ def small_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: Stacke
     return _SmallGraph.apply(x, g, "pre" if use_cnt == "pre" else bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F),
                              (rho.L, rho.H, rho.C),
                              *f[:6], *rho[:6])
+
+
+# =============================================================================
+# 129 to 448 nodes: the same forward and backward, one launch each, over tiles of 64 rows (csrc/mid_graph.hip)
+# =============================================================================
+MID_GRAPH = True
+MID_GRAPH_MIN_NODES = SMALL_GRAPH_MAX_NODES + 1
+MID_GRAPH_MAX_NODES = 448     # gnan_mid_graph_fwd / _bwd: seven row tiles (the largest Mutagenicity graph has 417 nodes, datasets.py:123-129)
+
+
+def mid_graph_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt=True) -> bool:
+    """Can ``gnan_mid_graph_fwd`` take this forward: a dense-coded graph of 129 to 448 nodes, features summed per node, post-rho
+    shell normalisation or none (not ``use_cnt="pre"``), a one-channel rho, at most 64 shells?"""
+    if use_cnt == "pre" or (use_cnt and g.cnt is None):
+        return False
+    return bool(MID_GRAPH and SMALL_GRAPH_FORWARD and g.is_dense and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad
+                and MID_GRAPH_MIN_NODES <= x.shape[0] <= MID_GRAPH_MAX_NODES and g.n_rows == g.n_cols == x.shape[0]
+                and g.n_codes <= 64 and x.shape[1] == f.F and rho.F == 1 and f.L in (2, 3) and rho.L in (2, 3) and 1 <= f.H <= 64
+                and 1 <= rho.H <= 64 and 1 <= f.C <= 8 and rho.C == 1
+                and all(t is None or t.dtype == torch.float32 for t in tuple(f[:6]) + tuple(rho[:6])))
+
+
+class _MidGraph(torch.autograd.Function):
+    """:class:`_SmallGraph` for 129 to 448 nodes: ``Y`` (``[n, C]``) or its sum over the nodes (``[C, 1]``) by ONE launch;
+    backward: one launch (``gnan_mid_graph_bwd``) when the gradients of both f and rho are wanted, else the general path's
+    kernels on the saved node sums and rho table.  ``use_cnt``: False / True (post-rho shell normalisation)."""
+
+    @staticmethod
+    def forward(ctx, x, g, use_cnt, graph_sum, fm, rm, *params):
+        Lf, Hf, Cf, F = fm
+        Lr, Hr, Cr = rm
+        fp, rp = params[:6], params[6:]
+        xk = Fn._rows(x.detach())
+        n, D = xk.shape[0], g.n_codes
+        dev = xk.device
+        keep_f = [None if t is None else Fn._c(t.detach()) for t in fp]
+        keep_r = [None if t is None else Fn._c(t.detach()) for t in rp]
+        S = torch.empty((n, Cf), dtype=torch.float32, device=dev)
+        lut = torch.empty((D, Cr), dtype=torch.float32, device=dev)
+        Y = None if graph_sum else torch.empty((n, Cf), dtype=torch.float32, device=dev)
+        Ysum = torch.empty(Cf, dtype=torch.float32, device=dev) if graph_sum else None
+        ws = _workspace(dev, _lib.lib().gnan_mid_graph_workspace_bytes(n, F, Cf))     # (a captured step's own: see _SmallGraph.forward)
+        cnt = g.cnt if use_cnt else None
+        a = _lib.MidGraphArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), n=n, F=F, f=_small_mlp(keep_f, Lf, Hf, Cf),
+                              rho=_small_mlp(keep_r, Lr, Hr, Cr), code=_lib.ptr(g.code), D=D, reserved=0, cnt=_lib.ptr(cnt),
+                              cnt_stride=0 if cnt is None else cnt.stride(0), S=_lib.ptr(S), lut=_lib.ptr(lut), Y=_lib.ptr(Y),
+                              Ysum=_lib.ptr(Ysum), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
+        _lib.check(_lib.lib().gnan_mid_graph_fwd(a, _lib.stream_of(xk)), "gnan_mid_graph_fwd")
+        ctx.g, ctx.use_cnt, ctx.graph_sum, ctx.fm, ctx.rm = g, use_cnt, graph_sum, fm, rm
+        ctx.present = [t is not None for t in params]
+        ctx.dests = Fn._grad_dests_of(params)
+        ctx.save_for_backward(xk, S, lut, *[t for t in params if t is not None])
+        return Ysum.view(-1, 1) if graph_sum else Y
+
+    @staticmethod
+    def backward(ctx, d_out):
+        saved = list(ctx.saved_tensors)
+        x, S, lut = saved[:3]
+        rest = saved[3:]
+        params = [rest.pop(0) if pr else None for pr in ctx.present]
+        Lf, Hf, Cf, F = ctx.fm
+        Lr, Hr, Cr = ctx.rm
+        n = x.shape[0]
+        need_f, need_r = any(ctx.needs_input_grad[6:12]), any(ctx.needs_input_grad[12:])
+        if not (SMALL_GRAPH_BACKWARD and need_f and need_r and d_out.dtype == torch.float32
+                and all(t is None or t.dtype == torch.float32 for t in params)):
+            return _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r)
+        keep = [None if t is None else Fn._c(t.detach()) for t in params]
+        outs_f, outs_r = Fn._grad_outputs(keep[:6], ctx.dests[:6]), Fn._grad_outputs(keep[6:], ctx.dests[6:])
+
+        def grads(o):
+            return _lib.SmallMlpGrads(w_first=_lib.ptr(o[0]), b_first=_lib.ptr(o[1]),
+                                      w_mid=None if o[2] is None else _lib.ptr(o[2][0]),
+                                      b_mid=None if o[3] is None else _lib.ptr(o[3][0]), w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
+        g_out = d_out.detach().contiguous()
+        cnt = ctx.g.cnt if ctx.use_cnt else None
+        ws = _workspace(x.device, _lib.lib().gnan_mid_graph_bwd_workspace_bytes(n, ctx.g.n_codes))
+        a = _lib.MidGraphBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, Cf),
+                                 rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(ctx.g.code), D=ctx.g.n_codes, reserved=0,
+                                 cnt=_lib.ptr(cnt), cnt_stride=0 if cnt is None else cnt.stride(0), S=_lib.ptr(S), lut=_lib.ptr(lut),
+                                 dY=None if ctx.graph_sum else _lib.ptr(g_out), dYsum=_lib.ptr(g_out) if ctx.graph_sum else None,
+                                 df=grads(outs_f), drho=grads(outs_r), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
+        _lib.check(_lib.lib().gnan_mid_graph_bwd(a, _lib.stream_of(x)), "gnan_mid_graph_bwd")
+        return (None, None, None, None, None, None, *outs_f, *outs_r)
+
+
+def mid_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool):
+    """:func:`small_graph_forward` for a dense-coded graph of 129 to 448 nodes (``gnan_mid_graph_fwd``): ``[n, C]`` node outputs,
+    or ``[C, 1]`` with ``graph_sum``."""
+    _lib.require_device(x, f.w_last, rho.w_last, g.code)
+    return _MidGraph.apply(x, g, bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C), *f[:6], *rho[:6])
 
 
 # =============================================================================

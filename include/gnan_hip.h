@@ -1251,6 +1251,74 @@ typedef struct gnan_small_graph_bwd_args {
 size_t gnan_small_graph_bwd_workspace_bytes(int32_t n, int32_t D);
 int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_stream_t stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The same forward and backward, one launch each, for dense-coded graphs of up to 448 nodes (added under ABI 51: new entry points, no struct changed; csrc/mid_graph.hip): the
+ * last workgroup walks the graph in tiles of 64 rows — a [64][n] block of hop codes and a [64][64] block of row weights in LDS
+ * at a time — with the arithmetic and the orders of gnan_small_graph_fwd, so a graph both cover gets the same bits from both.
+ * Covers n <= 448, D <= 64, a one-channel rho, post-rho shell normalisation (cnt) or none, L in {2, 3}, 1 <= H <= 64,
+ * C <= 8; GNAN_ERR_UNSUPPORTED otherwise, with the offending value in gnan_last_error().  code must be 4-byte aligned.
+ * Every argument is checked before the first HIP call.  workspace (both calls may share one): at least
+ * gnan_mid_graph_workspace_bytes(n, F, f.C) / gnan_mid_graph_bwd_workspace_bytes(n, D) bytes, 8-byte aligned, whose first 16
+ * are ZERO before the first launch (both kernels leave them zero); one workspace per stream.
+ * Backward: workgroup k < F forms dS over the row tiles itself and runs gnan_fmlp_bwd's body on feature k; the table gradient's
+ * rows are split over ceil(n / 32) rho workgroups that leave float64 partials in the workspace, and the last of them to arrive
+ * adds the partials in group order and runs the same body on rho.  No workgroup waits for another.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_mid_graph_args {
+  const float* x;            /* [n, F], row stride x_stride */
+  int64_t x_stride;
+  int32_t n, F;
+  gnan_small_mlp f;          /* the F shape functions */
+  gnan_small_mlp rho;        /* one scalar MLP, C == 1 */
+  const uint8_t* code;       /* [n, n] hop codes (gnan_dense_to_code) */
+  int32_t D;
+  int32_t reserved;          /* 0 */
+  const int32_t* cnt;        /* optional [n, cnt_stride] shell sizes */
+  int64_t cnt_stride;
+  float* S;                  /* [n, f.C] */
+  float* lut;                /* [D] */
+  float* Y;                  /* optional [n, f.C] */
+  float* Ysum;               /* optional [f.C] */
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_mid_graph_args;
+typedef struct gnan_mid_graph_bwd_args {
+  const float* x;
+  int64_t x_stride;
+  int32_t n, F;
+  gnan_small_mlp f;
+  gnan_small_mlp rho;
+  const uint8_t* code;
+  int32_t D;
+  int32_t reserved;          /* 0 */
+  const int32_t* cnt;
+  int64_t cnt_stride;
+  const float* S;            /* [n, f.C] node sums of the forward */
+  const float* lut;          /* [D] rho table of the forward */
+  const float* dY;           /* [n, f.C] or NULL */
+  const float* dYsum;        /* [f.C] or NULL (used when dY is NULL) */
+  gnan_small_mlp_grads df;
+  gnan_small_mlp_grads drho;
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_mid_graph_bwd_args;
+/* what the two launches of a shape look like (host only: no pointer, no GPU) */
+typedef struct gnan_mid_graph_info {
+  int32_t row_tiles;         /* ceil(n / 64) */
+  int32_t rho_groups;        /* rho workgroups of the backward: ceil(n / 32) */
+  int32_t fwd_grid;          /* workgroups of 256 threads: F + 1 */
+  int32_t bwd_grid;          /* F + rho_groups */
+  int32_t fwd_lds_bytes;     /* dynamic + static LDS of a forward workgroup */
+  int32_t bwd_lds_bytes;     /* ... of a backward workgroup */
+  int64_t fwd_workspace_bytes;
+  int64_t bwd_workspace_bytes;
+} gnan_mid_graph_info;
+size_t gnan_mid_graph_workspace_bytes(int32_t n, int32_t F, int32_t C);
+size_t gnan_mid_graph_bwd_workspace_bytes(int32_t n, int32_t D);
+int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t C, gnan_mid_graph_info* out);
+int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream);
+int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream);
+
 /* The backward pass of gnan_small_batch_fwd: launch 1 — blockIdx.y = graph, the workgroups of gnan_small_graph_bwd per graph — leaves
  * every graph's contribution to the gradients of f and rho in its slab of the workspace; launch 2 adds the slabs in graph
  * order into df / drho.  dY [total_nodes, f.C], or dYsum [n_graphs, f.C] (the gradient of the per-graph read-out).  Covers
