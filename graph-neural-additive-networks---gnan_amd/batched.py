@@ -30,7 +30,7 @@ from . import _lib
 from .aggregate import rho_aggregate
 from .graph import HopGraph
 from .modules import _PathBase
-from .small_graph import _small_mlp
+from .small_graph import _cnt_pair, _kept, _mlp_grads, _save, _saved, _small_mlp
 
 BATCH_KERNEL = True            # the one-launch forward where it applies (tests compare with the CSR route)
 BATCH_KERNEL_MAX_NODES = 128
@@ -220,8 +220,7 @@ class _BatchedGraphs(torch.autograd.Function):
         xk = Fn._rows(x.detach().float())
         dev = xk.device
         G, N, D = blocks.n_graphs, blocks.total_nodes, blocks.n_codes
-        keep_f = [None if t is None else Fn._c(t.detach()) for t in params[:6]]
-        keep_r = [None if t is None else Fn._c(t.detach()) for t in params[6:]]
+        keep = _kept(params)
         S = torch.empty((N, Cf), dtype=torch.float32, device=dev)
         lut = torch.empty((G, D, Cr), dtype=torch.float32, device=dev)
         Y = None if graph_sum else torch.empty((N, Cf), dtype=torch.float32, device=dev)
@@ -230,27 +229,22 @@ class _BatchedGraphs(torch.autograd.Function):
         ws = torch.empty(need // 4 + 1, dtype=torch.int32, device=dev)
         ws[: 32 * G].zero_()                                                 # the graphs' arrival counters (a 128-byte line each)
         a = _lib.SmallBatchArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), total_nodes=N, F=F, n_graphs=G,
-                                max_nodes=blocks.max_nodes, f=_small_mlp(keep_f, Lf, Hf, Cf),
-                                rho=_small_mlp(keep_r, Lr, Hr, Cr), code=_lib.ptr(blocks.code),
+                                max_nodes=blocks.max_nodes, f=_small_mlp(keep[:6], Lf, Hf, Cf),
+                                rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(blocks.code),
                                 node_off=_lib.ptr(blocks.node_off), code_off=_lib.ptr(blocks.code_off), D=D,
                                 rho_raw_hops=int(raw_hops), rest_zero=int(raw_hops), S=_lib.ptr(S), lut=_lib.ptr(lut),
                                 Y=_lib.ptr(Y), Ysum=_lib.ptr(Ysum), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4,
-                                cnt=_lib.ptr(cnt), cnt_stride=0 if cnt is None else cnt.stride(0))
+                                **_cnt_pair(cnt))
         _lib.check(_lib.lib().gnan_small_batch_fwd(a, _lib.stream_of(xk)), "gnan_small_batch_fwd")
         ctx.blocks, ctx.graph_sum, ctx.fm, ctx.rm = blocks, graph_sum, fm, rm
         ctx.cnt, ctx.raw_hops = cnt, bool(raw_hops)
-        ctx.present = [t is not None for t in params]
-        ctx.dests = Fn._grad_dests_of(params)
-        ctx.save_for_backward(xk, S, lut, *[t for t in params if t is not None])
+        _save(ctx, (xk, S, lut), params)
         return Ysum if graph_sum else Y
 
     @staticmethod
     def backward(ctx, d_out):
         from . import functional as Fn
-        saved = list(ctx.saved_tensors)
-        x, S, lut = saved[:3]
-        rest = saved[3:]
-        params = [rest.pop(0) if pr else None for pr in ctx.present]
+        (x, S, lut), params = _saved(ctx, 3)
         Lf, Hf, Cf, F = ctx.fm
         Lr, Hr, Cr = ctx.rm
         need_f, need_r = any(ctx.needs_input_grad[7:13]), any(ctx.needs_input_grad[13:])
@@ -258,22 +252,17 @@ class _BatchedGraphs(torch.autograd.Function):
         if (BATCH_BACKWARD_KERNEL and Cr in (1, Cf) and blocks.n_codes <= 64 and d_out.dtype == torch.float32
                 and all(t is None or t.dtype == torch.float32 for t in params)):
             # two launches: every graph's workgroups leave its share of the gradients in a slab, the slabs are added in order
-            keep = [None if t is None else Fn._c(t.detach()) for t in params]
+            keep = _kept(params)
             outs_f, outs_r = Fn._grad_outputs(keep[:6], ctx.dests[:6]), Fn._grad_outputs(keep[6:], ctx.dests[6:])
-
-            def grads(o):
-                return _lib.SmallMlpGrads(w_first=_lib.ptr(o[0]), b_first=_lib.ptr(o[1]),
-                                          w_mid=None if o[2] is None else _lib.ptr(o[2][0]),
-                                          b_mid=None if o[3] is None else _lib.ptr(o[3][0]), w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
             g_out = d_out.detach().contiguous()
             a = _lib.SmallBatchBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), total_nodes=blocks.total_nodes, F=F,
                                        n_graphs=blocks.n_graphs, max_nodes=blocks.max_nodes, f=_small_mlp(keep[:6], Lf, Hf, Cf),
                                        rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(blocks.code),
                                        node_off=_lib.ptr(blocks.node_off), code_off=_lib.ptr(blocks.code_off), D=blocks.n_codes,
                                        rho_raw_hops=int(ctx.raw_hops), rest_zero=int(ctx.raw_hops), S=_lib.ptr(S), lut=_lib.ptr(lut),
-                                       cnt=_lib.ptr(ctx.cnt), cnt_stride=0 if ctx.cnt is None else ctx.cnt.stride(0),
+                                       **_cnt_pair(ctx.cnt),
                                        dY=None if ctx.graph_sum else _lib.ptr(g_out),
-                                       dYsum=_lib.ptr(g_out) if ctx.graph_sum else None, df=grads(outs_f), drho=grads(outs_r),
+                                       dYsum=_lib.ptr(g_out) if ctx.graph_sum else None, df=_mlp_grads(outs_f), drho=_mlp_grads(outs_r),
                                        workspace=None, workspace_bytes=0)
             need = _lib.lib().gnan_small_batch_bwd_workspace_bytes(a)
             if need <= BATCH_BACKWARD_MAX_WORKSPACE:

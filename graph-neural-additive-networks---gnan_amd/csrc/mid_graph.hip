@@ -372,33 +372,12 @@ __global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdPar
 
 template <int C>
 int launch_mid_bwd(const MidBwdParams& p, hipStream_t st) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_graph_bwd_kernel<C>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kBwdDynBytes));
-  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "mid_graph_bwd: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+  if (int rc = raise_dyn_lds<&mid_graph_bwd_kernel<C>>(kBwdDynBytes, "mid_graph_bwd")) return rc;
   hipLaunchKernelGGL((mid_graph_bwd_kernel<C>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(kThreads), kBwdDynBytes, st, p);
   return gnan::check_launch("mid_graph_bwd_kernel");
 }
 
-// what both entry points refuse: sizes and MLP shapes outside the kernels' cover, each named
-int mid_shape_ok(const char* who, int n, int F, int D, const gnan_small_mlp* f, const gnan_small_mlp* rho) {
-  GNAN_REQUIRE(n >= 1 && F >= 1 && D >= 1, "%s: bad sizes n=%d F=%d D=%d", who, n, F, D);
-  if (n > kMidNodes) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers n <= %d nodes (got n=%d)", who, kMidNodes, n);
-  if (D > kMidD) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers D <= %d shells (got D=%d)", who, kMidD, D);
-  if (f && (f->C < 1 || f->C > kMaxC))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= C <= %d output channels (got C=%d)", who, kMaxC, f->C);
-  if (rho && rho->C != 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers a one-channel rho (got rho.C=%d)", who, rho->C);
-  const gnan_small_mlp* m[2] = {f, rho};
-  for (int t = 0; t < 2; ++t) {
-    if (m[t] == nullptr) continue;
-    if (m[t]->L != 2 && m[t]->L != 3)
-      return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers L in {2, 3} (got L=%d for %s)", who, m[t]->L, t ? "rho" : "f");
-    if (m[t]->H < 1 || m[t]->H > kMaxH)
-      return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= H <= %d (got H=%d for %s)", who, kMaxH, m[t]->H, t ? "rho" : "f");
-  }
-  return GNAN_OK;
-}
-
-bool mlp_ptrs_ok(const gnan_small_mlp* m) { return m->w_first && m->w_last && (m->L == 2 || m->w_mid); }
+constexpr RouteLimits kMidCover = {kMidNodes, kMidD, kMaxC, false};      // what both entry points and the route query take
 
 }  // namespace
 
@@ -415,8 +394,7 @@ extern "C" int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t 
   GNAN_REQUIRE(out != nullptr, "mid_graph_describe: null out");
   gnan_small_mlp f{};
   f.L = 3; f.H = 1; f.C = C;
-  const int rc = mid_shape_ok("mid_graph_describe", n, F, D, &f, nullptr);
-  if (rc != GNAN_OK) return rc;
+  if (int rc = shape_ok("mid_graph_describe", kMidCover, n, F, D, &f, nullptr)) return rc;
   out->row_tiles = (n + kTile - 1) / kTile;
   out->rho_groups = (n + kRhoRows - 1) / kRhoRows;
   out->fwd_grid = F + 1;
@@ -430,30 +408,20 @@ extern "C" int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t 
 
 extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
-  const int rc = mid_shape_ok("mid_graph", a->n, a->F, a->D, &a->f, &a->rho);
-  if (rc != GNAN_OK) return rc;
+  if (int rc = shape_ok("mid_graph", kMidCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x != nullptr, "mid_graph: null x");
   GNAN_REQUIRE(a->code != nullptr, "mid_graph: null code");
   GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->code) % 4 == 0, "mid_graph: code must be 4-byte aligned (got %p)",
                static_cast<const void*>(a->code));
   GNAN_REQUIRE(a->S && a->lut && (a->Y || a->Ysum), "mid_graph: null S / lut / outputs");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "mid_graph: null weights");
-  GNAN_REQUIRE(a->x_stride >= a->F, "mid_graph: row stride x_stride=%lld smaller than F=%d", static_cast<long long>(a->x_stride), a->F);
-  GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "mid_graph: row stride cnt_stride=%lld smaller than D=%d",
-               static_cast<long long>(a->cnt_stride), a->D);
-  const size_t need = gnan_mid_graph_workspace_bytes(a->n, a->F, a->f.C);
-  if (a->workspace == nullptr || a->workspace_bytes < need)
-    return gnan::fail(GNAN_ERR_WORKSPACE, "mid_graph: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  if (int rc = strides_ok("mid_graph", a)) return rc;
+  if (int rc = workspace_ok("mid_graph", a, gnan_mid_graph_workspace_bytes(a->n, a->F, a->f.C))) return rc;
   MidParams p;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
-  p.f = to_mlp(&a->f); p.r = to_mlp(&a->rho);
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  fwd_fields(p, a, a->n);
   p.S = a->S; p.lut = a->lut; p.Y = a->Y; p.Ysum = a->Ysum;
-  p.counter = static_cast<unsigned*>(a->workspace);
-  p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 16);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_graph_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFwdDynBytes));
-  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "mid_graph: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+  split_workspace(a->workspace, p.counter, p.part);
+  if (int rc = raise_dyn_lds<&mid_graph_kernel>(kFwdDynBytes, "mid_graph")) return rc;
   hipLaunchKernelGGL(mid_graph_kernel, dim3(static_cast<unsigned>(a->F) + 1u), dim3(kThreads), kFwdDynBytes,
                      static_cast<hipStream_t>(stream), p);
   return gnan::check_launch("mid_graph_kernel");
@@ -461,42 +429,23 @@ extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t st
 
 extern "C" int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
-  const int rc = mid_shape_ok("mid_graph_bwd", a->n, a->F, a->D, &a->f, &a->rho);
-  if (rc != GNAN_OK) return rc;
+  if (int rc = shape_ok("mid_graph_bwd", kMidCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x != nullptr, "mid_graph_bwd: null x");
   GNAN_REQUIRE(a->code != nullptr, "mid_graph_bwd: null code");
   GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->code) % 4 == 0, "mid_graph_bwd: code must be 4-byte aligned (got %p)",
                static_cast<const void*>(a->code));
   GNAN_REQUIRE(a->S && a->lut && (a->dY || a->dYsum), "mid_graph_bwd: null S / lut / output gradient");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "mid_graph_bwd: null weights");
-  GNAN_REQUIRE(a->x_stride >= a->F, "mid_graph_bwd: row stride x_stride=%lld smaller than F=%d", static_cast<long long>(a->x_stride),
-               a->F);
-  GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "mid_graph_bwd: row stride cnt_stride=%lld smaller than D=%d",
-               static_cast<long long>(a->cnt_stride), a->D);
+  if (int rc = strides_ok("mid_graph_bwd", a)) return rc;
   GNAN_REQUIRE(grads_ok(&a->f, &a->df) && grads_ok(&a->rho, &a->drho),
                "mid_graph_bwd: a gradient pointer for every weight, and for a bias exactly where there is one");
-  const size_t need = gnan_mid_graph_bwd_workspace_bytes(a->n, a->D);
-  if (a->workspace == nullptr || a->workspace_bytes < need)
-    return gnan::fail(GNAN_ERR_WORKSPACE, "mid_graph_bwd: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  if (int rc = workspace_ok("mid_graph_bwd", a, gnan_mid_graph_bwd_workspace_bytes(a->n, a->D))) return rc;
   GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->workspace) % 8 == 0, "mid_graph_bwd: workspace must be 8-byte aligned (got %p)", a->workspace);
   MidBwdParams p;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
-  p.f = to_weights(&a->f, &a->df); p.r = to_weights(&a->rho, &a->drho);
-  p.f_mid = a->f.L == 3; p.r_mid = a->rho.L == 3;
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  bwd_fields(p, a, a->n, &a->df, &a->drho);
   p.S = a->S; p.lut = a->lut; p.dY = a->dY; p.dYsum = a->dYsum;
   p.rho_groups = (a->n + kRhoRows - 1) / kRhoRows;
-  p.counter = static_cast<unsigned*>(a->workspace);
-  p.part = reinterpret_cast<double*>(static_cast<char*>(a->workspace) + 16);
+  split_workspace(a->workspace, p.counter, p.part);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (a->f.C) {
-    case 1: return launch_mid_bwd<1>(p, st);
-    case 2: return launch_mid_bwd<2>(p, st);
-    case 3: return launch_mid_bwd<3>(p, st);
-    case 4: return launch_mid_bwd<4>(p, st);
-    case 5: return launch_mid_bwd<5>(p, st);
-    case 6: return launch_mid_bwd<6>(p, st);
-    case 7: return launch_mid_bwd<7>(p, st);
-    default: return launch_mid_bwd<8>(p, st);
-  }
+  return with_channels(a->f.C, [&](auto c) { return launch_mid_bwd<decltype(c)::value>(p, st); });
 }

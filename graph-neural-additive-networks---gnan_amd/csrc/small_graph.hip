@@ -725,15 +725,17 @@ int launch_small_bwd(const SmallBwdParams& p, hipStream_t st) {
     hipLaunchKernelGGL((small_graph_bwd_kernel<C, 1>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(256),
                        small_bwd_dyn_bytes<1>(p.pre_rho != 0), st, p);
   } else {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_graph_bwd_kernel<C, 2>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       static_cast<int>(small_bwd_dyn_bytes<2>(true)));
-    if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_graph_bwd: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+    if (int rc = raise_dyn_lds<&small_graph_bwd_kernel<C, 2>>(small_bwd_dyn_bytes<2>(true), "small_graph_bwd")) return rc;
     hipLaunchKernelGGL((small_graph_bwd_kernel<C, 2>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(256),
                        small_bwd_dyn_bytes<2>(p.pre_rho != 0), st, p);
   }
   return gnan::check_launch("small_graph_bwd_kernel");
 }
+
+// the routes' covers: up to 256 shells and a rho channel per output channel forward; 64 shells backward, where the one-graph
+// kernel takes a one-channel rho only
+constexpr RouteLimits kSmallFwdCover = {kMaxNodes, 256, kMaxC, true}, kSmallBwdCover = {kMaxNodes, kWave, kMaxC, false},
+                      kBatchBwdCover = {kMaxNodes, kWave, kMaxC, true};
 
 }  // namespace
 
@@ -743,27 +745,18 @@ extern "C" size_t gnan_small_graph_workspace_bytes(int32_t n, int32_t F, int32_t
 
 extern "C" int gnan_small_graph_fwd(const gnan_small_graph_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph: null args");
-  GNAN_REQUIRE(a->n >= 1 && a->F >= 1 && a->D >= 1, "small_graph: bad sizes n=%d F=%d D=%d", a->n, a->F, a->D);
-  if (a->n > kMaxNodes || a->D > 256 || !mlp_ok(&a->f, kMaxC) || !mlp_ok(&a->rho, kMaxC) ||
-      (a->rho.C != 1 && a->rho.C != a->f.C))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_graph: covers n <= %d nodes, D <= 256 shells, L in {2, 3}, H <= %d, C <= %d and a "
-                      "rho of one channel or one per output channel (got n=%d D=%d L=%d/%d H=%d/%d C=%d/%d)", kMaxNodes, kMaxH,
-                      kMaxC, a->n, a->D, a->f.L, a->rho.L, a->f.H, a->rho.H, a->f.C, a->rho.C);
+  if (int rc = shape_ok("small_graph", kSmallFwdCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->S && a->lut && (a->Y || a->Ysum), "small_graph: null x / code / S / lut / outputs");
-  GNAN_REQUIRE(a->x_stride >= a->F && (a->cnt == nullptr || a->cnt_stride >= a->D), "small_graph: row stride smaller than the width");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_graph: null weights");
+  if (int rc = strides_ok("small_graph", a)) return rc;
   if (a->pre_rho && (a->cnt == nullptr || a->rho.C != 1 || a->D > kWave))
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_graph: pre-rho normalisation needs the shell sizes, a one-channel rho and D <= %d "
                       "(got cnt=%p rho.C=%d D=%d)", kWave, static_cast<const void*>(a->cnt), a->rho.C, a->D);
-  const size_t need = gnan_small_graph_workspace_bytes(a->n, a->F, a->f.C);
-  if (a->workspace == nullptr || a->workspace_bytes < need)
-    return gnan::fail(GNAN_ERR_WORKSPACE, "small_graph: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  if (int rc = workspace_ok("small_graph", a, gnan_small_graph_workspace_bytes(a->n, a->F, a->f.C))) return rc;
   SmallParams p;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
-  p.f = to_mlp(&a->f); p.r = to_mlp(&a->rho);
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  fwd_fields(p, a, a->n);
   p.S = a->S; p.lut = a->lut; p.Y = a->Y; p.Ysum = a->Ysum;
-  p.counter = static_cast<unsigned*>(a->workspace);
-  p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 16);
+  split_workspace(a->workspace, p.counter, p.part);
   p.rho_raw = 0; p.rest_zero = 0; p.pre_rho = a->pre_rho != 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned rho_groups = p.pre_rho ? static_cast<unsigned>((a->n * a->D + kWave - 1) / kWave) : 1u;
@@ -772,9 +765,7 @@ extern "C" int gnan_small_graph_fwd(const gnan_small_graph_args* a, gnan_stream_
                        small_cols_floats(1) * sizeof(float), st, p);
   } else {
     constexpr size_t lds = small_cols_floats(2) * sizeof(float);          // 64 KB of tables + the static weight image
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_graph_kernel<2>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_graph: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+    if (int rc = raise_dyn_lds<&small_graph_kernel<2>>(lds, "small_graph")) return rc;
     hipLaunchKernelGGL(small_graph_kernel<2>, dim3(static_cast<unsigned>(a->F) + rho_groups), dim3(kWaves * kWave), lds, st, p);
   }
   return gnan::check_launch("small_graph_kernel");
@@ -787,20 +778,14 @@ extern "C" size_t gnan_small_graph_bwd_workspace_bytes(int32_t n, int32_t D) {
 
 extern "C" int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
-  GNAN_REQUIRE(a->n >= 1 && a->F >= 1 && a->D >= 1, "small_graph_bwd: bad sizes n=%d F=%d D=%d", a->n, a->F, a->D);
-  if (a->n > kMaxNodes || a->D > kWave || !mlp_ok(&a->f, kMaxC) || !mlp_ok(&a->rho, 1))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_graph_bwd: covers n <= %d nodes, D <= %d shells, L in {2, 3}, H <= %d, C <= %d and a "
-                      "one-channel rho (got n=%d D=%d L=%d/%d H=%d/%d C=%d/%d)", kMaxNodes, kWave, kMaxH, kMaxC, a->n, a->D,
-                      a->f.L, a->rho.L, a->f.H, a->rho.H, a->f.C, a->rho.C);
+  if (int rc = shape_ok("small_graph_bwd", kSmallBwdCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->S && a->lut && (a->dY || a->dYsum), "small_graph_bwd: null x / code / S / lut / output gradient");
-  GNAN_REQUIRE(a->x_stride >= a->F && (a->cnt == nullptr || a->cnt_stride >= a->D), "small_graph_bwd: row stride smaller than the width");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_graph_bwd: null weights");
+  if (int rc = strides_ok("small_graph_bwd", a)) return rc;
   GNAN_REQUIRE(grads_ok(&a->f, &a->df) && grads_ok(&a->rho, &a->drho),
                "small_graph_bwd: a gradient pointer for every weight, and for a bias exactly where there is one");
   SmallBwdParams p;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
-  p.f = to_weights(&a->f, &a->df); p.r = to_weights(&a->rho, &a->drho);
-  p.f_mid = a->f.L == 3; p.r_mid = a->rho.L == 3;
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  bwd_fields(p, a, a->n, &a->df, &a->drho);
   p.S = a->S; p.lut = a->lut; p.dY = a->dY; p.dYsum = a->dYsum; p.pre_rho = a->pre_rho != 0;
   GNAN_REQUIRE(!p.pre_rho || a->cnt != nullptr, "small_graph_bwd: pre-rho normalisation needs the shell sizes");
   p.rho_groups = 1; p.rows_per = a->n; p.part = nullptr; p.counter = nullptr; p.rho_raw = 0; p.rest_zero = 0; p.rho_c = 1;
@@ -813,23 +798,12 @@ extern "C" int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_str
     if (groups > 1 && a->workspace != nullptr && a->workspace_bytes >= need) {
       p.rows_per = (a->n + groups - 1) / groups;
       p.rho_groups = (a->n + p.rows_per - 1) / p.rows_per;
-      p.counter = static_cast<unsigned*>(a->workspace);
-      p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 16);
+      split_workspace(a->workspace, p.counter, p.part);
     }
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (a->f.C) {
-    case 1: return launch_small_bwd<1>(p, st);
-    case 2: return launch_small_bwd<2>(p, st);
-    case 3: return launch_small_bwd<3>(p, st);
-    case 4: return launch_small_bwd<4>(p, st);
-    case 5: return launch_small_bwd<5>(p, st);
-    case 6: return launch_small_bwd<6>(p, st);
-    case 7: return launch_small_bwd<7>(p, st);
-    default: return launch_small_bwd<8>(p, st);
-  }
+  return with_channels(a->f.C, [&](auto c) { return launch_small_bwd<decltype(c)::value>(p, st); });
 }
-
 
 extern "C" size_t gnan_small_batch_workspace_bytes(int32_t n_graphs, int64_t total_nodes, int32_t F, int32_t C) {
   return static_cast<size_t>(n_graphs) * 128 + static_cast<size_t>(total_nodes) * F * C * sizeof(float);    // counters (a line each) | part
@@ -839,27 +813,21 @@ extern "C" int gnan_small_batch_fwd(const gnan_small_batch_args* a, gnan_stream_
   GNAN_REQUIRE(a != nullptr, "small_batch: null args");
   GNAN_REQUIRE(a->n_graphs >= 0 && a->F >= 1 && a->D >= 1 && a->total_nodes >= 0, "small_batch: bad sizes");
   if (a->n_graphs == 0) return GNAN_OK;
-  if (a->max_nodes < 1 || a->max_nodes > kMaxNodes || a->D > 256 || !mlp_ok(&a->f, kMaxC) || !mlp_ok(&a->rho, kMaxC) ||
-      (a->rho.C != 1 && a->rho.C != a->f.C))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch: covers graphs of <= %d nodes, D <= 256 shells, L in {2, 3}, H <= %d, C <= %d "
-                      "and a rho of one channel or one per output channel (got max n=%d D=%d L=%d/%d H=%d/%d C=%d/%d)", kMaxNodes,
-                      kMaxH, kMaxC, a->max_nodes, a->D, a->f.L, a->rho.L, a->f.H, a->rho.H, a->f.C, a->rho.C);
+  if (a->max_nodes < 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch: covers graphs of >= 1 node (got max_nodes=%d)", a->max_nodes);
+  if (int rc = shape_ok("small_batch", kSmallFwdCover, a->max_nodes, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->node_off && a->code_off && a->S && a->lut && (a->Y || a->Ysum),
                "small_batch: null x / code / offsets / S / lut / outputs");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_batch: null weights");
   GNAN_REQUIRE(a->x_stride >= a->F, "small_batch: row stride smaller than the width");
   GNAN_REQUIRE(a->n_graphs <= 65535, "small_batch: at most 65535 graphs per launch");
   GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "small_batch: cnt row stride smaller than D");
   if (a->cnt && (a->D > kWave || a->rho.C != 1))
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch: shell sizes need D <= %d and a one-channel rho (got D=%d rho.C=%d)", kWave,
                       a->D, a->rho.C);
-  const size_t need = gnan_small_batch_workspace_bytes(a->n_graphs, a->total_nodes, a->F, a->f.C);
-  if (a->workspace == nullptr || a->workspace_bytes < need)
-    return gnan::fail(GNAN_ERR_WORKSPACE, "small_batch: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  if (int rc = workspace_ok("small_batch", a, gnan_small_batch_workspace_bytes(a->n_graphs, a->total_nodes, a->F, a->f.C))) return rc;
   BatchParams bp;
   SmallParams& p = bp.base;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = 0; p.F = a->F;
-  p.f = to_mlp(&a->f); p.r = to_mlp(&a->rho);
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  fwd_fields(p, a, 0);
   p.S = a->S; p.lut = a->lut; p.Y = a->Y; p.Ysum = a->Ysum;
   p.counter = static_cast<unsigned*>(a->workspace);
   p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + static_cast<size_t>(a->n_graphs) * 128);
@@ -871,9 +839,7 @@ extern "C" int gnan_small_batch_fwd(const gnan_small_batch_args* a, gnan_stream_
     hipLaunchKernelGGL(small_graph_batch_kernel<1>, grid, dim3(kWaves * kWave), small_cols_floats(1) * sizeof(float), st, bp);
   } else {
     constexpr size_t lds = small_cols_floats(2) * sizeof(float);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_graph_batch_kernel<2>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_batch: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+    if (int rc = raise_dyn_lds<&small_graph_batch_kernel<2>>(lds, "small_batch")) return rc;
     hipLaunchKernelGGL(small_graph_batch_kernel<2>, grid, dim3(kWaves * kWave), lds, st, bp);
   }
   return gnan::check_launch("small_graph_batch_kernel");
@@ -902,10 +868,7 @@ int launch_small_batch_bwd(const BatchBwdParams& bp, int n_graphs, int max_nodes
   if (max_nodes <= 64) {
     hipLaunchKernelGGL((small_graph_batch_bwd_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(false), st, bp);
   } else {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_graph_batch_bwd_kernel<C, 2>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       static_cast<int>(small_bwd_dyn_bytes<2>(false)));
-    if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_batch_bwd: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+    if (int rc = raise_dyn_lds<&small_graph_batch_bwd_kernel<C, 2>>(small_bwd_dyn_bytes<2>(false), "small_batch_bwd")) return rc;
     hipLaunchKernelGGL((small_graph_batch_bwd_kernel<C, 2>), grid, dim3(256), small_bwd_dyn_bytes<2>(false), st, bp);
   }
   return gnan::check_launch("small_graph_batch_bwd_kernel");
@@ -937,13 +900,12 @@ extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_str
       }
     return GNAN_OK;
   }
-  if (a->max_nodes < 1 || a->max_nodes > kMaxNodes || a->D > kWave || !mlp_ok(&a->f, kMaxC) || !mlp_ok(&a->rho, kMaxC) ||
-      (a->rho.C != 1 && a->rho.C != a->f.C))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch_bwd: covers graphs of <= %d nodes, D <= %d shells, L in {2, 3}, H <= %d, C <= %d "
-                      "and a rho of one channel or one per output channel (got max n=%d D=%d L=%d/%d H=%d/%d C=%d/%d)", kMaxNodes,
-                      kWave, kMaxH, kMaxC, a->max_nodes, a->D, a->f.L, a->rho.L, a->f.H, a->rho.H, a->f.C, a->rho.C);
+  if (a->max_nodes < 1)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch_bwd: covers graphs of >= 1 node (got max_nodes=%d)", a->max_nodes);
+  if (int rc = shape_ok("small_batch_bwd", kBatchBwdCover, a->max_nodes, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->node_off && a->code_off && a->S && a->lut && (a->dY || a->dYsum),
                "small_batch_bwd: null x / code / offsets / S / lut / output gradient");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_batch_bwd: null weights");
   GNAN_REQUIRE(a->x_stride >= a->F, "small_batch_bwd: row stride smaller than the width");
   GNAN_REQUIRE(a->n_graphs <= 65535, "small_batch_bwd: at most 65535 graphs per launch");
   GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "small_batch_bwd: cnt row stride smaller than D");
@@ -952,9 +914,8 @@ extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_str
   // ONE graph (a batch-size-1 step through graph slots): its share IS the gradient — the kernel writes the caller's tensors,
   // no slab, no reduction launch (the kernel shifts graph g's pointers by g * slab = 0)
   const bool direct = a->n_graphs == 1;
-  const size_t need = direct ? 0 : static_cast<size_t>(a->n_graphs) * static_cast<size_t>(slab) * sizeof(float);
-  if (!direct && (a->workspace == nullptr || a->workspace_bytes < need))
-    return gnan::fail(GNAN_ERR_WORKSPACE, "small_batch_bwd: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  if (!direct)
+    if (int rc = workspace_ok("small_batch_bwd", a, static_cast<size_t>(a->n_graphs) * static_cast<size_t>(slab) * sizeof(float))) return rc;
   float* slabs = static_cast<float*>(a->workspace);
   // graph 0's slab as the kernels' gradient tensors (the kernel shifts them by g * slab)
   gnan_small_mlp_grads gf = {slabs + at[0], a->f.b_first ? slabs + at[1] : nullptr, slabs + at[2],
@@ -965,27 +926,16 @@ extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_str
   if (direct) { gf = a->df; gr = a->drho; }
   BatchBwdParams bp;
   SmallBwdParams& p = bp.base;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = 0; p.F = a->F;
-  p.f = to_weights(&a->f, &gf); p.r = to_weights(&a->rho, &gr);
+  bwd_fields(p, a, 0, &gf, &gr);
   if (a->f.L != 3) { p.f.d_w_mid = nullptr; p.f.d_b_mid = nullptr; }
   if (a->rho.L != 3) { p.r.d_w_mid = nullptr; p.r.d_b_mid = nullptr; }
-  p.f_mid = a->f.L == 3; p.r_mid = a->rho.L == 3;
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
   p.S = a->S; p.lut = a->lut; p.dY = a->dYsum ? nullptr : a->dY; p.dYsum = a->dYsum; p.pre_rho = 0;
   p.rho_groups = 1; p.rows_per = 0; p.part = nullptr; p.counter = nullptr;
   p.rho_raw = a->rho_raw_hops != 0; p.rest_zero = a->rest_zero != 0; p.rho_c = a->rho.C;
   bp.node_off = a->node_off; bp.code_off = a->code_off; bp.slab = slab; bp.dy_per_graph = a->dYsum != nullptr;
-  int rc;
-  switch (a->f.C) {
-    case 1: rc = launch_small_batch_bwd<1>(bp, a->n_graphs, a->max_nodes, st); break;
-    case 2: rc = launch_small_batch_bwd<2>(bp, a->n_graphs, a->max_nodes, st); break;
-    case 3: rc = launch_small_batch_bwd<3>(bp, a->n_graphs, a->max_nodes, st); break;
-    case 4: rc = launch_small_batch_bwd<4>(bp, a->n_graphs, a->max_nodes, st); break;
-    case 5: rc = launch_small_batch_bwd<5>(bp, a->n_graphs, a->max_nodes, st); break;
-    case 6: rc = launch_small_batch_bwd<6>(bp, a->n_graphs, a->max_nodes, st); break;
-    case 7: rc = launch_small_batch_bwd<7>(bp, a->n_graphs, a->max_nodes, st); break;
-    default: rc = launch_small_batch_bwd<8>(bp, a->n_graphs, a->max_nodes, st); break;
-  }
+  const int rc = with_channels(a->f.C, [&](auto c) {
+    return launch_small_batch_bwd<decltype(c)::value>(bp, a->n_graphs, a->max_nodes, st);
+  });
   if (rc != GNAN_OK || direct) return rc;
   ReduceSeg seg;
   for (int t = 0; t < 13; ++t) seg.at[t] = at[t];

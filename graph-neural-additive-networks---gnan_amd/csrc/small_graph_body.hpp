@@ -1,7 +1,10 @@
-// Pieces the one-launch small-graph kernels share (csrc/small_graph.hip, csrc/small_graph_nam.hip): the LDS image of one
-// scalar MLP's weights, its evaluation on a block of 64 inputs by four waves, and the host-side conversions of the C ABI's
-// gnan_small_mlp.
+// Pieces the one-launch graph routes share (csrc/small_graph.hip, csrc/small_graph_nam.hip, csrc/mid_graph.hip): the LDS image of
+// one scalar MLP's weights, its evaluation on a block of 64 inputs by four waves, and — at the end — the host side of their entry
+// points: the conversions of the C ABI's gnan_small_mlp, the ONE validator of sizes and MLP shapes (a route's limits are a
+// RouteLimits next to its entry points), the pointer test, and the launch helpers.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "fmlp_bwd_body.hpp"
 
@@ -176,16 +179,111 @@ inline bool grads_ok(const gnan_small_mlp* m, const gnan_small_mlp_grads* g) {
          (m->L == 2 || ((m->b_mid == nullptr) == (g->b_mid == nullptr))) && ((m->b_last == nullptr) == (g->b_last == nullptr));
 }
 
-inline bool mlp_ok(const gnan_small_mlp* m, int max_c) {
-  return (m->L == 2 || m->L == 3) && m->H >= 1 && m->H <= kMaxH && m->C >= 1 && m->C <= max_c && m->w_first && m->w_last &&
-         (m->L == 2 || m->w_mid);
-}
-
 inline Mlp to_mlp(const gnan_small_mlp* m) {
   Mlp r;
   r.L = m->L; r.H = m->H; r.C = m->C;
   r.w_first = m->w_first; r.b_first = m->b_first; r.w_mid = m->w_mid; r.b_mid = m->b_mid; r.w_last = m->w_last; r.b_last = m->b_last;
   return r;
+}
+
+// ---- host side of the entry points (csrc/small_graph.hip, csrc/small_graph_nam.hip, csrc/mid_graph.hip) ------------------------------
+
+// A route's cover, as data next to its entry points: the most nodes, the most shells, the most output channels of f, and whether rho
+// may have one channel per output channel of f besides the one channel every route takes.
+struct RouteLimits {
+  int max_nodes, max_shells, max_c;
+  bool rho_per_channel;
+};
+
+// What every launching entry point refuses first: sizes and MLP shapes outside the route's cover — one refusal per violated limit,
+// naming the limit and the value.  Shapes only: pointers are mlp_ptrs_ok's.  (f or rho may be NULL: a query about sizes alone.)
+inline int shape_ok(const char* who, const RouteLimits& lim, int n, int F, int D, const gnan_small_mlp* f, const gnan_small_mlp* rho) {
+  GNAN_REQUIRE(n >= 1 && F >= 1 && D >= 1, "%s: bad sizes n=%d F=%d D=%d", who, n, F, D);
+  if (n > lim.max_nodes) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers n <= %d nodes (got n=%d)", who, lim.max_nodes, n);
+  if (D > lim.max_shells) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers D <= %d shells (got D=%d)", who, lim.max_shells, D);
+  if (f && (f->C < 1 || f->C > lim.max_c))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= C <= %d output channels (got C=%d)", who, lim.max_c, f->C);
+  if (rho && rho->C != 1 && !(lim.rho_per_channel && f && rho->C == f->C))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers a one-channel rho%s (got rho.C=%d)", who,
+                      lim.rho_per_channel ? " or a channel per output channel" : "", rho->C);
+  const gnan_small_mlp* m[2] = {f, rho};
+  for (int t = 0; t < 2; ++t) {
+    if (m[t] == nullptr) continue;
+    if (m[t]->L != 2 && m[t]->L != 3)
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers L in {2, 3} (got L=%d for %s)", who, m[t]->L, t ? "rho" : "f");
+    if (m[t]->H < 1 || m[t]->H > kMaxH)
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= H <= %d (got H=%d for %s)", who, kMaxH, m[t]->H, t ? "rho" : "f");
+  }
+  return GNAN_OK;
+}
+
+// THE pointer test of a stack whose shape was accepted (L == 1: the NAM read-out's Linear(1, C), only its last layer exists)
+inline bool mlp_ptrs_ok(const gnan_small_mlp* m) { return m->w_last && (m->L == 1 || (m->w_first && (m->L == 2 || m->w_mid))); }
+
+template <class A>
+int strides_ok(const char* who, const A* a) {
+  GNAN_REQUIRE(a->x_stride >= a->F, "%s: row stride x_stride=%lld smaller than F=%d", who, static_cast<long long>(a->x_stride), a->F);
+  GNAN_REQUIRE(a->cnt == nullptr || a->cnt_stride >= a->D, "%s: row stride cnt_stride=%lld smaller than D=%d", who,
+               static_cast<long long>(a->cnt_stride), a->D);
+  return GNAN_OK;
+}
+
+template <class A>
+int workspace_ok(const char* who, const A* a, size_t need) {
+  if (a->workspace == nullptr || a->workspace_bytes < need)
+    return gnan::fail(GNAN_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", who, a->workspace_bytes, need);
+  return GNAN_OK;
+}
+
+// fn(std::integral_constant<int, C>) for the kernels' output-channel counts 1 .. 8 (the validator refused everything else)
+template <class Fn>
+int with_channels(int C, Fn&& fn) {
+  switch (C) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 5: return fn(std::integral_constant<int, 5>{});
+    case 6: return fn(std::integral_constant<int, 6>{});
+    case 7: return fn(std::integral_constant<int, 7>{});
+    default: return fn(std::integral_constant<int, 8>{});
+  }
+}
+
+// Raise a kernel's dynamic-LDS limit: once per kernel instance, at its first use (the eager warm-up of a step that is captured
+// later — never inside a capture); the first result is remembered and a failure is reported on every call.
+template <auto Kernel>
+int raise_dyn_lds(size_t bytes, const char* who) {
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(attr));
+  return GNAN_OK;
+}
+
+// The fields the ABI structs of every route share, into a kernel's parameter record: the forward's (weights only) ...
+template <class P, class A>
+void graph_fields(P& p, const A* a, int n) {
+  p.x = a->x; p.x_stride = a->x_stride; p.n = n; p.F = a->F;
+  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+}
+template <class P, class A>
+void fwd_fields(P& p, const A* a, int n) {
+  graph_fields(p, a, n);
+  p.f = to_mlp(&a->f); p.r = to_mlp(&a->rho);
+}
+// ... and the backward's (weights and where their gradients go)
+template <class P, class A>
+void bwd_fields(P& p, const A* a, int n, const gnan_small_mlp_grads* df, const gnan_small_mlp_grads* drho) {
+  graph_fields(p, a, n);
+  p.f = to_weights(&a->f, df); p.r = to_weights(&a->rho, drho);
+  p.f_mid = a->f.L == 3; p.r_mid = a->rho.L == 3;
+}
+
+// a one-graph workspace: the first 16 bytes the arrival counter, the rest the partials
+template <class T>
+void split_workspace(void* workspace, unsigned*& counter, T*& part) {
+  counter = static_cast<unsigned*>(workspace);
+  part = reinterpret_cast<T*>(static_cast<char*>(workspace) + 16);
 }
 
 }  // namespace gnan_small

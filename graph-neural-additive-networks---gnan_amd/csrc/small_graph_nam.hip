@@ -359,24 +359,21 @@ constexpr int kMaxBwdWorkgroups = 128;
 
 template <int CN>
 int launch_nam_bwd(const NamBwdParams& p, hipStream_t st) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_graph_nam_bwd_kernel<CN>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(nam_bwd_dyn_bytes()));
-  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_graph_nam_bwd: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+  if (int rc = raise_dyn_lds<&small_graph_nam_bwd_kernel<CN>>(nam_bwd_dyn_bytes(), "small_graph_nam_bwd")) return rc;
   hipLaunchKernelGGL((small_graph_nam_bwd_kernel<CN>), dim3(static_cast<unsigned>(p.F) + 1), dim3(256), nam_bwd_dyn_bytes(), st, p);
   return gnan::check_launch("small_graph_nam_bwd_kernel");
 }
 
-bool nam_ok(const gnan_small_mlp* m) {
-  if (m->L == 1) return m->C >= 1 && m->C <= kMaxC && m->w_last != nullptr;
-  return mlp_ok(m, kMaxC);
-}
+constexpr RouteLimits kNamCover = {kMaxNodes, kWave, 1, false};          // one-wide f and rho ...
 
-int check_common(const char* who, int n, int F, int D, const gnan_small_mlp* f, const gnan_small_mlp* rho, const gnan_small_mlp* nam) {
-  GNAN_REQUIRE(n >= 1 && F >= 1 && D >= 1, "%s: bad sizes n=%d F=%d D=%d", who, n, F, D);
-  if (n > kMaxNodes || D > kWave || !mlp_ok(f, 1) || !mlp_ok(rho, 1) || !nam_ok(nam))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers n <= %d nodes, D <= %d shells, one-wide f and rho with L in {2, 3}, H <= %d, a read-out "
-                      "with L in {1, 2, 3} and C <= %d (got n=%d D=%d L=%d/%d/%d H=%d/%d/%d C=%d/%d/%d)", who, kMaxNodes, kWave, kMaxH,
-                      kMaxC, n, D, f->L, rho->L, nam->L, f->H, rho->H, nam->H, f->C, rho->C, nam->C);
+// ... and the read-out on top of the shared cover: a Linear(1, C) per feature (L == 1) or an MLP, C <= 8
+int check_cover(const char* who, int n, int F, int D, const gnan_small_mlp* f, const gnan_small_mlp* rho, const gnan_small_mlp* nam) {
+  if (int rc = shape_ok(who, kNamCover, n, F, D, f, rho)) return rc;
+  if (nam->C < 1 || nam->C > kMaxC)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= C <= %d read-out channels (got C=%d)", who, kMaxC, nam->C);
+  if (nam->L < 1 || nam->L > 3) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers L in {1, 2, 3} (got L=%d for the read-out)", who, nam->L);
+  if (nam->L != 1 && (nam->H < 1 || nam->H > kMaxH))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= H <= %d (got H=%d for the read-out)", who, kMaxH, nam->H);
   return GNAN_OK;
 }
 
@@ -390,23 +387,18 @@ extern "C" size_t gnan_small_graph_nam_workspace_bytes(int32_t F, int32_t C) {
 
 extern "C" int gnan_small_graph_nam_fwd(const gnan_small_graph_nam_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph_nam: null args");
-  if (int rc = check_common("small_graph_nam", a->n, a->F, a->D, &a->f, &a->rho, &a->nam)) return rc;
+  if (int rc = check_cover("small_graph_nam", a->n, a->F, a->D, &a->f, &a->rho, &a->nam)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->fx && a->lut && a->hidden && a->out, "small_graph_nam: null x / code / fx / lut / hidden / out");
-  GNAN_REQUIRE(a->x_stride >= a->F && (a->cnt == nullptr || a->cnt_stride >= a->D), "small_graph_nam: row stride smaller than the width");
-  const size_t need = gnan_small_graph_nam_workspace_bytes(a->F, a->nam.C);
-  if (a->workspace == nullptr || a->workspace_bytes < need)
-    return gnan::fail(GNAN_ERR_WORKSPACE, "small_graph_nam: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho) && mlp_ptrs_ok(&a->nam), "small_graph_nam: null weights");
+  if (int rc = strides_ok("small_graph_nam", a)) return rc;
+  if (int rc = workspace_ok("small_graph_nam", a, gnan_small_graph_nam_workspace_bytes(a->F, a->nam.C))) return rc;
   NamParams p;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
-  p.f = to_mlp(&a->f); p.r = to_mlp(&a->rho); p.nam = to_mlp(&a->nam);
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  fwd_fields(p, a, a->n);
+  p.nam = to_mlp(&a->nam);
   p.fx = a->fx; p.lut = a->lut; p.hidden = a->hidden; p.out = a->out;
-  p.counter = static_cast<unsigned*>(a->workspace);
-  p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 16);
+  split_workspace(a->workspace, p.counter, p.part);
   constexpr size_t lds = nam_cols_floats() * sizeof(float);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_graph_nam_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (attr != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_graph_nam: hipFuncSetAttribute: %s", hipGetErrorString(attr));
+  if (int rc = raise_dyn_lds<&small_graph_nam_kernel>(lds, "small_graph_nam")) return rc;
   hipLaunchKernelGGL(small_graph_nam_kernel, dim3(static_cast<unsigned>(a->F)), dim3(kWaves * kWave), lds,
                      static_cast<hipStream_t>(stream), p);
   return gnan::check_launch("small_graph_nam_kernel");
@@ -414,7 +406,7 @@ extern "C" int gnan_small_graph_nam_fwd(const gnan_small_graph_nam_args* a, gnan
 
 extern "C" int gnan_small_graph_nam_bwd(const gnan_small_graph_nam_bwd_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph_nam_bwd: null args");
-  if (int rc = check_common("small_graph_nam_bwd", a->n, a->F, a->D, &a->f, &a->rho, &a->nam)) return rc;
+  if (int rc = check_cover("small_graph_nam_bwd", a->n, a->F, a->D, &a->f, &a->rho, &a->nam)) return rc;
   // Workgroup F waits for the F producers of the same launch.  They wait for nobody, so the wait ends as soon as every one
   // of them has been dispatched — whatever order the dispatcher picks — PROVIDED a producer can always find a free slot next
   // to the waiting workgroup: the launch is kept small enough (at most one workgroup per compute unit of the smallest
@@ -423,7 +415,8 @@ extern "C" int gnan_small_graph_nam_bwd(const gnan_small_graph_nam_bwd_args* a, 
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_graph_nam_bwd: covers F <= %d features (one co-resident workgroup each; got F=%d)",
                       kMaxBwdWorkgroups - 1, a->F);
   GNAN_REQUIRE(a->x && a->code && a->fx && a->lut && a->hidden && a->d_out, "small_graph_nam_bwd: null x / code / fx / lut / hidden / d_out");
-  GNAN_REQUIRE(a->x_stride >= a->F && (a->cnt == nullptr || a->cnt_stride >= a->D), "small_graph_nam_bwd: row stride smaller than the width");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho) && mlp_ptrs_ok(&a->nam), "small_graph_nam_bwd: null weights");
+  if (int rc = strides_ok("small_graph_nam_bwd", a)) return rc;
   GNAN_REQUIRE(grads_ok(&a->f, &a->df) && grads_ok(&a->rho, &a->drho),
                "small_graph_nam_bwd: a gradient pointer for every weight, and for a bias exactly where there is one");
   if (a->nam.L == 1)
@@ -431,26 +424,12 @@ extern "C" int gnan_small_graph_nam_bwd(const gnan_small_graph_nam_bwd_args* a, 
                  "small_graph_nam_bwd: gradient pointers of the one-layer read-out");
   else
     GNAN_REQUIRE(grads_ok(&a->nam, &a->dnam), "small_graph_nam_bwd: a gradient pointer for every weight of the read-out");
-  const size_t need = gnan_small_graph_nam_workspace_bytes(a->F, a->nam.C);
-  if (a->workspace == nullptr || a->workspace_bytes < need)
-    return gnan::fail(GNAN_ERR_WORKSPACE, "small_graph_nam_bwd: workspace %zu B < required %zu B", a->workspace_bytes, need);
+  if (int rc = workspace_ok("small_graph_nam_bwd", a, gnan_small_graph_nam_workspace_bytes(a->F, a->nam.C))) return rc;
   NamBwdParams p;
-  p.x = a->x; p.x_stride = a->x_stride; p.n = a->n; p.F = a->F;
-  p.f = to_weights(&a->f, &a->df); p.r = to_weights(&a->rho, &a->drho); p.nam = to_weights(&a->nam, &a->dnam);
-  p.f_mid = a->f.L == 3; p.r_mid = a->rho.L == 3; p.nam_L = a->nam.L;
-  p.code = a->code; p.D = a->D; p.cnt = a->cnt; p.cnt_stride = a->cnt_stride;
+  bwd_fields(p, a, a->n, &a->df, &a->drho);
+  p.nam = to_weights(&a->nam, &a->dnam); p.nam_L = a->nam.L;
   p.fx = a->fx; p.lut = a->lut; p.hidden = a->hidden; p.d_out = a->d_out;
-  p.counter = static_cast<unsigned*>(a->workspace);
-  p.dh = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + 16);
+  split_workspace(a->workspace, p.counter, p.dh);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (a->nam.C) {
-    case 1: return launch_nam_bwd<1>(p, st);
-    case 2: return launch_nam_bwd<2>(p, st);
-    case 3: return launch_nam_bwd<3>(p, st);
-    case 4: return launch_nam_bwd<4>(p, st);
-    case 5: return launch_nam_bwd<5>(p, st);
-    case 6: return launch_nam_bwd<6>(p, st);
-    case 7: return launch_nam_bwd<7>(p, st);
-    default: return launch_nam_bwd<8>(p, st);
-  }
+  return with_channels(a->nam.C, [&](auto c) { return launch_nam_bwd<decltype(c)::value>(p, st); });
 }

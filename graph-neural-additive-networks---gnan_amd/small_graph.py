@@ -1,16 +1,21 @@
-"""One-launch forward and backward of SMALL dense-coded graphs (``csrc/small_graph.hip``, ``csrc/small_graph_nam.hip``) — what a
-graph-level task feeds per step (trainer.py:23-86 with ``batch_size = 1``; SURVEY.md section 8d C2: 30 nodes on average).
+"""One-launch forward and backward of SMALL dense-coded graphs (``csrc/small_graph.hip``, ``csrc/small_graph_nam.hip``,
+``csrc/mid_graph.hip``) — what a graph-level task feeds per step (trainer.py:23-86 with ``batch_size = 1``; SURVEY.md section 8d C2:
+30 nodes on average).
 
 * :func:`small_graph_forward` — features summed per node, rho on the distinct distances (or, ``use_cnt="pre"``, on the n x D
   normalised distances of GNAN.py:65-67), the normalised aggregation and the graph read-out: GNAN.py:55-79 / 146-172,
   models.py:358-384 with ``readout_n_layers == 0``;
-* :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381);
-* :func:`mid_graph_forward` — the first of the three for graphs of 129 to 448 nodes, over tiles of 64 rows (``csrc/mid_graph.hip``).
+* :func:`mid_graph_forward` — the same for graphs of 129 to 448 nodes, over tiles of 64 rows;
+* :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381).
 
-Both are autograd nodes whose backward pass is one launch as well.  The general kernels (``functional``) take everything these
-do not cover; the ``*_applies`` predicates say which is which.
+All are autograd nodes whose backward pass is one launch as well (the first two are ONE node, :class:`_OneLaunch`, told its route).
+The general kernels (``functional``) take everything these do not cover; the ``*_applies`` predicates say which is which: each
+is the shared test of the graph (:func:`_graph_ok`) and of the MLP stacks (:func:`_stack_ok`) with the route's limits, which stand
+next to it.  The library's copy of the same limits: the ``RouteLimits`` next to each route's entry points.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 
@@ -24,18 +29,31 @@ SMALL_GRAPH_FORWARD = True
 SMALL_GRAPH_MAX_NODES = 128   # gnan_small_graph_fwd / _bwd: one block of 64 nodes (static LDS) or two (64 KB of tables)
 SMALL_GRAPH_BACKWARD = True   # ... and its backward pass (gnan_small_graph_bwd)
 _SMALL_WS = {}               # (device index, stream) -> workspace whose counter word the kernel leaves zero
+_MAX_HIDDEN, _MAX_CHANNELS = 64, 8     # every route's MLP kernels: hidden width, output channels
+_FORWARD_CODES = 256         # hop codes gnan_small_graph_fwd / gnan_small_batch_fwd take ...
+_ONE_LAUNCH_CODES = 64       # ... and the one-launch backward passes, pre-rho, the NAM and the mid route: a lane per shell
+
+
+def _graph_ok(x, g, lo: int, hi: int, max_codes: int) -> bool:
+    """A dense-coded graph of ``lo`` to ``hi`` nodes and at most ``max_codes`` codes; its features float32 on the device, their
+    gradient not wanted."""
+    return bool(g.is_dense and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad and lo <= x.shape[0] <= hi
+                and g.n_rows == g.n_cols == x.shape[0] and g.n_codes <= max_codes)
+
+
+def _stack_ok(m: StackedMLP, max_c: int = _MAX_CHANNELS, depths=(2, 3)) -> bool:
+    """These stacked MLPs are float32 with L, H, C inside the kernels' cover (``L == 1``: a Linear(1, C), no hidden width)."""
+    return bool(m.L in depths and (m.L == 1 or 1 <= m.H <= _MAX_HIDDEN) and 1 <= m.C <= max_c
+                and all(t is None or t.dtype == torch.float32 for t in m[:6]))
 
 
 def small_graph_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, pre_rho: bool = False) -> bool:
     """Can ``gnan_small_graph_fwd`` take this forward (features summed per node; post-rho normalisation, or — ``pre_rho`` — the
     stand-alone file's rho(distance / shell size), GNAN.py:65-67, with a one-channel rho and at most 64 shells)?"""
-    if pre_rho and not (g.cnt is not None and rho.C == 1 and g.n_codes <= 64 and SMALL_GRAPH_BACKWARD):
+    if pre_rho and not (g.cnt is not None and rho.C == 1 and g.n_codes <= _ONE_LAUNCH_CODES and SMALL_GRAPH_BACKWARD):
         return False
-    return bool(SMALL_GRAPH_FORWARD and g.is_dense and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad
-                and 1 <= x.shape[0] <= SMALL_GRAPH_MAX_NODES and g.n_rows == g.n_cols == x.shape[0] and g.n_codes <= 256
-                and x.shape[1] == f.F and rho.F == 1 and f.L in (2, 3) and rho.L in (2, 3) and 1 <= f.H <= 64
-                and 1 <= rho.H <= 64 and f.C <= 8 and rho.C in (1, f.C)
-                and all(t is None or t.dtype == torch.float32 for t in tuple(f[:6]) + tuple(rho[:6])))
+    return bool(SMALL_GRAPH_FORWARD and _graph_ok(x, g, 1, SMALL_GRAPH_MAX_NODES, _FORWARD_CODES) and x.shape[1] == f.F
+                and rho.F == 1 and _stack_ok(f) and _stack_ok(rho) and rho.C in (1, f.C))
 
 
 def _small_mlp(keep, L, H, C) -> "_lib.SmallMlp":
@@ -45,94 +63,132 @@ def _small_mlp(keep, L, H, C) -> "_lib.SmallMlp":
                          b_mid=_lib.ptr(b_mid), w_last=_lib.ptr(keep[4]), b_last=_lib.ptr(keep[5]))
 
 
-class _SmallGraph(torch.autograd.Function):
-    """``Y`` (``[n, C]``) or its sum over the nodes (``[C, 1]``, ``graph_sum``) by ONE launch; backward: one launch too
-    (``gnan_small_graph_bwd``: one rho channel, <= 64 shells), else the general path's kernels on the saved node sums and rho
-    table — transposed aggregation, table gradient, the two small-batch MLP backward launches (their gradients land in the flat
-    gradient buffers directly).  ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67)."""
+def _mlp_grads(o, L: int = 2) -> "_lib.SmallMlpGrads":
+    """Where the gradients of one stack go (``Fn._grad_outputs``); ``L == 1``: the NAM read-out's Linear(1, C) has a last layer only."""
+    if L == 1:
+        return _lib.SmallMlpGrads(w_first=None, b_first=None, w_mid=None, b_mid=None, w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
+    return _lib.SmallMlpGrads(w_first=_lib.ptr(o[0]), b_first=_lib.ptr(o[1]), w_mid=None if o[2] is None else _lib.ptr(o[2][0]),
+                              b_mid=None if o[3] is None else _lib.ptr(o[3][0]), w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
+
+
+def _kept(tensors) -> list:
+    """Detached contiguous copies (None stays None): what the kernels read."""
+    return [None if t is None else Fn._c(t.detach()) for t in tensors]
+
+
+def _cnt_pair(cnt) -> dict:
+    """The ``cnt`` / ``cnt_stride`` fields of every argument struct."""
+    return dict(cnt=_lib.ptr(cnt), cnt_stride=0 if cnt is None else cnt.stride(0))
+
+
+def _save(ctx, lead, params) -> None:
+    """Save ``lead`` and the parameters that exist; remember which do and where their gradients go."""
+    ctx.present = [t is not None for t in params]
+    ctx.dests = Fn._grad_dests_of(params)
+    ctx.save_for_backward(*lead, *[t for t in params if t is not None])
+
+
+def _saved(ctx, n_lead: int):
+    """``(lead, params)`` as :func:`_save` took them: the absent parameters are None again."""
+    saved = list(ctx.saved_tensors)
+    rest = saved[n_lead:]
+    return saved[:n_lead], [rest.pop(0) if pr else None for pr in ctx.present]
+
+
+def _workspace(dev, need: int) -> torch.Tensor:
+    """The kernels' counter + scratch: zero-filled, left zero by every launch, one per (device, stream) — or the captured step's."""
+    if torch.cuda.is_current_stream_capturing():
+        # a captured step owns its workspace: zeroed eagerly BEFORE the capture (graphed.GraphedCallable) — every capture
+        # runs on the framework's one capture stream, so a buffer keyed by stream would be shared by all captured steps,
+        # and one allocated inside a capture would have its zero fill recorded, never run
+        ws = Fn.CAPTURE_SCRATCH
+        if ws is None or (ws.numel() - Fn.ARRIVE_SLOTS) * 4 < need:      # (its last words are arrival counters)
+            ws = torch.zeros(need // 4 + 1, dtype=torch.int32, device=dev)     # (recorded fill: runs at every replay)
+        return ws
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _SMALL_WS.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = _SMALL_WS[key] = torch.zeros(max(need // 4 + 1, 1 << 16), dtype=torch.int32, device=dev)
+    return ws
+
+
+class _Route(NamedTuple):
+    """What tells the two one-launch routes of :class:`_OneLaunch` apart."""
+    name: str            # the library's entry points ``<name>_fwd`` / ``_bwd`` and ``<name>_workspace_bytes`` / ``_bwd_workspace_bytes``
+    args: type           # ... and their argument structs
+    bwd_args: type
+    flag: str            # the struct field that says pre-rho (``reserved``, always 0, where the route has no pre-rho)
+    bwd_borrows: bool    # the backward always takes a workspace (else only under pre-rho)
+
+
+_SMALL = _Route("gnan_small_graph", _lib.SmallGraphArgs, _lib.SmallGraphBwdArgs, "pre_rho", False)
+_MID = _Route("gnan_mid_graph", _lib.MidGraphArgs, _lib.MidGraphBwdArgs, "reserved", True)
+
+
+class _OneLaunch(torch.autograd.Function):
+    """``Y`` (``[n, C]``) or its sum over the nodes (``[C, 1]``, ``graph_sum``) by ONE launch of ``route``'s forward; backward: one
+    launch too (``gnan_small_graph_bwd`` / ``gnan_mid_graph_bwd``: one rho channel, <= 64 shells, the gradients of both f and rho
+    wanted — or pre-rho), else the general path's kernels on the saved node sums and rho table — transposed aggregation, table
+    gradient, the two small-batch MLP backward launches (their gradients land in the flat gradient buffers directly).
+    ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67; the small route only)."""
 
     @staticmethod
-    def forward(ctx, x, g, use_cnt, graph_sum, fm, rm, *params):
+    def forward(ctx, route, x, g, use_cnt, graph_sum, fm, rm, *params):
         Lf, Hf, Cf, F = fm
         Lr, Hr, Cr = rm
-        fp, rp = params[:6], params[6:]
         xk = Fn._rows(x.detach())
         n, D = xk.shape[0], g.n_codes
         dev = xk.device
-        keep_f = [None if t is None else Fn._c(t.detach()) for t in fp]
-        keep_r = [None if t is None else Fn._c(t.detach()) for t in rp]
+        keep = _kept(params)
         pre_rho = use_cnt == "pre"
         S = torch.empty((n, Cf), dtype=torch.float32, device=dev)
         lut = torch.empty((n * D if pre_rho else D, Cr), dtype=torch.float32, device=dev)
         Y = None if graph_sum else torch.empty((n, Cf), dtype=torch.float32, device=dev)
         Ysum = torch.empty(Cf, dtype=torch.float32, device=dev) if graph_sum else None
-        need = _lib.lib().gnan_small_graph_workspace_bytes(n, F, Cf)
-        if torch.cuda.is_current_stream_capturing():
-            # a captured step owns its workspace: zeroed eagerly BEFORE the capture (graphed.GraphedCallable) — every capture
-            # runs on the framework's one capture stream, so a buffer keyed by stream would be shared by all captured steps,
-            # and one allocated inside a capture would have its zero fill recorded, never run
-            ws = Fn.CAPTURE_SCRATCH
-            if ws is None or (ws.numel() - Fn.ARRIVE_SLOTS) * 4 < need:      # (its last words are arrival counters)
-                ws = torch.zeros(need // 4 + 1, dtype=torch.int32, device=dev)     # (recorded fill: runs at every replay)
-        else:
-            key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-            ws = _SMALL_WS.get(key)
-            if ws is None or ws.numel() * 4 < need:
-                ws = _SMALL_WS[key] = torch.zeros(max(need // 4 + 1, 1 << 16), dtype=torch.int32, device=dev)
-        cnt = g.cnt if use_cnt else None
-        a = _lib.SmallGraphArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), n=n, F=F, f=_small_mlp(keep_f, Lf, Hf, Cf),
-                                rho=_small_mlp(keep_r, Lr, Hr, Cr), code=_lib.ptr(g.code), D=D, pre_rho=int(pre_rho),
-                                cnt=_lib.ptr(cnt), cnt_stride=0 if cnt is None else cnt.stride(0), S=_lib.ptr(S),
-                                lut=_lib.ptr(lut), Y=_lib.ptr(Y),
-                                Ysum=_lib.ptr(Ysum), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
-        _lib.check(_lib.lib().gnan_small_graph_fwd(a, _lib.stream_of(xk)), "gnan_small_graph_fwd")
-        ctx.g, ctx.use_cnt, ctx.graph_sum, ctx.fm, ctx.rm = g, use_cnt, graph_sum, fm, rm
-        ctx.present = [t is not None for t in params]
-        ctx.dests = Fn._grad_dests_of(params)
-        ctx.save_for_backward(xk, S, lut, *[t for t in params if t is not None])
+        ws = _workspace(dev, getattr(_lib.lib(), route.name + "_workspace_bytes")(n, F, Cf))
+        a = route.args(x=_lib.ptr(xk), x_stride=xk.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, Cf),
+                       rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(g.code), D=D, **{route.flag: int(pre_rho)},
+                       **_cnt_pair(g.cnt if use_cnt else None), S=_lib.ptr(S), lut=_lib.ptr(lut), Y=_lib.ptr(Y), Ysum=_lib.ptr(Ysum),
+                       workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
+        _lib.check(getattr(_lib.lib(), route.name + "_fwd")(a, _lib.stream_of(xk)), route.name + "_fwd")
+        ctx.route, ctx.g, ctx.use_cnt, ctx.graph_sum, ctx.fm, ctx.rm = route, g, use_cnt, graph_sum, fm, rm
+        _save(ctx, (xk, S, lut), params)
         return Ysum.view(-1, 1) if graph_sum else Y
 
     @staticmethod
     def backward(ctx, d_out):
-        saved = list(ctx.saved_tensors)
-        x, S, lut = saved[:3]
-        rest = saved[3:]
-        params = [rest.pop(0) if pr else None for pr in ctx.present]
+        (x, S, lut), params = _saved(ctx, 3)
+        route = ctx.route
         Lf, Hf, Cf, F = ctx.fm
         Lr, Hr, Cr = ctx.rm
-        n = x.shape[0]
-        need_f, need_r = any(ctx.needs_input_grad[6:12]), any(ctx.needs_input_grad[12:])
+        n, D = x.shape[0], ctx.g.n_codes
+        need_f, need_r = any(ctx.needs_input_grad[7:13]), any(ctx.needs_input_grad[13:])
         pre_rho = ctx.use_cnt == "pre"          # (small_graph_applies admitted it only where the one launch below covers it)
-        if ((SMALL_GRAPH_BACKWARD and Cr == 1 and ctx.g.n_codes <= 64 and d_out.dtype == torch.float32
-                and all(t is None or t.dtype == torch.float32 for t in params)) and ((need_f and need_r) or pre_rho)):
-            # one launch: every workgroup forms the operand (or table) gradient it needs itself, then the small-batch MLP backward
-            keep = [None if t is None else Fn._c(t.detach()) for t in params]
-            outs_f, outs_r = Fn._grad_outputs(keep[:6], ctx.dests[:6]), Fn._grad_outputs(keep[6:], ctx.dests[6:])
-
-            def grads(o):
-                return _lib.SmallMlpGrads(w_first=_lib.ptr(o[0]), b_first=_lib.ptr(o[1]),
-                                          w_mid=None if o[2] is None else _lib.ptr(o[2][0]),
-                                          b_mid=None if o[3] is None else _lib.ptr(o[3][0]), w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
-            g_out = d_out.detach().contiguous()
-            cnt = ctx.g.cnt if ctx.use_cnt else None
-            ws = _workspace(x.device, _lib.lib().gnan_small_graph_bwd_workspace_bytes(n, ctx.g.n_codes)) if pre_rho else None
-            a = _lib.SmallGraphBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, Cf),
-                                       rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(ctx.g.code), D=ctx.g.n_codes,
-                                       pre_rho=int(pre_rho), cnt=_lib.ptr(cnt), cnt_stride=0 if cnt is None else cnt.stride(0),
-                                       S=_lib.ptr(S),
-                                       lut=_lib.ptr(lut), dY=None if ctx.graph_sum else _lib.ptr(g_out),
-                                       dYsum=_lib.ptr(g_out) if ctx.graph_sum else None, df=grads(outs_f), drho=grads(outs_r),
-                                       workspace=_lib.ptr(ws), workspace_bytes=0 if ws is None else ws.numel() * 4)
-            _lib.check(_lib.lib().gnan_small_graph_bwd(a, _lib.stream_of(x)), "gnan_small_graph_bwd")
-            if not need_f:
-                outs_f = [None] * 6
-            if not need_r:
-                outs_r = [None] * 6
-            return (None, None, None, None, None, None, *outs_f, *outs_r)
-        if pre_rho:
-            raise RuntimeError("the one-launch small-graph forward with pre-rho normalisation was taken where its backward "
-                               "does not apply (float32 parameters and output gradient expected)")
-        return _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r)
+        if not ((SMALL_GRAPH_BACKWARD and Cr == 1 and D <= _ONE_LAUNCH_CODES and d_out.dtype == torch.float32
+                 and all(t is None or t.dtype == torch.float32 for t in params)) and ((need_f and need_r) or pre_rho)):
+            if pre_rho:
+                raise RuntimeError("the one-launch small-graph forward with pre-rho normalisation was taken where its backward "
+                                   "does not apply (float32 parameters and output gradient expected)")
+            return (None, *_general_backward(ctx, x, S, lut, params, d_out, need_f, need_r))
+        # one launch: every workgroup forms the operand (or table) gradient it needs itself, then the small-batch MLP backward
+        keep = _kept(params)
+        outs_f, outs_r = Fn._grad_outputs(keep[:6], ctx.dests[:6]), Fn._grad_outputs(keep[6:], ctx.dests[6:])
+        g_out = d_out.detach().contiguous()
+        ws = None
+        if route.bwd_borrows or pre_rho:
+            ws = _workspace(x.device, getattr(_lib.lib(), route.name + "_bwd_workspace_bytes")(n, D))
+        a = route.bwd_args(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, Cf),
+                           rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(ctx.g.code), D=D, **{route.flag: int(pre_rho)},
+                           **_cnt_pair(ctx.g.cnt if ctx.use_cnt else None), S=_lib.ptr(S), lut=_lib.ptr(lut),
+                           dY=None if ctx.graph_sum else _lib.ptr(g_out), dYsum=_lib.ptr(g_out) if ctx.graph_sum else None,
+                           df=_mlp_grads(outs_f), drho=_mlp_grads(outs_r), workspace=_lib.ptr(ws),
+                           workspace_bytes=0 if ws is None else ws.numel() * 4)
+        _lib.check(getattr(_lib.lib(), route.name + "_bwd")(a, _lib.stream_of(x)), route.name + "_bwd")
+        if not need_f:
+            outs_f = [None] * 6
+        if not need_r:
+            outs_r = [None] * 6
+        return (None, None, None, None, None, None, None, *outs_f, *outs_r)
 
 
 def _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r):
@@ -158,9 +214,8 @@ def small_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: Stacke
     """The forward of GNAN.py:146-172 / models.py:358-384 (post-rho; ``use_cnt="pre"``: GNAN.py:55-79, pre-rho) on a small
     dense-coded graph by ``gnan_small_graph_fwd``: ``[n, C]`` node outputs, or ``[C, 1]`` with ``graph_sum`` (GNAN.py:75-79)."""
     _lib.require_device(x, f.w_last, rho.w_last, g.code)
-    return _SmallGraph.apply(x, g, "pre" if use_cnt == "pre" else bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F),
-                             (rho.L, rho.H, rho.C),
-                             *f[:6], *rho[:6])
+    return _OneLaunch.apply(_SMALL, x, g, "pre" if use_cnt == "pre" else bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F),
+                            (rho.L, rho.H, rho.C), *f[:6], *rho[:6])
 
 
 # =============================================================================
@@ -176,105 +231,20 @@ def mid_graph_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedM
     shell normalisation or none (not ``use_cnt="pre"``), a one-channel rho, at most 64 shells?"""
     if use_cnt == "pre" or (use_cnt and g.cnt is None):
         return False
-    return bool(MID_GRAPH and SMALL_GRAPH_FORWARD and g.is_dense and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad
-                and MID_GRAPH_MIN_NODES <= x.shape[0] <= MID_GRAPH_MAX_NODES and g.n_rows == g.n_cols == x.shape[0]
-                and g.n_codes <= 64 and x.shape[1] == f.F and rho.F == 1 and f.L in (2, 3) and rho.L in (2, 3) and 1 <= f.H <= 64
-                and 1 <= rho.H <= 64 and 1 <= f.C <= 8 and rho.C == 1
-                and all(t is None or t.dtype == torch.float32 for t in tuple(f[:6]) + tuple(rho[:6])))
-
-
-class _MidGraph(torch.autograd.Function):
-    """:class:`_SmallGraph` for 129 to 448 nodes: ``Y`` (``[n, C]``) or its sum over the nodes (``[C, 1]``) by ONE launch;
-    backward: one launch (``gnan_mid_graph_bwd``) when the gradients of both f and rho are wanted, else the general path's
-    kernels on the saved node sums and rho table.  ``use_cnt``: False / True (post-rho shell normalisation)."""
-
-    @staticmethod
-    def forward(ctx, x, g, use_cnt, graph_sum, fm, rm, *params):
-        Lf, Hf, Cf, F = fm
-        Lr, Hr, Cr = rm
-        fp, rp = params[:6], params[6:]
-        xk = Fn._rows(x.detach())
-        n, D = xk.shape[0], g.n_codes
-        dev = xk.device
-        keep_f = [None if t is None else Fn._c(t.detach()) for t in fp]
-        keep_r = [None if t is None else Fn._c(t.detach()) for t in rp]
-        S = torch.empty((n, Cf), dtype=torch.float32, device=dev)
-        lut = torch.empty((D, Cr), dtype=torch.float32, device=dev)
-        Y = None if graph_sum else torch.empty((n, Cf), dtype=torch.float32, device=dev)
-        Ysum = torch.empty(Cf, dtype=torch.float32, device=dev) if graph_sum else None
-        ws = _workspace(dev, _lib.lib().gnan_mid_graph_workspace_bytes(n, F, Cf))     # (a captured step's own: see _SmallGraph.forward)
-        cnt = g.cnt if use_cnt else None
-        a = _lib.MidGraphArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), n=n, F=F, f=_small_mlp(keep_f, Lf, Hf, Cf),
-                              rho=_small_mlp(keep_r, Lr, Hr, Cr), code=_lib.ptr(g.code), D=D, reserved=0, cnt=_lib.ptr(cnt),
-                              cnt_stride=0 if cnt is None else cnt.stride(0), S=_lib.ptr(S), lut=_lib.ptr(lut), Y=_lib.ptr(Y),
-                              Ysum=_lib.ptr(Ysum), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
-        _lib.check(_lib.lib().gnan_mid_graph_fwd(a, _lib.stream_of(xk)), "gnan_mid_graph_fwd")
-        ctx.g, ctx.use_cnt, ctx.graph_sum, ctx.fm, ctx.rm = g, use_cnt, graph_sum, fm, rm
-        ctx.present = [t is not None for t in params]
-        ctx.dests = Fn._grad_dests_of(params)
-        ctx.save_for_backward(xk, S, lut, *[t for t in params if t is not None])
-        return Ysum.view(-1, 1) if graph_sum else Y
-
-    @staticmethod
-    def backward(ctx, d_out):
-        saved = list(ctx.saved_tensors)
-        x, S, lut = saved[:3]
-        rest = saved[3:]
-        params = [rest.pop(0) if pr else None for pr in ctx.present]
-        Lf, Hf, Cf, F = ctx.fm
-        Lr, Hr, Cr = ctx.rm
-        n = x.shape[0]
-        need_f, need_r = any(ctx.needs_input_grad[6:12]), any(ctx.needs_input_grad[12:])
-        if not (SMALL_GRAPH_BACKWARD and need_f and need_r and d_out.dtype == torch.float32
-                and all(t is None or t.dtype == torch.float32 for t in params)):
-            return _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r)
-        keep = [None if t is None else Fn._c(t.detach()) for t in params]
-        outs_f, outs_r = Fn._grad_outputs(keep[:6], ctx.dests[:6]), Fn._grad_outputs(keep[6:], ctx.dests[6:])
-
-        def grads(o):
-            return _lib.SmallMlpGrads(w_first=_lib.ptr(o[0]), b_first=_lib.ptr(o[1]),
-                                      w_mid=None if o[2] is None else _lib.ptr(o[2][0]),
-                                      b_mid=None if o[3] is None else _lib.ptr(o[3][0]), w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
-        g_out = d_out.detach().contiguous()
-        cnt = ctx.g.cnt if ctx.use_cnt else None
-        ws = _workspace(x.device, _lib.lib().gnan_mid_graph_bwd_workspace_bytes(n, ctx.g.n_codes))
-        a = _lib.MidGraphBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, Cf),
-                                 rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(ctx.g.code), D=ctx.g.n_codes, reserved=0,
-                                 cnt=_lib.ptr(cnt), cnt_stride=0 if cnt is None else cnt.stride(0), S=_lib.ptr(S), lut=_lib.ptr(lut),
-                                 dY=None if ctx.graph_sum else _lib.ptr(g_out), dYsum=_lib.ptr(g_out) if ctx.graph_sum else None,
-                                 df=grads(outs_f), drho=grads(outs_r), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
-        _lib.check(_lib.lib().gnan_mid_graph_bwd(a, _lib.stream_of(x)), "gnan_mid_graph_bwd")
-        return (None, None, None, None, None, None, *outs_f, *outs_r)
+    return bool(MID_GRAPH and SMALL_GRAPH_FORWARD and _graph_ok(x, g, MID_GRAPH_MIN_NODES, MID_GRAPH_MAX_NODES, _ONE_LAUNCH_CODES)
+                and x.shape[1] == f.F and rho.F == 1 and _stack_ok(f) and _stack_ok(rho, max_c=1))
 
 
 def mid_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool):
     """:func:`small_graph_forward` for a dense-coded graph of 129 to 448 nodes (``gnan_mid_graph_fwd``): ``[n, C]`` node outputs,
     or ``[C, 1]`` with ``graph_sum``."""
     _lib.require_device(x, f.w_last, rho.w_last, g.code)
-    return _MidGraph.apply(x, g, bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C), *f[:6], *rho[:6])
+    return _OneLaunch.apply(_MID, x, g, bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C), *f[:6], *rho[:6])
 
 
 # =============================================================================
 # ... with a NAM read-out over the per-feature aggregates (csrc/small_graph_nam.hip)
 # =============================================================================
-SMALL_GRAPH_NAM = True
-
-
-def _workspace(dev, need: int) -> torch.Tensor:
-    """The kernels' counter + scratch: zero-filled, left zero by every launch, one per (device, stream) — or the captured
-    step's own (see ``_SmallGraph.forward``)."""
-    if torch.cuda.is_current_stream_capturing():
-        ws = Fn.CAPTURE_SCRATCH
-        if ws is None or (ws.numel() - Fn.ARRIVE_SLOTS) * 4 < need:      # (its last words are arrival counters)
-            ws = torch.zeros(need // 4 + 1, dtype=torch.int32, device=dev)
-        return ws
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _SMALL_WS.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = _SMALL_WS[key] = torch.zeros(max(need // 4 + 1, 1 << 16), dtype=torch.int32, device=dev)
-    return ws
-
-
 def _nam_mlp(keep, L, H, C) -> "_lib.SmallMlp":
     if L == 1:                                       # Linear(1, C) per feature: w_last [F, C]
         return _lib.SmallMlp(L=1, H=0, C=C, w_first=None, b_first=None, w_mid=None, b_mid=None, w_last=_lib.ptr(keep[4]),
@@ -287,12 +257,9 @@ SMALL_GRAPH_NAM_MAX_FEATURES = 127   # the backward's workgroups (one per featur
 
 def small_graph_nam_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, nam: StackedMLP) -> bool:
     """Can ``gnan_small_graph_nam_fwd`` / ``_bwd`` take this graph-level forward with a NAM read-out?"""
-    stacks = tuple(f[:6]) + tuple(rho[:6]) + tuple(nam[:6])
-    return bool(SMALL_GRAPH_NAM and g.is_dense and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad
-                and 1 <= x.shape[0] <= SMALL_GRAPH_MAX_NODES and g.n_rows == g.n_cols == x.shape[0] and g.n_codes <= 64
-                and x.shape[1] == f.F == nam.F and f.F <= SMALL_GRAPH_NAM_MAX_FEATURES and rho.F == 1 and f.C == 1 and rho.C == 1 and f.L in (2, 3) and rho.L in (2, 3)
-                and nam.L in (1, 2, 3) and 1 <= f.H <= 64 and 1 <= rho.H <= 64 and (nam.L == 1 or 1 <= nam.H <= 64)
-                and 1 <= nam.C <= 8 and all(t is None or t.dtype == torch.float32 for t in stacks))
+    return bool(_graph_ok(x, g, 1, SMALL_GRAPH_MAX_NODES, _ONE_LAUNCH_CODES) and x.shape[1] == f.F == nam.F
+                and f.F <= SMALL_GRAPH_NAM_MAX_FEATURES and rho.F == 1 and _stack_ok(f, max_c=1) and _stack_ok(rho, max_c=1)
+                and _stack_ok(nam, depths=(1, 2, 3)))
 
 
 class _SmallGraphNam(torch.autograd.Function):
@@ -305,52 +272,40 @@ class _SmallGraphNam(torch.autograd.Function):
         Ln, Hn, Cn = nm
         xk = Fn._rows(x.detach())
         n, D, dev = xk.shape[0], g.n_codes, xk.device
-        keep = [None if t is None else Fn._c(t.detach()) for t in params]
+        keep = _kept(params)
         fx = torch.empty((F, n), dtype=torch.float32, device=dev)
         lut = torch.empty(D, dtype=torch.float32, device=dev)
         hidden = torch.empty(F, dtype=torch.float32, device=dev)
         out = torch.empty(Cn, dtype=torch.float32, device=dev)
         ws = _workspace(dev, _lib.lib().gnan_small_graph_nam_workspace_bytes(F, Cn))
-        cnt = g.cnt if use_cnt else None
         a = _lib.SmallGraphNamArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, 1),
                                    rho=_small_mlp(keep[6:12], Lr, Hr, 1), nam=_nam_mlp(keep[12:], Ln, Hn, Cn),
-                                   code=_lib.ptr(g.code), D=D, reserved=0, cnt=_lib.ptr(cnt),
-                                   cnt_stride=0 if cnt is None else cnt.stride(0), fx=_lib.ptr(fx), lut=_lib.ptr(lut),
-                                   hidden=_lib.ptr(hidden), out=_lib.ptr(out), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
+                                   code=_lib.ptr(g.code), D=D, reserved=0, **_cnt_pair(g.cnt if use_cnt else None), fx=_lib.ptr(fx),
+                                   lut=_lib.ptr(lut), hidden=_lib.ptr(hidden), out=_lib.ptr(out), workspace=_lib.ptr(ws),
+                                   workspace_bytes=ws.numel() * 4)
         _lib.check(_lib.lib().gnan_small_graph_nam_fwd(a, _lib.stream_of(xk)), "gnan_small_graph_nam_fwd")
         ctx.g, ctx.use_cnt, ctx.fm, ctx.rm, ctx.nm = g, use_cnt, fm, rm, nm
-        ctx.present = [t is not None for t in params]
-        ctx.dests = Fn._grad_dests_of(params)
-        ctx.save_for_backward(xk, fx, lut, hidden, *[t for t in params if t is not None])
+        _save(ctx, (xk, fx, lut, hidden), params)
         return out.view(-1, 1)
 
     @staticmethod
     def backward(ctx, d_out):
-        saved = list(ctx.saved_tensors)
-        x, fx, lut, hidden = saved[:4]
-        rest = saved[4:]
-        params = [rest.pop(0) if pr else None for pr in ctx.present]
+        (x, fx, lut, hidden), params = _saved(ctx, 4)
         Lf, Hf, F = ctx.fm
         Lr, Hr = ctx.rm
         Ln, Hn, Cn = ctx.nm
         n, dev = x.shape[0], x.device
-        keep = [None if t is None else Fn._c(t.detach()) for t in params]
+        keep = _kept(params)
         outs = [Fn._grad_outputs(keep[i:i + 6], ctx.dests[i:i + 6]) for i in (0, 6, 12)]
-
-        def grads(o, L):
-            if L == 1:
-                return _lib.SmallMlpGrads(w_first=None, b_first=None, w_mid=None, b_mid=None, w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
-            return _lib.SmallMlpGrads(w_first=_lib.ptr(o[0]), b_first=_lib.ptr(o[1]), w_mid=None if o[2] is None else _lib.ptr(o[2][0]),
-                                      b_mid=None if o[3] is None else _lib.ptr(o[3][0]), w_last=_lib.ptr(o[4]), b_last=_lib.ptr(o[5]))
         g_out = d_out.detach().to(torch.float32).contiguous().view(-1)
         ws = _workspace(dev, _lib.lib().gnan_small_graph_nam_workspace_bytes(F, Cn))
-        cnt = ctx.g.cnt if ctx.use_cnt else None
         a = _lib.SmallGraphNamBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, 1),
                                       rho=_small_mlp(keep[6:12], Lr, Hr, 1), nam=_nam_mlp(keep[12:], Ln, Hn, Cn),
-                                      code=_lib.ptr(ctx.g.code), D=ctx.g.n_codes, reserved=0, cnt=_lib.ptr(cnt),
-                                      cnt_stride=0 if cnt is None else cnt.stride(0), fx=_lib.ptr(fx), lut=_lib.ptr(lut),
-                                      hidden=_lib.ptr(hidden), d_out=_lib.ptr(g_out), df=grads(outs[0], Lf), drho=grads(outs[1], Lr),
-                                      dnam=grads(outs[2], Ln), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
+                                      code=_lib.ptr(ctx.g.code), D=ctx.g.n_codes, reserved=0,
+                                      **_cnt_pair(ctx.g.cnt if ctx.use_cnt else None), fx=_lib.ptr(fx), lut=_lib.ptr(lut),
+                                      hidden=_lib.ptr(hidden), d_out=_lib.ptr(g_out), df=_mlp_grads(outs[0], Lf),
+                                      drho=_mlp_grads(outs[1], Lr), dnam=_mlp_grads(outs[2], Ln), workspace=_lib.ptr(ws),
+                                      workspace_bytes=ws.numel() * 4)
         _lib.check(_lib.lib().gnan_small_graph_nam_bwd(a, _lib.stream_of(x)), "gnan_small_graph_nam_bwd")
         flat = []
         for i, o in zip((0, 6, 12), outs):
@@ -466,8 +421,8 @@ def slot_tier(graph: HopGraph):
 
 
 def slot_graph_applies(slot: SlotGraph, f: StackedMLP, rho: StackedMLP) -> bool:
-    return bool(f.F == slot.F and rho.F == 1 and f.L in (2, 3) and rho.L in (2, 3) and 1 <= f.H <= 64 and 1 <= rho.H <= 64
-                and f.C <= 8 and rho.C == 1 and all(t is None or t.dtype == torch.float32 for t in tuple(f[:6]) + tuple(rho[:6])))
+    """The stacks' side of ``gnan_small_batch_fwd`` / ``_bwd`` with shell sizes (the graph's side: :meth:`SlotGraph.fits`)."""
+    return bool(f.F == slot.F and rho.F == 1 and _stack_ok(f) and _stack_ok(rho, max_c=1))
 
 
 def slot_graph_forward(slot: SlotGraph, f: StackedMLP, rho: StackedMLP, use_cnt: bool) -> torch.Tensor:
