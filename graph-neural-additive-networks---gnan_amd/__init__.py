@@ -9,7 +9,7 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind the C ABI in
 from . import GNAN, batched, harness, interpret, models  # noqa: F401  (mirror modules + f-3 / f-4)
 from .aggregate import rho_aggregate  # noqa: F401
 from .functional import StackedMLP, feature_mlps, stack_mlps  # noqa: F401
-from .graph import HopGraph, hop_inputs, shell_counts_csr  # noqa: F401
+from .graph import HopGraph, attach_hop_graphs, hop_inputs, shell_counts_csr  # noqa: F401
 
 
 
@@ -23,4 +23,4 @@ def optim_params(model):
 
 
 __all__ = ["GNAN", "models", "batched", "HopGraph", "StackedMLP", "feature_mlps", "rho_aggregate", "stack_mlps",
-           "hop_inputs", "shell_counts_csr", "optim_params"]
+           "hop_inputs", "shell_counts_csr", "optim_params", "attach_hop_graphs"]

@@ -426,6 +426,26 @@ class BfsKhopArgs(C.Structure):
     ]
 
 
+BFS_BLOCKS_MAX_NODES = 512      # GNAN_BFS_BLOCKS_MAX_NODES
+
+
+class BfsBlocksArgs(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p), ("n_edges", C.c_int64), ("graph_of", C.c_void_p), ("n_nodes", C.c_int64),
+        ("node_off", C.c_void_p), ("code_off", C.c_void_p), ("bit_off", C.c_void_p), ("tile_graph", C.c_void_p),
+        ("tile_src", C.c_void_p), ("sizes", C.c_void_p), ("n_tiles", C.c_int32), ("n_graphs", C.c_int32), ("max_nodes", C.c_int32),
+        ("max_hops", C.c_int32), ("code", C.c_void_p), ("max_hop", C.c_void_p), ("status", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class ShellCountsBlocksArgs(C.Structure):
+    _fields_ = [
+        ("code", C.c_void_p), ("graph_of", C.c_void_p), ("n_nodes", C.c_int64), ("node_off", C.c_void_p), ("code_off", C.c_void_p),
+        ("cnt_off", C.c_void_p), ("max_hop", C.c_void_p), ("n_graphs", C.c_int32), ("max_nodes", C.c_int32), ("cnt", C.c_void_p),
+    ]
+
+
 class RestTermArgs(C.Structure):
     _fields_ = [
         ("Y", C.c_void_p), ("y_stride", C.c_int64), ("n", C.c_int64), ("total", C.c_void_p), ("W", C.c_int32),
@@ -564,6 +584,9 @@ SYMBOLS = {
     "gnan_bfs_dense": (C.c_int, [C.POINTER(BfsDenseArgs), C.c_void_p]),
     "gnan_bfs_khop_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gnan_bfs_khop": (C.c_int, [C.POINTER(BfsKhopArgs), C.c_void_p]),
+    "gnan_bfs_blocks_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "gnan_bfs_blocks": (C.c_int, [C.POINTER(BfsBlocksArgs), C.c_void_p]),
+    "gnan_shell_counts_blocks": (C.c_int, [C.POINTER(ShellCountsBlocksArgs), C.c_void_p]),
     "gnan_colsum_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
     "gnan_dense_to_code": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,

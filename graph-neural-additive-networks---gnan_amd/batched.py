@@ -138,6 +138,26 @@ class HopBlocks:
         blocks._batch_vector = bv
         return blocks
 
+    @staticmethod
+    def from_edge_index(edge_index: torch.Tensor, batch_vector: torch.Tensor, num_graphs: Optional[int] = None, *,
+                        sizes: Optional[Sequence[int]] = None) -> "HopBlocks":
+        """From a PyG-style batch — ``edge_index [2, E]`` with global node ids, the sorted ``batch_vector`` (node -> graph) — by
+        the launch of :meth:`HopGraph.batch_from_edge_index` (``gnan_bfs_blocks``): field by field what :meth:`from_blocks` makes of
+        the graphs' hop matrices, without forming them.  The block of a graph beyond the kernel's bound is computed by
+        :meth:`HopGraph.from_edge_index` and copied in.  ``sizes``: the graphs' node counts where the caller knows them (saves the
+        read of ``batch_vector``)."""
+        from .graph import _BlocksBuild, batch_sizes
+        _lib.require_device(edge_index, batch_vector)
+        sizes = batch_sizes(batch_vector, num_graphs) if sizes is None else [int(s) for s in sizes]
+        b = _BlocksBuild(edge_index, batch_vector, sizes, None, align=1, reserve_oversize=True)
+        max_hop = b.read()
+        for g, n in enumerate(sizes):
+            if n > b.bound:
+                hg = b.oversize(g)
+                b.code[b.code_off_host[g]: b.code_off_host[g + 1]].copy_(hg.code.reshape(-1))
+                max_hop[g] = hg.n_codes - 2
+        return HopBlocks(b.code, b.node_off, b.code_off, sizes, max(max_hop, default=0))
+
     def batch_vector(self) -> torch.Tensor:
         if getattr(self, "slots", False):
             raise _lib.GnanHipError("these blocks are the slots of a captured step: their sizes live on the device only")
@@ -176,6 +196,19 @@ def collate(batch):
     (:class:`HopBlocks`) stands where the reference's ``dist_batch`` does — ``model(x_batch, blocks, batch_vector)``."""
     xs, dists, ys = zip(*batch)
     blocks = HopBlocks.from_blocks(dists)
+    return torch.cat(xs, dim=0), blocks, torch.cat([y.reshape(-1) for y in ys], dim=0), blocks.batch_vector()
+
+
+def collate_edges(batch):
+    """:func:`collate` for graphs that come with their edges: ``batch`` is a list of ``(x [n_g, F], edge_index [2, E_g], y)``
+    device tensors, ``edge_index`` in the graph's own node ids; the same 4-tuple, the blocks by
+    :meth:`HopBlocks.from_edge_index` — no hop matrix is formed and no graph is looked at on its own."""
+    from .graph import cat_edges
+    xs, eis, ys = zip(*batch)
+    _lib.require_device(*xs, *eis)
+    sizes = [int(x.shape[0]) for x in xs]
+    ei, graph_of = cat_edges(eis, sizes, xs[0].device)
+    blocks = HopBlocks.from_edge_index(ei, graph_of, len(sizes), sizes=sizes)
     return torch.cat(xs, dim=0), blocks, torch.cat([y.reshape(-1) for y in ys], dim=0), blocks.batch_vector()
 
 

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -331,6 +331,44 @@ class HopGraph:
         D = max_hop + 2
         cnt = torch.cat([cnt256[:, : D - 1], cnt256[:, _lib.MAX_CODES - 1:]], dim=1).contiguous()
         return HopGraph(n_rows=n, n_cols=n, n_codes=D, code=code, cnt=cnt)
+
+    @staticmethod
+    def batch_from_edge_index(edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: Optional[int] = None,
+                              max_hops: Optional[int] = None, *, sizes: Optional[Sequence[int]] = None) -> List["HopGraph"]:
+        """:meth:`from_edge_index` for MANY small graphs at once (``gnan_bfs_blocks`` + ``gnan_shell_counts_blocks``, csrc/bfs_blocks.hip):
+        ``edge_index [2, E]`` with global node ids and the sorted ``batch [N]`` (node -> graph), as a PyG ``Batch`` holds them.  Returns one
+        dense-layout :class:`HopGraph` per graph id — an id no node carries gives an empty graph — each field bit-identical to
+        ``from_edge_index(ei_g - node_off[g], n_g, max_hops)``.  ``max_hops``: None or ``K >= 2`` (truncated, still dense).
+
+        Four launches whatever the number of graphs, and ONE read of their results (``max_hop`` and ``status`` in one tensor); the
+        graphs' sizes are one more read of ``batch`` unless the caller knows them (``sizes``, as :func:`attach_hop_graphs` does).
+        ``code`` and ``cnt`` of the graphs are contiguous views of two packed buffers — graph order, every code block on a
+        :data:`BFS_BLOCKS_ALIGN`-byte boundary (:func:`packed_offsets`) — nothing is allocated or concatenated per graph.  A graph
+        of more than ``_lib.BFS_BLOCKS_MAX_NODES`` nodes goes through :meth:`from_edge_index` and owns its tensors."""
+        if max_hops is not None and (int(max_hops) != max_hops or max_hops < 2):
+            raise ValueError(f"max_hops must be None or an integer >= 2 (got {max_hops!r}): from_edge_index(..., 1) is a CSR layout")
+        _lib.require_device(edge_index, batch)
+        sizes = batch_sizes(batch, num_graphs) if sizes is None else [int(s) for s in sizes]
+        b = _BlocksBuild(edge_index, batch, sizes, max_hops, align=BFS_BLOCKS_ALIGN, reserve_oversize=False)
+        max_hop = b.read()
+        D = [mh + 2 for mh in max_hop]
+        cnt_off = packed_offsets([n * d if n <= b.bound else 0 for n, d in zip(sizes, D)])
+        cnt = torch.empty(cnt_off[-1], dtype=torch.int32, device=b.dev)
+        if cnt_off[-1]:
+            cnt_off_dev = torch.tensor(cnt_off, dtype=torch.int64).to(b.dev)
+            a = _lib.ShellCountsBlocksArgs(code=_lib.ptr(b.code), graph_of=_lib.ptr(b.graph_of), n_nodes=b.n_nodes, node_off=_lib.ptr(b.node_off),
+                                           code_off=_lib.ptr(b.code_off), cnt_off=_lib.ptr(cnt_off_dev), max_hop=_lib.ptr(b.result),
+                                           n_graphs=len(sizes), max_nodes=b.max_nodes, cnt=_lib.ptr(cnt))
+            _lib.check(_lib.lib().gnan_shell_counts_blocks(a, _lib.stream_of(cnt)), "gnan_shell_counts_blocks")
+        out = []
+        for g, n in enumerate(sizes):
+            if n > b.bound:
+                out.append(b.oversize(g))
+                continue
+            co, no = b.code_off_host[g], cnt_off[g]
+            out.append(HopGraph(n_rows=n, n_cols=n, n_codes=D[g], code=b.code[co: co + n * n].view(n, n),
+                                cnt=cnt[no: no + n * D[g]].view(n, D[g])))
+        return out
 
     # ------------------------------------------------------------------ derived structures
     def long_row_plan(self, row_ids: Optional[torch.Tensor] = None, threshold: int = LONG_ROW_THRESHOLD) -> LongRowPlan:
@@ -1141,6 +1179,154 @@ def _khop_csr(src: torch.Tensor, dst: torch.Tensor, n: int, K: int, rows: Option
     if nnz < 2 ** 31:
         rowptr = rowptr.to(torch.int32)
     return HopGraph.from_csr(rowptr, col, code, n_cols=n, n_codes=K + 2, cnt=cnt)
+
+
+BFS_BLOCKS_ALIGN = 16        # HopGraph.batch_from_edge_index: every graph's code block starts on such a boundary of the packed buffer
+                             # (gnan_mid_graph_fwd reads code rows as 4-byte words; HopBlocks keeps its blocks back to back)
+
+
+def packed_offsets(counts: Sequence[int], align: int = 1) -> List[int]:
+    """Where blocks of ``counts`` entries start in a packed buffer whose blocks begin on multiples of ``align`` (``[G + 1]``)."""
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + -(-int(c) // align) * align)
+    return off
+
+
+def bfs_blocks_workspace_bytes(sizes: Sequence[int]) -> int:
+    """``gnan_bfs_blocks_workspace_bytes``: the in-adjacency bit matrices, ``n_g`` rows of ``ceil(n_g / 64)`` 64-bit words."""
+    return 8 * sum(n * ((n + 63) // 64) for n in sizes if 1 <= n <= _lib.BFS_BLOCKS_MAX_NODES)
+
+
+def batch_sizes(batch: torch.Tensor, num_graphs: Optional[int] = None) -> List[int]:
+    """Nodes per graph id of a sorted ``batch`` vector (one device read: the counts, and whether it is sorted)."""
+    _lib.require_device(batch)
+    G = 0 if num_graphs is None else int(num_graphs)
+    if batch.numel() == 0:
+        return [0] * G
+    bv = batch.long()
+    head = torch.stack([(bv[1:] < bv[:-1]).any().long(), bv.min()])
+    unsorted, lowest, *sizes = torch.cat([head, torch.bincount(bv.clamp_min(0), minlength=G)]).tolist()
+    if lowest < 0:
+        raise _lib.GnanHipError("batch holds a negative graph id")
+    if unsorted:
+        raise _lib.GnanHipError("batch must be sorted (the nodes of a graph are consecutive)")
+    if num_graphs is not None and len(sizes) > G:
+        raise ValueError(f"batch names graph {len(sizes) - 1}, num_graphs is {G}")
+    return sizes
+
+
+class _BlocksBuild:
+    """One ``gnan_bfs_blocks`` call: the host-side offsets and tile list (one upload), the launch, and what its callers share —
+    :meth:`read` (the ONE device read: every graph's largest hop; raises on a status flag) and :meth:`oversize` (a graph beyond the
+    kernel's bound through :meth:`HopGraph.from_edge_index`).  ``reserve_oversize``: such a graph still owns ``n_g^2`` bytes of
+    ``code`` (the :class:`gnan_amd.batched.HopBlocks` layout) instead of none."""
+
+    def __init__(self, edge_index, graph_of, sizes, max_hops, align: int, reserve_oversize: bool):
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+            raise ValueError(f"edge_index must be [2, E], got {tuple(edge_index.shape)}")
+        L = _lib.lib()
+        bound = self.bound = _lib.BFS_BLOCKS_MAX_NODES
+        dev = self.dev = edge_index.device
+        self.sizes, self.max_hops = sizes, max_hops
+        G, N = len(sizes), sum(sizes)
+        if graph_of.numel() != N:
+            raise ValueError(f"batch names {graph_of.numel()} nodes, the graphs' sizes add up to {N}")
+        self.n_nodes = N
+        ei = edge_index.long()
+        self.src, self.dst = ei[0].contiguous(), ei[1].contiguous()
+        self.graph_of = graph_of.to(device=dev, dtype=torch.int32).contiguous()
+        n_t = torch.tensor(sizes, dtype=torch.int64)
+        covered = n_t <= bound
+        words = (n_t + 63) // 64
+        zero = torch.zeros(1, dtype=torch.int64)
+        node_off = torch.cat([zero, torch.cumsum(n_t, 0)])
+        blocks = n_t * n_t if reserve_oversize else torch.where(covered, n_t * n_t, zero)
+        code_off = torch.cat([zero, torch.cumsum((blocks + align - 1) // align * align, 0)])
+        bit_off = torch.cat([zero, torch.cumsum(torch.where(covered, n_t * words, zero), 0)])
+        # a tile = up to 64 sources of one graph; the largest graphs first (their tiles take longest: no tail behind the small ones)
+        order = torch.argsort(n_t, descending=True, stable=True)
+        order = order[covered[order] & (n_t[order] > 0)]
+        per = words[order]
+        T = int(per.sum())
+        tile_graph = torch.repeat_interleave(order, per)
+        tile_src = (torch.arange(T) - torch.repeat_interleave(torch.cumsum(per, 0) - per, per)) * 64
+        ints = torch.cat([node_off, tile_graph, tile_src, zero]).to(torch.int32)
+        ints = ints[: ints.numel() // 2 * 2]
+        meta = torch.cat([code_off, bit_off, ints.view(torch.int64)]).to(dev)              # ONE upload
+        self.code_off, bit_off_dev, ints_dev = meta[: G + 1], meta[G + 1: 2 * G + 2], meta[2 * G + 2:].view(torch.int32)
+        self.node_off, tile_graph_dev, tile_src_dev = ints_dev[: G + 1], ints_dev[G + 1: G + 1 + T], ints_dev[G + 1 + T: G + 1 + 2 * T]
+        self.code_off_host, self.node_off_host = code_off.tolist(), node_off.tolist()
+        self.max_nodes = int(n_t[covered].max()) if bool(covered.any()) else 0
+        # (zeros where blocks are padded to a boundary: the bytes between them are the buffer's too, and two calls give equal buffers)
+        self.code = (torch.empty if align == 1 else torch.zeros)(self.code_off_host[-1], dtype=torch.uint8, device=dev)
+        self.result = (torch.empty if G else torch.zeros)(G + 2, dtype=torch.int32, device=dev)    # max_hop [G] | status [2]
+        sizes32 = n_t.to(torch.int32)
+        need = int(L.gnan_bfs_blocks_workspace_bytes(sizes32.data_ptr(), G))
+        ws = torch.empty(max(1, need // 8), dtype=torch.int64, device=dev)
+        a = _lib.BfsBlocksArgs(src=_lib.ptr(self.src), dst=_lib.ptr(self.dst), n_edges=int(self.src.numel()), graph_of=_lib.ptr(self.graph_of),
+                               n_nodes=N, node_off=_lib.ptr(self.node_off), code_off=_lib.ptr(self.code_off), bit_off=_lib.ptr(bit_off_dev),
+                               tile_graph=_lib.ptr(tile_graph_dev), tile_src=_lib.ptr(tile_src_dev), sizes=sizes32.data_ptr(), n_tiles=T,
+                               n_graphs=G, max_nodes=self.max_nodes, max_hops=255 if max_hops is None else min(int(max_hops), 254),
+                               code=_lib.ptr(self.code), max_hop=_lib.ptr(self.result), status=_lib.ptr(self.result[G:]),
+                               workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 8)
+        _lib.check(L.gnan_bfs_blocks(a, _lib.stream_of(self.code)), "gnan_bfs_blocks")
+        self._edge_graph = None
+
+    def read(self) -> List[int]:
+        *max_hop, flags, _ = self.result.tolist()
+        if flags & 4:
+            raise _lib.GnanHipError(f"edge_index holds a node id outside [0, {self.n_nodes})")
+        if flags & 2:
+            raise _lib.GnanHipError("edge_index holds an edge whose ends lie in two different graphs")
+        if flags & 1:
+            raise _lib.GnanHipError("a shortest path longer than 254 hops cannot be coded in one byte")
+        return max_hop
+
+    def oversize(self, g: int) -> "HopGraph":
+        """Graph ``g`` by the one-graph route (after :meth:`read`: every node id is known to be valid)."""
+        if self._edge_graph is None:
+            self._edge_graph = self.graph_of[self.src]
+        keep = self._edge_graph == g
+        ei = torch.stack([self.src[keep], self.dst[keep]]) - self.node_off_host[g]
+        return HopGraph.from_edge_index(ei, self.sizes[g], self.max_hops)
+
+
+def cat_edges(edge_indices: Sequence[torch.Tensor], sizes: Sequence[int], device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-graph ``edge_index`` tensors (local node ids) as one PyG-style batch: ``(edge_index [2, sum E_g]`` with global ids,
+    ``batch [sum n_g]`` int32).  A handful of launches whatever the number of graphs; the sizes come from the shapes."""
+    G, N = len(sizes), sum(sizes)
+    counts = [int(e.shape[1]) for e in edge_indices]
+    E = sum(counts)
+    host = torch.tensor([packed_offsets(sizes)[:G], counts, list(sizes)], dtype=torch.int64).to(device)
+    if E:
+        ei = torch.cat([e for e in edge_indices], dim=1).long()
+        ei = ei + torch.repeat_interleave(host[0], host[1], output_size=E)
+    else:
+        ei = torch.zeros((2, 0), dtype=torch.int64, device=device)
+    graph_of = torch.repeat_interleave(torch.arange(G, dtype=torch.int32, device=device), host[2], output_size=N)
+    return ei, graph_of
+
+
+def attach_hop_graphs(datas, max_hops: Optional[int] = None, pair_budget: int = 1 << 30):
+    """Set ``data.gnan_graph`` — what the modules' forward prefers over dense inputs — on every object of ``datas`` (device ``x
+    [n, F]`` and ``edge_index [2, E]`` with the graph's own node ids): :meth:`HopGraph.batch_from_edge_index` over chunks of at most
+    ``pair_budget`` code bytes (``sum n_g^2``; a single larger graph is a chunk of its own).  Returns the list."""
+    datas = list(datas)
+    sizes = [int(d.x.shape[0]) for d in datas]
+    start = 0
+    while start < len(datas):
+        end, pairs = start, 0
+        while end < len(datas) and (end == start or pairs + sizes[end] ** 2 <= pair_budget):
+            pairs += sizes[end] ** 2
+            end += 1
+        chunk = datas[start:end]
+        _lib.require_device(*[d.x for d in chunk], *[d.edge_index for d in chunk])
+        ei, graph_of = cat_edges([d.edge_index for d in chunk], sizes[start:end], chunk[0].x.device)
+        for d, g in zip(chunk, HopGraph.batch_from_edge_index(ei, graph_of, len(chunk), max_hops, sizes=sizes[start:end])):
+            d.gnan_graph = g
+        start = end
+    return datas
 
 
 def shell_counts_csr(rowptr: torch.Tensor, code: torch.Tensor, n_cols: int, n_codes: int) -> torch.Tensor:

@@ -1596,6 +1596,71 @@ typedef struct gnan_bfs_khop_args {
 int gnan_bfs_khop(const gnan_bfs_khop_args* a, gnan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * All-pairs hop codes of MANY small graphs from ONE edge list (added under ABI 51; csrc/bfs_blocks.hip): what
+ * gnan_bfs_dense does for one graph per call, for a whole batch in a fixed number of launches (clear, edges, BFS).
+ *   edges     src / dst int64 [n_edges], global node ids, any order, duplicates and self loops allowed, directed as given
+ *   graph_of  int32 [n_nodes], sorted: node -> graph;  node_off int32 [G + 1], code_off int64 [G + 1] (the HopBlocks layout;
+ *             code_off need not be dense: graph g's block is the n_g * n_g bytes at code + code_off[g])
+ *   code      uint8: code[code_off[g] + i * n_g + j] = hop(i -> j) in graph g, 255 if unreachable or beyond max_hops
+ *   max_hop   int32 [G]: the largest listed hop of each graph
+ *   status    int32 [2]: status[0] flag bits — 1: a shortest path longer than 254 hops (only with max_hops >= 255, which means
+ *             "no truncation"; max_hops <= 254 truncates silently); 2: an edge whose ends lie in two graphs; 4: a node id outside
+ *             [0, n_nodes) (or a graph_of entry that contradicts node_off).  Flagged edges are not followed and never index
+ *             memory.  status[1] = the largest max_hop.  code is valid only if status[0] == 0.
+ * The three are cleared by the call.  An edge sets one bit of its graph's in-adjacency bit matrix (row dst, bit src; n_g rows
+ * of ceil(n_g / 64) 64-bit words at workspace + 8 * bit_off[g]); a BFS workgroup serves one TILE — up to 64 consecutive sources
+ * of one graph: tile t is the sources tile_src[t] .. of graph tile_graph[t] — with the graph's matrix in LDS.
+ * A graph of more than max_nodes nodes is left alone (no bits, no tile may name it; the caller takes it through
+ * gnan_bfs_dense); max_nodes <= GNAN_BFS_BLOCKS_MAX_NODES, GNAN_ERR_UNSUPPORTED beyond, before any HIP call.
+ * sizes is a HOST array (as gnan_spmm_args.short_row): the entry point checks the workspace against
+ * gnan_bfs_blocks_workspace_bytes(sizes, n_graphs) = 8 * sum over the graphs of at most GNAN_BFS_BLOCKS_MAX_NODES nodes
+ * of n_g * ceil(n_g / 64), which is also bit_off's running sum.
+ * ------------------------------------------------------------------------------------------- */
+#define GNAN_BFS_BLOCKS_MAX_NODES 512
+size_t gnan_bfs_blocks_workspace_bytes(const int32_t* sizes, int32_t n_graphs);
+typedef struct gnan_bfs_blocks_args {
+  const int64_t* src;        /* [n_edges] */
+  const int64_t* dst;        /* [n_edges] */
+  int64_t n_edges;
+  const int32_t* graph_of;   /* [n_nodes] */
+  int64_t n_nodes;
+  const int32_t* node_off;   /* [n_graphs + 1] */
+  const int64_t* code_off;   /* [n_graphs + 1] */
+  const int64_t* bit_off;    /* [n_graphs + 1], in 64-bit words */
+  const int32_t* tile_graph; /* [n_tiles] */
+  const int32_t* tile_src;   /* [n_tiles] */
+  const int32_t* sizes;      /* HOST [n_graphs] */
+  int32_t n_tiles;
+  int32_t n_graphs;
+  int32_t max_nodes;
+  int32_t max_hops;          /* >= 1; >= 255: no truncation */
+  uint8_t* code;
+  int32_t* max_hop;          /* [n_graphs] */
+  int32_t* status;           /* [2] */
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_bfs_blocks_args;
+int gnan_bfs_blocks(const gnan_bfs_blocks_args* a, gnan_stream_t stream);
+
+/* Shell sizes of the blocks gnan_bfs_blocks wrote, once the caller has read max_hop (D_g = max_hop[g] + 2 decides the packed
+ * layout): for node row i of graph g, cnt[cnt_off[g] + i * D_g + d] = #{ j : code == d } for d = 0 .. D_g - 2, and the count of
+ * 255 codes in the last column — what HopGraph.from_edge_index keeps of gnan_bfs_dense's [n, 256] table.  A wave per row, an
+ * integer histogram in LDS.  Graphs of more than max_nodes nodes are left alone. */
+typedef struct gnan_shell_counts_blocks_args {
+  const uint8_t* code;
+  const int32_t* graph_of;   /* [n_nodes] */
+  int64_t n_nodes;
+  const int32_t* node_off;   /* [n_graphs + 1] */
+  const int64_t* code_off;   /* [n_graphs + 1] */
+  const int64_t* cnt_off;    /* [n_graphs + 1], in int32 entries */
+  const int32_t* max_hop;    /* [n_graphs] */
+  int32_t n_graphs;
+  int32_t max_nodes;
+  int32_t* cnt;
+} gnan_shell_counts_blocks_args;
+int gnan_shell_counts_blocks(const gnan_shell_counts_blocks_args* a, gnan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph hygiene for captured steps (gnan_amd/graphed.py; nothing comparable in the reference, which issues every
  * epoch's launches from Python, trainer.py:23-86).  `graph` is a hipGraph_t obtained by stream capture and not yet
  * instantiated: every memset node is replaced by a kernel node performing the same fill, with the same dependencies
