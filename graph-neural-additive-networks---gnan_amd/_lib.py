@@ -177,6 +177,10 @@ class SpmmArgs(C.Structure):
         ("hub_index", C.c_void_p), ("hub_seg_start", C.c_void_p), ("hub_seg_row", C.c_void_p), ("hub_seg_slot", C.c_void_p),
         ("hub_row_slot_ptr", C.c_void_p), ("hub_cls_seg_ptr", C.c_void_p), ("hub_q_lo", C.c_int64), ("n_hub", C.c_int32),
         ("n_hub_seg", C.c_int32), ("hub_seg_max_per_class", C.c_int32),
+        ("stream_index", C.c_void_p), ("stream_cls_pair_ptr", C.c_void_p), ("stream_cls_chunk_ptr", C.c_void_p),
+        ("stream_chunk_first_seg", C.c_void_p), ("stream_seg_slot", C.c_void_p), ("stream_row_slot_ptr", C.c_void_p),
+        ("stream_q_lo", C.c_int64), ("stream_q_hi", C.c_int64), ("stream_chunk", C.c_int32), ("stream_code", C.c_int32),
+        ("n_stream_seg", C.c_int32), ("stream_max_chunks_per_class", C.c_int32),
     ]
 
 
@@ -190,6 +194,7 @@ class SpmmLaunchInfo(C.Structure):
         ("classed", C.c_int32), ("n_slice_blocks", C.c_int32), ("n_tile_blocks", C.c_int32), ("n_tiles", C.c_int32),
         ("row_q0", C.c_int64), ("short_tile", C.c_int32 * (SHORT_LMAX + 1)),
         ("n_seg_blocks", C.c_int32), ("n_segs", C.c_int32), ("n_hub_seg_blocks", C.c_int32), ("n_hub_segs", C.c_int32),
+        ("n_stream_blocks", C.c_int32), ("n_stream_segs", C.c_int32),
     ]
 
     def as_dict(self) -> dict:

@@ -100,6 +100,11 @@ BLOCKED_HUBS_MIN_NNZ = 1 << 24     # ... on graphs of at least this many pairs (
 BLOCKED_HUB_BLOCK_BYTES = 4 << 20  # ... operand rows of one (class, block): one XCD's L2 (HopGraph.blocked_hub_plan); swept on C4 with the
 BLOCKED_HUB_BLOCKS = 4             # ... ranked blocks per class (the columns behind them share one more) and with the
 BLOCKED_HUB_SEG_PAIRS = 256        # ... pairs a lane group carries at most (a longer run is cut into pieces): DESIGN.md 4.1
+PAIR_STREAM = True             # ... and the rows between the tiles and the hubs as a column-blocked pair stream, a chunk per lane group
+PAIR_STREAM_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs (its own gate)
+PAIR_STREAM_MIN_PAIRS = 5          # ... rows of this many pairs up to the hub threshold (HopGraph.pair_stream_plan), in place of the
+PAIR_STREAM_BLOCKS = 2             # ... classed rows; ranked blocks of BLOCKED_HUB_BLOCK_BYTES per class, and
+PAIR_STREAM_CHUNK_PAIRS = 32       # ... entries a lane group takes (a multiple of 16); swept on C4: DESIGN.md 4.1
 
 
 def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -242,7 +247,21 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         if self_sum.dtype != torch.float32 or self_sum.dim() != 2 or self_sum.shape[1] != n_out or not self_sum.is_contiguous():
             raise ValueError("self_sum must be a contiguous float32 [parts, n_rows] tensor")
         a.self_sum, a.self_parts = _lib.ptr(self_sum), int(self_sum.shape[0])
-        if (CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
+        stream = None
+        if (PAIR_STREAM and g.nnz >= PAIR_STREAM_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
+                and s_total is not None and S.dtype == torch.float32 and 32 < S.shape[1] <= 256
+                and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
+            # the rows between the tiles and the hubs as one queue of pairs per column class, in popularity-block order, a chunk per
+            # lane group; None where their pairs carry more than one hop code: the classed rows below then
+            stream = g.pair_stream_plan(max(PAIR_STREAM_MIN_PAIRS, SHORT_ROW_LMAX + 1), max(1, BLOCKED_HUB_BLOCK_BYTES // (S.shape[1] * 4)),
+                                        PAIR_STREAM_BLOCKS, PAIR_STREAM_CHUNK_PAIRS)
+        if stream is not None:
+            a.stream_index, a.stream_cls_pair_ptr = _lib.ptr(stream.index), _lib.ptr(stream.cls_pair_ptr)
+            a.stream_cls_chunk_ptr, a.stream_chunk_first_seg = _lib.ptr(stream.cls_chunk_ptr), _lib.ptr(stream.chunk_first_seg)
+            a.stream_seg_slot, a.stream_row_slot_ptr = _lib.ptr(stream.seg_slot), _lib.ptr(stream.row_slot_ptr)
+            a.stream_q_lo, a.stream_q_hi, a.stream_chunk, a.stream_code = stream.q_lo, stream.q_hi, stream.chunk_pairs, stream.code
+            a.n_stream_seg, a.stream_max_chunks_per_class = stream.n_seg, stream.max_chunks_per_class
+        elif (CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
                 and s_total is not None and S.dtype == torch.float32 and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
             # the rows between the tiles and the hubs in segments of one column class each, a class per XCD
             rows = g.classed_row_plan(max(CLASSED_ROWS_MIN_PAIRS, SHORT_ROW_LMAX + 1))

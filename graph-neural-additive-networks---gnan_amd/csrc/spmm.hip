@@ -17,8 +17,8 @@
 //
 // This file: the forward's entry points and routing, the persistent narrow kernel, the hub rows' fix-up, the combine passes of the
 // classed rows and of the blocked hub segments, and the shell sums.
-// spmm_kernel itself is csrc/spmm_fwd_body.hpp (an object per VEC), the gradients are csrc/spmm_grad.hip, what they share is
-// csrc/spmm_common.hpp.
+// spmm_kernel itself is csrc/spmm_fwd_body.hpp (an object per VEC), the pair stream's two kernels are csrc/spmm_stream.hip, the
+// gradients are csrc/spmm_grad.hip, what they share is csrc/spmm_common.hpp.
 #include "spmm_common.hpp"
 
 namespace {
@@ -499,6 +499,7 @@ extern "C" size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a) {
   if (!a) return 0;
   size_t floats = hub_partial_offset(a);                               // the hub slices' partials, then the classed rows'
   if (a->hub_index && a->n_hub_seg > 0) floats += static_cast<size_t>(a->n_hub_seg);   // ... then the blocked hub segments'
+  if (a->stream_index && a->n_stream_seg > 0) floats += static_cast<size_t>(a->n_stream_seg);   // ... then the pair stream's
   return floats * sizeof(float);
 }
 
@@ -531,6 +532,7 @@ extern "C" int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_
   if (int rc = plan_tiles(p, r.vec, r.lpr, r.dense, r.smalld, a->seg_max_per_class, a->hub_seg_max_per_class)) return rc;
   out->n_seg_blocks = p.n_seg_blocks; out->n_segs = p.n_seg_blocks > 0 ? a->n_seg : 0;
   out->n_hub_seg_blocks = p.n_hub_blocks; out->n_hub_segs = p.n_hub_blocks > 0 ? a->n_hub_seg : 0;
+  out->n_stream_blocks = gnan::stream_blocks(a, r.lpr); out->n_stream_segs = out->n_stream_blocks > 0 ? a->n_stream_seg : 0;
   out->classed = p.cls_index != nullptr;
   out->n_slice_blocks = p.n_slice_blocks; out->n_tile_blocks = p.n_tile_blocks; out->n_tiles = p.n_tiles;
   out->row_q0 = p.row_q0;
@@ -551,10 +553,12 @@ extern "C" int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream) {
   if (int rc = pick_route(a, &r)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (r.hot) return a->W == 1 ? launch_hot<1>(p, st) : (a->W == 2 ? launch_hot<2>(p, st) : launch_hot<4>(p, st));
+  if (int rc0 = gnan::launch_stream(a, r.lpr, st)) return rc0;     // (the pair stream's phase comes first in time)
   const int rc = r.vec == 8 ? gnan::launch_lpr<8>(a, r.lpr, r.dense, r.smalld, st)
                             : (r.vec == 4 ? gnan::launch_lpr<4>(a, r.lpr, r.dense, r.smalld, st) : gnan::launch_lpr<1>(a, r.lpr, r.dense, r.smalld, st));
   if (rc) return rc;
   if (int rc2 = launch_fixup(p, st)) return rc2;
   if (int rc2 = launch_hub_combine(p, st)) return rc2;
-  return launch_seg_combine(p, st);
+  if (int rc2 = launch_seg_combine(p, st)) return rc2;
+  return gnan::launch_stream_combine(a, st);
 }

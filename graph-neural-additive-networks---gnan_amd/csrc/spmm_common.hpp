@@ -305,6 +305,12 @@ __device__ __forceinline__ void load_index_run(const int32_t* col, const uint8_t
   for (int r = 0; r < N; ++r) codev[r] = static_cast<int>((cw[r / 4] >> (8 * (r % 4))) & 0xffu);
 }
 
+// One step of a lane group's butterfly inside a DPP row of 16 lanes (seg_body, csrc/spmm_fwd_body.hpp; csrc/spmm_stream.hip)
+template <int CTRL>
+__device__ __forceinline__ float dpp_row(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
 // Short-row tiles (short_tile, csrc/spmm_fwd_body.hpp): rows of exactly L pairs that one lane group takes at a time
 __host__ __device__ constexpr int short_rows_per_group(int L) { return L == 0 ? 8 : (8 / L > 0 ? 8 / L : 1); }
 
@@ -423,6 +429,21 @@ inline int validate(const gnan_spmm_args* a) {
                  "spmm: incomplete blocked hub plan (segments, slots, a class table, the hub rows the last n_hub of n_rows behind the "
                  "tiled and the classed rows, long_threshold set)");
   }
+  if (a->stream_index) {
+    // (read by the stream's own kernels and, as the skipped range, by the self_sum instance of spmm_kernel)
+    if (!(a->self_sum && a->s_total && a->short_lmax > 0))
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: the pair stream is served on the self_sum route (short-row runs declared, s_total set) only");
+    GNAN_REQUIRE(a->stream_chunk > 0 && a->stream_chunk % 16 == 0, "spmm: the pair stream's chunk must be a positive multiple of 16 (got %d)",
+                 a->stream_chunk);
+    GNAN_REQUIRE(a->seg_index == nullptr, "spmm: a pair stream and a classed row plan cannot both take rows [%lld, %lld)",
+                 static_cast<long long>(a->stream_q_lo), static_cast<long long>(a->stream_q_hi));
+    GNAN_REQUIRE(a->stream_cls_pair_ptr && a->stream_cls_chunk_ptr && a->stream_chunk_first_seg && a->stream_seg_slot &&
+                 a->stream_row_slot_ptr && a->n_stream_seg > 0 && a->stream_max_chunks_per_class > 0 &&
+                 a->stream_q_lo >= a->short_row[a->short_lmax + 1] && a->stream_q_lo < a->stream_q_hi &&
+                 a->stream_q_hi <= (a->hub_index ? a->hub_q_lo : a->n_rows) && a->stream_code >= 0 && a->stream_code < 4 && a->D <= 4,
+                 "spmm: incomplete pair stream plan (class tables, chunk and slot tables, rows behind the tiled runs and before the hub "
+                 "rows, one hop code below 4)");
+  }
   if (a->n_long > 0) {
     GNAN_REQUIRE(a->rowptr != nullptr || (a->n_long == a->n_rows && a->long_threshold == 0),
                  "spmm: a row plan for the dense layout must slice every row (n_long == n_rows, long_threshold == 0)");
@@ -445,6 +466,12 @@ inline size_t seg_partial_offset(const gnan_spmm_args* a) {
 inline size_t hub_partial_offset(const gnan_spmm_args* a) {
   size_t floats = seg_partial_offset(a);
   if (a->seg_index && a->seg_q_hi > a->seg_q_lo) floats += static_cast<size_t>(a->seg_q_hi - a->seg_q_lo) * 8;
+  return floats;
+}
+// ... and the pair stream's [n_stream_seg] floats behind those
+inline size_t stream_partial_offset(const gnan_spmm_args* a) {
+  size_t floats = hub_partial_offset(a);
+  if (a->hub_index && a->n_hub_seg > 0) floats += static_cast<size_t>(a->n_hub_seg);
   return floats;
 }
 
@@ -485,6 +512,8 @@ inline Params make_params(const gnan_spmm_args* a) {
   if (a->seg_index) {   // (behind the hub slices' [n_slices, 2, W] partials: seg_partial_offset)
     p.seg_q_lo = a->seg_q_lo; p.seg_q_hi = a->seg_q_hi;
     p.seg_partial = static_cast<float*>(a->workspace) + seg_partial_offset(a);
+  } else if (a->stream_index) {   // (validate(): no classed row plan beside it) the pair stream's rows: skipped by the row blocks alike
+    p.seg_q_lo = a->stream_q_lo; p.seg_q_hi = a->stream_q_hi;
   }
   p.hub_index = a->hub_index; p.hub_seg_start = a->hub_seg_start; p.hub_seg_row = a->hub_seg_row; p.hub_seg_slot = a->hub_seg_slot;
   p.hub_row_slot_ptr = a->hub_row_slot_ptr; p.hub_cls_seg_ptr = a->hub_cls_seg_ptr;
@@ -589,6 +618,7 @@ inline int forward_only_self_sum(const gnan_spmm_args* a, const char* who) {
 inline int forward_only_index(const gnan_spmm_args* a, const char* who, bool reads_packed = false) {
   GNAN_REQUIRE(a->cls_index == nullptr, "%s: the classed hub plan is read by gnan_spmm_fwd only", who);
   GNAN_REQUIRE(a->hub_index == nullptr, "%s: blocked hub segments are read by gnan_spmm_fwd only", who);
+  GNAN_REQUIRE(a->stream_index == nullptr, "%s: the pair stream is read by gnan_spmm_fwd only", who);
   GNAN_REQUIRE(reads_packed || !a->packed_index, "%s: packed index entries are read by gnan_spmm_fwd only", who);
   return GNAN_OK;
 }
@@ -610,4 +640,9 @@ namespace gnan {
 // one object per VEC (csrc/spmm_fwd_v1.hip, _v4, _v8).  The caller launches the hub rows' fix-up behind it.
 template <int VEC>
 int launch_lpr(const gnan_spmm_args* a, int lpr, bool dense, bool smalld, hipStream_t st);
+// The pair stream (gnan_spmm_args.stream_*; csrc/spmm_stream.hip, an object of its own): the stream's kernel, launched ahead of
+// spmm_kernel, and its combine, launched behind it; both return at once without a stream.  stream_blocks: the former's workgroups.
+int stream_blocks(const gnan_spmm_args* a, int lpr);
+int launch_stream(const gnan_spmm_args* a, int lpr, hipStream_t st);
+int launch_stream_combine(const gnan_spmm_args* a, hipStream_t st);
 }  // namespace gnan

@@ -360,11 +360,7 @@ __device__ __forceinline__ void short_tiles(const Params& p, int t) {
 // seg_partial[(q - seg_q_lo) * 8 + c]; the combine pass (spmm_seg_combine_kernel, csrc/spmm.hip) adds a row's classes, the rest term
 // and the self term.  Weights as rows_body folds them under SMALLD; 16 index entries per round, four gathers in flight,
 // no branch around a gather: a slot past the segment's end reads the segment's last row again (an L1 hit) and is dropped by a select.
-// No LDS, no barrier, no atomics; the lane butterfly's first four steps are DPP row operations.
-template <int CTRL>
-__device__ __forceinline__ float dpp_row(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
+// No LDS, no barrier, no atomics; the lane butterfly's first four steps are DPP row operations (dpp_row, csrc/spmm_common.hpp).
 
 // HUB: the blocked hub segments (gnan_spmm_args.hub_*) — the same body over the hub plan's arrays; the float goes to the segment's slot
 // of the row-major enumeration, hub_partial[hub_seg_slot[s]] (spmm_hub_combine_kernel, csrc/spmm.hip, adds a row's slots).

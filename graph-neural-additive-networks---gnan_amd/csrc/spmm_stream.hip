@@ -1,0 +1,184 @@
+// The pair stream of the reference-order inference route (gnan_spmm_args.stream_*, HopGraph.pair_stream_plan): the rows between the tiles
+// and the hubs as one queue of pairs per column class, sorted by the columns' popularity block and cut into chunks.
+//
+// seg_body (csrc/spmm_fwd_body.hpp) pays per segment for a row id, two bounds, a weight row and an index round of its own, and a wave runs
+// as long as the longest of its segments: a segment per (row, class, block) of a row of 5 .. 512 pairs holds 1.4 .. 3.8 pairs, too few
+// to carry that.  Here a lane group owns a CHUNK of the queue instead — its start is arithmetic — and walks it 16 entries per round
+// whatever rows they belong to: no row id, no bounds, no weight is loaded (every pair of the stream carries one hop code, so the weight is
+// applied once per row, in the combine).  A segment is a maximal run of one row inside a chunk; the entry that ends one carries bit 31,
+// and there the group reduces its accumulators to ONE float and stores it at the segment's slot of the row-major enumeration.  The
+// gathers of a batch are issued whatever segment they belong to, so they stay in flight across segment ends.
+// Workgroup b takes class b & 7 (the XCD's L2 then holds one eighth of the hot operand rows) and its lane groups consecutive chunks, so
+// a class's queue runs in popularity-block order, most listed first.  A code object of its own: the aggregation's other kernels keep
+// their registers.  No LDS, no barrier, no atomics.
+#include "spmm_common.hpp"
+
+namespace {
+
+struct StreamParams {
+  const float* S;
+  int W;
+  int64_t s_stride;
+  const int32_t* index;
+  const int32_t* cls_pair_ptr;
+  const int32_t* cls_chunk_ptr;
+  const int32_t* chunk_first_seg;
+  const int32_t* seg_slot;
+  const int32_t* row_slot_ptr;
+  float* partial;     // [n_seg]
+  int64_t q_lo;
+  int n_rows;         // rows of the stream
+  int n_seg;
+  int chunk;
+  int code;
+};
+
+constexpr unsigned kStreamLast = 1u << 31;
+
+// the lane group's sum of r over its LPR lanes: seg_body's butterfly (four DPP row steps, ds_bpermute above 16 lanes)
+template <int LPR>
+__device__ __forceinline__ float group_sum(float r) {
+  r += dpp_row<0xB1>(r);    // quad_perm [1, 0, 3, 2]: lane ^ 1
+  r += dpp_row<0x4E>(r);    // quad_perm [2, 3, 0, 1]: lane ^ 2
+  r += dpp_row<0x141>(r);   // row_half_mirror: the other quad of the eight (its four lanes hold one value)
+  r += dpp_row<0x140>(r);   // row_mirror: the other half of the sixteen
+#pragma unroll
+  for (int off = 16; off < LPR; off <<= 1) r += __shfl_xor(r, off);
+  return r;
+}
+
+template <int LPR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
+void spmm_stream_kernel(const StreamParams p) {
+  static_assert(LPR >= 16, "a DPP row per lane group, one index entry per lane and round");
+  constexpr int VEC = 4;
+  constexpr int G = kWave / LPR;
+  constexpr int IW = 16;    // index entries per round
+  constexpr int FLY = 4;    // gathers in flight per lane
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int sub = lane % LPR;
+  const int slot = lane / LPR;
+  const int cls = static_cast<int>(blockIdx.x) & 7;
+  const int t0 = p.cls_chunk_ptr[cls];
+  const int g = ((static_cast<int>(blockIdx.x) >> 3) * 4 + wave) * G + slot;    // the group's chunk of this class's queue
+  if (g >= p.cls_chunk_ptr[cls + 1] - t0) return;   // (the whole group)
+  const int64_t lo = p.cls_pair_ptr[cls] + static_cast<int64_t>(g) * p.chunk;
+  const int64_t left = p.cls_pair_ptr[cls + 1] - lo;
+  const int n = static_cast<int>(left < p.chunk ? left : p.chunk);    // (the class's last chunk may be short)
+  const int32_t* idx = p.index + lo;
+  const int seg0 = p.chunk_first_seg[t0 + g];
+  const bool col_ok = sub * VEC < p.W;
+  const float* Sl = p.S + (col_ok ? sub * VEC : 0);   // (a lane past the columns reads column 0, dropped below)
+  Vec<VEC> acc;
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) acc.v[v] = 0.f;
+  int k = 0;                                           // segments of the chunk flushed so far
+  int next = 0;
+  if (sub < IW && sub < n) next = idx[sub];
+  for (int base = 0; base < n; base += IW) {
+    const int m = n - base < IW ? n - base : IW;
+    const int ent = next;
+    // a round ends at most IW segments: their slots, one per lane, as the index entries are fetched
+    int sl = 0;
+    if (sub < IW && seg0 + k + sub < p.n_seg) sl = p.seg_slot[seg0 + k + sub];
+    next = 0;
+    if (sub < IW && base + IW + sub < n) next = idx[base + IW + sub];
+    int kr = 0;                                        // ... of this round
+#pragma unroll
+    for (int j0 = 0; j0 < IW; j0 += FLY) {
+      if (j0 >= m) break;
+      Vec<VEC> sv[FLY];
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) {   // no branch around a gather: a slot past the end reads the chunk's last row again, dropped below
+        const int j = j0 + u < m ? j0 + u : m - 1;
+        const unsigned en = static_cast<unsigned>(__shfl(ent, j, LPR));
+        sv[u] = load_vec<VEC>(Sl + static_cast<int64_t>(en & kPackMask) * p.s_stride);
+      }
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) {
+        const bool ok = j0 + u < m;
+        const unsigned en = static_cast<unsigned>(__shfl(ent, ok ? j0 + u : m - 1, LPR));
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc.v[v] = ok ? acc.v[v] + sv[u].v[v] : acc.v[v];   // (a select: 0 * inf would be a NaN)
+        if (ok && (en & kStreamLast)) {   // (uniform over the lane group)
+          float r = (acc.v[0] + acc.v[1]) + (acc.v[2] + acc.v[3]);
+          r = col_ok ? r : 0.f;
+          r = group_sum<LPR>(r);
+          const int s = __shfl(sl, kr, LPR);
+          if (sub == 0) p.partial[s] = r;
+          ++kr;
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) acc.v[v] = 0.f;
+        }
+      }
+    }
+    k += kr;
+  }
+}
+
+// combine: one thread per stream row r — its slots in index order, the one weight, the rest and self terms as spmm_seg_combine_kernel
+// forms them:   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, (w_code - w_rest) * (((p_0 + p_1) + p_2) + ...)))
+// One fixed shape per row: bit-reproducible.
+__global__ __launch_bounds__(256) void spmm_stream_combine_kernel(const Params p, const StreamParams sp) {
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= sp.n_rows) return;
+  const int64_t q = sp.q_lo + r;
+  const int64_t o = out_row(p, q, q);
+  const int s0 = sp.row_slot_ptr[r], s1 = sp.row_slot_ptr[r + 1];
+  float y = 0.f;
+  for (int s = s0; s < s1; ++s) y += sp.partial[s];
+  double T = 0.0;
+  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
+  const int rest = p.D - 1;
+  const SmallW sw = small_weights(p, q);
+  const float w_rest = sw.pick(rest);
+  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
+  const float w = sp.code < rest ? sw.pick(sp.code) - w_rest : 0.f;
+  y = w * y;
+  y = fmaf(w_rest, static_cast<float>(T), y);
+  y = fmaf(w_self, self_term(p, o), y);
+  p.Y[o * p.y_stride] = y;
+}
+
+StreamParams stream_params(const gnan_spmm_args* a) {
+  StreamParams sp;
+  sp.S = static_cast<const float*>(a->S); sp.W = a->W; sp.s_stride = a->s_stride;
+  sp.index = a->stream_index; sp.cls_pair_ptr = a->stream_cls_pair_ptr; sp.cls_chunk_ptr = a->stream_cls_chunk_ptr;
+  sp.chunk_first_seg = a->stream_chunk_first_seg; sp.seg_slot = a->stream_seg_slot; sp.row_slot_ptr = a->stream_row_slot_ptr;
+  sp.partial = static_cast<float*>(a->workspace) + stream_partial_offset(a);
+  sp.q_lo = a->stream_q_lo; sp.n_rows = static_cast<int>(a->stream_q_hi - a->stream_q_lo);
+  sp.n_seg = a->n_stream_seg; sp.chunk = a->stream_chunk; sp.code = a->stream_code;
+  return sp;
+}
+
+}  // namespace
+
+// (validate(): the stream comes on the self_sum route, which pick_route() admits for 16 lanes or more only)
+int gnan::stream_blocks(const gnan_spmm_args* a, int lpr) {
+  if (a->stream_index == nullptr || lpr < 16) return 0;
+  const int64_t per = 4 * static_cast<int64_t>(kWave / lpr);     // chunks per workgroup
+  const int64_t nb = 8 * ((static_cast<int64_t>(a->stream_max_chunks_per_class) + per - 1) / per);
+  return nb > 0x3fffffffLL ? -1 : static_cast<int>(nb);
+}
+
+int gnan::launch_stream(const gnan_spmm_args* a, int lpr, hipStream_t st) {
+  if (a->stream_index == nullptr) return GNAN_OK;
+  const int nb = stream_blocks(a, lpr);
+  if (nb <= 0 || lpr * 4 < a->W || a->s_dtype != GNAN_F32)   // (one pass of the lane group over the columns, as the tiles)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: the pair stream needs fp32 rows read 16 B per lane by 16 lanes or more (W in (32, 256])");
+  const StreamParams sp = stream_params(a);
+  const dim3 grid(static_cast<unsigned>(nb)), block(256);
+  if (lpr == 16) hipLaunchKernelGGL(spmm_stream_kernel<16>, grid, block, 0, st, sp);
+  else if (lpr == 32) hipLaunchKernelGGL(spmm_stream_kernel<32>, grid, block, 0, st, sp);
+  else hipLaunchKernelGGL(spmm_stream_kernel<64>, grid, block, 0, st, sp);
+  return gnan::check_launch("spmm_stream_kernel");
+}
+
+int gnan::launch_stream_combine(const gnan_spmm_args* a, hipStream_t st) {
+  if (a->stream_index == nullptr) return GNAN_OK;
+  const Params p = make_params(a);
+  const StreamParams sp = stream_params(a);
+  hipLaunchKernelGGL(spmm_stream_combine_kernel, dim3(static_cast<unsigned>((sp.n_rows + 255) / 256)), dim3(256), 0, st, p, sp);
+  return gnan::check_launch("spmm_stream_combine_kernel");
+}

@@ -149,6 +149,42 @@ class BlockedHubPlan:
                                                            self.cls_seg_ptr))
 
 
+STREAM_LAST = 1 << 31             # PairStreamPlan.index: "last pair of its segment" (the packed entry's top bit; codes stay below 4)
+
+
+@dataclass
+class PairStreamPlan:
+    """:meth:`HopGraph.pair_stream_plan`: the pairs of rows ``[q_lo, q_hi)`` of a degree-sorted copy as one STREAM per column class
+    ``col & 7`` (``gnan_spmm_args.stream_*``).  ``index`` is class-major, within a class by popularity block, then by row, a row's
+    pairs in their own order; class ``c`` owns the pairs ``[cls_pair_ptr[c], cls_pair_ptr[c + 1])``, cut into chunks of ``chunk_pairs``
+    entries (the class's last chunk may be shorter): chunks ``[cls_chunk_ptr[c], cls_chunk_ptr[c + 1])``.  A SEGMENT is a maximal run of
+    one row inside one chunk; its last entry carries :data:`STREAM_LAST`.  ``chunk_first_seg[t]`` is the first segment of chunk ``t`` in
+    queue order; ``seg_slot[s]`` is segment ``s``'s place in the ROW-major enumeration (row, then queue order), and row ``q_lo + r`` owns
+    the slots ``[row_slot_ptr[r], row_slot_ptr[r + 1])``.  Every pair of the stream carries the hop code ``code``."""
+    q_lo: int
+    q_hi: int
+    min_pairs: int
+    block_rows: int
+    n_blocks: int                 # ranked blocks; block ``n_blocks`` is the cold remainder
+    chunk_pairs: int
+    code: int
+    n_seg: int
+    n_chunks: int
+    max_chunks_per_class: int     # chunks of the largest class (sizes the launch)
+    index: torch.Tensor           # int32 [pairs of the stream rows]
+    cls_pair_ptr: torch.Tensor    # int32 [9]
+    cls_chunk_ptr: torch.Tensor   # int32 [9]
+    chunk_first_seg: torch.Tensor  # int32 [n_chunks]
+    seg_slot: torch.Tensor        # int32 [n_seg]
+    row_slot_ptr: torch.Tensor    # int32 [q_hi - q_lo + 1]
+    block_pairs: list             # pairs per block, 0 .. n_blocks (for the record)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.index, self.cls_pair_ptr, self.cls_chunk_ptr, self.chunk_first_seg,
+                                                           self.seg_slot, self.row_slot_ptr))
+
+
 @dataclass
 class SelfFreePlan:
     """:meth:`HopGraph.self_free_plan`: the graph without its rows' self pairs, and which nodes its remaining pairs list."""
@@ -186,6 +222,7 @@ class HopGraph:
     _short_runs: dict = field(default_factory=dict, repr=False)     # short_row_runs(): lmax -> ShortRowRuns
     _classed_rows: dict = field(default_factory=dict, repr=False)   # classed_row_plan(): (min_pairs, max_pairs) -> plan or None
     _blocked_hubs: dict = field(default_factory=dict, repr=False)   # blocked_hub_plan(): its parameters -> plan or None
+    _pair_streams: dict = field(default_factory=dict, repr=False)   # pair_stream_plan(): its parameters -> plan or None
     _sorted_copy: Optional["HopGraph"] = field(default=None, repr=False)
     _hot: Optional[tuple] = field(default=None, repr=False)           # hot_columns(): (ids or None,)
     _sorted_copy_hot: Optional["HopGraph"] = field(default=None, repr=False)
@@ -631,6 +668,75 @@ class HopGraph:
         return BlockedHubPlan(q_lo, R, int(block_rows), int(n_blocks), int(cap), n_seg, int((cls_ptr[1:] - cls_ptr[:-1]).max()), index,
                               seg_start, (seg_r + q_lo).to(torch.int32), seg_slot.to(torch.int32), row_slot_ptr.to(torch.int32),
                               cls_ptr.to(torch.int32), block_pairs, torch.bincount(seg_cb % NB, minlength=NB).tolist())
+
+    def pair_stream_plan(self, min_pairs: int, block_rows: int, n_blocks: int, chunk_pairs: int,
+                         max_pairs: int = LONG_ROW_THRESHOLD) -> Optional[PairStreamPlan]:
+        """The pairs of the rows of ``min_pairs .. max_pairs`` listed pairs of a DEGREE-SORTED copy (one range ``[q_lo, q_hi)``) as a
+        stream per column class, ordered by popularity block of :meth:`column_blocks`, then by row, and cut into chunks of
+        ``chunk_pairs`` entries: :class:`PairStreamPlan`.  ``None`` where no row qualifies, the pairs of the range carry more than one
+        hop code (the stream applies one weight per row, in its combine), ``chunk_pairs`` is no positive multiple of 16, or the
+        packed entries cannot hold the graph.  Framework ops on the graph's device (a stable sort of the range's pairs); cached per
+        graph and parameter set."""
+        key = (int(min_pairs), int(block_rows), int(n_blocks), int(chunk_pairs), int(max_pairs))
+        if key in self._pair_streams:
+            return self._pair_streams[key]
+        plan = None
+        if (not self.is_dense and self.n_cols <= (1 << PACK_SHIFT) and self.n_codes <= 4 and self.n_rows > 0 and self.nnz < 2 ** 31
+                and min(key[:4]) >= 1 and key[3] % 16 == 0):
+            plan = self._pair_stream_plan_torch(*key)
+        self._pair_streams[key] = plan
+        return plan
+
+    def _pair_stream_plan_torch(self, min_pairs: int, block_rows: int, n_blocks: int, chunk: int, max_pairs: int) -> Optional[PairStreamPlan]:
+        dev, K, NB = self.device, HUB_CLASSES, n_blocks + 1
+        rp = self.rowptr.long()
+        deg = rp[1:] - rp[:-1]
+        if bool((deg[1:] < deg[:-1]).any()):
+            raise ValueError("pair_stream_plan needs a degree-sorted copy (rows shortest first)")
+        q_lo, q_hi = (int(v) for v in torch.searchsorted(deg, torch.tensor([min_pairs, max_pairs + 1], device=dev)).tolist())
+        R = q_hi - q_lo
+        if R <= 0:
+            return None
+        e0, e1 = int(rp[q_lo]), int(rp[q_hi])
+        codes = self.code[e0:e1]
+        code = int(codes[0])
+        if bool((codes != code).any()):
+            return None
+        c = self.col[e0:e1].long()
+        blk = self.column_blocks(block_rows, n_blocks)[c]
+        row = torch.repeat_interleave(torch.arange(R, device=dev), deg[q_lo:q_hi])
+        key = ((c & (K - 1)) * NB + blk) * R + row                         # class, block, row; the sort keeps a row's pair order
+        block_pairs = torch.bincount(blk, minlength=NB).tolist()
+        order = torch.argsort(key, stable=True)
+        key, v = key[order], (c | (code << PACK_SHIFT))[order]
+        del c, blk, row, order
+        P = int(key.numel())
+        cls, row = key // (NB * R), key % R
+        cls_pair_ptr = torch.searchsorted(key, torch.arange(K + 1, device=dev) * (NB * R))
+        n_chunk_cls = (cls_pair_ptr[1:] - cls_pair_ptr[:-1] + chunk - 1) // chunk
+        cls_chunk_ptr = torch.cat([n_chunk_cls.new_zeros(1), torch.cumsum(n_chunk_cls, 0)])
+        pos = torch.arange(P, device=dev) - cls_pair_ptr[cls]               # place in its class's queue
+        first = pos % chunk == 0                                            # (a class starts a chunk)
+        first[1:] |= row[1:] != row[:-1]
+        last = torch.ones(P, dtype=torch.bool, device=dev)
+        last[:-1] = first[1:]
+        seg_of_pair = torch.cumsum(first, 0) - 1
+        n_seg = int(seg_of_pair[-1]) + 1
+        n_chunks = int(cls_chunk_ptr[-1])
+        t_cls = torch.repeat_interleave(torch.arange(K, device=dev), n_chunk_cls)
+        chunk_pair = cls_pair_ptr[t_cls] + (torch.arange(n_chunks, device=dev) - cls_chunk_ptr[t_cls]) * chunk
+        chunk_first_seg = seg_of_pair[chunk_pair]
+        seg_row = row[first]
+        by_row = torch.argsort(seg_row, stable=True)                       # the row-major enumeration: a row's segments in queue order
+        seg_slot = torch.empty(n_seg, dtype=torch.int64, device=dev)
+        seg_slot[by_row] = torch.arange(n_seg, device=dev)
+        row_slot_ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        row_slot_ptr[1:] = torch.cumsum(torch.bincount(seg_row, minlength=R), 0)
+        v = v | (last.long() << 31)
+        index = torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32).contiguous()
+        return PairStreamPlan(q_lo, q_hi, int(min_pairs), int(block_rows), int(n_blocks), int(chunk), code, n_seg, n_chunks,
+                              int(n_chunk_cls.max()), index, cls_pair_ptr.to(torch.int32), cls_chunk_ptr.to(torch.int32),
+                              chunk_first_seg.to(torch.int32), seg_slot.to(torch.int32), row_slot_ptr.to(torch.int32), block_pairs)
 
     def narrow_row_plan(self) -> LongRowPlan:
         """Hub-row plan for operand rows of one or two lanes: the low threshold while only a FEW rows exceed it (the tail

@@ -675,6 +675,31 @@ typedef struct gnan_spmm_args {
   int32_t n_hub;                     /* n_rows - hub_q_lo */
   int32_t n_hub_seg;
   int32_t hub_seg_max_per_class;
+  /* pair stream (the struct grew at its end once more; gnan_spmm_fwd only, optional, on the self_sum route alone and instead of the
+   * classed row segments: seg_index must be NULL; GNAN_ERR_UNSUPPORTED anywhere else).  Rows [stream_q_lo, stream_q_hi) of the
+   * degree-sorted copy (behind the tiled rows, before the hub rows) are not walked as rows.  Their pairs, which all carry the hop code
+   * stream_code, are listed per column class c = column & 7 — pairs [stream_cls_pair_ptr[c], stream_cls_pair_ptr[c + 1]) of
+   * stream_index (DEVICE arrays of 9) — sorted by popularity block, then by row, a row's pairs in their own order, and a class's queue
+   * is cut into CHUNKS of stream_chunk entries (a multiple of 16; the class's last chunk may be shorter): chunks
+   * [stream_cls_chunk_ptr[c], stream_cls_chunk_ptr[c + 1]).  A SEGMENT is a maximal run of one row inside one chunk; bit 31 of an
+   * entry (column | hop code << 29 below it) marks the last pair of its segment.  A kernel of its own, launched ahead of spmm_kernel,
+   * gives every chunk to one lane group — workgroup b takes class b & 7, its lane groups consecutive chunks — which adds the operand
+   * rows of a segment unweighted and stores ONE float per segment at partial[stream_seg_slot[stream_chunk_first_seg[t] + k]] (chunk t,
+   * its k-th segment) behind the blocked hub segments' partials in `workspace`.  stream_seg_slot is the segment's place in a ROW-major
+   * enumeration: row stream_q_lo + r owns partial[stream_row_slot_ptr[r] .. stream_row_slot_ptr[r + 1]).  A combine pass (a thread per
+   * row) adds a row's partials in index order, multiplies by wt(i, stream_code) - wt(i, D-1), then adds the rest and self terms as
+   * the classed rows' combine does.  s_total must be set.  No atomics.  NULL stream_index (the default): off */
+  const int32_t* stream_index;
+  const int32_t* stream_cls_pair_ptr;    /* [9] */
+  const int32_t* stream_cls_chunk_ptr;   /* [9] */
+  const int32_t* stream_chunk_first_seg; /* [chunks] */
+  const int32_t* stream_seg_slot;        /* [n_stream_seg] a permutation */
+  const int32_t* stream_row_slot_ptr;    /* [stream_q_hi - stream_q_lo + 1] */
+  int64_t stream_q_lo, stream_q_hi;
+  int32_t stream_chunk;
+  int32_t stream_code;
+  int32_t n_stream_seg;
+  int32_t stream_max_chunks_per_class;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
@@ -703,6 +728,8 @@ typedef struct gnan_spmm_launch_info {
   int32_t n_segs;                /* classed row segments */
   int32_t n_hub_seg_blocks;      /* workgroups of blocked hub segments (a multiple of 8, the launch's first); then n_slice_blocks == 0 */
   int32_t n_hub_segs;            /* blocked hub segments */
+  int32_t n_stream_blocks;       /* workgroups of the pair stream's own launch (a multiple of 8); 0: no pair stream */
+  int32_t n_stream_segs;         /* pair stream segments */
 } gnan_spmm_launch_info;
 
 int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_info* out);
