@@ -181,6 +181,7 @@ class SpmmArgs(C.Structure):
         ("stream_chunk_first_seg", C.c_void_p), ("stream_seg_slot", C.c_void_p), ("stream_row_slot_ptr", C.c_void_p),
         ("stream_q_lo", C.c_int64), ("stream_q_hi", C.c_int64), ("stream_chunk", C.c_int32), ("stream_code", C.c_int32),
         ("n_stream_seg", C.c_int32), ("stream_max_chunks_per_class", C.c_int32),
+        ("stream_row_seg", C.c_void_p),         # every row's segments in queue order: partial[s] is segment s's float (stream_seg_slot: not read)
     ]
 
 

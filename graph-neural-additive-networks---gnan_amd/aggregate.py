@@ -258,7 +258,7 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         if stream is not None:
             a.stream_index, a.stream_cls_pair_ptr = _lib.ptr(stream.index), _lib.ptr(stream.cls_pair_ptr)
             a.stream_cls_chunk_ptr, a.stream_chunk_first_seg = _lib.ptr(stream.cls_chunk_ptr), _lib.ptr(stream.chunk_first_seg)
-            a.stream_seg_slot, a.stream_row_slot_ptr = _lib.ptr(stream.seg_slot), _lib.ptr(stream.row_slot_ptr)
+            a.stream_row_seg, a.stream_row_slot_ptr = _lib.ptr(stream.row_seg), _lib.ptr(stream.row_slot_ptr)
             a.stream_q_lo, a.stream_q_hi, a.stream_chunk, a.stream_code = stream.q_lo, stream.q_hi, stream.chunk_pairs, stream.code
             a.n_stream_seg, a.stream_max_chunks_per_class = stream.n_seg, stream.max_chunks_per_class
         elif (CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1

@@ -437,7 +437,7 @@ inline int validate(const gnan_spmm_args* a) {
                  a->stream_chunk);
     GNAN_REQUIRE(a->seg_index == nullptr, "spmm: a pair stream and a classed row plan cannot both take rows [%lld, %lld)",
                  static_cast<long long>(a->stream_q_lo), static_cast<long long>(a->stream_q_hi));
-    GNAN_REQUIRE(a->stream_cls_pair_ptr && a->stream_cls_chunk_ptr && a->stream_chunk_first_seg && a->stream_seg_slot &&
+    GNAN_REQUIRE(a->stream_cls_pair_ptr && a->stream_cls_chunk_ptr && a->stream_chunk_first_seg && a->stream_row_seg &&
                  a->stream_row_slot_ptr && a->n_stream_seg > 0 && a->stream_max_chunks_per_class > 0 &&
                  a->stream_q_lo >= a->short_row[a->short_lmax + 1] && a->stream_q_lo < a->stream_q_hi &&
                  a->stream_q_hi <= (a->hub_index ? a->hub_q_lo : a->n_rows) && a->stream_code >= 0 && a->stream_code < 4 && a->D <= 4,

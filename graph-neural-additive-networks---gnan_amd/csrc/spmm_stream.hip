@@ -6,8 +6,11 @@
 // to carry that.  Here a lane group owns a CHUNK of the queue instead — its start is arithmetic — and walks it 16 entries per round
 // whatever rows they belong to: no row id, no bounds, no weight is loaded (every pair of the stream carries one hop code, so the weight is
 // applied once per row, in the combine).  A segment is a maximal run of one row inside a chunk; the entry that ends one carries bit 31,
-// and there the group reduces its accumulators to ONE float and stores it at the segment's slot of the row-major enumeration.  The
-// gathers of a batch are issued whatever segment they belong to, so they stay in flight across segment ends.
+// and there the group reduces its accumulators to ONE float.  The floats lie in QUEUE order — segment s of the plan's enumeration at
+// partial[s], chunk t's k-th at partial[chunk_first_seg[t] + k] — so a class's partials form one region that its XCD writes nearly
+// sequentially: lane kr of the group keeps the round's kr-th float and the round ends with one store of all of them.  The combine finds
+// a row's floats through row_seg (the row's segments, in queue order).  The gathers of a batch are issued whatever segment they belong
+// to, so they stay in flight across segment ends.
 // Workgroup b takes class b & 7 (the XCD's L2 then holds one eighth of the hot operand rows) and its lane groups consecutive chunks, so
 // a class's queue runs in popularity-block order, most listed first.  A code object of its own: the aggregation's other kernels keep
 // their registers.  No LDS, no barrier, no atomics.
@@ -23,9 +26,9 @@ struct StreamParams {
   const int32_t* cls_pair_ptr;
   const int32_t* cls_chunk_ptr;
   const int32_t* chunk_first_seg;
-  const int32_t* seg_slot;
-  const int32_t* row_slot_ptr;
-  float* partial;     // [n_seg]
+  const int32_t* row_seg;        // [n_seg] a row's segments (queue-order numbers), rows in turn
+  const int32_t* row_slot_ptr;   // [n_rows + 1] into row_seg
+  float* partial;     // [n_seg] in queue order
   int64_t q_lo;
   int n_rows;         // rows of the stream
   int n_seg;
@@ -79,12 +82,10 @@ void spmm_stream_kernel(const StreamParams p) {
   for (int base = 0; base < n; base += IW) {
     const int m = n - base < IW ? n - base : IW;
     const int ent = next;
-    // a round ends at most IW segments: their slots, one per lane, as the index entries are fetched
-    int sl = 0;
-    if (sub < IW && seg0 + k + sub < p.n_seg) sl = p.seg_slot[seg0 + k + sub];
     next = 0;
     if (sub < IW && base + IW + sub < n) next = idx[base + IW + sub];
     int kr = 0;                                        // ... of this round
+    float keep = 0.f;                                  // lane kr: the float of the round's kr-th finished segment
 #pragma unroll
     for (int j0 = 0; j0 < IW; j0 += FLY) {
       if (j0 >= m) break;
@@ -105,19 +106,21 @@ void spmm_stream_kernel(const StreamParams p) {
           float r = (acc.v[0] + acc.v[1]) + (acc.v[2] + acc.v[3]);
           r = col_ok ? r : 0.f;
           r = group_sum<LPR>(r);
-          const int s = __shfl(sl, kr, LPR);
-          if (sub == 0) p.partial[s] = r;
+          keep = sub == kr ? r : keep;                 // (group_sum leaves the sum in every lane)
           ++kr;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) acc.v[v] = 0.f;
         }
       }
     }
+    // a round ends at most IW segments: one store of their floats, consecutive in queue order
+    if (sub < kr && seg0 + k + sub < p.n_seg) p.partial[seg0 + k + sub] = keep;
     k += kr;
   }
 }
 
-// combine: one thread per stream row r — its slots in index order, the one weight, the rest and self terms as spmm_seg_combine_kernel
+// combine: one thread per stream row r — the floats of its segments row_seg[row_slot_ptr[r] .. row_slot_ptr[r + 1]) in that order (the
+// queue's: the chain the row-major slots gave), the one weight, the rest and self terms as spmm_seg_combine_kernel
 // forms them:   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, (w_code - w_rest) * (((p_0 + p_1) + p_2) + ...)))
 // One fixed shape per row: bit-reproducible.
 __global__ __launch_bounds__(256) void spmm_stream_combine_kernel(const Params p, const StreamParams sp) {
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void spmm_stream_combine_kernel(const Params p
   const int64_t o = out_row(p, q, q);
   const int s0 = sp.row_slot_ptr[r], s1 = sp.row_slot_ptr[r + 1];
   float y = 0.f;
-  for (int s = s0; s < s1; ++s) y += sp.partial[s];
+  for (int s = s0; s < s1; ++s) y += sp.partial[sp.row_seg[s]];
   double T = 0.0;
   for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
   const int rest = p.D - 1;
@@ -145,7 +148,7 @@ StreamParams stream_params(const gnan_spmm_args* a) {
   StreamParams sp;
   sp.S = static_cast<const float*>(a->S); sp.W = a->W; sp.s_stride = a->s_stride;
   sp.index = a->stream_index; sp.cls_pair_ptr = a->stream_cls_pair_ptr; sp.cls_chunk_ptr = a->stream_cls_chunk_ptr;
-  sp.chunk_first_seg = a->stream_chunk_first_seg; sp.seg_slot = a->stream_seg_slot; sp.row_slot_ptr = a->stream_row_slot_ptr;
+  sp.chunk_first_seg = a->stream_chunk_first_seg; sp.row_seg = a->stream_row_seg; sp.row_slot_ptr = a->stream_row_slot_ptr;
   sp.partial = static_cast<float*>(a->workspace) + stream_partial_offset(a);
   sp.q_lo = a->stream_q_lo; sp.n_rows = static_cast<int>(a->stream_q_hi - a->stream_q_lo);
   sp.n_seg = a->n_stream_seg; sp.chunk = a->stream_chunk; sp.code = a->stream_code;

@@ -159,8 +159,10 @@ class PairStreamPlan:
     pairs in their own order; class ``c`` owns the pairs ``[cls_pair_ptr[c], cls_pair_ptr[c + 1])``, cut into chunks of ``chunk_pairs``
     entries (the class's last chunk may be shorter): chunks ``[cls_chunk_ptr[c], cls_chunk_ptr[c + 1])``.  A SEGMENT is a maximal run of
     one row inside one chunk; its last entry carries :data:`STREAM_LAST`.  ``chunk_first_seg[t]`` is the first segment of chunk ``t`` in
-    queue order; ``seg_slot[s]`` is segment ``s``'s place in the ROW-major enumeration (row, then queue order), and row ``q_lo + r`` owns
-    the slots ``[row_slot_ptr[r], row_slot_ptr[r + 1])``.  Every pair of the stream carries the hop code ``code``."""
+    queue order, the enumeration the kernel stores its partials in (segment ``s`` at ``partial[s]``).  ``row_seg[row_slot_ptr[r] ..
+    row_slot_ptr[r + 1])`` are the queue-order numbers of row ``q_lo + r``'s segments, ascending: what the combine reads.  ``seg_slot``
+    (computed on demand, not held) is the inverse permutation, segment ``s``'s place in the ROW-major enumeration (row, then queue
+    order).  Every pair of the stream carries the hop code ``code``."""
     q_lo: int
     q_hi: int
     min_pairs: int
@@ -175,14 +177,21 @@ class PairStreamPlan:
     cls_pair_ptr: torch.Tensor    # int32 [9]
     cls_chunk_ptr: torch.Tensor   # int32 [9]
     chunk_first_seg: torch.Tensor  # int32 [n_chunks]
-    seg_slot: torch.Tensor        # int32 [n_seg]
+    row_seg: torch.Tensor         # int32 [n_seg] a permutation
     row_slot_ptr: torch.Tensor    # int32 [q_hi - q_lo + 1]
     block_pairs: list             # pairs per block, 0 .. n_blocks (for the record)
 
     @property
+    def seg_slot(self) -> torch.Tensor:
+        """int32 [n_seg]: the inverse of ``row_seg`` (the library does not read it; built per call)."""
+        slot = torch.empty_like(self.row_seg)
+        slot[self.row_seg.long()] = torch.arange(self.n_seg, dtype=torch.int32, device=self.row_seg.device)
+        return slot
+
+    @property
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in (self.index, self.cls_pair_ptr, self.cls_chunk_ptr, self.chunk_first_seg,
-                                                           self.seg_slot, self.row_slot_ptr))
+                                                           self.row_seg, self.row_slot_ptr))
 
 
 @dataclass
@@ -727,16 +736,14 @@ class HopGraph:
         chunk_pair = cls_pair_ptr[t_cls] + (torch.arange(n_chunks, device=dev) - cls_chunk_ptr[t_cls]) * chunk
         chunk_first_seg = seg_of_pair[chunk_pair]
         seg_row = row[first]
-        by_row = torch.argsort(seg_row, stable=True)                       # the row-major enumeration: a row's segments in queue order
-        seg_slot = torch.empty(n_seg, dtype=torch.int64, device=dev)
-        seg_slot[by_row] = torch.arange(n_seg, device=dev)
+        row_seg = torch.argsort(seg_row, stable=True)                      # row by row, a row's segments in queue order
         row_slot_ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
         row_slot_ptr[1:] = torch.cumsum(torch.bincount(seg_row, minlength=R), 0)
         v = v | (last.long() << 31)
         index = torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32).contiguous()
         return PairStreamPlan(q_lo, q_hi, int(min_pairs), int(block_rows), int(n_blocks), int(chunk), code, n_seg, n_chunks,
                               int(n_chunk_cls.max()), index, cls_pair_ptr.to(torch.int32), cls_chunk_ptr.to(torch.int32),
-                              chunk_first_seg.to(torch.int32), seg_slot.to(torch.int32), row_slot_ptr.to(torch.int32), block_pairs)
+                              chunk_first_seg.to(torch.int32), row_seg.to(torch.int32), row_slot_ptr.to(torch.int32), block_pairs)
 
     def narrow_row_plan(self) -> LongRowPlan:
         """Hub-row plan for operand rows of one or two lanes: the low threshold while only a FEW rows exceed it (the tail

@@ -684,22 +684,27 @@ typedef struct gnan_spmm_args {
    * [stream_cls_chunk_ptr[c], stream_cls_chunk_ptr[c + 1]).  A SEGMENT is a maximal run of one row inside one chunk; bit 31 of an
    * entry (column | hop code << 29 below it) marks the last pair of its segment.  A kernel of its own, launched ahead of spmm_kernel,
    * gives every chunk to one lane group — workgroup b takes class b & 7, its lane groups consecutive chunks — which adds the operand
-   * rows of a segment unweighted and stores ONE float per segment at partial[stream_seg_slot[stream_chunk_first_seg[t] + k]] (chunk t,
-   * its k-th segment) behind the blocked hub segments' partials in `workspace`.  stream_seg_slot is the segment's place in a ROW-major
-   * enumeration: row stream_q_lo + r owns partial[stream_row_slot_ptr[r] .. stream_row_slot_ptr[r + 1]).  A combine pass (a thread per
-   * row) adds a row's partials in index order, multiplies by wt(i, stream_code) - wt(i, D-1), then adds the rest and self terms as
-   * the classed rows' combine does.  s_total must be set.  No atomics.  NULL stream_index (the default): off */
+   * rows of a segment unweighted and stores ONE float per segment in QUEUE order, at partial[stream_chunk_first_seg[t] + k] (chunk t,
+   * its k-th segment; the enumeration is class-major, inside a class by block, then by row) behind the blocked hub segments' partials
+   * in `workspace`: a class's floats form one region, written nearly sequentially by the workgroups of that class.  Row
+   * stream_q_lo + r owns the segments stream_row_seg[stream_row_slot_ptr[r] .. stream_row_slot_ptr[r + 1]), listed in queue order
+   * (stream_row_seg, at the struct's end, is a permutation of 0 .. n_stream_seg - 1).  A combine pass (a thread per row) adds
+   * partial[stream_row_seg[s]] for s in index order, multiplies by wt(i, stream_code) - wt(i, D-1), then adds the rest and self
+   * terms as the classed rows' combine does.  stream_seg_slot — the inverse permutation, a segment's place in the row-major
+   * enumeration — is no longer read and may be NULL.  s_total must be set.  No atomics.  NULL stream_index (the default): off */
   const int32_t* stream_index;
   const int32_t* stream_cls_pair_ptr;    /* [9] */
   const int32_t* stream_cls_chunk_ptr;   /* [9] */
   const int32_t* stream_chunk_first_seg; /* [chunks] */
-  const int32_t* stream_seg_slot;        /* [n_stream_seg] a permutation */
+  const int32_t* stream_seg_slot;        /* not read (the partials lay in row-major slots once) */
   const int32_t* stream_row_slot_ptr;    /* [stream_q_hi - stream_q_lo + 1] */
   int64_t stream_q_lo, stream_q_hi;
   int32_t stream_chunk;
   int32_t stream_code;
   int32_t n_stream_seg;
   int32_t stream_max_chunks_per_class;
+  /* (the struct grew at its end) */
+  const int32_t* stream_row_seg;         /* [n_stream_seg] a permutation: every row's segments, in queue order */
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
