@@ -385,6 +385,12 @@ class MidGraphInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class SmallDropout(C.Structure):
+    """Training-mode Dropout of the shape functions on the one-launch routes (``gnan_small_dropout``): ``p`` in [0, 1), the
+    64-bit seed of the hash masks (csrc/dropout.hpp)."""
+    _fields_ = [("p", C.c_float), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
 class SmallGraphNamArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x_stride", C.c_int64), ("n", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
@@ -528,6 +534,10 @@ SYMBOLS = {
     "gnan_mid_graph_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MidGraphInfo)]),
     "gnan_mid_graph_fwd": (C.c_int, [C.POINTER(MidGraphArgs), C.c_void_p]),
     "gnan_mid_graph_bwd": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.c_void_p]),
+    "gnan_small_graph_fwd_drop": (C.c_int, [C.POINTER(SmallGraphArgs), C.POINTER(SmallDropout), C.c_void_p]),
+    "gnan_small_graph_bwd_drop": (C.c_int, [C.POINTER(SmallGraphBwdArgs), C.POINTER(SmallDropout), C.c_void_p]),
+    "gnan_mid_graph_fwd_drop": (C.c_int, [C.POINTER(MidGraphArgs), C.POINTER(SmallDropout), C.c_void_p]),
+    "gnan_mid_graph_bwd_drop": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.POINTER(SmallDropout), C.c_void_p]),
     "gnan_small_graph_nam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gnan_small_graph_nam_fwd": (C.c_int, [C.POINTER(SmallGraphNamArgs), C.c_void_p]),
     "gnan_small_graph_nam_bwd": (C.c_int, [C.POINTER(SmallGraphNamBwdArgs), C.c_void_p]),

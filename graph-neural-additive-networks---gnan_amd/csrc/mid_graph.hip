@@ -132,7 +132,16 @@ struct MidParams {
   unsigned* counter;    // zero before the first launch; the last workgroup zeroes it again
 };
 
-__global__ __launch_bounds__(kThreads) void mid_graph_kernel(const MidParams p) {
+// ... and under training-mode Dropout of the shape functions (gnan_mid_graph_fwd_drop with p > 0)
+struct MidDropParams : MidParams {
+  gnan_bwd::Drop drop;
+};
+
+// P = MidParams: the Dropout-free instance, the code it was.  P = MidDropParams: a kernel of its own whose shape-function
+// workgroups mask their hidden activations (mlp_block<true>; node = the row of x, feature = k).
+template <class P>
+__global__ __launch_bounds__(kThreads) void mid_graph_kernel(const P p) {
+  constexpr bool DROP = std::is_same<P, MidDropParams>::value;
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   __shared__ __attribute__((aligned(16))) float weights[kWeightFloats];
   __shared__ unsigned s_last;
@@ -158,7 +167,8 @@ __global__ __launch_bounds__(kThreads) void mid_graph_kernel(const MidParams p) 
     for (int b = 0; b < kMidBlocks; ++b) {
       const int j = b * kWave + lane;
       if (b < blocks) {                               // (uniform)
-        mlp_block(p.f, wl, xv[b], col_a, col_b, lane, wave, out);
+        if constexpr (DROP) mlp_block<true>(p.f, wl, xv[b], col_a, col_b, lane, wave, out, p.drop, gnan::drop_base(p.drop.seed, j, k));
+        else mlp_block(p.f, wl, xv[b], col_a, col_b, lane, wave, out);
         if (wave == 0 && j < n)
           for (int c = 0; c < C; ++c) p.part[(static_cast<int64_t>(k) * n + j) * C + c] = out[c];
       }
@@ -246,9 +256,9 @@ struct MidBwdParams {
   unsigned* counter;         // arrivals of the rho groups
 };
 
+// fdrop: the forward's Dropout of the shape functions (thresh 0: none) — the feature workgroups recompute its masks; rho has none.
 template <int C>
-__global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdParams p) {
-  extern __shared__ __attribute__((aligned(16))) float dyn[];
+__device__ __forceinline__ void mid_graph_bwd_body(const MidBwdParams& p, float* dyn, gnan_bwd::Drop fdrop) {
   __shared__ gnan_bwd::RedBuffer red;
   __shared__ double s_part[kWaves][kWave];
   __shared__ float s_lut[kWave];
@@ -294,8 +304,8 @@ __global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdPar
     __syncthreads();
     auto x_of = [&](int64_t node) { return p.x[node * p.x_stride + k]; };
     auto g_of = [&](int64_t node, int c) { return s_g[node * C + c]; };
-    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, 0, n, 0, nodrop, x_of, g_of, red);
-    else gnan_bwd::feature_grads<C, false>(p.f, k, 0, n, 0, nodrop, x_of, g_of, red);
+    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, 0, n, 0, fdrop, x_of, g_of, red);
+    else gnan_bwd::feature_grads<C, false>(p.f, k, 0, n, 0, fdrop, x_of, g_of, red);
     return;
   }
   // ---- table gradient of this group's rows -------------------------------------------------------------------------------------
@@ -371,9 +381,28 @@ __global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdPar
 }
 
 template <int C>
-int launch_mid_bwd(const MidBwdParams& p, hipStream_t st) {
+__global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdParams p) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  mid_graph_bwd_body<C>(p, dyn, gnan_bwd::Drop{0u, 1.f, 0ull});
+}
+
+// ... of a forward under Dropout (gnan_mid_graph_bwd_drop with p > 0)
+template <int C>
+__global__ __launch_bounds__(kThreads) void mid_graph_bwd_drop_kernel(const MidBwdParams p, const gnan_bwd::Drop drop) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  mid_graph_bwd_body<C>(p, dyn, drop);
+}
+
+template <int C>
+int launch_mid_bwd(const MidBwdParams& p, const gnan_bwd::Drop& drop, hipStream_t st) {
+  const dim3 grid(static_cast<unsigned>(p.F + p.rho_groups));
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
+    if (int rc = raise_dyn_lds<&mid_graph_bwd_drop_kernel<C>>(kBwdDynBytes, "mid_graph_bwd")) return rc;
+    hipLaunchKernelGGL((mid_graph_bwd_drop_kernel<C>), grid, dim3(kThreads), kBwdDynBytes, st, p, drop);
+    return gnan::check_launch("mid_graph_bwd_drop_kernel");
+  }
   if (int rc = raise_dyn_lds<&mid_graph_bwd_kernel<C>>(kBwdDynBytes, "mid_graph_bwd")) return rc;
-  hipLaunchKernelGGL((mid_graph_bwd_kernel<C>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(kThreads), kBwdDynBytes, st, p);
+  hipLaunchKernelGGL((mid_graph_bwd_kernel<C>), grid, dim3(kThreads), kBwdDynBytes, st, p);
   return gnan::check_launch("mid_graph_bwd_kernel");
 }
 
@@ -406,8 +435,9 @@ extern "C" int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t 
   return GNAN_OK;
 }
 
-extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream) {
-  GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
+namespace {
+// THE launcher of gnan_mid_graph_fwd (drop.thresh == 0) and gnan_mid_graph_fwd_drop
+int mid_fwd(const gnan_mid_graph_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
   if (int rc = shape_ok("mid_graph", kMidCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x != nullptr, "mid_graph: null x");
   GNAN_REQUIRE(a->code != nullptr, "mid_graph: null code");
@@ -417,18 +447,39 @@ extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t st
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "mid_graph: null weights");
   if (int rc = strides_ok("mid_graph", a)) return rc;
   if (int rc = workspace_ok("mid_graph", a, gnan_mid_graph_workspace_bytes(a->n, a->F, a->f.C))) return rc;
-  MidParams p;
+  MidDropParams p;
   fwd_fields(p, a, a->n);
   p.S = a->S; p.lut = a->lut; p.Y = a->Y; p.Ysum = a->Ysum;
   split_workspace(a->workspace, p.counter, p.part);
-  if (int rc = raise_dyn_lds<&mid_graph_kernel>(kFwdDynBytes, "mid_graph")) return rc;
-  hipLaunchKernelGGL(mid_graph_kernel, dim3(static_cast<unsigned>(a->F) + 1u), dim3(kThreads), kFwdDynBytes,
-                     static_cast<hipStream_t>(stream), p);
+  const dim3 grid(static_cast<unsigned>(a->F) + 1u);
+  if (drop.thresh != 0u) {                             // (the Dropout instance: a kernel of its own, the other untouched)
+    p.drop = drop;
+    if (int rc = raise_dyn_lds<&mid_graph_kernel<MidDropParams>>(kFwdDynBytes, "mid_graph")) return rc;
+    hipLaunchKernelGGL(mid_graph_kernel<MidDropParams>, grid, dim3(kThreads), kFwdDynBytes, static_cast<hipStream_t>(stream), p);
+    return gnan::check_launch("mid_graph_kernel (Dropout)");
+  }
+  if (int rc = raise_dyn_lds<&mid_graph_kernel<MidParams>>(kFwdDynBytes, "mid_graph")) return rc;
+  hipLaunchKernelGGL(mid_graph_kernel<MidParams>, grid, dim3(kThreads), kFwdDynBytes, static_cast<hipStream_t>(stream),
+                     static_cast<const MidParams&>(p));
   return gnan::check_launch("mid_graph_kernel");
 }
+}  // namespace
 
-extern "C" int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream) {
-  GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
+extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
+  return mid_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+}
+
+extern "C" int gnan_mid_graph_fwd_drop(const gnan_mid_graph_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
+  gnan_bwd::Drop drop;
+  if (int rc = drop_ok("mid_graph", d, &drop)) return rc;
+  return mid_fwd(a, drop, stream);
+}
+
+namespace {
+// THE launcher of gnan_mid_graph_bwd (drop.thresh == 0) and gnan_mid_graph_bwd_drop
+int mid_bwd(const gnan_mid_graph_bwd_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
   if (int rc = shape_ok("mid_graph_bwd", kMidCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x != nullptr, "mid_graph_bwd: null x");
   GNAN_REQUIRE(a->code != nullptr, "mid_graph_bwd: null code");
@@ -447,5 +498,18 @@ extern "C" int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_
   p.rho_groups = (a->n + kRhoRows - 1) / kRhoRows;
   split_workspace(a->workspace, p.counter, p.part);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return with_channels(a->f.C, [&](auto c) { return launch_mid_bwd<decltype(c)::value>(p, st); });
+  return with_channels(a->f.C, [&](auto c) { return launch_mid_bwd<decltype(c)::value>(p, drop, st); });
+}
+}  // namespace
+
+extern "C" int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
+  return mid_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+}
+
+extern "C" int gnan_mid_graph_bwd_drop(const gnan_mid_graph_bwd_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
+  gnan_bwd::Drop drop;
+  if (int rc = drop_ok("mid_graph_bwd", d, &drop)) return rc;
+  return mid_bwd(a, drop, stream);
 }

@@ -52,8 +52,10 @@ struct BatchParams {
 // NB: node blocks of 64 the graph may have (1: n <= 64, the tables fit the activation columns as before; 2: n <= 128, the
 // aggregation's tables need 64 KB).  Config 2's graphs have 30 nodes on average and 3 % of them
 // more than 64; 128 covers 99.98 %.
-template <int NB>
-__device__ __forceinline__ void small_graph_body(const SmallParams& p, float* cols) {
+// DROP: the shape functions' workgroups mask their hidden activations (mlp_block<true>; node = the row of x, feature = k); the
+// Dropout-free instances are the code they were.
+template <int NB, bool DROP = false>
+__device__ __forceinline__ void small_graph_body(const SmallParams& p, float* cols, gnan_bwd::Drop drop = gnan_bwd::Drop{0u, 1.f, 0ull}) {
   constexpr int kNodes = 64 * NB;
   // cols [small_cols_floats(NB)]: activation columns; the aggregation's tables later — node sums, outputs, rho table, row
   // weights [n][64], hop codes [n][n]
@@ -103,7 +105,8 @@ __device__ __forceinline__ void small_graph_body(const SmallParams& p, float* co
     for (int b = 0; b < NB; ++b) {
       const int j = b * kWave + lane;
       if (b * kWave < p.n) {                         // (uniform)
-        mlp_block(p.f, wl_, xv[b], col_a, col_b, lane, wave, out);
+        if constexpr (DROP) mlp_block<true>(p.f, wl_, xv[b], col_a, col_b, lane, wave, out, drop, gnan::drop_base(drop.seed, j, k));
+        else mlp_block(p.f, wl_, xv[b], col_a, col_b, lane, wave, out);
         if (wave == 0 && j < p.n)
           for (int c = 0; c < p.f.C; ++c) p.part[(static_cast<int64_t>(k) * p.n + j) * p.f.C + c] = out[c];
       }
@@ -269,6 +272,13 @@ __global__ __launch_bounds__(256) void small_graph_kernel(const SmallParams p) {
   small_graph_body<NB>(p, cols);
 }
 
+// ... under training-mode Dropout of the shape functions (gnan_small_graph_fwd_drop with p > 0): kernels of their own
+template <int NB>
+__global__ __launch_bounds__(256) void small_graph_drop_kernel(const SmallParams p, const gnan_bwd::Drop drop) {
+  extern __shared__ __attribute__((aligned(16))) float cols[];
+  small_graph_body<NB, true>(p, cols, drop);
+}
+
 template <int NB>
 __global__ __launch_bounds__(256) void small_graph_batch_kernel(const BatchParams bp) {
   extern __shared__ __attribute__((aligned(16))) float cols[];
@@ -341,8 +351,10 @@ constexpr int kBinStride = kWave + 1;
 constexpr int kRhoSlot = kMaxH * kMaxH + 5 * kMaxH, kRhoGroupsMax = 12;       // 12 slots = 207 KB: inside a captured step's 256-KB scratch
 
 // NB as in small_graph_kernel (2: n <= 128 — hop codes and the row-weight / bin area take 50 KB: dynamic LDS).
+// fdrop: the forward's Dropout of the shape functions (thresh 0: none) — the feature workgroups recompute its masks; rho has none.
 template <int C, int NB>
-__device__ __forceinline__ void small_graph_bwd_body(const SmallBwdParams& p, float* dyn) {
+__device__ __forceinline__ void small_graph_bwd_body(const SmallBwdParams& p, float* dyn,
+                                                     gnan_bwd::Drop fdrop = gnan_bwd::Drop{0u, 1.f, 0ull}) {
   constexpr int kNodes = 64 * NB;
   constexpr int kUFloats = kNodes * kWave > 2 * kWave * kBinStride ? kNodes * kWave : 2 * kWave * kBinStride;
   __shared__ gnan_bwd::RedBuffer red;                                           // dyn: s_u | s_code
@@ -441,8 +453,8 @@ __device__ __forceinline__ void small_graph_bwd_body(const SmallBwdParams& p, fl
     __syncthreads();
     auto x_of = [&](int64_t node) { return p.x[node * p.x_stride + k]; };
     auto g_of = [&](int64_t node, int c) { return s_g[node * C + c]; };
-    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, 0, n, 0, nodrop, x_of, g_of, red);
-    else gnan_bwd::feature_grads<C, false>(p.f, k, 0, n, 0, nodrop, x_of, g_of, red);
+    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, 0, n, 0, fdrop, x_of, g_of, red);
+    else gnan_bwd::feature_grads<C, false>(p.f, k, 0, n, 0, fdrop, x_of, g_of, red);
     return;
   }
   if (p.rho_c > 1) {
@@ -661,6 +673,13 @@ __global__ __launch_bounds__(256) void small_graph_bwd_kernel(const SmallBwdPara
   small_graph_bwd_body<C, NB>(p, dyn);
 }
 
+// ... of a forward under Dropout (gnan_small_graph_bwd_drop with p > 0)
+template <int C, int NB>
+__global__ __launch_bounds__(256) void small_graph_bwd_drop_kernel(const SmallBwdParams p, const gnan_bwd::Drop drop) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  small_graph_bwd_body<C, NB>(p, dyn, drop);
+}
+
 template <int C, int NB>
 __global__ __launch_bounds__(256) void small_graph_batch_bwd_kernel(const BatchBwdParams bp) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
@@ -720,14 +739,22 @@ constexpr size_t small_bwd_dyn_bytes(bool pre_rho) {
 }
 
 template <int C>
-int launch_small_bwd(const SmallBwdParams& p, hipStream_t st) {
+int launch_small_bwd(const SmallBwdParams& p, const gnan_bwd::Drop& drop, hipStream_t st) {
+  const dim3 grid(static_cast<unsigned>(p.F + p.rho_groups));
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
+    if (p.n <= 64) {
+      hipLaunchKernelGGL((small_graph_bwd_drop_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(p.pre_rho != 0), st, p, drop);
+    } else {
+      if (int rc = raise_dyn_lds<&small_graph_bwd_drop_kernel<C, 2>>(small_bwd_dyn_bytes<2>(true), "small_graph_bwd")) return rc;
+      hipLaunchKernelGGL((small_graph_bwd_drop_kernel<C, 2>), grid, dim3(256), small_bwd_dyn_bytes<2>(p.pre_rho != 0), st, p, drop);
+    }
+    return gnan::check_launch("small_graph_bwd_drop_kernel");
+  }
   if (p.n <= 64) {
-    hipLaunchKernelGGL((small_graph_bwd_kernel<C, 1>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(256),
-                       small_bwd_dyn_bytes<1>(p.pre_rho != 0), st, p);
+    hipLaunchKernelGGL((small_graph_bwd_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(p.pre_rho != 0), st, p);
   } else {
     if (int rc = raise_dyn_lds<&small_graph_bwd_kernel<C, 2>>(small_bwd_dyn_bytes<2>(true), "small_graph_bwd")) return rc;
-    hipLaunchKernelGGL((small_graph_bwd_kernel<C, 2>), dim3(static_cast<unsigned>(p.F + p.rho_groups)), dim3(256),
-                       small_bwd_dyn_bytes<2>(p.pre_rho != 0), st, p);
+    hipLaunchKernelGGL((small_graph_bwd_kernel<C, 2>), grid, dim3(256), small_bwd_dyn_bytes<2>(p.pre_rho != 0), st, p);
   }
   return gnan::check_launch("small_graph_bwd_kernel");
 }
@@ -743,8 +770,9 @@ extern "C" size_t gnan_small_graph_workspace_bytes(int32_t n, int32_t F, int32_t
   return 16 + static_cast<size_t>(F) * n * C * sizeof(float);      // counter (own 16 bytes) | part [F, n, C]
 }
 
-extern "C" int gnan_small_graph_fwd(const gnan_small_graph_args* a, gnan_stream_t stream) {
-  GNAN_REQUIRE(a != nullptr, "small_graph: null args");
+namespace {
+// THE launcher of gnan_small_graph_fwd (drop.thresh == 0) and gnan_small_graph_fwd_drop
+int small_fwd(const gnan_small_graph_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
   if (int rc = shape_ok("small_graph", kSmallFwdCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->S && a->lut && (a->Y || a->Ysum), "small_graph: null x / code / S / lut / outputs");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_graph: null weights");
@@ -760,15 +788,38 @@ extern "C" int gnan_small_graph_fwd(const gnan_small_graph_args* a, gnan_stream_
   p.rho_raw = 0; p.rest_zero = 0; p.pre_rho = a->pre_rho != 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned rho_groups = p.pre_rho ? static_cast<unsigned>((a->n * a->D + kWave - 1) / kWave) : 1u;
+  const dim3 grid(static_cast<unsigned>(a->F) + rho_groups), block(kWaves * kWave);
+  constexpr size_t lds1 = small_cols_floats(1) * sizeof(float);
+  constexpr size_t lds2 = small_cols_floats(2) * sizeof(float);           // 64 KB of tables + the static weight image
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
+    if (a->n <= 64) {
+      hipLaunchKernelGGL(small_graph_drop_kernel<1>, grid, block, lds1, st, p, drop);
+    } else {
+      if (int rc = raise_dyn_lds<&small_graph_drop_kernel<2>>(lds2, "small_graph")) return rc;
+      hipLaunchKernelGGL(small_graph_drop_kernel<2>, grid, block, lds2, st, p, drop);
+    }
+    return gnan::check_launch("small_graph_drop_kernel");
+  }
   if (a->n <= 64) {
-    hipLaunchKernelGGL(small_graph_kernel<1>, dim3(static_cast<unsigned>(a->F) + rho_groups), dim3(kWaves * kWave),
-                       small_cols_floats(1) * sizeof(float), st, p);
+    hipLaunchKernelGGL(small_graph_kernel<1>, grid, block, lds1, st, p);
   } else {
-    constexpr size_t lds = small_cols_floats(2) * sizeof(float);          // 64 KB of tables + the static weight image
-    if (int rc = raise_dyn_lds<&small_graph_kernel<2>>(lds, "small_graph")) return rc;
-    hipLaunchKernelGGL(small_graph_kernel<2>, dim3(static_cast<unsigned>(a->F) + rho_groups), dim3(kWaves * kWave), lds, st, p);
+    if (int rc = raise_dyn_lds<&small_graph_kernel<2>>(lds2, "small_graph")) return rc;
+    hipLaunchKernelGGL(small_graph_kernel<2>, grid, block, lds2, st, p);
   }
   return gnan::check_launch("small_graph_kernel");
+}
+}  // namespace
+
+extern "C" int gnan_small_graph_fwd(const gnan_small_graph_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_graph: null args");
+  return small_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+}
+
+extern "C" int gnan_small_graph_fwd_drop(const gnan_small_graph_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_graph: null args");
+  gnan_bwd::Drop drop;
+  if (int rc = drop_ok("small_graph", d, &drop)) return rc;
+  return small_fwd(a, drop, stream);
 }
 
 extern "C" size_t gnan_small_graph_bwd_workspace_bytes(int32_t n, int32_t D) {
@@ -776,8 +827,9 @@ extern "C" size_t gnan_small_graph_bwd_workspace_bytes(int32_t n, int32_t D) {
   return 16 + static_cast<size_t>(kRhoGroupsMax) * kRhoSlot * sizeof(float);   // counter (own 16 bytes) | part [<= 12][kRhoSlot]
 }
 
-extern "C" int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_stream_t stream) {
-  GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
+namespace {
+// THE launcher of gnan_small_graph_bwd (drop.thresh == 0) and gnan_small_graph_bwd_drop
+int small_bwd(const gnan_small_graph_bwd_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
   if (int rc = shape_ok("small_graph_bwd", kSmallBwdCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->S && a->lut && (a->dY || a->dYsum), "small_graph_bwd: null x / code / S / lut / output gradient");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_graph_bwd: null weights");
@@ -802,7 +854,20 @@ extern "C" int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_str
     }
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return with_channels(a->f.C, [&](auto c) { return launch_small_bwd<decltype(c)::value>(p, st); });
+  return with_channels(a->f.C, [&](auto c) { return launch_small_bwd<decltype(c)::value>(p, drop, st); });
+}
+}  // namespace
+
+extern "C" int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
+  return small_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+}
+
+extern "C" int gnan_small_graph_bwd_drop(const gnan_small_graph_bwd_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
+  gnan_bwd::Drop drop;
+  if (int rc = drop_ok("small_graph_bwd", d, &drop)) return rc;
+  return small_bwd(a, drop, stream);
 }
 
 extern "C" size_t gnan_small_batch_workspace_bytes(int32_t n_graphs, int64_t total_nodes, int32_t F, int32_t C) {

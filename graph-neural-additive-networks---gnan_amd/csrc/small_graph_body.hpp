@@ -81,10 +81,18 @@ __device__ __forceinline__ void stage_weights(const Mlp& m, int k, const MlpLds&
 
 // One scalar MLP on the 64 inputs of this node block: lane = input, the four waves split every hidden layer's units;
 // activations live in LDS columns a / b ([H][64]).  Wave 0 ends with the C outputs of its lane in out[].
+// DROP: training-mode Dropout behind every hidden ReLU (csrc/dropout.hpp) — `dbase` is the lane's drop_base(seed, node, feature),
+// hidden layer 0 is the one written into column a, layer 1 the one written into nxt: the coordinates of gnan_fmlp_fwd,
+// gnan_fmlp_bwd and gnan_dropout_mask.  The shape functions' workgroups only: rho carries no Dropout.
+template <bool DROP = false>
 __device__ __forceinline__ void mlp_block(const Mlp& m, const MlpLds& w, float xv, float* a, float* b, int lane, int wave,
-                                          float (&out)[kMaxC]) {
+                                          float (&out)[kMaxC], gnan_bwd::Drop drop = gnan_bwd::Drop{0u, 1.f, 0ull}, uint32_t dbase = 0u) {
   const int H = m.H, C = m.C;
-  for (int j = wave; j < H; j += kWaves) a[j * kWave + lane] = fmaxf(fmaf(xv, w.w1[j], w.b1[j]), 0.f);
+  for (int j = wave; j < H; j += kWaves) {
+    float h = fmaxf(fmaf(xv, w.w1[j], w.b1[j]), 0.f);
+    if constexpr (DROP) h = gnan::drop_keep(dbase, 0, j, drop.thresh) ? h * drop.scale : 0.f;
+    a[j * kWave + lane] = h;
+  }
   __syncthreads();
   float* cur = a;
   float* nxt = b;
@@ -125,7 +133,11 @@ __device__ __forceinline__ void mlp_block(const Mlp& m, const MlpLds& w, float x
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        if (o0 + t < o_hi) nxt[(o0 + t) * kWave + lane] = fmaxf(acc[t], 0.f);
+        if (o0 + t < o_hi) {
+          float h = fmaxf(acc[t], 0.f);
+          if constexpr (DROP) h = gnan::drop_keep(dbase, 1, o0 + t, drop.thresh) ? h * drop.scale : 0.f;
+          nxt[(o0 + t) * kWave + lane] = h;
+        }
     }
     __syncthreads();
     float* t = cur; cur = nxt; nxt = t;
@@ -214,6 +226,18 @@ inline int shape_ok(const char* who, const RouteLimits& lim, int n, int F, int D
     if (m[t]->H < 1 || m[t]->H > kMaxH)
       return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers 1 <= H <= %d (got H=%d for %s)", who, kMaxH, m[t]->H, t ? "rho" : "f");
   }
+  return GNAN_OK;
+}
+
+// The Dropout record of the *_drop entry points, checked on the host before anything else of theirs: NULL, p outside [0, 1) (NaN
+// included) and a non-zero reserved word are refused.  out->thresh == 0 (p == 0, or p below 2^-32): the plain kernels.
+inline int drop_ok(const char* who, const gnan_small_dropout* d, gnan_bwd::Drop* out) {
+  GNAN_REQUIRE(d != nullptr, "%s: null dropout record", who);
+  GNAN_REQUIRE(d->p >= 0.f && d->p < 1.f, "%s: dropout p must be in [0, 1) (got p=%g)", who, static_cast<double>(d->p));
+  GNAN_REQUIRE(d->reserved == 0, "%s: dropout reserved must be 0 (got reserved=%d)", who, d->reserved);
+  out->thresh = gnan::drop_threshold(d->p);
+  out->scale = out->thresh != 0u ? 1.f / (1.f - d->p) : 1.f;
+  out->seed = d->seed;
   return GNAN_OK;
 }
 

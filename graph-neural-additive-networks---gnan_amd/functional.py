@@ -855,6 +855,12 @@ class _DropoutMLPs(torch.autograd.Function):
         return (gx, None, None, None, None, None, None, None, *pg)
 
 
+def draw_dropout_seed() -> int:
+    """The 64-bit seed of one forward's Dropout masks: ONE draw from torch's CPU generator, whichever route the forward takes
+    (:func:`feature_mlps_dropout`, the one-launch graph routes of ``small_graph``) — ``torch.manual_seed`` fixes the masks."""
+    return int(torch.empty((), dtype=torch.int64).random_().item()) & ((1 << 63) - 1)
+
+
 def feature_mlps_dropout(x: torch.Tensor, p: StackedMLP, sum_features: bool, drop_p: float, seed: Optional[int] = None,
                          return_total: bool = False):
     """:func:`feature_mlps` in training mode with Dropout ``drop_p`` behind every hidden ReLU (GNAN.py:28,32).  ``seed``:
@@ -869,7 +875,7 @@ def feature_mlps_dropout(x: torch.Tensor, p: StackedMLP, sum_features: bool, dro
     if p.L == 1:                                         # a single Linear has no hidden ReLU: nothing to drop (GNAN.py:25-26)
         return feature_mlps(x, p, sum_features, return_total=return_total)
     if seed is None:
-        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        seed = draw_dropout_seed()
     out = _DropoutMLPs.apply(x, sum_features, float(drop_p), int(seed) & ((1 << 63) - 1), p.L, p.H, p.C, p.F, *p[:6])
     return (out, column_sums(out)) if return_total else out
 

@@ -377,11 +377,14 @@ class _PathBase(nn.Module):
     def _check_dropout(self):
         """Training-mode Dropout (GNAN.py:28,32; run.sh trains with 0.6) runs in the kernels: ``gnan_fmlp_fwd`` /
         ``gnan_fmlp_bwd`` apply a keep-mask that is a counter-based hash of (seed, node, feature, layer, unit), the seed
-        drawn from torch's generator once per forward (``functional.feature_mlps_dropout``).  Same distribution as
+        drawn from torch's generator once per forward (``functional.draw_dropout_seed``).  Same distribution as
         ``nn.Dropout``, not torch's Bernoulli stream — which depends on the order of the reference's Python loop and is not
         part of any contract.  The table path cannot hold per-node masks, so these steps use the direct kernels (the
         reference only trains with Dropout in its first epoch: it never leaves eval mode again after ``trainer.py:97``);
-        a one-time note says so."""
+        a one-time note says so.  Dense-coded graphs of up to 448 nodes keep their one-launch routes under Dropout
+        (``small_graph.SMALL_GRAPH_DROPOUT``: ``gnan_small_graph_fwd_drop`` / ``gnan_mid_graph_fwd_drop`` and their backward
+        passes hash the same coordinates, so a seed gives the same masks on either route); the NAM read-out, the batched and
+        slot routes and captured steps do not."""
         if self._dropout_active() and not getattr(self, "_dropout_noted", False):
             import warnings
             warnings.warn("gnan_amd: training-mode Dropout (p=%g) is active: the shape functions run through the direct "
@@ -390,6 +393,11 @@ class _PathBase(nn.Module):
 
     def _dropout_active(self) -> bool:
         return bool(self.training and self.dropout and self.dropout > 0)
+
+    def _dropout_record(self):
+        """``(p, seed)`` of this forward's masks: the ONE seed draw of the forward."""
+        from .functional import draw_dropout_seed
+        return (float(self.dropout), draw_dropout_seed())
 
     def _features(self, x, name, mlps, sum_features: bool, pad_ok: bool = False, want_total: bool = False,
                   out_dtype=torch.float32, room_rows: int = 0):
@@ -461,8 +469,13 @@ class _PathBase(nn.Module):
         """The whole forward by one launch where ``gnan_small_graph_fwd`` applies (a small dense-coded graph, features summed
         per node: what a graph-level task feeds per step; ``use_cnt``: False, True = post-rho normalisation, "pre" =
         GNAN.py:65-67), else None."""
+        from . import small_graph as sg
         from .small_graph import (MID_GRAPH_MAX_NODES, SMALL_GRAPH_MAX_NODES, SlotGraph, mid_graph_applies, mid_graph_forward,
                                   slot_graph_applies, slot_graph_forward, small_graph_applies, small_graph_forward)
+        drop = self._dropout_active()
+        if drop and (not sg.SMALL_GRAPH_DROPOUT or isinstance(g, SlotGraph) or torch.cuda.is_current_stream_capturing()):
+            return None                                  # the general Dropout route, as before (slots and captures: a captured
+                                                         # seed would freeze the masks; graphed.py / harness.py refuse such steps)
         if isinstance(g, SlotGraph):
             # a captured step of a batch-size-1 loop: the graph sits in slots, its size is the device's to know
             f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
@@ -473,14 +486,15 @@ class _PathBase(nn.Module):
         if not g.is_dense or x.shape[0] > MID_GRAPH_MAX_NODES:
             return None
         f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
-        if x.shape[0] > SMALL_GRAPH_MAX_NODES:          # 129 to 448 nodes: the same by tiles of 64 rows (gnan_mid_graph_fwd)
-            if not mid_graph_applies(x, g, f, rho, use_cnt):
-                return None
-            out = mid_graph_forward(x, g, f, rho, use_cnt, graph_sum)
-        elif not small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre"):
+        mid = x.shape[0] > SMALL_GRAPH_MAX_NODES        # 129 to 448 nodes: the same by tiles of 64 rows (gnan_mid_graph_fwd)
+        if not (mid_graph_applies(x, g, f, rho, use_cnt) if mid else small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre")):
             return None
+        # (the forward's ONE seed draw: only once the route is taken — a forward that goes on to the general route draws its own)
+        kw = {"dropout": self._dropout_record()} if drop else {}
+        if mid:
+            out = mid_graph_forward(x, g, f, rho, use_cnt, graph_sum, **kw)
         else:
-            out = small_graph_forward(x, g, f, rho, use_cnt, graph_sum)
+            out = small_graph_forward(x, g, f, rho, use_cnt, graph_sum, **kw)
         for name in ("lut", "fmlp", "spmm"):
             self._mark(name)
         return out
@@ -540,10 +554,9 @@ class StandaloneTensorGNAN(_PathBase):
         _lib.require_device(x)
         self._mark("start")
         g = self._graph(inputs, want_norm=bool(self.normalize_rho))
-        if not self._dropout_active():
-            small = self._small_graph(x, g, "pre" if self.normalize_rho else False, bool(self.is_graph_task))
-            if small is not None:
-                return small
+        small = self._small_graph(x, g, "pre" if self.normalize_rho else False, bool(self.is_graph_task))
+        if small is not None:
+            return small
         lut = None if self.normalize_rho else self._lut_global(g)
         self._mark("lut")
         S, total = self._operand(x, "fs", self.fs, True, not g.is_dense, graph=g)    # [N, C]
@@ -601,7 +614,7 @@ class _GNANCore(_PathBase):
         _lib.require_device(x)
         self._mark("start")
         g = self._graph(inputs, want_norm=True)            # GNAN.py:161 reads it unconditionally
-        if node_ids is None and not self._dropout_active():
+        if node_ids is None:
             small = self._small_graph(x, g, bool(self.normalize_rho), False)
             if small is not None:
                 return small
@@ -704,7 +717,7 @@ class TensorGNAN(_PathBase):
         self._mark("start")
         g = self._graph(inputs, want_norm=bool(self.normalize_rho))
         with_readout = self.is_graph_task and self.readout_n_layers > 0
-        if not with_readout and self.aggregation_order != "reference" and not self._dropout_active():
+        if not with_readout and self.aggregation_order != "reference":
             small = self._small_graph(x, g, bool(self.normalize_rho), bool(self.is_graph_task))
             if small is not None:
                 return small

@@ -28,6 +28,8 @@ from .graph import HopGraph, hop_inputs
 SMALL_GRAPH_FORWARD = True
 SMALL_GRAPH_MAX_NODES = 128   # gnan_small_graph_fwd / _bwd: one block of 64 nodes (static LDS) or two (64 KB of tables)
 SMALL_GRAPH_BACKWARD = True   # ... and its backward pass (gnan_small_graph_bwd)
+SMALL_GRAPH_DROPOUT = True    # training-mode Dropout of the shape functions stays on these routes (gnan_*_graph_fwd_drop / _bwd_drop);
+                              # off: such a forward takes the general kernels (functional.feature_mlps_dropout), as before
 _SMALL_WS = {}               # (device index, stream) -> workspace whose counter word the kernel leaves zero
 _MAX_HIDDEN, _MAX_CHANNELS = 64, 8     # every route's MLP kernels: hidden width, output channels
 _FORWARD_CODES = 256         # hop codes gnan_small_graph_fwd / gnan_small_batch_fwd take ...
@@ -130,10 +132,13 @@ class _OneLaunch(torch.autograd.Function):
     launch too (``gnan_small_graph_bwd`` / ``gnan_mid_graph_bwd``: one rho channel, <= 64 shells, the gradients of both f and rho
     wanted — or pre-rho), else the general path's kernels on the saved node sums and rho table — transposed aggregation, table
     gradient, the two small-batch MLP backward launches (their gradients land in the flat gradient buffers directly).
-    ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67; the small route only)."""
+    ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67; the small route only).
+    ``dropout``: None, or ``(p, seed)`` — training-mode Dropout behind every hidden ReLU of f (never of rho), masks hashed from
+    the seed (csrc/dropout.hpp; node = row of ``x``, feature = its column): both launches go through the ``_drop`` entry points
+    with the same record, and so does ``gnan_fmlp_bwd`` where the general backward runs."""
 
     @staticmethod
-    def forward(ctx, route, x, g, use_cnt, graph_sum, fm, rm, *params):
+    def forward(ctx, route, x, g, use_cnt, graph_sum, fm, rm, dropout, *params):
         Lf, Hf, Cf, F = fm
         Lr, Hr, Cr = rm
         xk = Fn._rows(x.detach())
@@ -150,8 +155,8 @@ class _OneLaunch(torch.autograd.Function):
                        rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(g.code), D=D, **{route.flag: int(pre_rho)},
                        **_cnt_pair(g.cnt if use_cnt else None), S=_lib.ptr(S), lut=_lib.ptr(lut), Y=_lib.ptr(Y), Ysum=_lib.ptr(Ysum),
                        workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4)
-        _lib.check(getattr(_lib.lib(), route.name + "_fwd")(a, _lib.stream_of(xk)), route.name + "_fwd")
-        ctx.route, ctx.g, ctx.use_cnt, ctx.graph_sum, ctx.fm, ctx.rm = route, g, use_cnt, graph_sum, fm, rm
+        _launch(route.name + "_fwd", a, dropout, xk)
+        ctx.route, ctx.g, ctx.use_cnt, ctx.graph_sum, ctx.fm, ctx.rm, ctx.dropout = route, g, use_cnt, graph_sum, fm, rm, dropout
         _save(ctx, (xk, S, lut), params)
         return Ysum.view(-1, 1) if graph_sum else Y
 
@@ -162,7 +167,7 @@ class _OneLaunch(torch.autograd.Function):
         Lf, Hf, Cf, F = ctx.fm
         Lr, Hr, Cr = ctx.rm
         n, D = x.shape[0], ctx.g.n_codes
-        need_f, need_r = any(ctx.needs_input_grad[7:13]), any(ctx.needs_input_grad[13:])
+        need_f, need_r = any(ctx.needs_input_grad[8:14]), any(ctx.needs_input_grad[14:])      # (eight arguments, then f's six, rho's six)
         pre_rho = ctx.use_cnt == "pre"          # (small_graph_applies admitted it only where the one launch below covers it)
         if not ((SMALL_GRAPH_BACKWARD and Cr == 1 and D <= _ONE_LAUNCH_CODES and d_out.dtype == torch.float32
                  and all(t is None or t.dtype == torch.float32 for t in params)) and ((need_f and need_r) or pre_rho)):
@@ -183,16 +188,27 @@ class _OneLaunch(torch.autograd.Function):
                            dY=None if ctx.graph_sum else _lib.ptr(g_out), dYsum=_lib.ptr(g_out) if ctx.graph_sum else None,
                            df=_mlp_grads(outs_f), drho=_mlp_grads(outs_r), workspace=_lib.ptr(ws),
                            workspace_bytes=0 if ws is None else ws.numel() * 4)
-        _lib.check(getattr(_lib.lib(), route.name + "_bwd")(a, _lib.stream_of(x)), route.name + "_bwd")
+        _launch(route.name + "_bwd", a, ctx.dropout, x)
         if not need_f:
             outs_f = [None] * 6
         if not need_r:
             outs_r = [None] * 6
-        return (None, None, None, None, None, None, None, *outs_f, *outs_r)
+        return (None, None, None, None, None, None, None, None, *outs_f, *outs_r)
+
+
+def _launch(entry: str, a, dropout, on: torch.Tensor) -> None:
+    """``entry(a, stream)``, or — ``dropout = (p, seed)`` — ``entry_drop(a, record, stream)``."""
+    if dropout is None:
+        _lib.check(getattr(_lib.lib(), entry)(a, _lib.stream_of(on)), entry)
+        return
+    d = _lib.SmallDropout(p=float(dropout[0]), reserved=0, seed=int(dropout[1]))
+    _lib.check(getattr(_lib.lib(), entry + "_drop")(a, d, _lib.stream_of(on)), entry + "_drop")
 
 
 def _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r):
-    """The backward of a one-launch forward by the general path's kernels on the node sums and the rho table it saved."""
+    """The backward of a one-launch forward by the general path's kernels on the node sums and the rho table it saved.  A forward
+    under Dropout: f's gradients by ``gnan_fmlp_bwd`` with the forward's ``(p, seed)`` — the same masks — never a Dropout-free
+    formula."""
     fp, rp = params[:6], params[6:]
     Lf, Hf, Cf, F = ctx.fm
     Lr, Hr, Cr = ctx.rm
@@ -201,21 +217,34 @@ def _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r):
     call = aggregate.AggregateCall(ctx.g, ctx.use_cnt, with_rest=False)
     dS, dlut = aggregate._aggregate_backward(call, S, lut, dY, need_f, need_r)
     pg_f = pg_r = [None] * 6
-    if need_f:
+    if need_f and ctx.dropout is not None and ctx.dropout[0] > 0:
+        pg_f = Fn._fmlp_backward_launch(x, fp, dS, True, Lf, Hf, Cf, F, dropout=ctx.dropout, dests=ctx.dests[:6])
+    elif need_f:
         _, pg_f = Fn._shape_function_grads(x, fp, ctx.present[:6], None, dS, True, Lf, Hf, Cf, F, dests=ctx.dests[:6])
     if need_r:
         u = hop_inputs(ctx.g.n_codes, x.device).view(-1, 1)
         _, pg_r = Fn._shape_function_grads(u, rp, ctx.present[6:], None, dlut.reshape(-1, Cr), False, Lr, Hr, Cr, 1,
                                         dests=ctx.dests[6:])
-    return (None, None, None, None, None, None, *pg_f, *pg_r)
+    return (None, None, None, None, None, None, None, *pg_f, *pg_r)
 
 
-def small_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool):
+def _dropout_record(dropout):
+    """``None`` or ``(p, seed)`` as :class:`_OneLaunch` takes it: p in [0, 1), the seed's 64 bits."""
+    if dropout is None:
+        return None
+    p, seed = float(dropout[0]), int(dropout[1])
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must be in [0, 1)")
+    return (p, seed & ((1 << 64) - 1))
+
+
+def small_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool, dropout=None):
     """The forward of GNAN.py:146-172 / models.py:358-384 (post-rho; ``use_cnt="pre"``: GNAN.py:55-79, pre-rho) on a small
-    dense-coded graph by ``gnan_small_graph_fwd``: ``[n, C]`` node outputs, or ``[C, 1]`` with ``graph_sum`` (GNAN.py:75-79)."""
+    dense-coded graph by ``gnan_small_graph_fwd``: ``[n, C]`` node outputs, or ``[C, 1]`` with ``graph_sum`` (GNAN.py:75-79).
+    ``dropout = (p, seed)``: training-mode Dropout of f (``gnan_small_graph_fwd_drop``; ``functional.draw_dropout_seed``)."""
     _lib.require_device(x, f.w_last, rho.w_last, g.code)
     return _OneLaunch.apply(_SMALL, x, g, "pre" if use_cnt == "pre" else bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F),
-                            (rho.L, rho.H, rho.C), *f[:6], *rho[:6])
+                            (rho.L, rho.H, rho.C), _dropout_record(dropout), *f[:6], *rho[:6])
 
 
 # =============================================================================
@@ -235,11 +264,12 @@ def mid_graph_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedM
                 and x.shape[1] == f.F and rho.F == 1 and _stack_ok(f) and _stack_ok(rho, max_c=1))
 
 
-def mid_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool):
-    """:func:`small_graph_forward` for a dense-coded graph of 129 to 448 nodes (``gnan_mid_graph_fwd``): ``[n, C]`` node outputs,
-    or ``[C, 1]`` with ``graph_sum``."""
+def mid_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool, dropout=None):
+    """:func:`small_graph_forward` for a dense-coded graph of 129 to 448 nodes (``gnan_mid_graph_fwd`` / ``_fwd_drop``): ``[n, C]``
+    node outputs, or ``[C, 1]`` with ``graph_sum``."""
     _lib.require_device(x, f.w_last, rho.w_last, g.code)
-    return _OneLaunch.apply(_MID, x, g, bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C), *f[:6], *rho[:6])
+    return _OneLaunch.apply(_MID, x, g, bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C),
+                            _dropout_record(dropout), *f[:6], *rho[:6])
 
 
 # =============================================================================

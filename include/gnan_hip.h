@@ -1351,6 +1351,34 @@ int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t C, gnan_mid
 int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream);
 int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The two one-launch routes above under training-mode Dropout of the SHAPE FUNCTIONS (GNAN.py:28,32: nn.Dropout behind every
+ * hidden ReLU of f; added under ABI 51: one new struct, four new entry points, no existing struct changed, the number did not
+ * move).  The arguments, covers, workspaces (and their zero-word rules) and the *_workspace_bytes queries are those of the plain
+ * entry points; the plain entry points are the p == 0 case of the same launchers.
+ * Masks: keep(node, feature, hidden layer, unit) is the counter-based hash of csrc/dropout.hpp over
+ *   node    = the row of x (0 .. n - 1),
+ *   feature = the column of x, i.e. the index k of the shape function,
+ *   layer   = 0 for the ReLU behind the first Linear, 1 for the one behind the hidden-to-hidden Linear (L == 3),
+ *   unit    = the hidden unit (0 .. H - 1),
+ * under the 64-bit seed — exactly the coordinates of gnan_fmlp_fwd / gnan_fmlp_bwd (dropout_p, dropout_seed) and of
+ * gnan_dropout_mask, so one (p, seed) gives the same masks on every route; kept activations are scaled by 1 / (1 - p).  No mask
+ * tensor exists: the backward recomputes the forward's masks and must be handed the same (p, seed).  rho carries no Dropout (no
+ * model class gives it one): its workgroups — the pre-rho ones included — are never masked.
+ * p > 0 launches Dropout instances of the kernels (kernels of their own); p == 0 launches the plain entry point's kernel, bit
+ * for bit.  Refused on the host, before any HIP call: a NULL record, p outside [0, 1) (NaN included), reserved != 0
+ * (GNAN_ERR_BAD_ARG); shapes outside the routes' cover stay GNAN_ERR_UNSUPPORTED with the plain entry points' messages.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_small_dropout {
+  float p;                   /* in [0, 1); 0 = no Dropout: the plain entry point's kernel, bit for bit */
+  int32_t reserved;          /* 0 */
+  uint64_t seed;             /* csrc/dropout.hpp */
+} gnan_small_dropout;
+int gnan_small_graph_fwd_drop(const gnan_small_graph_args* a, const gnan_small_dropout* d, gnan_stream_t stream);
+int gnan_small_graph_bwd_drop(const gnan_small_graph_bwd_args* a, const gnan_small_dropout* d, gnan_stream_t stream);
+int gnan_mid_graph_fwd_drop(const gnan_mid_graph_args* a, const gnan_small_dropout* d, gnan_stream_t stream);
+int gnan_mid_graph_bwd_drop(const gnan_mid_graph_bwd_args* a, const gnan_small_dropout* d, gnan_stream_t stream);
+
 /* The backward pass of gnan_small_batch_fwd: launch 1 — blockIdx.y = graph, the workgroups of gnan_small_graph_bwd per graph — leaves
  * every graph's contribution to the gradients of f and rho in its slab of the workspace; launch 2 adds the slabs in graph
  * order into df / drho.  dY [total_nodes, f.C], or dYsum [n_graphs, f.C] (the gradient of the per-graph read-out).  Covers
