@@ -47,17 +47,11 @@ def _spmm_args(g: HopGraph, S, lut, use_cnt, s_total, out, row_ids, per_row_lut,
         cnt=_lib.ptr(g.cnt) if use_cnt else None, cnt_stride=g.cnt.stride(0),
         s_total=_lib.ptr(s_total), weight_by_col=int(weight_by_col), minus_rest=int(minus_rest),
         reduce_cr=int(reduce_cr), scatter_out=int(scatter_out), Y=_lib.ptr(out), y_stride=out.stride(0),
-        long_threshold=(plan.threshold if plan is not None else 0),
-        long_rows=_lib.ptr(plan.rows) if plan is not None else None,
-        long_slice_ptr=_lib.ptr(plan.slice_ptr) if plan is not None else None,
-        n_long=(plan.n_long if plan is not None else 0), n_slices=(plan.n_slices if plan is not None else 0),
-        slice_edges=(plan.slice_edges if plan is not None else 0),
         workspace=_lib.ptr(workspace), workspace_bytes=(workspace.numel() * 4 if workspace is not None else 0),
         s_by_code=int(s_by_code), nnz=(0 if (g.col is None or not WIDE_INDEX_LOADS) else int(g.col.numel())),
         packed_index=int(packed))
-    if getattr(plan, "index", None) is not None and plan.n_long > 0:
-        a.cls_index, a.cls_slice_start = _lib.ptr(plan.index), _lib.ptr(plan.slice_start)
-        a.cls_slice_row, a.cls_slot_slice, a.cls_n_slots = _lib.ptr(plan.slice_row), _lib.ptr(plan.slot_slice), plan.n_slots
+    if plan is not None:
+        plan.bind(a)
     if hot_rows and packed and HOT_ROWS_IN_LDS:
         # the appended compact copy of the most listed rows sits behind the real ones: its head is served from LDS — where it
         # receives enough of the pairs to pay for the persistent kernel's lower occupancy (10M-node R-MAT: 32 % at W = 1,
@@ -247,41 +241,21 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         if self_sum.dtype != torch.float32 or self_sum.dim() != 2 or self_sum.shape[1] != n_out or not self_sum.is_contiguous():
             raise ValueError("self_sum must be a contiguous float32 [parts, n_rows] tensor")
         a.self_sum, a.self_parts = _lib.ptr(self_sum), int(self_sum.shape[0])
-        stream = None
-        if (PAIR_STREAM and g.nnz >= PAIR_STREAM_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
-                and s_total is not None and S.dtype == torch.float32 and 32 < S.shape[1] <= 256
-                and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
-            # the rows between the tiles and the hubs as one queue of pairs per column class, in popularity-block order, a chunk per
-            # lane group; None where their pairs carry more than one hop code: the classed rows below then
-            stream = g.pair_stream_plan(max(PAIR_STREAM_MIN_PAIRS, SHORT_ROW_LMAX + 1), max(1, BLOCKED_HUB_BLOCK_BYTES // (S.shape[1] * 4)),
-                                        PAIR_STREAM_BLOCKS, PAIR_STREAM_CHUNK_PAIRS)
-        if stream is not None:
-            a.stream_index, a.stream_cls_pair_ptr = _lib.ptr(stream.index), _lib.ptr(stream.cls_pair_ptr)
-            a.stream_cls_chunk_ptr, a.stream_chunk_first_seg = _lib.ptr(stream.cls_chunk_ptr), _lib.ptr(stream.chunk_first_seg)
-            a.stream_row_seg, a.stream_row_slot_ptr = _lib.ptr(stream.row_seg), _lib.ptr(stream.row_slot_ptr)
-            a.stream_q_lo, a.stream_q_hi, a.stream_chunk, a.stream_code = stream.q_lo, stream.q_hi, stream.chunk_pairs, stream.code
-            a.n_stream_seg, a.stream_max_chunks_per_class = stream.n_seg, stream.max_chunks_per_class
-        elif (CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
-                and s_total is not None and S.dtype == torch.float32 and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
-            # the rows between the tiles and the hubs in segments of one column class each, a class per XCD
-            rows = g.classed_row_plan(max(CLASSED_ROWS_MIN_PAIRS, SHORT_ROW_LMAX + 1))
-            if rows is not None:
-                a.seg_index, a.seg_start, a.seg_row = _lib.ptr(rows.index), _lib.ptr(rows.seg_start), _lib.ptr(rows.seg_row)
-                a.cls_seg_ptr, a.seg_mask = _lib.ptr(rows.cls_seg_ptr), _lib.ptr(rows.mask)
-                a.seg_q_lo, a.seg_q_hi, a.n_seg, a.seg_max_per_class = rows.q_lo, rows.q_hi, rows.n_seg, rows.max_per_class
-        if (BLOCKED_HUBS and g.nnz >= BLOCKED_HUBS_MIN_NNZ and scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1
-                and s_total is not None and S.dtype == torch.float32 and plan is not None and plan.n_long > 0
-                and plan.threshold == LONG_ROW_THRESHOLD):
-            # the hub rows in segments of one (column class, popularity block) each, every XCD walking its class's blocks most listed
-            # first: they leave the slice plan — no slice blocks, no fix-up launch
-            hubs = g.blocked_hub_plan(max(1, BLOCKED_HUB_BLOCK_BYTES // (S.shape[1] * 4)), BLOCKED_HUB_BLOCKS, BLOCKED_HUB_SEG_PAIRS)
-            if hubs is not None:
-                a.long_rows = a.long_slice_ptr = a.cls_index = a.cls_slice_start = a.cls_slice_row = a.cls_slot_slice = None
-                a.n_long = a.n_slices = a.cls_n_slots = 0                 # (long_threshold stays: the row blocks leave the hub rows out by it)
-                a.hub_index, a.hub_seg_start, a.hub_seg_row = _lib.ptr(hubs.index), _lib.ptr(hubs.seg_start), _lib.ptr(hubs.seg_row)
-                a.hub_seg_slot, a.hub_row_slot_ptr = _lib.ptr(hubs.seg_slot), _lib.ptr(hubs.row_slot_ptr)
-                a.hub_cls_seg_ptr, a.hub_q_lo, a.n_hub = _lib.ptr(hubs.cls_seg_ptr), hubs.q_lo, hubs.n_hub
-                a.n_hub_seg, a.hub_seg_max_per_class = hubs.n_seg, hubs.max_per_class
+        # what the plans of this route share: the packed degree-sorted copy walked in tiles, fp32 rows, the fused one-channel read-out
+        # with a rest total, the default hub threshold.  Each plan adds its switch, its size gate and its own terms
+        if (scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1 and s_total is not None
+                and S.dtype == torch.float32 and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
+            W, lo, rows, hubs = S.shape[1], SHORT_ROW_LMAX + 1, None, None
+            block_rows = max(1, BLOCKED_HUB_BLOCK_BYTES // (W * 4)) if W else 0      # operand rows of one (class, block): one XCD's L2
+            if PAIR_STREAM and g.nnz >= PAIR_STREAM_MIN_NNZ and 32 < W <= 256:      # None for two hop codes: the classed rows then
+                rows = g.pair_stream_plan(max(PAIR_STREAM_MIN_PAIRS, lo), block_rows, PAIR_STREAM_BLOCKS, PAIR_STREAM_CHUNK_PAIRS)
+            if rows is None and CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ:
+                rows = g.classed_row_plan(max(CLASSED_ROWS_MIN_PAIRS, lo))
+            if BLOCKED_HUBS and g.nnz >= BLOCKED_HUBS_MIN_NNZ and plan is not None and plan.n_long > 0:
+                hubs = g.blocked_hub_plan(block_rows, BLOCKED_HUB_BLOCKS, BLOCKED_HUB_SEG_PAIRS)
+            for wide in (rows, hubs):                     # (in this order: the hubs' bind takes the hub rows out of the slice plan)
+                if wide is not None:
+                    wide.bind(a)
     need = _lib.lib().gnan_spmm_fwd_workspace_bytes(a)
     ws = None
     if need:

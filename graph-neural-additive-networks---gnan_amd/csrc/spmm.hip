@@ -288,9 +288,8 @@ int launch_fixup(const Params& p, hipStream_t st) {
 
 // combine: the classed rows' segments (seg_body, csrc/spmm_fwd_body.hpp) -> the rows' read-out.  One thread per classed row:
 //   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))))
-// p_c the row's partial of class c where the mask says it exists (else 0: the workspace is never cleared), T the sum of s_total in
-// float64 rounded once (a float32 chain over W columns would put more roundings on the rest term than a 5-pair row's bound counts),
-// a_i as the other epilogues read it.  One fixed shape per row: bit-reproducible.
+// p_c the row's partial of class c where the mask says it exists (else 0: the workspace is never cleared), T and a_i by
+// combine_store (csrc/spmm_common.hpp).  One fixed shape per row: bit-reproducible.
 __global__ __launch_bounds__(256) void spmm_seg_combine_kernel(const Params p) {
   const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r >= p.seg_q_hi - p.seg_q_lo) return;
@@ -303,16 +302,7 @@ __global__ __launch_bounds__(256) void spmm_seg_combine_kernel(const Params p) {
   float c[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) c[k] = (mask >> k) & 1u ? v[k] : 0.f;
-  float y = ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
-  double T = 0.0;
-  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
-  const int rest = p.D - 1;
-  const SmallW sw = small_weights(p, q);
-  const float w_rest = sw.pick(rest);
-  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
-  y = fmaf(w_rest, static_cast<float>(T), y);
-  y = fmaf(w_self, self_term(p, o), y);
-  p.Y[o * p.y_stride] = y;
+  combine_store(p, q, o, ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7])));
 }
 
 int launch_seg_combine(const Params& p, hipStream_t st) {
@@ -338,16 +328,7 @@ __global__ __launch_bounds__(256) void spmm_hub_combine_kernel(const Params p) {
   for (int off = kWave / 2; off >= 1; off >>= 1) y += __shfl_xor(y, off);
   if (lane != 0) return;
   const int64_t q = p.hub_q_lo + r;
-  const int64_t o = out_row(p, q, q);
-  double T = 0.0;
-  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
-  const int rest = p.D - 1;
-  const SmallW sw = small_weights(p, q);
-  const float w_rest = sw.pick(rest);
-  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
-  y = fmaf(w_rest, static_cast<float>(T), y);
-  y = fmaf(w_self, self_term(p, o), y);
-  p.Y[o * p.y_stride] = y;
+  combine_store(p, q, out_row(p, q, q), y);
 }
 
 int launch_hub_combine(const Params& p, hipStream_t st) {

@@ -258,6 +258,27 @@ __device__ __forceinline__ SmallW small_weights(const Params& p, int64_t i) {
   return s;
 }
 
+// The end of the combine kernels (spmm_seg_combine_kernel, spmm_hub_combine_kernel, spmm_stream_combine_kernel): row q's sum y of
+// listed terms gets the rest and self terms and is stored,   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, y))
+// T the sum of s_total in float64 rounded once (a float32 chain over W columns would put more roundings on the rest term than a
+// 5-pair row's bound counts), a_i as the other epilogues read it.  ONE_CODE (the stream): y is the raw sum of pairs of the one hop
+// code `code` and takes their folded weight w_code - w_rest first; else y carries its weights already.  o = out_row(p, q, q) comes
+// from the caller, read where each kernel read it before (ahead of the seg and stream kernels' sums, behind the hub kernel's butterfly):
+// with the read in here the stream kernel's SGPR count moved.
+template <bool ONE_CODE = false>
+__device__ __forceinline__ void combine_store(const Params& p, int64_t q, int64_t o, float y, int code = 0) {
+  double T = 0.0;
+  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
+  const int rest = p.D - 1;
+  const SmallW sw = small_weights(p, q);
+  const float w_rest = sw.pick(rest);
+  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
+  if constexpr (ONE_CODE) y = (code < rest ? sw.pick(code) - w_rest : 0.f) * y;
+  y = fmaf(w_rest, static_cast<float>(T), y);
+  y = fmaf(w_self, self_term(p, o), y);
+  p.Y[o * p.y_stride] = y;
+}
+
 // A lane's run of N consecutive (col, code) entries as wide loads: N * 4 bytes of column ids (4-byte aligned) and N bytes of
 // hop codes (byte aligned; gfx950 runs HSA code in unaligned-access mode) instead of 2 N scalar loads.  With one lane per
 // row (W = 1: 16 entries per lane and round) the scalar loads were 32 of the 48 memory instructions of a round, each
@@ -352,6 +373,9 @@ __device__ __forceinline__ void slice_range(const Params& p, int64_t i, int a, i
 inline bool aligned(const void* ptr, size_t n) { return (reinterpret_cast<uintptr_t>(ptr) % n) == 0; }
 constexpr int kHotLdsFloats = 16384;   // 64 KB of hot operand rows per workgroup (the default dynamic-LDS limit): two workgroups per CU
 
+// the self_sum route as the classed rows, the blocked hubs and the pair stream need it: short-row runs declared, s_total set
+inline bool self_route_with_tiles(const gnan_spmm_args* a) { return a->self_sum && a->s_total && a->short_lmax > 0; }
+
 inline int validate(const gnan_spmm_args* a) {
   GNAN_REQUIRE(a != nullptr, "spmm: null args");
   GNAN_REQUIRE(a->n_rows >= 0 && a->n_cols >= 0, "spmm: negative size");
@@ -409,7 +433,7 @@ inline int validate(const gnan_spmm_args* a) {
   }
   if (a->seg_index) {
     // (one pair of requirements: the fields are read by the self_sum instance alone, over a well-formed plan)
-    if (!(a->self_sum && a->s_total && a->short_lmax > 0))
+    if (!self_route_with_tiles(a))
       return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: classed row segments are served on the self_sum route (short-row runs declared, "
                         "s_total set) only");
     GNAN_REQUIRE(a->seg_start && a->seg_row && a->cls_seg_ptr && a->seg_mask && a->n_seg > 0 && a->seg_max_per_class > 0 &&
@@ -419,7 +443,7 @@ inline int validate(const gnan_spmm_args* a) {
   }
   if (a->hub_index) {
     // (read by the self_sum instance alone, in place of a hub-row plan)
-    if (!(a->self_sum && a->s_total && a->short_lmax > 0 && a->n_long == 0 && a->cls_index == nullptr))
+    if (!(self_route_with_tiles(a) && a->n_long == 0 && a->cls_index == nullptr))
       return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: blocked hub segments are served on the self_sum route (short-row runs declared, "
                         "s_total set) without a hub-row plan only");
     GNAN_REQUIRE(a->hub_seg_start && a->hub_seg_row && a->hub_seg_slot && a->hub_row_slot_ptr && a->hub_cls_seg_ptr && a->n_hub > 0 &&
@@ -431,7 +455,7 @@ inline int validate(const gnan_spmm_args* a) {
   }
   if (a->stream_index) {
     // (read by the stream's own kernels and, as the skipped range, by the self_sum instance of spmm_kernel)
-    if (!(a->self_sum && a->s_total && a->short_lmax > 0))
+    if (!self_route_with_tiles(a))
       return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: the pair stream is served on the self_sum route (short-row runs declared, s_total set) only");
     GNAN_REQUIRE(a->stream_chunk > 0 && a->stream_chunk % 16 == 0, "spmm: the pair stream's chunk must be a positive multiple of 16 (got %d)",
                  a->stream_chunk);

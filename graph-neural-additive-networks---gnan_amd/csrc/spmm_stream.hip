@@ -131,17 +131,7 @@ __global__ __launch_bounds__(256) void spmm_stream_combine_kernel(const Params p
   const int s0 = sp.row_slot_ptr[r], s1 = sp.row_slot_ptr[r + 1];
   float y = 0.f;
   for (int s = s0; s < s1; ++s) y += sp.partial[sp.row_seg[s]];
-  double T = 0.0;
-  for (int f = 0; f < p.W; ++f) T += static_cast<double>(p.s_total[f]);
-  const int rest = p.D - 1;
-  const SmallW sw = small_weights(p, q);
-  const float w_rest = sw.pick(rest);
-  const float w_self = rest > 0 ? sw.w[0] - w_rest : 0.f;    // (the fold of rows_body)
-  const float w = sp.code < rest ? sw.pick(sp.code) - w_rest : 0.f;
-  y = w * y;
-  y = fmaf(w_rest, static_cast<float>(T), y);
-  y = fmaf(w_self, self_term(p, o), y);
-  p.Y[o * p.y_stride] = y;
+  combine_store<true>(p, q, o, y, sp.code);
 }
 
 StreamParams stream_params(const gnan_spmm_args* a) {

@@ -23,23 +23,18 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from . import wide_plans
+from .wide_plans import (CLASSED_HUB_THRESHOLD, CLASSED_SLICE_EDGES, HUB_CLASSES, LONG_ROW_THRESHOLD, PACK_SHIFT, SLICE_EDGES,  # noqa: F401
+                         STREAM_LAST, BlockedHubPlan, ClassedHubPlan, ClassedRowPlan, LongRowPlan, PairStreamPlan)
 
-LONG_ROW_THRESHOLD = 512   # rows with more listed pairs than this go through the slice kernel
-LONG_ROW_THRESHOLD_NARROW = 64   # ... for operand rows of one or two lanes: a single LANE walks such a row, and the few rows
+LONG_ROW_THRESHOLD_NARROW = 64   # the hub threshold for operand rows of one or two lanes: a single LANE walks such a row, and the few rows
                                  # of a few hundred pairs set the kernel's duration (arxiv-shaped backward: 127 -> 25 us)
 NARROW_PLAN_MAX_ROWS = 8192
-SLICE_EDGES = 2048         # pairs per slice of a hub row
-PACK_SHIFT = 29            # packed index entries: column id in the low 29 bits, hop code above (gnan_spmm_args.packed_index)
 HOT_COLUMNS_MIN = 16384     # ... and no fewer than this (smaller graphs: their hot values survive in L2 as they are)
 HOT_COLUMNS = 262144        # neighbours whose operand rows get a compact second copy (narrow operands, HopGraph.hot_columns)
 HOT_COLUMNS_MIN_NNZ = 1 << 24    # below this the two extra launches that fill the copy cost more than the gathers save
 HOT_COLUMNS_MIN_SHARE = 0.15     # ... and so does a graph whose K most listed neighbours receive less than this share of the pairs
-
-
 LONG_PLAN_IN_HIP = True     # HopGraph.long_row_plan() by gnan_long_row_plan_count / _fill
-HUB_CLASSES = 8                 # classed hub plan (HopGraph.classed_hub_plan): column class col & 7, one per XCD of the MI355X
-CLASSED_HUB_THRESHOLD = 512     # ... its hub rows: more listed pairs than this
-CLASSED_SLICE_EDGES = 2048      # ... pairs per slice of one (hub row, class)
 CLASSED_PLAN_IN_HIP = True      # ... by gnan_classed_plan_count / _fill (False: the framework route below; CPU tensors always)
 TRANSPOSE_IN_HIP = True     # HopGraph.transposed() by gnan_csr_transpose
 PB_PLAN_IN_HIP = True       # the pair-level work of HopGraph.pb_plan by gnan_pb_plan_* (False: framework ops; CPU tensors always)
@@ -76,125 +71,6 @@ class PbPlan:
 
 
 @dataclass
-class LongRowPlan:
-    """Hub rows of a CSR graph, cut into fixed-size slices (deterministic reduction order)."""
-    rows: Optional[torch.Tensor]        # int32 [n_long] output-row indices
-    slice_ptr: Optional[torch.Tensor]   # int32 [n_long + 1]
-    n_long: int = 0
-    n_slices: int = 0
-    threshold: int = LONG_ROW_THRESHOLD
-    slice_edges: int = SLICE_EDGES
-
-
-@dataclass
-class ClassedHubPlan(LongRowPlan):
-    """A hub-row plan whose slices each hold the pairs of ONE column class ``col & 7`` (``gnan_spmm_args.cls_*``): ``rows`` are
-    the hub slots, ``slice_ptr`` a slot's slices (class-major, so the fix-up adds them in a fixed order); the slots' pairs are
-    copied, stably partitioned by class, into ``index`` (``col | code << 29``); slice ``s`` covers ``index[slice_start[s],
-    slice_start[s + 1])`` of slot ``slice_row[s]``; slice workgroup ``b`` takes ``slot_slice[b]`` — entry ``b >> 3`` of class
-    ``b & 7``'s queue, ``-1`` past its end — so that the round-robin dispatch keeps a class on one XCD and its L2."""
-    index: Optional[torch.Tensor] = None         # int32 [pairs of the hub slots]
-    slice_start: Optional[torch.Tensor] = None   # int64 [n_slices + 1]
-    slice_row: Optional[torch.Tensor] = None     # int32 [n_slices]
-    slot_slice: Optional[torch.Tensor] = None    # int32 [n_slots]
-    n_slots: int = 0
-
-
-@dataclass
-class ClassedRowPlan:
-    """:meth:`HopGraph.classed_row_plan`: the pairs of rows ``[q_lo, q_hi)`` of a degree-sorted copy as SEGMENTS, one per (row,
-    column class ``col & 7``) that holds a pair (``gnan_spmm_args.seg_*``).  ``index`` (``col | code << 29``) is class-major, within
-    a class in row order, within a segment in the row's own pair order; segment ``s`` covers ``index[seg_start[s], seg_start[s + 1])``
-    of row ``seg_row[s]``; class ``c`` owns segments ``[cls_seg_ptr[c], cls_seg_ptr[c + 1])``; bit ``c`` of ``mask[q - q_lo]`` says
-    whether row ``q`` has a segment of class ``c``."""
-    q_lo: int
-    q_hi: int
-    min_pairs: int
-    n_seg: int
-    max_per_class: int            # segments of the largest class (sizes the launch)
-    index: torch.Tensor           # int32 [pairs of the classed rows]
-    seg_start: torch.Tensor       # int64 [n_seg + 1]
-    seg_row: torch.Tensor         # int32 [n_seg]
-    cls_seg_ptr: torch.Tensor     # int32 [9]
-    mask: torch.Tensor            # uint8 [q_hi - q_lo]
-
-
-@dataclass
-class BlockedHubPlan:
-    """:meth:`HopGraph.blocked_hub_plan`: the pairs of the hub rows ``[q_lo, n_rows)`` of a degree-sorted copy as SEGMENTS of at most
-    ``seg_pairs`` pairs of one (row, column class ``col & 7``, popularity block) each (``gnan_spmm_args.hub_*``).  ``index``
-    (``col | code << 29``) and the segments are in QUEUE order: class-major, within a class block-major, then by row, then by piece; a
-    segment keeps the row's own pair order.  Segment ``s`` covers ``index[seg_start[s], seg_start[s + 1])`` of row ``seg_row[s]``; class
-    ``c`` owns segments ``[cls_seg_ptr[c], cls_seg_ptr[c + 1])``; ``seg_slot[s]`` is the segment's place in the ROW-major enumeration
-    (row, class, block, piece), and row ``q_lo + r`` owns the slots ``[row_slot_ptr[r], row_slot_ptr[r + 1])``."""
-    q_lo: int
-    n_hub: int
-    block_rows: int
-    n_blocks: int                 # ranked blocks; block ``n_blocks`` is the cold remainder
-    seg_pairs: int
-    n_seg: int
-    max_per_class: int            # segments of the largest class (sizes the launch)
-    index: torch.Tensor           # int32 [pairs of the hub rows]
-    seg_start: torch.Tensor       # int64 [n_seg + 1]
-    seg_row: torch.Tensor         # int32 [n_seg]
-    seg_slot: torch.Tensor        # int32 [n_seg]
-    row_slot_ptr: torch.Tensor    # int32 [n_hub + 1]
-    cls_seg_ptr: torch.Tensor     # int32 [9]
-    block_pairs: list             # pairs per block, 0 .. n_blocks (for the record)
-    block_segs: list              # segments per block
-
-    @property
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.index, self.seg_start, self.seg_row, self.seg_slot, self.row_slot_ptr,
-                                                           self.cls_seg_ptr))
-
-
-STREAM_LAST = 1 << 31             # PairStreamPlan.index: "last pair of its segment" (the packed entry's top bit; codes stay below 4)
-
-
-@dataclass
-class PairStreamPlan:
-    """:meth:`HopGraph.pair_stream_plan`: the pairs of rows ``[q_lo, q_hi)`` of a degree-sorted copy as one STREAM per column class
-    ``col & 7`` (``gnan_spmm_args.stream_*``).  ``index`` is class-major, within a class by popularity block, then by row, a row's
-    pairs in their own order; class ``c`` owns the pairs ``[cls_pair_ptr[c], cls_pair_ptr[c + 1])``, cut into chunks of ``chunk_pairs``
-    entries (the class's last chunk may be shorter): chunks ``[cls_chunk_ptr[c], cls_chunk_ptr[c + 1])``.  A SEGMENT is a maximal run of
-    one row inside one chunk; its last entry carries :data:`STREAM_LAST`.  ``chunk_first_seg[t]`` is the first segment of chunk ``t`` in
-    queue order, the enumeration the kernel stores its partials in (segment ``s`` at ``partial[s]``).  ``row_seg[row_slot_ptr[r] ..
-    row_slot_ptr[r + 1])`` are the queue-order numbers of row ``q_lo + r``'s segments, ascending: what the combine reads.  ``seg_slot``
-    (computed on demand, not held) is the inverse permutation, segment ``s``'s place in the ROW-major enumeration (row, then queue
-    order).  Every pair of the stream carries the hop code ``code``."""
-    q_lo: int
-    q_hi: int
-    min_pairs: int
-    block_rows: int
-    n_blocks: int                 # ranked blocks; block ``n_blocks`` is the cold remainder
-    chunk_pairs: int
-    code: int
-    n_seg: int
-    n_chunks: int
-    max_chunks_per_class: int     # chunks of the largest class (sizes the launch)
-    index: torch.Tensor           # int32 [pairs of the stream rows]
-    cls_pair_ptr: torch.Tensor    # int32 [9]
-    cls_chunk_ptr: torch.Tensor   # int32 [9]
-    chunk_first_seg: torch.Tensor  # int32 [n_chunks]
-    row_seg: torch.Tensor         # int32 [n_seg] a permutation
-    row_slot_ptr: torch.Tensor    # int32 [q_hi - q_lo + 1]
-    block_pairs: list             # pairs per block, 0 .. n_blocks (for the record)
-
-    @property
-    def seg_slot(self) -> torch.Tensor:
-        """int32 [n_seg]: the inverse of ``row_seg`` (the library does not read it; built per call)."""
-        slot = torch.empty_like(self.row_seg)
-        slot[self.row_seg.long()] = torch.arange(self.n_seg, dtype=torch.int32, device=self.row_seg.device)
-        return slot
-
-    @property
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.index, self.cls_pair_ptr, self.cls_chunk_ptr, self.chunk_first_seg,
-                                                           self.row_seg, self.row_slot_ptr))
-
-
-@dataclass
 class SelfFreePlan:
     """:meth:`HopGraph.self_free_plan`: the graph without its rows' self pairs, and which nodes its remaining pairs list."""
     twin: "HopGraph"              # same rows, the pair (i, i, code 0) removed from every row; ``cnt`` IS the graph's tensor
@@ -227,11 +103,8 @@ class HopGraph:
     _degree_plan: Optional[LongRowPlan] = field(default=None, repr=False)
     _dense_plans: dict = field(default_factory=dict, repr=False)
     _plans: dict = field(default_factory=dict, repr=False)          # hub-row plans by threshold (other than the default)
-    _classed: dict = field(default_factory=dict, repr=False)        # classed_hub_plan(): (order, threshold, slice_edges) -> plan
+    _wide: dict = field(default_factory=dict, repr=False)           # the classed and blocked plans: (kind, *parameters) -> plan or None
     _short_runs: dict = field(default_factory=dict, repr=False)     # short_row_runs(): lmax -> ShortRowRuns
-    _classed_rows: dict = field(default_factory=dict, repr=False)   # classed_row_plan(): (min_pairs, max_pairs) -> plan or None
-    _blocked_hubs: dict = field(default_factory=dict, repr=False)   # blocked_hub_plan(): its parameters -> plan or None
-    _pair_streams: dict = field(default_factory=dict, repr=False)   # pair_stream_plan(): its parameters -> plan or None
     _sorted_copy: Optional["HopGraph"] = field(default=None, repr=False)
     _hot: Optional[tuple] = field(default=None, repr=False)           # hot_columns(): (ids or None,)
     _sorted_copy_hot: Optional["HopGraph"] = field(default=None, repr=False)
@@ -429,7 +302,7 @@ class HopGraph:
         if row_ids is None and LONG_PLAN_IN_HIP and self.rowptr.is_cuda and 0 < self.n_rows < 2 ** 31:
             plan = self._long_row_plan_hip(threshold)
         else:
-            plan = self._long_row_plan_torch(row_ids, threshold)
+            plan = wide_plans.long_row_plan(self, row_ids, threshold)
         if row_ids is None:
             if threshold == LONG_ROW_THRESHOLD:
                 self._plan = plan
@@ -438,7 +311,7 @@ class HopGraph:
         return plan
 
     def _long_row_plan_hip(self, threshold: int) -> LongRowPlan:
-        """gnan_long_row_plan_count / _fill (csrc/graph_build.hip): the same arrays as the framework route below."""
+        """gnan_long_row_plan_count / _fill (csrc/graph_build.hip): the same arrays as ``wide_plans.long_row_plan``."""
         L, dev = _lib.lib(), self.device
         need = L.gnan_long_row_plan_workspace_bytes(self.n_rows)
         ws = torch.empty((need + 255) // 256 * 64, dtype=torch.int32, device=dev)
@@ -456,47 +329,35 @@ class HopGraph:
                                              ws.numel() * 4, _lib.ptr(rows), _lib.ptr(ptr), st), "gnan_long_row_plan_fill")
         return LongRowPlan(rows, ptr, n_long, int(ptr[-1].item()), threshold=threshold)
 
-    def _long_row_plan_torch(self, row_ids, threshold: int) -> LongRowPlan:
-        deg = (self.rowptr[1:] - self.rowptr[:-1])
-        if row_ids is not None:
-            deg = deg[row_ids.long()]
-        long_rows = torch.nonzero(deg > threshold).flatten()
-        n_long = int(long_rows.numel())
-        if n_long == 0:
-            plan = LongRowPlan(None, None, threshold=threshold)
-        else:
-            n_sl = (deg[long_rows] + SLICE_EDGES - 1) // SLICE_EDGES
-            ptr = torch.zeros(n_long + 1, dtype=torch.int64, device=self.device)
-            ptr[1:] = torch.cumsum(n_sl, 0)
-            plan = LongRowPlan(long_rows.to(torch.int32), ptr.to(torch.int32), n_long, int(ptr[-1]), threshold=threshold)
-        return plan
+    def _cached(self, key: tuple, build):        # _wide[key], built once (a plan or None)
+        if key not in self._wide:
+            self._wide[key] = build()
+        return self._wide[key]
 
     def classed_hub_plan(self, row_ids: Optional[torch.Tensor] = None, threshold: Optional[int] = None,
                          slice_edges: Optional[int] = None) -> Optional[LongRowPlan]:
         """The hub rows of :meth:`long_row_plan` (``row_ids``: slot ``q`` is adjacency row ``row_ids[q]``) as a
         :class:`ClassedHubPlan`, the plain plan when there are no hub rows, ``None`` where the packed entries cannot hold the
         graph (dense, more than 2^29 neighbours or 8 codes).  Cached for the identity order and for :meth:`degree_schedule`'s."""
-        if self.is_dense or self.n_cols > (1 << PACK_SHIFT) or self.n_codes > 8:
+        if not wide_plans.holds_packed(self, 8, int32_pairs=False):
             return None
         threshold = CLASSED_HUB_THRESHOLD if threshold is None else threshold
         slice_edges = CLASSED_SLICE_EDGES if slice_edges is None else slice_edges
         order = "id" if row_ids is None else ("degree" if row_ids is self._degree_order else None)
-        key = (order, int(threshold), int(slice_edges))
-        if order is not None and key in self._classed:
-            return self._classed[key]
-        base = self.long_row_plan(row_ids, threshold)
-        if base.n_long == 0:
-            plan = base
-        elif CLASSED_PLAN_IN_HIP and self.rowptr.is_cuda and self.nnz < 2 ** 31:
-            plan = self._classed_hub_plan_hip(base, row_ids, slice_edges)
-        else:
-            plan = self._classed_hub_plan_torch(base, row_ids, slice_edges)
+        key = ("classed_hubs", order, int(threshold), int(slice_edges))
+        if order is not None and key in self._wide:
+            return self._wide[key]
+        plan = self.long_row_plan(row_ids, threshold)
+        if plan.n_long > 0 and CLASSED_PLAN_IN_HIP and self.rowptr.is_cuda and self.nnz < 2 ** 31:
+            plan = self._classed_hub_plan_hip(plan, row_ids, slice_edges)
+        elif plan.n_long > 0:
+            plan = wide_plans.classed_hub_plan(self, plan, row_ids, slice_edges)
         if order is not None:
-            self._classed[key] = plan
+            self._wide[key] = plan
         return plan
 
     def _classed_hub_plan_hip(self, base: LongRowPlan, row_ids, slice_edges: int) -> ClassedHubPlan:
-        """gnan_classed_plan_count / _fill (csrc/graph_build.hip): the same arrays as the framework route below."""
+        """gnan_classed_plan_count / _fill (csrc/graph_build.hip): the same arrays as ``wide_plans.classed_hub_plan``."""
         L, dev = _lib.lib(), self.device
         n_long = int(base.n_long)
         need = L.gnan_classed_plan_workspace_bytes(n_long)
@@ -522,228 +383,33 @@ class HopGraph:
                               index=index[:pairs], slice_start=slice_start, slice_row=slice_row, slot_slice=slot_slice,
                               n_slots=int(slot_slice.numel()))
 
-    def _classed_hub_plan_torch(self, base: LongRowPlan, row_ids, slice_edges: int) -> ClassedHubPlan:
-        dev, K, SE = self.device, HUB_CLASSES, int(slice_edges)
-        q = base.rows.long()
-        i = row_ids.long()[q] if row_ids is not None else q
-        rp = self.rowptr.long()
-        lo, deg = rp[i], rp[i + 1] - rp[i]
-        R = int(q.numel())
-        slot = torch.repeat_interleave(torch.arange(R, device=dev), deg)
-        first = torch.cumsum(deg, 0) - deg
-        e = lo[slot] + torch.arange(int(slot.numel()), device=dev) - first[slot]
-        c = self.col[e].long()
-        v = c | (self.code[e].long() << PACK_SHIFT)
-        key = slot * K + (c & (K - 1))
-        index = torch.where(v >= (1 << 31), v - (1 << 32), v)[torch.argsort(key, stable=True)].to(torch.int32)
-        cnt = torch.bincount(key, minlength=R * K)
-        nsl = (cnt + SE - 1) // SE
-        pair_off = torch.cumsum(cnt, 0) - cnt
-        slice_off = torch.cumsum(nsl, 0) - nsl
-        n_slices = int(nsl.sum())
-        t = torch.repeat_interleave(torch.arange(R * K, device=dev), nsl)              # (slot, class) of every slice
-        j = torch.arange(n_slices, device=dev) - slice_off[t]
-        slice_start = torch.cat([pair_off[t] + j * SE, cnt.sum().view(1)])
-        g = t % K
-        pos = torch.empty(n_slices, dtype=torch.int64, device=dev)                    # place in its class's queue (slice order)
-        longest = 0
-        for k in range(K):
-            m = torch.nonzero(g == k).flatten()
-            pos[m] = torch.arange(int(m.numel()), device=dev)
-            longest = max(longest, int(m.numel()))
-        slot_slice = torch.full((K * longest,), -1, dtype=torch.int32, device=dev)
-        slot_slice[pos * K + g] = torch.arange(n_slices, dtype=torch.int32, device=dev)
-        slice_ptr = torch.cat([slice_off.view(R, K)[:, 0], torch.tensor([n_slices], device=dev)]).to(torch.int32)
-        return ClassedHubPlan(base.rows, slice_ptr, R, n_slices, threshold=base.threshold, slice_edges=SE, index=index,
-                              slice_start=slice_start, slice_row=(t // K).to(torch.int32), slot_slice=slot_slice,
-                              n_slots=K * longest)
-
     def classed_row_plan(self, min_pairs: int, max_pairs: int = LONG_ROW_THRESHOLD) -> Optional[ClassedRowPlan]:
-        """The rows of ``min_pairs .. max_pairs`` listed pairs of a DEGREE-SORTED copy (rows shortest first: they are one range
-        ``[q_lo, q_hi)``, and so are their pairs) cut into one segment per (row, column class): :class:`ClassedRowPlan`.  ``None``
-        where no row qualifies or the packed entries cannot hold the graph.  Framework ops on the graph's device (a stable sort of
-        the range's pairs by (class, row)); cached per graph."""
+        """The rows of ``min_pairs .. max_pairs`` listed pairs of a DEGREE-SORTED copy (rows shortest first: one range ``[q_lo, q_hi)``,
+        and so are their pairs) cut into one segment per (row, column class): :class:`ClassedRowPlan`; ``None`` where no row qualifies
+        or the packed entries cannot hold the graph.  Framework ops on the graph's device (``wide_plans``); cached per graph."""
         key = (int(min_pairs), int(max_pairs))
-        if key in self._classed_rows:
-            return self._classed_rows[key]
-        plan = None
-        if not self.is_dense and self.n_cols <= (1 << PACK_SHIFT) and self.n_codes <= 8 and self.n_rows > 0 and self.nnz < 2 ** 31:
-            plan = self._classed_row_plan_torch(*key)
-        self._classed_rows[key] = plan
-        return plan
+        return self._cached(("classed_rows", *key), lambda: wide_plans.classed_row_plan(self, *key)
+                            if wide_plans.holds_packed(self) and self.n_rows > 0 else None)
 
-    def _classed_row_plan_torch(self, min_pairs: int, max_pairs: int) -> Optional[ClassedRowPlan]:
-        dev, K = self.device, HUB_CLASSES
-        rp = self.rowptr.long()
-        deg = rp[1:] - rp[:-1]
-        if bool((deg[1:] < deg[:-1]).any()):
-            raise ValueError("classed_row_plan needs a degree-sorted copy (rows shortest first)")
-        q_lo, q_hi = (int(v) for v in torch.searchsorted(deg, torch.tensor([min_pairs, max_pairs + 1], device=dev)).tolist())
-        R = q_hi - q_lo
-        if R <= 0:
-            return None
-        e0, e1 = int(rp[q_lo]), int(rp[q_hi])
-        if self.colp is not None:
-            v = self.colp[e0:e1]
-        else:
-            w = self.col[e0:e1].long() | (self.code[e0:e1].long() << PACK_SHIFT)
-            v = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
-        row = torch.repeat_interleave(torch.arange(R, device=dev), deg[q_lo:q_hi])
-        key = (self.col[e0:e1].long() & (K - 1)) * R + row                    # class-major, then row; the sort keeps a row's order
-        index = v[torch.argsort(key, stable=True)].contiguous()
-        cnt = torch.bincount(key, minlength=K * R)
-        del key, row
-        seg = torch.nonzero(cnt).flatten()                                   # (class, row) of every segment, in plan order
-        n_seg = int(seg.numel())
-        seg_start = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-        seg_start[1:] = torch.cumsum(cnt[seg], 0)
-        cls_ptr = torch.searchsorted(seg, torch.arange(K + 1, device=dev) * R)
-        has = (cnt.view(K, R) > 0).long()
-        mask = (has << torch.arange(K, device=dev).view(K, 1)).sum(0).to(torch.uint8)
-        return ClassedRowPlan(q_lo, q_hi, int(min_pairs), n_seg, int((cls_ptr[1:] - cls_ptr[:-1]).max()), index, seg_start,
-                              (seg % R + q_lo).to(torch.int32), cls_ptr.to(torch.int32), mask.contiguous())
+    column_blocks = wide_plans.column_blocks      # (block_rows, n_blocks) -> the popularity block of every column
 
-    def column_blocks(self, block_rows: int, n_blocks: int) -> torch.Tensor:
-        """Popularity block of every column (int64 ``[n_cols]``): the columns of one class ``col & 7`` ranked by how often the graph's
-        pairs list them — most listed first, ties by column id — ``block_rows`` to a block; ranks from ``block_rows * n_blocks`` on
-        share block ``n_blocks``, the cold remainder."""
-        dev, K = self.device, HUB_CLASSES
-        listed = torch.bincount(self.col.long(), minlength=self.n_cols)
-        by_count = torch.argsort(listed, descending=True, stable=True)              # ties keep the ascending column id
-        order = by_count[torch.argsort(by_count & (K - 1), stable=True)]             # class-major, a class's columns by rank
-        cls_first = torch.cumsum(torch.bincount(order & (K - 1), minlength=K), 0)
-        cls_first = torch.cat([cls_first.new_zeros(1), cls_first[:-1]])
-        rank = torch.empty(self.n_cols, dtype=torch.int64, device=dev)
-        rank[order] = torch.arange(self.n_cols, device=dev) - cls_first[order & (K - 1)]
-        return torch.clamp(rank // int(block_rows), max=int(n_blocks))
-
-    def blocked_hub_plan(self, block_rows: int, n_blocks: int, seg_pairs: int,
-                         threshold: int = LONG_ROW_THRESHOLD) -> Optional[BlockedHubPlan]:
+    def blocked_hub_plan(self, block_rows: int, n_blocks: int, seg_pairs: int, threshold: int = LONG_ROW_THRESHOLD) -> Optional[BlockedHubPlan]:
         """The rows of more than ``threshold`` listed pairs of a DEGREE-SORTED copy (its last rows) cut into segments by (row, column
-        class, popularity block of :meth:`column_blocks`), a run of more than ``seg_pairs`` pairs into pieces: :class:`BlockedHubPlan`.
-        ``None`` without such a row or where the packed entries cannot hold the graph.  Framework ops on the graph's device (stable
-        sorts of the hub rows' pairs and of the columns' counts); cached per graph and parameter set."""
+        class, popularity block of :meth:`column_blocks`), a run of more than ``seg_pairs`` pairs into pieces: :class:`BlockedHubPlan`;
+        ``None`` without such a row or where the packed entries cannot hold the graph.  Cached per graph and parameter set."""
         key = (int(block_rows), int(n_blocks), int(seg_pairs), int(threshold))
-        if key in self._blocked_hubs:
-            return self._blocked_hubs[key]
-        plan = None
-        if (not self.is_dense and self.n_cols <= (1 << PACK_SHIFT) and self.n_codes <= 8 and self.n_rows > 0 and self.nnz < 2 ** 31
-                and min(key[:3]) >= 1):
-            plan = self._blocked_hub_plan_torch(*key)
-        self._blocked_hubs[key] = plan
-        return plan
-
-    def _blocked_hub_plan_torch(self, block_rows: int, n_blocks: int, cap: int, threshold: int) -> Optional[BlockedHubPlan]:
-        dev, K, NB = self.device, HUB_CLASSES, n_blocks + 1
-        rp = self.rowptr.long()
-        deg = rp[1:] - rp[:-1]
-        if bool((deg[1:] < deg[:-1]).any()):
-            raise ValueError("blocked_hub_plan needs a degree-sorted copy (rows shortest first)")
-        q_lo = int(torch.searchsorted(deg, torch.tensor([threshold + 1], device=dev)))
-        R = self.n_rows - q_lo
-        if R <= 0:
-            return None
-        e0 = int(rp[q_lo])
-        c = self.col[e0:].long()
-        if self.colp is not None:
-            v = self.colp[e0:]
-        else:
-            w = c | (self.code[e0:].long() << PACK_SHIFT)
-            v = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
-        blk = self.column_blocks(block_rows, n_blocks)[c]
-        row = torch.repeat_interleave(torch.arange(R, device=dev), deg[q_lo:])
-        key = (((c & (K - 1)) * NB + blk) * R + row)                       # class, block, row; the sort keeps a row's pair order
-        block_pairs = torch.bincount(blk, minlength=NB).tolist()
-        del c, blk, row
-        index = v[torch.argsort(key, stable=True)].contiguous()
-        cnt = torch.bincount(key, minlength=K * NB * R)
-        del key
-        run = torch.nonzero(cnt).flatten()                                 # (class, block, row) of every run, in queue order
-        pieces = (cnt[run] + cap - 1) // cap
-        pair_off = torch.cumsum(cnt[run], 0) - cnt[run]
-        n_seg = int(pieces.sum())
-        t = torch.repeat_interleave(torch.arange(int(run.numel()), device=dev), pieces)      # the run of every segment
-        j = torch.arange(n_seg, device=dev) - (torch.cumsum(pieces, 0) - pieces)[t]          # ... and which piece of it
-        seg_start = torch.cat([pair_off[t] + j * cap, cnt.sum().view(1)])
-        seg_key = run[t]
-        seg_r, seg_cb = seg_key % R, seg_key // R
-        cls_ptr = torch.searchsorted(seg_key, torch.arange(K + 1, device=dev) * (NB * R))
-        # the row-major enumeration (row, class, block, piece): a stable sort of the queue order by (row, class, block) keeps the pieces
-        by_row = torch.argsort(seg_r * (K * NB) + seg_cb, stable=True)
-        seg_slot = torch.empty(n_seg, dtype=torch.int64, device=dev)
-        seg_slot[by_row] = torch.arange(n_seg, device=dev)
-        row_slot_ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-        row_slot_ptr[1:] = torch.cumsum(torch.bincount(seg_r, minlength=R), 0)
-        return BlockedHubPlan(q_lo, R, int(block_rows), int(n_blocks), int(cap), n_seg, int((cls_ptr[1:] - cls_ptr[:-1]).max()), index,
-                              seg_start, (seg_r + q_lo).to(torch.int32), seg_slot.to(torch.int32), row_slot_ptr.to(torch.int32),
-                              cls_ptr.to(torch.int32), block_pairs, torch.bincount(seg_cb % NB, minlength=NB).tolist())
+        return self._cached(("blocked_hubs", *key), lambda: wide_plans.blocked_hub_plan(self, *key)
+                            if wide_plans.holds_packed(self) and self.n_rows > 0 and min(key[:3]) >= 1 else None)
 
     def pair_stream_plan(self, min_pairs: int, block_rows: int, n_blocks: int, chunk_pairs: int,
                          max_pairs: int = LONG_ROW_THRESHOLD) -> Optional[PairStreamPlan]:
         """The pairs of the rows of ``min_pairs .. max_pairs`` listed pairs of a DEGREE-SORTED copy (one range ``[q_lo, q_hi)``) as a
         stream per column class, ordered by popularity block of :meth:`column_blocks`, then by row, and cut into chunks of
-        ``chunk_pairs`` entries: :class:`PairStreamPlan`.  ``None`` where no row qualifies, the pairs of the range carry more than one
-        hop code (the stream applies one weight per row, in its combine), ``chunk_pairs`` is no positive multiple of 16, or the
-        packed entries cannot hold the graph.  Framework ops on the graph's device (a stable sort of the range's pairs); cached per
-        graph and parameter set."""
+        ``chunk_pairs`` entries: :class:`PairStreamPlan`, cached.  ``None`` where no row qualifies, the range's pairs carry more than one hop
+        code (one weight per row, in the combine), ``chunk_pairs`` is no positive multiple of 16, or the packed entries cannot hold the graph."""
         key = (int(min_pairs), int(block_rows), int(n_blocks), int(chunk_pairs), int(max_pairs))
-        if key in self._pair_streams:
-            return self._pair_streams[key]
-        plan = None
-        if (not self.is_dense and self.n_cols <= (1 << PACK_SHIFT) and self.n_codes <= 4 and self.n_rows > 0 and self.nnz < 2 ** 31
-                and min(key[:4]) >= 1 and key[3] % 16 == 0):
-            plan = self._pair_stream_plan_torch(*key)
-        self._pair_streams[key] = plan
-        return plan
-
-    def _pair_stream_plan_torch(self, min_pairs: int, block_rows: int, n_blocks: int, chunk: int, max_pairs: int) -> Optional[PairStreamPlan]:
-        dev, K, NB = self.device, HUB_CLASSES, n_blocks + 1
-        rp = self.rowptr.long()
-        deg = rp[1:] - rp[:-1]
-        if bool((deg[1:] < deg[:-1]).any()):
-            raise ValueError("pair_stream_plan needs a degree-sorted copy (rows shortest first)")
-        q_lo, q_hi = (int(v) for v in torch.searchsorted(deg, torch.tensor([min_pairs, max_pairs + 1], device=dev)).tolist())
-        R = q_hi - q_lo
-        if R <= 0:
-            return None
-        e0, e1 = int(rp[q_lo]), int(rp[q_hi])
-        codes = self.code[e0:e1]
-        code = int(codes[0])
-        if bool((codes != code).any()):
-            return None
-        c = self.col[e0:e1].long()
-        blk = self.column_blocks(block_rows, n_blocks)[c]
-        row = torch.repeat_interleave(torch.arange(R, device=dev), deg[q_lo:q_hi])
-        key = ((c & (K - 1)) * NB + blk) * R + row                         # class, block, row; the sort keeps a row's pair order
-        block_pairs = torch.bincount(blk, minlength=NB).tolist()
-        order = torch.argsort(key, stable=True)
-        key, v = key[order], (c | (code << PACK_SHIFT))[order]
-        del c, blk, row, order
-        P = int(key.numel())
-        cls, row = key // (NB * R), key % R
-        cls_pair_ptr = torch.searchsorted(key, torch.arange(K + 1, device=dev) * (NB * R))
-        n_chunk_cls = (cls_pair_ptr[1:] - cls_pair_ptr[:-1] + chunk - 1) // chunk
-        cls_chunk_ptr = torch.cat([n_chunk_cls.new_zeros(1), torch.cumsum(n_chunk_cls, 0)])
-        pos = torch.arange(P, device=dev) - cls_pair_ptr[cls]               # place in its class's queue
-        first = pos % chunk == 0                                            # (a class starts a chunk)
-        first[1:] |= row[1:] != row[:-1]
-        last = torch.ones(P, dtype=torch.bool, device=dev)
-        last[:-1] = first[1:]
-        seg_of_pair = torch.cumsum(first, 0) - 1
-        n_seg = int(seg_of_pair[-1]) + 1
-        n_chunks = int(cls_chunk_ptr[-1])
-        t_cls = torch.repeat_interleave(torch.arange(K, device=dev), n_chunk_cls)
-        chunk_pair = cls_pair_ptr[t_cls] + (torch.arange(n_chunks, device=dev) - cls_chunk_ptr[t_cls]) * chunk
-        chunk_first_seg = seg_of_pair[chunk_pair]
-        seg_row = row[first]
-        row_seg = torch.argsort(seg_row, stable=True)                      # row by row, a row's segments in queue order
-        row_slot_ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-        row_slot_ptr[1:] = torch.cumsum(torch.bincount(seg_row, minlength=R), 0)
-        v = v | (last.long() << 31)
-        index = torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32).contiguous()
-        return PairStreamPlan(q_lo, q_hi, int(min_pairs), int(block_rows), int(n_blocks), int(chunk), code, n_seg, n_chunks,
-                              int(n_chunk_cls.max()), index, cls_pair_ptr.to(torch.int32), cls_chunk_ptr.to(torch.int32),
-                              chunk_first_seg.to(torch.int32), row_seg.to(torch.int32), row_slot_ptr.to(torch.int32), block_pairs)
+        return self._cached(("pair_stream", *key), lambda: wide_plans.pair_stream_plan(self, *key)
+                            if wide_plans.holds_packed(self, 4) and self.n_rows > 0 and min(key[:4]) >= 1 and key[3] % 16 == 0 else None)
 
     def narrow_row_plan(self) -> LongRowPlan:
         """Hub-row plan for operand rows of one or two lanes: the low threshold while only a FEW rows exceed it (the tail
