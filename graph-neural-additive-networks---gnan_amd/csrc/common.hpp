@@ -27,6 +27,17 @@ inline int check_launch(const char* what) {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// compute units of the current device (256 where it cannot be asked)
+inline int cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return cus;
+}
+
 // True in exactly ONE workgroup of the grid: the last to get here.  `counter` is zero before the first launch of the pass and the
 // last workgroup leaves it zero (no fill per launch: a captured hipMemset replays once on this runtime, csrc/graph_fix.hip).  What
 // the other workgroups stored before the call is visible to the last one after it.  One thread per workgroup fences: an agent-scope

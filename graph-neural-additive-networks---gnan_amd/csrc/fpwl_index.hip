@@ -1,6 +1,6 @@
 // Shape functions by DIRECT-INDEX table look-up (gfx950): the piece of x is found by arithmetic, not by a search.
 //
-// fpwl_fast_kernel (csrc/fpwl.hip) walks an 8-level search tree per look-up: ~10 dependent LDS round trips and ~38 vector
+// fpwl_fast_kernel (csrc/fpwl_fast.hip) walks an 8-level search tree per look-up: ~10 dependent LDS round trips and ~38 vector
 // instructions, which — not HBM — set its time (SQ counters, profiles/r04_sq_fpwl.csv).  Here every feature gets a
 // uniform grid of B buckets over the range the data actually takes (`range`, one column min / max pass per feature
 // matrix: a HINT — any x is looked up exactly, see below), and a table entry per bucket:
@@ -30,13 +30,13 @@
 // gives 0.98-1.18 ms for half lines (FGX = 16, what fpwl_fast_kernel does) against 0.90 ms for full lines on the
 // 10M x 64 matrix (a framework element-wise kernel: 0.86).  The x rows of the next round are requested before the
 // current round's look-ups.  Column sums / feature sum / kept pieces in the epilogue as in fpwl_fast_kernel.
-#include "common.hpp"
+#include "fpwl_common.hpp"
 #include "fpwl_bucket.hpp"
 
 #include <cstdint>
-#include <type_traits>
 
 namespace {
+using namespace gnan::fpwl;
 
 constexpr int FPT = 4;
 
@@ -64,21 +64,8 @@ struct IndexParams {
   const uint32_t* row_keep;  // SELF instances: a bit per node, clear = the node's row is not stored (gnan_fpwl_args.row_keep), or NULL
 };
 
-typedef __attribute__((address_space(3))) const float lds_cfloat;
-typedef __attribute__((address_space(3))) const uint16_t lds_cu16;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) const f32x2_t lds_cfloat2;
-__device__ __forceinline__ float lds_f32(int addr) { return *reinterpret_cast<lds_cfloat*>(static_cast<uintptr_t>(static_cast<unsigned>(addr))); }
+typedef __attribute__((address_space(3))) const uint16_t lds_cu16;    // (the other raw LDS reads: csrc/fpwl_common.hpp)
 __device__ __forceinline__ int lds_u16(int addr) { return *reinterpret_cast<lds_cu16*>(static_cast<uintptr_t>(static_cast<unsigned>(addr))); }
-__device__ __forceinline__ float2 lds_f32x2(int addr) {
-  const f32x2_t v = *reinterpret_cast<lds_cfloat2*>(static_cast<uintptr_t>(static_cast<unsigned>(addr)));
-  return make_float2(v.x, v.y);
-}
-
-__device__ __forceinline__ unsigned bf16_bits(float f) {      // round-to-nearest-even, as torch.bfloat16
-  const unsigned u = __float_as_uint(f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // v + (the value of lane ^ 1 / lane ^ 2 / the mirrored lane of the 8-lane half row) as DPP operands of the VALU: the row sums of the
 // SELF instances must stay off the LDS pipe, which bounds this kernel (__shfl_xor is a ds_bpermute_b32: three more LDS operations
@@ -157,7 +144,7 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
   static_assert(FG == 16 || FG == 32, "feature groups of 16 (half lines) or 32 (full lines)");
   constexpr int TPN = FG / FPT, B = 1 << LOGB, NODES = BS / TPN;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)smem));
+  const unsigned lds_base = lds_address(smem);
   constexpr int kTableBytes = FG * B * 2;
   const int a_pairs = p.tot_cap + FG * KF;                       // anchor pairs (a_i, a_{i+1}), 8 bytes each
   float2* an_l = reinterpret_cast<float2*>(smem + kTableBytes / 4);
@@ -174,11 +161,7 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
   // group order by sum_groups_kernel (walking the nine groups of a 144-feature model inside each of 662 small workgroups paid
   // nine LDS images per 256 nodes and left most of the chip idle: 94 us for 24M look-ups)
   const bool split = SUM && p.part != nullptr;
-  if (!SUM || split) {                              // (id % 8) = XCD, groups of a node block adjacent inside it (FG = 16: shared lines)
-    const int64_t id = blockIdx.x;
-    g_first = static_cast<int>((id >> 3) % p.n_groups);
-    nb = ((id >> 3) / p.n_groups) * 8 + (id & 7);
-  }
+  if (!SUM || split) xcd_block(blockIdx.x, p.n_groups, nb, g_first);   // (FG = 16: the groups of a node block share lines)
   const int64_t n_lo = nb * p.nodes_per_block;
   if (n_lo >= p.n) return;
   const int64_t n_hi = n_lo + p.nodes_per_block < p.n ? n_lo + p.nodes_per_block : p.n;
@@ -298,11 +281,7 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
       } else {
         float4 r = make_float4(y[0], y[1], y[2], y[3]);
         if constexpr (OUT16) {
-          const unsigned b0 = bf16_bits(r.x), b1 = bf16_bits(r.y), b2 = bf16_bits(r.z), b3 = bf16_bits(r.w);
-          uint16_t* o16 = reinterpret_cast<uint16_t*>(p.out) + n * p.out_stride + (k0 + q * FPT);
-          *reinterpret_cast<uint2*>(o16) = make_uint2(b0 | (b1 << 16), b2 | (b3 << 16));
-          r = make_float4(__uint_as_float(b0 << 16), __uint_as_float(b1 << 16), __uint_as_float(b2 << 16),
-                          __uint_as_float(b3 << 16));
+          r = store_bf16_quad(reinterpret_cast<uint16_t*>(p.out) + n * p.out_stride + (k0 + q * FPT), r);
         } else {
           if (!SELF || keep) *reinterpret_cast<float4*>(p.out + n * p.out_stride + k0 + q * FPT) = r;
         }
@@ -413,6 +392,8 @@ __global__ __launch_bounds__(BS) void fpwl_index_kernel(const IndexParams p) {
       }
     }
     if constexpr (!SUM) {
+      // block_column_sums (csrc/fpwl_common.hpp), written out: through the helper four rows instances took two registers fewer
+      // and every one other code (profiles/r21_fpwl_split_code_objects.txt); this kernel keeps its registers
       if (p.col_partial) {   // fixed-order workgroup reduction: NODES node slots per feature, float64 (as fpwl_fast_kernel)
         float* red = smem;
         __syncthreads();
@@ -471,17 +452,6 @@ __global__ __launch_bounds__(256) void sum_total_final_kernel(const double* __re
   if (threadIdx.x == 0) total[0] = static_cast<float>(red[0]);
 }
 
-int cu_count_() {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 struct IndexPlan {
   bool ok;
   bool split;              // feature sum with a workgroup per (node block, group) + sum_groups_kernel
@@ -515,12 +485,12 @@ IndexPlan index_plan(const gnan_fpwl_args* a) {
   pl.fg = (a->F % 32 == 0 && !(a->flags & GNAN_FPWL_INDEX_HALF_LINES)) ? 32 : 16;
   pl.tot_cap = a->max_group_pieces * (pl.fg / 16);      // (max_group_pieces: the largest run of 16 consecutive features)
   pl.lds = image_bytes(pl.fg, pl.logb, pl.tot_cap);
-  if (pl.fg == 32 && pl.lds > 150 * 1024) {
+  if (pl.fg == 32 && pl.lds > kMaxLds) {
     pl.fg = 16;
     pl.tot_cap = a->max_group_pieces;
     pl.lds = image_bytes(16, pl.logb, pl.tot_cap);
   }
-  if (pl.lds > 150 * 1024) return pl;
+  if (pl.lds > kMaxLds) return pl;
   // measured on the 10M x 64 matrix (tools/lookup_ab.py): per-feature rows 0.99 ms / bf16 rows 0.82 ms with 512 threads
   // against 1.01 / 0.95 with 1024; the feature sum the other way round (0.97 against 0.69: its 8-lane sums and the
   // read-modify-write of the output want the 16 waves)
@@ -533,41 +503,13 @@ IndexPlan index_plan(const gnan_fpwl_args* a) {
              a->sum_workspace_bytes >= static_cast<size_t>(n_groups) * static_cast<size_t>(a->n) * sizeof(float);
   if (pl.split) {
     pl.bs = 512;
-    int per_cu = static_cast<int>((160 * 1024) / pl.lds);
-    if (per_cu > 2048 / pl.bs) per_cu = 2048 / pl.bs;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t resident = static_cast<int64_t>(cu_count_()) * per_cu;
-    const int unit = 64, overhead = 500;
-    int64_t best_cost = -1;
-    int best = 2048;
-    for (int npb = 256; npb <= 16384; npb += unit) {
-      const int64_t wgs = ((a->n + npb - 1) / npb + 7) / 8 * 8 * n_groups;
-      const int64_t rounds = (wgs + resident - 1) / resident;
-      const int64_t cost = rounds * (npb + overhead);
-      if (best_cost < 0 || cost < best_cost || (cost == best_cost && npb > best)) { best_cost = cost; best = npb; }
-    }
-    pl.npb = best;
+    pl.npb = tuned_block(a->n, n_groups, resident_workgroups(pl.lds, pl.bs), 256, 16384, 64, 500, true);
   } else if (a->n < 262144) {
-    const int64_t npb = (a->n / 1024 + 255) / 256 * 256;
-    pl.npb = static_cast<int>(npb < 256 ? 256 : (npb > 4096 ? 4096 : npb));
+    pl.npb = small_batch_block(a->n);
   } else {
-    int per_cu = static_cast<int>((160 * 1024) / pl.lds);
-    if (per_cu > 2048 / pl.bs) per_cu = 2048 / pl.bs;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t resident = static_cast<int64_t>(cu_count_()) * per_cu;
-    const int64_t groups = a->sum_features ? 1 : a->F / pl.fg;
     // (with one or two workgroups per CU the grid is only a handful of rounds: blocks up to 16384 nodes so that the last round
     //  can be a full one — 10M rows, two groups: 9 rounds of 8704 nodes instead of 9.5 of 8192)
-    const int unit = 64, overhead = 500;
-    int64_t best_cost = -1;
-    int best = 4096;
-    for (int npb = 2048; npb <= 16384; npb += unit) {
-      const int64_t wgs = (a->n + npb - 1) / npb * groups;
-      const int64_t rounds = (wgs + resident - 1) / resident;
-      const int64_t cost = rounds * (npb + overhead);
-      if (best_cost < 0 || cost < best_cost || (cost == best_cost && npb > best)) { best_cost = cost; best = npb; }
-    }
-    pl.npb = best;
+    pl.npb = tuned_block(a->n, a->sum_features ? 1 : n_groups, resident_workgroups(pl.lds, pl.bs), 2048, 16384, 64, 500);
   }
   pl.ok = true;
   return pl;
@@ -575,12 +517,11 @@ IndexPlan index_plan(const gnan_fpwl_args* a) {
 
 }  // namespace
 
-// (called by gnan_fpwl_fwd / gnan_fpwl_total_workspace_bytes, csrc/fpwl.hip)
-bool gnan_index_applies(const gnan_fpwl_args* a) { return index_plan(a).ok; }
-int gnan_index_nodes_per_block(const gnan_fpwl_args* a) { return index_plan(a).npb; }
+// (called by gnan_fpwl_fwd / gnan_fpwl_total_workspace_bytes, csrc/fpwl.hip; declared in csrc/fpwl_common.hpp)
+bool gnan::fpwl::index_applies(const gnan_fpwl_args* a) { return index_plan(a).ok; }
+int gnan::fpwl::index_nodes_per_block(const gnan_fpwl_args* a) { return index_plan(a).npb; }
 
-// col_partial: the column-sum partials ([node blocks][F] doubles) or NULL
-int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st) {
+int gnan::fpwl::index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st) {
   const IndexPlan pl = index_plan(a);
   if (!pl.ok) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_index: arguments outside what the direct-index kernel serves");
   // everything that can be refused is refused BEFORE the first launch (a caller that retries another kernel on an error code —
@@ -605,9 +546,7 @@ int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st)
   p.n_groups = a->F / pl.fg;
   p.nodes_per_block = pl.npb;
   p.tot_cap = pl.tot_cap;
-  int step0 = 0;
-  while ((step0 ? step0 * 2 : 1) <= a->max_pieces - 1) step0 = step0 ? step0 * 2 : 1;
-  p.step0 = step0;
+  p.step0 = step0_of(a->max_pieces);
   p.sum_features = a->sum_features;
   p.out = static_cast<float*>(a->out); p.out_stride = a->out_stride;
   p.col_partial = col_partial;
@@ -620,15 +559,7 @@ int gnan_index_fwd(const gnan_fpwl_args* a, double* col_partial, hipStream_t st)
   const int64_t bx = (p.n + p.nodes_per_block - 1) / p.nodes_per_block;
   const int64_t wgs = (a->sum_features && !pl.split) ? bx : (bx + 7) / 8 * 8 * p.n_groups;
   if (wgs > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl: too many nodes for one launch");
-  auto go = [&](auto kernel) {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(lds));
-      if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_index: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(wgs)), dim3(pl.bs), lds, st, p);
-    return gnan::check_launch("fpwl_index_kernel");
-  };
+  auto go = [&](auto kernel) { return launch_with_lds(kernel, "fpwl_index_kernel", dim3(static_cast<unsigned>(wgs)), pl.bs, lds, st, p); };
   auto by_mode = [&](auto fg_c, auto bs_c, auto lb_c) {
     constexpr int G = decltype(fg_c)::value, S = decltype(bs_c)::value, LB = decltype(lb_c)::value;
     if (a->out_dtype == GNAN_BF16) return go(fpwl_index_kernel<G, false, true, LB, S>);
@@ -673,7 +604,7 @@ extern "C" int gnan_fpwl_row_sum_parts(const gnan_fpwl_args* a) {
 }
 
 // bytes of gnan_fpwl_args.sum_workspace this call would use (0: none): what index_plan's split needs
-size_t gnan_index_sum_workspace_bytes(const gnan_fpwl_args* a) {
+size_t gnan::fpwl::index_sum_workspace_bytes(const gnan_fpwl_args* a) {
   if (!a || !a->sum_features || a->n < 16384 || a->n >= kSplitSumMaxNodes) return 0;
   gnan_fpwl_args probe = *a;
   probe.sum_workspace = nullptr;

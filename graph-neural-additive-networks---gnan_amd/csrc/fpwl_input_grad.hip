@@ -12,16 +12,15 @@
 //                          look-ups).  One workgroup per feature, weights in LDS, a wave per piece, lane = hidden unit.
 //   fpwl_input_grad_kernel the look-up: a workgroup owns a block of nodes and a feature group of the table plan, stages
 //                          the group's anchors and dfdx rows in LDS ((1 + C) floats per piece: less than the forward's
-//                          image), thread = (node, up to 4 features) searches as csrc/fpwl.hip:fpwl_kernel does and
-//                          sums the channels by a chain of fused multiply-adds.  x in, gx out, the gradient rows once:
-//                          ~8 B per look-up with one channel.  No atomics, no cross-thread sums: bit-reproducible, and a
-//                          NaN stays in the element it belongs to.
-#include "common.hpp"
+//                          image), thread = (node, up to 4 features) searches as csrc/fpwl.hip:fpwl_kernel does (search<FPT>,
+//                          csrc/fpwl_common.hpp) and sums the channels by a chain of fused multiply-adds.  x in, gx out, the
+//                          gradient rows once: ~8 B per look-up with one channel.  No atomics, no cross-thread sums:
+//                          bit-reproducible, and a NaN stays in the element it belongs to.
+#include "fpwl_common.hpp"
 #include "piece_points.hpp"
 
 namespace {
-
-__host__ __device__ __forceinline__ int table_stride(int C) { return C > 1 ? (C | 1) : 1; }   // as csrc/fpwl.hip
+using namespace gnan::fpwl;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // per-piece derivatives
@@ -169,19 +168,18 @@ struct Plan {
   int64_t n_blocks;
 };
 
-// Thread = (node, FPT features), as csrc/fpwl.hip's Map.  VEC: FPT == 4 and a quad of x / gx is one 16-byte request.
+// Thread = (node, FPT features): Map (csrc/fpwl_common.hpp).  VEC: FPT == 4 and a quad of x / gx is one 16-byte request.
 template <int FG, int BS, bool VEC>
 __global__ __launch_bounds__(BS) void fpwl_input_grad_kernel(const InputGradParams p) {
-  constexpr int FPT = FG < 4 ? FG : 4, TPN = FG / FPT, NODES = BS / TPN;
+  constexpr int FPT = Map<FG, BS>::FPT, TPN = Map<FG, BS>::TPN, NODES = Map<FG, BS>::NODES;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int s_off[FG + 1];
   const int tid = threadIdx.x;
   const int q = tid % TPN, nl = tid / TPN;
   const int C = p.C, Cs = table_stride(C);
-  // the groups of one node block read different sectors of the same x rows: adjacent ids of one XCD (id % 8), csrc/fpwl.hip
-  const int64_t id = blockIdx.x;
-  const int g = static_cast<int>((id >> 3) % p.n_groups);
-  const int64_t nb = ((id >> 3) / p.n_groups) * 8 + (id & 7);
+  int g;
+  int64_t nb;
+  xcd_block(blockIdx.x, p.n_groups, nb, g);
   const int64_t n_lo = nb * p.nodes_per_block;
   if (n_lo >= p.n) return;
   const int64_t n_hi = n_lo + p.nodes_per_block < p.n ? n_lo + p.nodes_per_block : p.n;
@@ -232,7 +230,9 @@ __global__ __launch_bounds__(BS) void fpwl_input_grad_kernel(const InputGradPara
 #pragma unroll
       for (int f = 0; f < FPT; ++f) xv[f] = live[f] ? xr[f] : 0.f;
     }
-    // i = #{ j in 1..pn : anchor[po + j] <= x }: the forward's search (csrc/fpwl.hip:search), FPT features in lock-step
+    // i = #{ j in 1..pn : anchor[po + j] <= x }: search<FPT> (csrc/fpwl_common.hpp), FPT features in lock-step.  Written out:
+    // through the helper fpwl_input_grad_kernel<4, 256, false> took 78 registers for 80 and all instances other code
+    // (profiles/r21_fpwl_split_code_objects.txt)
     int idx[FPT];
 #pragma unroll
     for (int f = 0; f < FPT; ++f) idx[f] = 0;
@@ -279,17 +279,9 @@ __global__ __launch_bounds__(BS) void fpwl_input_grad_kernel(const InputGradPara
 
 template <int FG, int BS>
 int launch_input_grad(const InputGradParams& p, const Plan& plan, hipStream_t st) {
-  const int64_t wgs = (plan.n_blocks + 7) / 8 * 8 * p.n_groups;      // see the id -> (node block, group) map
+  const int64_t wgs = (plan.n_blocks + 7) / 8 * 8 * p.n_groups;      // see xcd_block
   if (wgs > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_input_grad: too many nodes for one launch");
-  auto go = [&](auto kernel) {
-    if (plan.lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(plan.lds));
-      if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_input_grad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(wgs)), dim3(BS), plan.lds, st, p);
-    return gnan::check_launch("fpwl_input_grad_kernel");
-  };
+  auto go = [&](auto kernel) { return launch_with_lds(kernel, "fpwl_input_grad_kernel", dim3(static_cast<unsigned>(wgs)), BS, plan.lds, st, p); };
   if constexpr (FG % 4 == 0) {
     if (plan.vec) return go(fpwl_input_grad_kernel<FG, BS, true>);
   }
@@ -315,8 +307,7 @@ int plan_input_grad(const gnan_fpwl_input_grad_args* a, Plan* plan) {
   GNAN_REQUIRE(a->grad_stride >= gw, "fpwl_input_grad: grad row stride smaller than the gradient width");
   auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) % 16) == 0; };
   plan->block_size = fg >= 8 ? 512 : 256;
-  const int64_t npb = (a->n / 1024 + 255) / 256 * 256;
-  plan->nodes_per_block = static_cast<int>(npb < 256 ? 256 : (npb > 4096 ? 4096 : npb));
+  plan->nodes_per_block = small_batch_block(a->n);
   plan->n_groups = (a->F + fg - 1) / fg;
   plan->vec = fg % 4 == 0 && a->F % 4 == 0 && a->x_stride % 4 == 0 && a->gx_stride % 4 == 0 && aligned(a->x) && aligned(a->gx);
   plan->lds = static_cast<size_t>(a->max_group_pieces) * (1 + cs) * sizeof(float);
@@ -349,9 +340,7 @@ extern "C" int gnan_fpwl_input_grad(const gnan_fpwl_input_grad_args* a, gnan_str
   InputGradParams p;
   p.x = a->x; p.n = a->n; p.x_stride = a->x_stride; p.F = a->F; p.C = a->C;
   p.off = a->off; p.anchor = a->anchor; p.dfdx = a->dfdx;
-  int step0 = 0;
-  while ((step0 ? step0 * 2 : 1) <= a->max_pieces - 1) step0 = step0 ? step0 * 2 : 1;
-  p.step0 = step0;
+  p.step0 = step0_of(a->max_pieces);
   p.n_groups = plan.n_groups;
   p.nodes_per_block = plan.nodes_per_block;
   p.sum_features = a->sum_features ? 1 : 0;

@@ -3,7 +3,7 @@
 // f_k : R -> R^C is piecewise linear with the same kinks for all C channels (the kinks are zero crossings of the hidden
 // pre-activations, gnan_amd/pwl.py), so a look-up has a scalar part — which piece does x[n, k] fall into — and a vector part —
 // add val[piece, :] + slope[piece, :] * (x - anchor[piece]) to the node's C accumulators (backward: add the node's C
-// upstream gradients to the piece's moments).  fpwl.hip does both with thread = node: C > 1 then means C serial LDS round
+// upstream gradients to the piece's moments).  fpwl.hip / fpwl_moments.hip do both with thread = node: C > 1 then means C serial LDS round
 // trips per look-up behind one search, node-strided (uncoalesced) reads of x and of the gradient, a table image that is
 // reloaded per feature behind two barriers, and one workgroup per CU (arxiv-shaped, C = 40: look-up 2.3 ms, moments
 // 4.5 ms for 21.8M look-ups).  Here
@@ -18,24 +18,17 @@
 //                              them to bins[piece][:] — the C lanes hit C consecutive bins: conflict-free.
 // Same arithmetic per term as fpwl.hip (fmaf(slope, dx, val), added in feature order; fixed_bits() terms), replaces
 // GNAN.py:57-62 / its autograd for models with several output channels (node classification: C = classes).
-#include "common.hpp"
-
-#include <cstdlib>
+#include "fpwl_common.hpp"
 
 namespace {
 
 using gnan::kWave;
+using namespace gnan::fpwl;
 
 // global-memory pointer that keeps its address space through an empty asm statement (a generic pointer would turn the
 // loads into flat loads, which also count against the LDS counter and serialise with the LDS atomics)
 typedef __attribute__((address_space(1))) const float gfloat;
 __device__ __forceinline__ gfloat* as_global(const float* ptr) { return (gfloat*)ptr; }
-
-// (same as fpwl.hip)
-__device__ __forceinline__ unsigned long long fixed_bits(float v, double s) {
-  const double d = fma(static_cast<double>(v), s, 6755399441055744.0);
-  return static_cast<unsigned long long>(__double_as_longlong(d)) - 0x4338000000000000ull;
-}
 
 // ---------------------------------------------------------------------------------------------
 // phase 1: piece[n, k] = off[k] + #{ j >= 1 : anchor[off[k] + j] <= x[n, k] },  dx[n, k] = x[n, k] - anchor[piece[n, k]]
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(256) void fpwl_rows_fwd_kernel(const RowsParams p) 
 
 // ---------------------------------------------------------------------------------------------
 // phase 2, backward:  M[t, 0, c] += g[n, c]     M[t, 1, c] += g[n, c] * dx[n, k]      for t = piece[n, k]
-// (g = grad[n, c] with sum_features, grad[n, k*C + c] without), in 64-bit fixed point (fpwl.hip)
+// (g = grad[n, c] with sum_features, grad[n, k*C + c] without), in 64-bit fixed point (fixed_bits, fpwl_common.hpp)
 // ---------------------------------------------------------------------------------------------
 struct RowsMomentParams {
   int64_t n;
@@ -432,7 +425,143 @@ extern "C" size_t gnan_fpwl_locate_bytes(const gnan_fpwl_args* a) {
   return static_cast<size_t>(a->n) * static_cast<size_t>(a->F) * 4;   // bytes of EACH of piece and dx
 }
 
-int gnan_locate_tree(const gnan_fpwl_args* a, int32_t* piece, float* dx, hipStream_t st);   // csrc/fpwl.hip
+namespace {
+// ---------------------------------------------------------------------------------------------
+// Phase 1 with the tree search of the one-channel kernels (csrc/fpwl_common.hpp): the piece of every (node, feature) and
+// dx = x - anchor, [n, F] each.  Same structure as fpwl_moments_c1_kernel (csrc/fpwl_moments_c1_body.hpp) — skewed breadth-first
+// trees of a 16-feature group in LDS, thread = (node, 4 features), the piece's anchor tracked by the search, partial last
+// group and unaligned rows allowed, XCD-aware workgroup map — and 3x the rate of the sorted-array search it replaces
+// (10M nodes x 64 features: 3.4 -> 1.6 ms; used from 262 144 nodes).
+// ---------------------------------------------------------------------------------------------
+struct LocateTreeParams {
+  Params f;            // x, off, anchor, grouping (n_groups of FG features), nodes_per_block, soff_offset
+  int32_t* piece;      // [n, F]
+  float* dx;           // [n, F]
+  int vec_x, vec_out;  // 16-byte loads of x / stores of piece and dx
+};
+
+template <int FG, int NSTEP, int BS>
+__global__ __launch_bounds__(BS) void fpwl_locate_tree_kernel(const LocateTreeParams lp) {
+  static_assert(FG % 4 == 0, "feature quads");
+  constexpr int FPT = 4, TPN = FG / FPT, NODES = BS / TPN, P2 = 1 << NSTEP;
+  const Params& p = lp.f;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x;
+  const int q = tid % TPN, nl = tid / TPN;
+  // (xcd_block, build_trees, tree_base and the tracked descent of csrc/fpwl_common.hpp are written out, as in
+  //  fpwl_moments_c1_kernel: so the code is the parent's instruction for instruction)
+  const int64_t id = blockIdx.x;                                        // (id % 8) = XCD, groups of a node block adjacent inside it
+  const int grp = static_cast<int>((id >> 3) % p.n_groups);
+  const int64_t nb = ((id >> 3) / p.n_groups) * 8 + (id & 7);
+  const int64_t n_lo = nb * p.nodes_per_block;
+  if (n_lo >= p.n) return;
+  const int64_t n_hi = n_lo + p.nodes_per_block < p.n ? n_lo + p.nodes_per_block : p.n;
+  const int k0 = grp * FG;
+  const int nf = p.F - k0 < FG ? p.F - k0 : FG;                         // live features of the group
+  const int base = p.off[k0];
+  int* s_off = reinterpret_cast<int*>(smem) + p.soff_offset;
+  const unsigned lds_base = lds_address(smem);
+  if (tid <= FG) s_off[tid] = p.off[k0 + (tid < nf ? tid : nf)] - base;
+  __syncthreads();
+  for (int i = tid; i < FG * P2; i += BS) {
+    const int f = i >> NSTEP, k = i & (P2 - 1);
+    float v = __builtin_nanf("");          // padding: NaN <= x is false for EVERY x (+inf <= +inf would be true)
+    if (k) {
+      const int j = tree_sorted_index<NSTEP>(k);
+      if (j < s_off[f + 1] - s_off[f]) v = p.anchor[base + s_off[f] + j];
+    }
+    smem[i + (f / FPT) * kTreeSkew] = v;
+  }
+  __syncthreads();
+  const int Q = static_cast<int>(lds_base) + q * ((FPT * P2 + kTreeSkew) * 4);   // tree of the thread's first feature
+  int nQ = -Q, nQ4 = 4 - Q;
+  asm volatile("" : "+v"(nQ), "+v"(nQ4));           // two opaque registers: compare, select, shift-add per step
+  int row0[FPT];                                    // global table row of the feature's piece 0, minus P2
+  float a0[FPT];
+  bool live[FPT];
+#pragma unroll
+  for (int f = 0; f < FPT; ++f) {
+    live[f] = q * FPT + f < nf;
+    row0[f] = base + s_off[q * FPT + f] - P2;
+    a0[f] = live[f] ? p.anchor[base + s_off[q * FPT + f]] : 0.f;
+  }
+  for (int64_t n = n_lo + nl; n < n_hi; n += NODES) {
+    float xv[FPT];
+    const float* xr = p.x + n * p.x_stride + k0 + q * FPT;
+    if (lp.vec_x && nf == FG) {
+      const float4 t = *reinterpret_cast<const float4*>(xr);
+      xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+    } else {
+#pragma unroll
+      for (int f = 0; f < FPT; ++f) xv[f] = live[f] ? xr[f] : 0.f;
+    }
+    int a[FPT];
+    float last[FPT];
+#pragma unroll
+    for (int f = 0; f < FPT; ++f) {
+      a[f] = Q + 4;                                 // node 1 = root
+      last[f] = a0[f];
+    }
+#pragma unroll
+    for (int step = 0; step < NSTEP; ++step) {
+#pragma unroll
+      for (int f = 0; f < FPT; ++f) {
+        const float e = lds_f32(a[f] + f * (P2 * 4));
+        const bool right = e <= xv[f];
+        a[f] = (a[f] << 1) + (right ? nQ4 : nQ);
+        last[f] = right ? e : last[f];
+      }
+    }
+    const int64_t o = n * p.F + k0 + q * FPT;
+    int pr[FPT];
+    float dd[FPT];
+#pragma unroll
+    for (int f = 0; f < FPT; ++f) {
+      pr[f] = row0[f] + ((a[f] - Q) >> 2);
+      dd[f] = xv[f] - last[f];
+    }
+    if (lp.vec_out && nf == FG) {
+      *reinterpret_cast<int4*>(lp.piece + o) = make_int4(pr[0], pr[1], pr[2], pr[3]);
+      *reinterpret_cast<float4*>(lp.dx + o) = make_float4(dd[0], dd[1], dd[2], dd[3]);
+    } else {
+#pragma unroll
+      for (int f = 0; f < FPT; ++f)
+        if (live[f]) { lp.piece[o + f] = pr[f]; lp.dx[o + f] = dd[f]; }
+    }
+  }
+}
+
+template <int NSTEP>
+int launch_locate_tree(LocateTreeParams lp, hipStream_t st) {
+  constexpr int FG = 16, BS = 512;
+  Params& p = lp.f;
+  size_t lds = tree_words(FG, NSTEP) * sizeof(float);
+  p.soff_offset = static_cast<int>(lds / sizeof(float));
+  lds += (FG + 1) * sizeof(int);
+  p.nodes_per_block = tuned_moment_block(p.n, p.n_groups, lds, BS);
+  const int64_t bx = ((p.n + p.nodes_per_block - 1) / p.nodes_per_block + 7) / 8 * 8;   // whole rounds of the 8 XCDs
+  if (bx * p.n_groups > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_locate: too many nodes for one launch");
+  return launch_with_lds(fpwl_locate_tree_kernel<FG, NSTEP, BS>, "fpwl_locate_tree_kernel", dim3(static_cast<unsigned>(bx * p.n_groups)),
+                         BS, lds, st, lp);
+}
+
+// -1: not applicable, gnan_fpwl_locate uses the sorted-array kernel
+int locate_tree(const gnan_fpwl_args* a, int32_t* piece, float* dx, hipStream_t st) {
+  // (small batches: the sorted-array kernel's few large workgroups win — arxiv-shaped 0.102 against 0.141 ms; 10M nodes
+  //  x 64 features: 3.4 ms against 1.6 ms the other way)
+  if (a->max_pieces > 1024 || a->n < 262144) return -1;
+  LocateTreeParams lp;
+  gnan_fpwl_args b = *a;
+  b.features_per_group = 16;                        // the search has its own grouping, whatever the tables were planned for
+  b.C = 1;
+  lp.f = base_params(&b);
+  lp.f.n_groups = (a->F + 15) / 16;
+  lp.piece = piece; lp.dx = dx;
+  lp.vec_x = a->F % 4 == 0 && a->x_stride % 4 == 0 && reinterpret_cast<uintptr_t>(a->x) % 16 == 0;
+  lp.vec_out = a->F % 4 == 0 && reinterpret_cast<uintptr_t>(piece) % 16 == 0 && reinterpret_cast<uintptr_t>(dx) % 16 == 0;
+  return by_nstep(nstep_of(a->max_pieces), [&](auto ns) { return launch_locate_tree<decltype(ns)::value>(lp, st); });
+}
+}  // namespace
 
 extern "C" int gnan_fpwl_locate(const gnan_fpwl_args* a, int32_t* piece, float* dx, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fpwl_locate: null args");
@@ -442,12 +571,10 @@ extern "C" int gnan_fpwl_locate(const gnan_fpwl_args* a, int32_t* piece, float* 
   GNAN_REQUIRE(a->x_stride >= a->F, "fpwl_locate: x row stride smaller than F");
   GNAN_REQUIRE(a->max_pieces >= 1, "fpwl_locate: max_pieces must be >= 1");
   // the tree search of the C == 1 kernels (skewed breadth-first trees, thread = (node, 4 features)) where it applies
-  if (int rc = gnan_locate_tree(a, piece, dx, static_cast<hipStream_t>(stream)); rc != -1) return rc;
+  if (int rc = locate_tree(a, piece, dx, static_cast<hipStream_t>(stream)); rc != -1) return rc;
   LocateParams p;
   p.x = a->x; p.n = a->n; p.x_stride = a->x_stride; p.F = a->F; p.off = a->off; p.anchor = a->anchor;
-  int step0 = 0;
-  while ((step0 ? step0 * 2 : 1) <= a->max_pieces - 1) step0 = step0 ? step0 * 2 : 1;
-  p.step0 = step0;
+  p.step0 = step0_of(a->max_pieces);
   // features per chunk: their anchors (at most max_pieces each) fit a 64-KiB image
   int chunk = (16 * 1024 - 8) / a->max_pieces;
   if (chunk < 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_locate: %d pieces per feature exceed the LDS image", a->max_pieces);
@@ -463,14 +590,8 @@ extern "C" int gnan_fpwl_locate(const gnan_fpwl_args* a, int32_t* piece, float* 
   const int64_t bx = (a->n + npb - 1) / npb;
   if (bx > 0x7fffffffLL || n_chunks > 65535) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_locate: grid too large");
   const size_t lds = (static_cast<size_t>((chunk + 1 + 3) & ~3) + static_cast<size_t>(chunk) * a->max_pieces) * sizeof(float);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fpwl_locate_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_locate: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(fpwl_locate_kernel, dim3(static_cast<unsigned>(bx), static_cast<unsigned>(n_chunks)), dim3(1024), lds,
-                     static_cast<hipStream_t>(stream), p);
-  return gnan::check_launch("fpwl_locate_kernel");
+  return launch_with_lds(fpwl_locate_kernel, "fpwl_locate_kernel", dim3(static_cast<unsigned>(bx), static_cast<unsigned>(n_chunks)), 1024,
+                         lds, static_cast<hipStream_t>(stream), p);
 }
 
 namespace {
@@ -489,13 +610,7 @@ int launch_rows_fwd(const RowsParams& p, hipStream_t st) {
 
 template <int CP2>
 int launch_rows_moments(const RowsMomentParams& p, size_t lds, dim3 grid, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fpwl_rows_moments_kernel<CP2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_rows_moments: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL((fpwl_rows_moments_kernel<CP2>), grid, dim3(1024), lds, st, p);
-  return gnan::check_launch("fpwl_rows_moments_kernel");
+  return launch_with_lds(fpwl_rows_moments_kernel<CP2>, "fpwl_rows_moments_kernel", grid, 1024, lds, st, p);
 }
 }  // namespace
 
@@ -574,16 +689,8 @@ int rows_moments(const gnan_fpwl_args* a, const int32_t* piece, const float* dx,
     probe->n_blocks = (a->n + npb - 1) / npb;
     return GNAN_OK;
   }
-  if (pairs) {
-    // 33..42 channels: a pair of channels per lane, three nodes per step (see fpwl_rows_moments_pairs_kernel)
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fpwl_rows_moments_pairs_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-      if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_rows_moments: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(fpwl_rows_moments_pairs_kernel, grid, dim3(1024), lds, st, p);
-    return gnan::check_launch("fpwl_rows_moments_pairs_kernel");
-  }
+  // 33..42 channels: a pair of channels per lane, three nodes per step (see fpwl_rows_moments_pairs_kernel)
+  if (pairs) return launch_with_lds(fpwl_rows_moments_pairs_kernel, "fpwl_rows_moments_pairs_kernel", grid, 1024, lds, st, p);
   switch (cp2_of(cc)) {
     case 8: return launch_rows_moments<8>(p, lds, grid, st);
     case 16: return launch_rows_moments<16>(p, lds, grid, st);

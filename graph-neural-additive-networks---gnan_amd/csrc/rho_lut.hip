@@ -4,7 +4,7 @@
 // scalar, i.e. exactly piecewise linear like the shape functions (pwl_build.hip tabulates it as a one-feature table).  This
 // kernel turns the shell counts straight into the per-row weight table of the aggregation kernel:
 //     lut[i, d, :] = val[p] + slope[p] * (x - anchor[p]),   x = u[d] / max(cnt[i, d], 1),   p = #{ anchors 1.. <= x }
-// (the same arithmetic per look-up as fpwl.hip) — D look-ups per row instead of a [N*D, H] activation tensor per layer.
+// (the same arithmetic per look-up as the look-up kernels, csrc/fpwl.hip and csrc/fpwl_fast.hip) — D look-ups per row instead of a [N*D, H] activation tensor per layer.
 // HBM-bound: 4 B of cnt in, 4*C B of lut out per (row, code); the anchors sit in LDS, (val, slope) rows come from L1/L2.
 #include "common.hpp"
 

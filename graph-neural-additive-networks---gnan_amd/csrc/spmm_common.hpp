@@ -647,16 +647,7 @@ inline int forward_only_index(const gnan_spmm_args* a, const char* who, bool rea
   return GNAN_OK;
 }
 
-// compute units of the current device (the persistent kernels run two workgroups on each)
-inline int cu_count() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
-}
+using gnan::cu_count;   // (csrc/common.hpp; the persistent kernels run two workgroups on each compute unit)
 }  // namespace
 
 namespace gnan {

@@ -42,7 +42,7 @@ class PwlTables(NamedTuple):
 
 
 def table_stride(C: int) -> int:
-    """Floats per (val | slope) row of the LDS tables: odd for C > 1 (bank conflicts, csrc/fpwl.hip ``table_stride``)."""
+    """Floats per (val | slope) row of the LDS tables: odd for C > 1 (bank conflicts, csrc/fpwl_common.hpp ``table_stride``)."""
     return (C | 1) if C > 1 else 1
 
 

@@ -1,6 +1,6 @@
 """The table path's per-piece moments restated on the CPU, with a DERIVED bound per element — TEST INFRASTRUCTURE ONLY (numpy; no GPU).
 
-The kernels (csrc/fpwl.hip, csrc/fpwl_rows.hip) bin, per piece t of a feature and per channel c,
+The kernels (csrc/fpwl_moments.hip, csrc/fpwl_moments_c1_body.hpp, csrc/fpwl_rows.hip) bin, per piece t of a feature and per channel c,
 
     M0[t, c] = sum g            M1[t, c] = sum g (x - anchor[t])          over the nodes whose x falls into the piece,
 
@@ -41,7 +41,7 @@ from typing import NamedTuple
 import numpy as np
 
 U = 2.0 ** -24
-MAGIC = 6755399441055744.0            # 1.5 * 2^52 (csrc/fpwl.hip fixed_bits)
+MAGIC = 6755399441055744.0            # 1.5 * 2^52 (csrc/fpwl_common.hpp fixed_bits)
 MAGIC_BITS = 0x4338000000000000
 
 
@@ -350,7 +350,7 @@ def _fixed_bits(v64, s, trunc=False):
 
 
 def _search(a, xs, step0, strict=False):
-    """``search<>`` of csrc/fpwl.hip: idx = #{ j in 1..pn : a[j] <= x } by descending powers of two."""
+    """``search<>`` of csrc/fpwl_common.hpp: idx = #{ j in 1..pn : a[j] <= x } by descending powers of two."""
     pn = len(a) - 1
     idx = np.zeros(len(xs), dtype=np.int64)
     step = step0
