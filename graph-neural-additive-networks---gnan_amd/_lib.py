@@ -391,6 +391,12 @@ class SmallDropout(C.Structure):
     _fields_ = [("p", C.c_float), ("reserved", C.c_int32), ("seed", C.c_uint64)]
 
 
+class SmallDropoutDev(C.Structure):
+    """... with the seed in a device cell (``gnan_small_dropout_dev``): what a captured step's kernels read, the cell rewritten
+    before every replay (``gnan_dropout_seed_set``)."""
+    _fields_ = [("p", C.c_float), ("reserved", C.c_int32), ("seed", C.c_void_p)]
+
+
 class SmallGraphNamArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x_stride", C.c_int64), ("n", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
@@ -545,6 +551,13 @@ SYMBOLS = {
     "gnan_small_batch_fwd": (C.c_int, [C.POINTER(SmallBatchArgs), C.c_void_p]),
     "gnan_small_batch_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmallBatchBwdArgs)]),
     "gnan_small_batch_bwd": (C.c_int, [C.POINTER(SmallBatchBwdArgs), C.c_void_p]),
+    "gnan_dropout_seed_set": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "gnan_small_graph_fwd_drop_dev": (C.c_int, [C.POINTER(SmallGraphArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_small_graph_bwd_drop_dev": (C.c_int, [C.POINTER(SmallGraphBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_mid_graph_fwd_drop_dev": (C.c_int, [C.POINTER(MidGraphArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_mid_graph_bwd_drop_dev": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_small_batch_fwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_small_batch_bwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
     "gnan_hops_to_code": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnan_dense_blocks_to_code": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),

@@ -30,7 +30,7 @@ from . import _lib
 from .aggregate import rho_aggregate
 from .graph import HopGraph
 from .modules import _PathBase
-from .small_graph import _cnt_pair, _kept, _mlp_grads, _save, _saved, _small_mlp
+from .small_graph import _cnt_pair, _kept, _launch, _mlp_grads, _save, _saved, _small_mlp
 
 BATCH_KERNEL = True            # the one-launch forward where it applies (tests compare with the CSR route)
 BATCH_KERNEL_MAX_NODES = 128
@@ -243,10 +243,14 @@ class _BatchedGraphs(torch.autograd.Function):
     else the general kernels on the blocks' CSR from the saved node sums and rho table."""
 
     @staticmethod
-    def forward(ctx, x, blocks: HopBlocks, graph_sum, fm, rm, cnt, raw_hops, *params):
+    def forward(ctx, x, blocks: HopBlocks, graph_sum, fm, rm, cnt, raw_hops, dropout, *params):
         """``cnt`` (``[total_nodes, >= D]`` int32 shell sizes) and ``raw_hops=False``: the semantics of models.py:358-384 instead
         of the batched script's — rho on ``1 / (1 + hop)``, rho(0) on the unlisted pairs, weights divided by the shell size
-        (``small_graph.SlotGraph``: a batch-size-1 loop through ONE captured step whatever the graphs' sizes)."""
+        (``small_graph.SlotGraph``: a batch-size-1 loop through ONE captured step whatever the graphs' sizes).
+        ``dropout``: None, or ``(p, seed cell)`` — training-mode Dropout of f for those semantics only, the seed in a device cell
+        (``gnan_small_batch_fwd_drop_dev`` / ``_bwd_drop_dev``; mask node = the row of the packed ``x``)."""
+        if dropout is not None and not (torch.is_tensor(dropout[1]) and not raw_hops):
+            raise _lib.GnanHipError("Dropout on the batched kernels: the slots' semantics (raw_hops=False) with the seed in a device cell")
         from . import functional as Fn
         Lf, Hf, Cf, F = fm
         Lr, Hr, Cr = rm
@@ -268,8 +272,8 @@ class _BatchedGraphs(torch.autograd.Function):
                                 rho_raw_hops=int(raw_hops), rest_zero=int(raw_hops), S=_lib.ptr(S), lut=_lib.ptr(lut),
                                 Y=_lib.ptr(Y), Ysum=_lib.ptr(Ysum), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4,
                                 **_cnt_pair(cnt))
-        _lib.check(_lib.lib().gnan_small_batch_fwd(a, _lib.stream_of(xk)), "gnan_small_batch_fwd")
-        ctx.blocks, ctx.graph_sum, ctx.fm, ctx.rm = blocks, graph_sum, fm, rm
+        _launch("gnan_small_batch_fwd", a, dropout, xk)
+        ctx.blocks, ctx.graph_sum, ctx.fm, ctx.rm, ctx.dropout = blocks, graph_sum, fm, rm, dropout
         ctx.cnt, ctx.raw_hops = cnt, bool(raw_hops)
         _save(ctx, (xk, S, lut), params)
         return Ysum if graph_sum else Y
@@ -280,7 +284,7 @@ class _BatchedGraphs(torch.autograd.Function):
         (x, S, lut), params = _saved(ctx, 3)
         Lf, Hf, Cf, F = ctx.fm
         Lr, Hr, Cr = ctx.rm
-        need_f, need_r = any(ctx.needs_input_grad[7:13]), any(ctx.needs_input_grad[13:])
+        need_f, need_r = any(ctx.needs_input_grad[8:14]), any(ctx.needs_input_grad[14:])      # (eight arguments, then f's six, rho's six)
         blocks = ctx.blocks
         if (BATCH_BACKWARD_KERNEL and Cr in (1, Cf) and blocks.n_codes <= 64 and d_out.dtype == torch.float32
                 and all(t is None or t.dtype == torch.float32 for t in params)):
@@ -301,8 +305,8 @@ class _BatchedGraphs(torch.autograd.Function):
             if need <= BATCH_BACKWARD_MAX_WORKSPACE:
                 ws = torch.empty(need // 4 + 1, dtype=torch.float32, device=x.device)
                 a.workspace, a.workspace_bytes = _lib.ptr(ws), ws.numel() * 4
-                _lib.check(_lib.lib().gnan_small_batch_bwd(a, _lib.stream_of(x)), "gnan_small_batch_bwd")
-                return (None, None, None, None, None, None, None, *[o if need_f else None for o in outs_f],
+                _launch("gnan_small_batch_bwd", a, ctx.dropout, x)
+                return (None, None, None, None, None, None, None, None, *[o if need_f else None for o in outs_f],
                         *[o if need_r else None for o in outs_r])
         if ctx.cnt is not None or not ctx.raw_hops:
             raise _lib.GnanHipError("gnan_small_batch_bwd does not cover this slot step (more than 64 hop codes, a rho of several "
@@ -319,7 +323,7 @@ class _BatchedGraphs(torch.autograd.Function):
             hops = torch.arange(D - 1, dtype=torch.float32, device=x.device).view(-1, 1)     # rho's inputs: the raw hop counts
             _, pg_r = Fn._shape_function_grads(hops, params[6:], ctx.present[6:], None, dlut[: D - 1].reshape(-1, Cr), False,
                                                Lr, Hr, Cr, 1, dests=ctx.dests[6:])
-        return (None, None, None, None, None, None, None, *pg_f, *pg_r)
+        return (None, None, None, None, None, None, None, None, *pg_f, *pg_r)
 
 
 class TensorGNAN(_PathBase):
@@ -361,7 +365,7 @@ class TensorGNAN(_PathBase):
                 and blocks.total_nodes <= BATCH_KERNEL_MAX_TOTAL_NODES and blocks.n_codes <= 256 and f.H <= 64 and f.C <= 8 and x_batch.dtype == torch.float32
                 and not x_batch.requires_grad and blocks.n_graphs <= 65535):
             fm, rm = (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C)
-            return _BatchedGraphs.apply(x_batch, blocks, bool(self.is_graph_task), fm, rm, None, True, *f[:6], *rho[:6])
+            return _BatchedGraphs.apply(x_batch, blocks, bool(self.is_graph_task), fm, rm, None, True, None, *f[:6], *rho[:6])
         if blocks is not None:
             g = blocks.csr()
         else:

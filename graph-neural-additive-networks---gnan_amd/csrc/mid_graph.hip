@@ -135,6 +135,7 @@ struct MidParams {
 // ... and under training-mode Dropout of the shape functions (gnan_mid_graph_fwd_drop with p > 0)
 struct MidDropParams : MidParams {
   gnan_bwd::Drop drop;
+  const uint64_t* seed_dev;     // NULL (drop.seed came by value), or the device cell the seed is read from (gnan_mid_graph_fwd_drop_dev)
 };
 
 // P = MidParams: the Dropout-free instance, the code it was.  P = MidDropParams: a kernel of its own whose shape-function
@@ -152,6 +153,8 @@ __global__ __launch_bounds__(kThreads) void mid_graph_kernel(const P p) {
   const int blocks = (n + kTile - 1) / kTile;
   float out[kMaxC];
   const MlpLds wl = carve(weights);
+  uint64_t seed = 0ull;                                // (Dropout only) by value, or from its device cell: one wave-uniform load
+  if constexpr (DROP) seed = p.seed_dev ? *p.seed_dev : p.drop.seed;
   // the first tile's codes and shell sizes are requested now, by every workgroup (any may be the last): they fly during the MLPs
   TileRegs<kTile> regs;
   tile_fetch<kTile>(regs, p.code, p.cnt, p.cnt_stride, n, p.D, 0);
@@ -167,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void mid_graph_kernel(const P p) {
     for (int b = 0; b < kMidBlocks; ++b) {
       const int j = b * kWave + lane;
       if (b < blocks) {                               // (uniform)
-        if constexpr (DROP) mlp_block<true>(p.f, wl, xv[b], col_a, col_b, lane, wave, out, p.drop, gnan::drop_base(p.drop.seed, j, k));
+        if constexpr (DROP) mlp_block<true>(p.f, wl, xv[b], col_a, col_b, lane, wave, out, p.drop, gnan::drop_base(seed, j, k));
         else mlp_block(p.f, wl, xv[b], col_a, col_b, lane, wave, out);
         if (wave == 0 && j < n)
           for (int c = 0; c < C; ++c) p.part[(static_cast<int64_t>(k) * n + j) * C + c] = out[c];
@@ -388,17 +391,18 @@ __global__ __launch_bounds__(kThreads) void mid_graph_bwd_kernel(const MidBwdPar
 
 // ... of a forward under Dropout (gnan_mid_graph_bwd_drop with p > 0)
 template <int C>
-__global__ __launch_bounds__(kThreads) void mid_graph_bwd_drop_kernel(const MidBwdParams p, const gnan_bwd::Drop drop) {
+__global__ __launch_bounds__(kThreads) void mid_graph_bwd_drop_kernel(const MidBwdParams p, gnan_bwd::Drop drop, const uint64_t* seed_dev) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
+  if (seed_dev) drop.seed = *seed_dev;               // (gnan_mid_graph_bwd_drop_dev: the seed's device cell)
   mid_graph_bwd_body<C>(p, dyn, drop);
 }
 
 template <int C>
-int launch_mid_bwd(const MidBwdParams& p, const gnan_bwd::Drop& drop, hipStream_t st) {
+int launch_mid_bwd(const MidBwdParams& p, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(p.F + p.rho_groups));
   if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
     if (int rc = raise_dyn_lds<&mid_graph_bwd_drop_kernel<C>>(kBwdDynBytes, "mid_graph_bwd")) return rc;
-    hipLaunchKernelGGL((mid_graph_bwd_drop_kernel<C>), grid, dim3(kThreads), kBwdDynBytes, st, p, drop);
+    hipLaunchKernelGGL((mid_graph_bwd_drop_kernel<C>), grid, dim3(kThreads), kBwdDynBytes, st, p, drop, seed_dev);
     return gnan::check_launch("mid_graph_bwd_drop_kernel");
   }
   if (int rc = raise_dyn_lds<&mid_graph_bwd_kernel<C>>(kBwdDynBytes, "mid_graph_bwd")) return rc;
@@ -436,8 +440,9 @@ extern "C" int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t 
 }
 
 namespace {
-// THE launcher of gnan_mid_graph_fwd (drop.thresh == 0) and gnan_mid_graph_fwd_drop
-int mid_fwd(const gnan_mid_graph_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
+// THE launcher of gnan_mid_graph_fwd (drop.thresh == 0), gnan_mid_graph_fwd_drop and gnan_mid_graph_fwd_drop_dev (seed_dev: the seed's
+// device cell, else NULL)
+int mid_fwd(const gnan_mid_graph_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
   if (int rc = shape_ok("mid_graph", kMidCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x != nullptr, "mid_graph: null x");
   GNAN_REQUIRE(a->code != nullptr, "mid_graph: null code");
@@ -453,7 +458,7 @@ int mid_fwd(const gnan_mid_graph_args* a, const gnan_bwd::Drop& drop, gnan_strea
   split_workspace(a->workspace, p.counter, p.part);
   const dim3 grid(static_cast<unsigned>(a->F) + 1u);
   if (drop.thresh != 0u) {                             // (the Dropout instance: a kernel of its own, the other untouched)
-    p.drop = drop;
+    p.drop = drop; p.seed_dev = seed_dev;
     if (int rc = raise_dyn_lds<&mid_graph_kernel<MidDropParams>>(kFwdDynBytes, "mid_graph")) return rc;
     hipLaunchKernelGGL(mid_graph_kernel<MidDropParams>, grid, dim3(kThreads), kFwdDynBytes, static_cast<hipStream_t>(stream), p);
     return gnan::check_launch("mid_graph_kernel (Dropout)");
@@ -467,19 +472,27 @@ int mid_fwd(const gnan_mid_graph_args* a, const gnan_bwd::Drop& drop, gnan_strea
 
 extern "C" int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
-  return mid_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+  return mid_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
 }
 
 extern "C" int gnan_mid_graph_fwd_drop(const gnan_mid_graph_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
   gnan_bwd::Drop drop;
   if (int rc = drop_ok("mid_graph", d, &drop)) return rc;
-  return mid_fwd(a, drop, stream);
+  return mid_fwd(a, drop, nullptr, stream);
+}
+
+extern "C" int gnan_mid_graph_fwd_drop_dev(const gnan_mid_graph_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("mid_graph", d, &drop, &seed_dev)) return rc;
+  return mid_fwd(a, drop, seed_dev, stream);
 }
 
 namespace {
-// THE launcher of gnan_mid_graph_bwd (drop.thresh == 0) and gnan_mid_graph_bwd_drop
-int mid_bwd(const gnan_mid_graph_bwd_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
+// THE launcher of gnan_mid_graph_bwd (drop.thresh == 0), gnan_mid_graph_bwd_drop and gnan_mid_graph_bwd_drop_dev
+int mid_bwd(const gnan_mid_graph_bwd_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
   if (int rc = shape_ok("mid_graph_bwd", kMidCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x != nullptr, "mid_graph_bwd: null x");
   GNAN_REQUIRE(a->code != nullptr, "mid_graph_bwd: null code");
@@ -498,18 +511,26 @@ int mid_bwd(const gnan_mid_graph_bwd_args* a, const gnan_bwd::Drop& drop, gnan_s
   p.rho_groups = (a->n + kRhoRows - 1) / kRhoRows;
   split_workspace(a->workspace, p.counter, p.part);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return with_channels(a->f.C, [&](auto c) { return launch_mid_bwd<decltype(c)::value>(p, drop, st); });
+  return with_channels(a->f.C, [&](auto c) { return launch_mid_bwd<decltype(c)::value>(p, drop, seed_dev, st); });
 }
 }  // namespace
 
 extern "C" int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
-  return mid_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+  return mid_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
 }
 
 extern "C" int gnan_mid_graph_bwd_drop(const gnan_mid_graph_bwd_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
   gnan_bwd::Drop drop;
   if (int rc = drop_ok("mid_graph_bwd", d, &drop)) return rc;
-  return mid_bwd(a, drop, stream);
+  return mid_bwd(a, drop, nullptr, stream);
+}
+
+extern "C" int gnan_mid_graph_bwd_drop_dev(const gnan_mid_graph_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "mid_graph_bwd: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("mid_graph_bwd", d, &drop, &seed_dev)) return rc;
+  return mid_bwd(a, drop, seed_dev, stream);
 }

@@ -53,9 +53,11 @@ struct BatchParams {
 // aggregation's tables need 64 KB).  Config 2's graphs have 30 nodes on average and 3 % of them
 // more than 64; 128 covers 99.98 %.
 // DROP: the shape functions' workgroups mask their hidden activations (mlp_block<true>; node = the row of x, feature = k); the
-// Dropout-free instances are the code they were.
+// Dropout-free instances are the code they were.  node_base: the mask's node coordinate of this graph's row 0 — 0 for a graph of
+// its own, node_off[g] for graph g of a batch (the row of the packed x), so the graphs of a batch draw different masks.
 template <int NB, bool DROP = false>
-__device__ __forceinline__ void small_graph_body(const SmallParams& p, float* cols, gnan_bwd::Drop drop = gnan_bwd::Drop{0u, 1.f, 0ull}) {
+__device__ __forceinline__ void small_graph_body(const SmallParams& p, float* cols, gnan_bwd::Drop drop = gnan_bwd::Drop{0u, 1.f, 0ull},
+                                                 int64_t node_base = 0) {
   constexpr int kNodes = 64 * NB;
   // cols [small_cols_floats(NB)]: activation columns; the aggregation's tables later — node sums, outputs, rho table, row
   // weights [n][64], hop codes [n][n]
@@ -105,7 +107,7 @@ __device__ __forceinline__ void small_graph_body(const SmallParams& p, float* co
     for (int b = 0; b < NB; ++b) {
       const int j = b * kWave + lane;
       if (b * kWave < p.n) {                         // (uniform)
-        if constexpr (DROP) mlp_block<true>(p.f, wl_, xv[b], col_a, col_b, lane, wave, out, drop, gnan::drop_base(drop.seed, j, k));
+        if constexpr (DROP) mlp_block<true>(p.f, wl_, xv[b], col_a, col_b, lane, wave, out, drop, gnan::drop_base(drop.seed, node_base + j, k));
         else mlp_block(p.f, wl_, xv[b], col_a, col_b, lane, wave, out);
         if (wave == 0 && j < p.n)
           for (int c = 0; c < p.f.C; ++c) p.part[(static_cast<int64_t>(k) * p.n + j) * p.f.C + c] = out[c];
@@ -272,11 +274,32 @@ __global__ __launch_bounds__(256) void small_graph_kernel(const SmallParams p) {
   small_graph_body<NB>(p, cols);
 }
 
-// ... under training-mode Dropout of the shape functions (gnan_small_graph_fwd_drop with p > 0): kernels of their own
+// ... under training-mode Dropout of the shape functions (gnan_small_graph_fwd_drop / _fwd_drop_dev with p > 0): kernels of their
+// own.  seed_dev: NULL (the seed came by value, in the record), or the device cell the seed is read from — one wave-uniform load;
+// what a captured step needs, whose by-value seed would be frozen into the graph.
 template <int NB>
-__global__ __launch_bounds__(256) void small_graph_drop_kernel(const SmallParams p, const gnan_bwd::Drop drop) {
+__global__ __launch_bounds__(256) void small_graph_drop_kernel(const SmallParams p, gnan_bwd::Drop drop, const uint64_t* seed_dev) {
   extern __shared__ __attribute__((aligned(16))) float cols[];
+  if (seed_dev) drop.seed = *seed_dev;
   small_graph_body<NB, true>(p, cols, drop);
+}
+
+// graph g of a batch, for the Dropout kernel (small_graph_batch_kernel below keeps its own lines: it stays the code it was): its
+// runs of the batch's arrays; returns its first node's row in the packed x
+__device__ __forceinline__ int64_t graph_of_batch(const BatchParams& bp, int g, SmallParams& p) {
+  p = bp.base;
+  const int64_t o = bp.node_off[g];
+  p.n = static_cast<int>(bp.node_off[g + 1] - o);
+  p.x += o * p.x_stride;
+  p.code += bp.code_off[g];
+  p.S += o * p.f.C;
+  if (p.cnt) p.cnt += o * p.cnt_stride;
+  if (p.Y) p.Y += o * p.f.C;
+  if (p.Ysum) p.Ysum += static_cast<int64_t>(g) * p.f.C;
+  p.lut += static_cast<int64_t>(g) * p.D * p.r.C;
+  p.part += o * p.F * p.f.C;
+  p.counter += 32 * g;                                // a 128-byte line of its own per graph (arrivals of graphs sharing a line queue up behind each other)
+  return o;
 }
 
 template <int NB>
@@ -296,6 +319,17 @@ __global__ __launch_bounds__(256) void small_graph_batch_kernel(const BatchParam
   p.part += o * p.F * p.f.C;
   p.counter += 32 * g;                                // a 128-byte line of its own per graph (arrivals of graphs sharing a line queue up behind each other)
   small_graph_body<NB>(p, cols);
+}
+
+// ... under Dropout of the shape functions (gnan_small_batch_fwd_drop_dev with p > 0; the slots' semantics only): a kernel of its
+// own.  The mask's node coordinate is the row of the packed x, node_off[g] + the local row.
+template <int NB>
+__global__ __launch_bounds__(256) void small_graph_batch_drop_kernel(const BatchParams bp, gnan_bwd::Drop drop, const uint64_t* seed_dev) {
+  extern __shared__ __attribute__((aligned(16))) float cols[];
+  drop.seed = *seed_dev;
+  SmallParams p;
+  const int64_t node_base = graph_of_batch(bp, blockIdx.y, p);
+  small_graph_body<NB, true>(p, cols, drop, node_base);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -352,9 +386,10 @@ constexpr int kRhoSlot = kMaxH * kMaxH + 5 * kMaxH, kRhoGroupsMax = 12;       //
 
 // NB as in small_graph_kernel (2: n <= 128 — hop codes and the row-weight / bin area take 50 KB: dynamic LDS).
 // fdrop: the forward's Dropout of the shape functions (thresh 0: none) — the feature workgroups recompute its masks; rho has none.
+// node_base: the masks' node coordinate of this graph's row 0, as in small_graph_body.
 template <int C, int NB>
 __device__ __forceinline__ void small_graph_bwd_body(const SmallBwdParams& p, float* dyn,
-                                                     gnan_bwd::Drop fdrop = gnan_bwd::Drop{0u, 1.f, 0ull}) {
+                                                     gnan_bwd::Drop fdrop = gnan_bwd::Drop{0u, 1.f, 0ull}, int64_t node_base = 0) {
   constexpr int kNodes = 64 * NB;
   constexpr int kUFloats = kNodes * kWave > 2 * kWave * kBinStride ? kNodes * kWave : 2 * kWave * kBinStride;
   __shared__ gnan_bwd::RedBuffer red;                                           // dyn: s_u | s_code
@@ -451,10 +486,11 @@ __device__ __forceinline__ void small_graph_bwd_body(const SmallBwdParams& p, fl
       s_g[e] = acc;
     }
     __syncthreads();
-    auto x_of = [&](int64_t node) { return p.x[node * p.x_stride + k]; };
-    auto g_of = [&](int64_t node, int c) { return s_g[node * C + c]; };
-    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, 0, n, 0, fdrop, x_of, g_of, red);
-    else gnan_bwd::feature_grads<C, false>(p.f, k, 0, n, 0, fdrop, x_of, g_of, red);
+    // (feature_grads hashes the masks over the node numbers it is given: node_base .. node_base + n - 1)
+    auto x_of = [&](int64_t node) { return p.x[(node - node_base) * p.x_stride + k]; };
+    auto g_of = [&](int64_t node, int c) { return s_g[(node - node_base) * C + c]; };
+    if (p.f_mid) gnan_bwd::feature_grads<C, true>(p.f, k, node_base, node_base + n, 0, fdrop, x_of, g_of, red);
+    else gnan_bwd::feature_grads<C, false>(p.f, k, node_base, node_base + n, 0, fdrop, x_of, g_of, red);
     return;
   }
   if (p.rho_c > 1) {
@@ -673,11 +709,41 @@ __global__ __launch_bounds__(256) void small_graph_bwd_kernel(const SmallBwdPara
   small_graph_bwd_body<C, NB>(p, dyn);
 }
 
-// ... of a forward under Dropout (gnan_small_graph_bwd_drop with p > 0)
+// ... of a forward under Dropout (gnan_small_graph_bwd_drop / _bwd_drop_dev with p > 0); seed_dev as in small_graph_drop_kernel
 template <int C, int NB>
-__global__ __launch_bounds__(256) void small_graph_bwd_drop_kernel(const SmallBwdParams p, const gnan_bwd::Drop drop) {
+__global__ __launch_bounds__(256) void small_graph_bwd_drop_kernel(const SmallBwdParams p, gnan_bwd::Drop drop, const uint64_t* seed_dev) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
+  if (seed_dev) drop.seed = *seed_dev;
   small_graph_bwd_body<C, NB>(p, dyn, drop);
+}
+
+// graph g of a batch, for the Dropout kernel (small_graph_batch_bwd_kernel keeps its own lines): its runs of the batch's arrays and
+// its slab of gradients; returns its first node's row in the packed x
+template <int C>
+__device__ __forceinline__ int64_t graph_of_batch(const BatchBwdParams& bp, int g, SmallBwdParams& p) {
+  p = bp.base;
+  const int64_t o = bp.node_off[g];
+  p.n = static_cast<int>(bp.node_off[g + 1] - o);
+  p.x += o * p.x_stride;
+  p.code += bp.code_off[g];
+  p.S += o * C;
+  if (p.cnt) p.cnt += o * p.cnt_stride;
+  p.lut += static_cast<int64_t>(g) * p.D * p.rho_c;
+  if (bp.dy_per_graph) p.dYsum += static_cast<int64_t>(g) * C;
+  else p.dY += o * C;
+  // graph g's slab of gradients: the same tensor layout, bp.slab floats further on
+  const int64_t by = static_cast<int64_t>(g) * bp.slab;
+  gnan_bwd::Weights* ws[2] = {&p.f, &p.r};
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    gnan_bwd::Weights& w = *ws[t];
+    w.d_w_first += by; w.d_w_last += by;
+    if (w.d_b_first) w.d_b_first += by;
+    if (w.d_w_mid) w.d_w_mid += by;
+    if (w.d_b_mid) w.d_b_mid += by;
+    if (w.d_b_last) w.d_b_last += by;
+  }
+  return o;
 }
 
 template <int C, int NB>
@@ -707,6 +773,18 @@ __global__ __launch_bounds__(256) void small_graph_batch_bwd_kernel(const BatchB
     if (w.d_b_last) w.d_b_last += by;
   }
   small_graph_bwd_body<C, NB>(p, dyn);
+}
+
+// ... of a forward under Dropout (gnan_small_batch_bwd_drop_dev with p > 0): a kernel of its own; the masks of
+// small_graph_batch_drop_kernel (node = the row of the packed x)
+template <int C, int NB>
+__global__ __launch_bounds__(256) void small_graph_batch_bwd_drop_kernel(const BatchBwdParams bp, gnan_bwd::Drop drop,
+                                                                         const uint64_t* seed_dev) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  drop.seed = *seed_dev;
+  SmallBwdParams p;
+  const int64_t node_base = graph_of_batch<C>(bp, blockIdx.y, p);
+  small_graph_bwd_body<C, NB>(p, dyn, drop, node_base);
 }
 
 // out[e] = sum_g slabs[g][e], graphs in order, eight graphs' terms requested together; the slab is the twelve gradient tensors
@@ -739,14 +817,14 @@ constexpr size_t small_bwd_dyn_bytes(bool pre_rho) {
 }
 
 template <int C>
-int launch_small_bwd(const SmallBwdParams& p, const gnan_bwd::Drop& drop, hipStream_t st) {
+int launch_small_bwd(const SmallBwdParams& p, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(p.F + p.rho_groups));
   if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
     if (p.n <= 64) {
-      hipLaunchKernelGGL((small_graph_bwd_drop_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(p.pre_rho != 0), st, p, drop);
+      hipLaunchKernelGGL((small_graph_bwd_drop_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(p.pre_rho != 0), st, p, drop, seed_dev);
     } else {
       if (int rc = raise_dyn_lds<&small_graph_bwd_drop_kernel<C, 2>>(small_bwd_dyn_bytes<2>(true), "small_graph_bwd")) return rc;
-      hipLaunchKernelGGL((small_graph_bwd_drop_kernel<C, 2>), grid, dim3(256), small_bwd_dyn_bytes<2>(p.pre_rho != 0), st, p, drop);
+      hipLaunchKernelGGL((small_graph_bwd_drop_kernel<C, 2>), grid, dim3(256), small_bwd_dyn_bytes<2>(p.pre_rho != 0), st, p, drop, seed_dev);
     }
     return gnan::check_launch("small_graph_bwd_drop_kernel");
   }
@@ -771,8 +849,9 @@ extern "C" size_t gnan_small_graph_workspace_bytes(int32_t n, int32_t F, int32_t
 }
 
 namespace {
-// THE launcher of gnan_small_graph_fwd (drop.thresh == 0) and gnan_small_graph_fwd_drop
-int small_fwd(const gnan_small_graph_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
+// THE launcher of gnan_small_graph_fwd (drop.thresh == 0), gnan_small_graph_fwd_drop and gnan_small_graph_fwd_drop_dev (seed_dev: the
+// seed's device cell, else NULL)
+int small_fwd(const gnan_small_graph_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
   if (int rc = shape_ok("small_graph", kSmallFwdCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->S && a->lut && (a->Y || a->Ysum), "small_graph: null x / code / S / lut / outputs");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_graph: null weights");
@@ -793,10 +872,10 @@ int small_fwd(const gnan_small_graph_args* a, const gnan_bwd::Drop& drop, gnan_s
   constexpr size_t lds2 = small_cols_floats(2) * sizeof(float);           // 64 KB of tables + the static weight image
   if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
     if (a->n <= 64) {
-      hipLaunchKernelGGL(small_graph_drop_kernel<1>, grid, block, lds1, st, p, drop);
+      hipLaunchKernelGGL(small_graph_drop_kernel<1>, grid, block, lds1, st, p, drop, seed_dev);
     } else {
       if (int rc = raise_dyn_lds<&small_graph_drop_kernel<2>>(lds2, "small_graph")) return rc;
-      hipLaunchKernelGGL(small_graph_drop_kernel<2>, grid, block, lds2, st, p, drop);
+      hipLaunchKernelGGL(small_graph_drop_kernel<2>, grid, block, lds2, st, p, drop, seed_dev);
     }
     return gnan::check_launch("small_graph_drop_kernel");
   }
@@ -812,14 +891,22 @@ int small_fwd(const gnan_small_graph_args* a, const gnan_bwd::Drop& drop, gnan_s
 
 extern "C" int gnan_small_graph_fwd(const gnan_small_graph_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph: null args");
-  return small_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+  return small_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
 }
 
 extern "C" int gnan_small_graph_fwd_drop(const gnan_small_graph_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph: null args");
   gnan_bwd::Drop drop;
   if (int rc = drop_ok("small_graph", d, &drop)) return rc;
-  return small_fwd(a, drop, stream);
+  return small_fwd(a, drop, nullptr, stream);
+}
+
+extern "C" int gnan_small_graph_fwd_drop_dev(const gnan_small_graph_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_graph: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("small_graph", d, &drop, &seed_dev)) return rc;
+  return small_fwd(a, drop, seed_dev, stream);
 }
 
 extern "C" size_t gnan_small_graph_bwd_workspace_bytes(int32_t n, int32_t D) {
@@ -828,8 +915,8 @@ extern "C" size_t gnan_small_graph_bwd_workspace_bytes(int32_t n, int32_t D) {
 }
 
 namespace {
-// THE launcher of gnan_small_graph_bwd (drop.thresh == 0) and gnan_small_graph_bwd_drop
-int small_bwd(const gnan_small_graph_bwd_args* a, const gnan_bwd::Drop& drop, gnan_stream_t stream) {
+// THE launcher of gnan_small_graph_bwd (drop.thresh == 0), gnan_small_graph_bwd_drop and gnan_small_graph_bwd_drop_dev
+int small_bwd(const gnan_small_graph_bwd_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
   if (int rc = shape_ok("small_graph_bwd", kSmallBwdCover, a->n, a->F, a->D, &a->f, &a->rho)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->S && a->lut && (a->dY || a->dYsum), "small_graph_bwd: null x / code / S / lut / output gradient");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_graph_bwd: null weights");
@@ -854,32 +941,54 @@ int small_bwd(const gnan_small_graph_bwd_args* a, const gnan_bwd::Drop& drop, gn
     }
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return with_channels(a->f.C, [&](auto c) { return launch_small_bwd<decltype(c)::value>(p, drop, st); });
+  return with_channels(a->f.C, [&](auto c) { return launch_small_bwd<decltype(c)::value>(p, drop, seed_dev, st); });
 }
 }  // namespace
 
 extern "C" int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
-  return small_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, stream);
+  return small_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
 }
 
 extern "C" int gnan_small_graph_bwd_drop(const gnan_small_graph_bwd_args* a, const gnan_small_dropout* d, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
   gnan_bwd::Drop drop;
   if (int rc = drop_ok("small_graph_bwd", d, &drop)) return rc;
-  return small_bwd(a, drop, stream);
+  return small_bwd(a, drop, nullptr, stream);
+}
+
+extern "C" int gnan_small_graph_bwd_drop_dev(const gnan_small_graph_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_graph_bwd: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("small_graph_bwd", d, &drop, &seed_dev)) return rc;
+  return small_bwd(a, drop, seed_dev, stream);
 }
 
 extern "C" size_t gnan_small_batch_workspace_bytes(int32_t n_graphs, int64_t total_nodes, int32_t F, int32_t C) {
   return static_cast<size_t>(n_graphs) * 128 + static_cast<size_t>(total_nodes) * F * C * sizeof(float);    // counters (a line each) | part
 }
 
-extern "C" int gnan_small_batch_fwd(const gnan_small_batch_args* a, gnan_stream_t stream) {
-  GNAN_REQUIRE(a != nullptr, "small_batch: null args");
+namespace {
+// What the *_drop_dev batch entry points cover inside the plain ones' cover: the slots' semantics (models.py:358-384) — rho on
+// 1 / (1 + hop), rho(0) on the unlisted pairs, a one-channel rho.  (The batched script's own rho carries a per-pair Dropout.)
+template <class A>
+int slot_semantics_ok(const char* who, const A* a) {
+  if (a->rho_raw_hops != 0)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: Dropout covers rho_raw_hops == 0 (got rho_raw_hops=%d)", who, a->rho_raw_hops);
+  if (a->rest_zero != 0) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: Dropout covers rest_zero == 0 (got rest_zero=%d)", who, a->rest_zero);
+  if (a->rho.C != 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: Dropout covers a one-channel rho (got rho.C=%d)", who, a->rho.C);
+  return GNAN_OK;
+}
+
+// THE launcher of gnan_small_batch_fwd (seed_dev == NULL) and gnan_small_batch_fwd_drop_dev
+int small_batch_fwd(const gnan_small_batch_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a->n_graphs >= 0 && a->F >= 1 && a->D >= 1 && a->total_nodes >= 0, "small_batch: bad sizes");
   if (a->n_graphs == 0) return GNAN_OK;
   if (a->max_nodes < 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch: covers graphs of >= 1 node (got max_nodes=%d)", a->max_nodes);
   if (int rc = shape_ok("small_batch", kSmallFwdCover, a->max_nodes, a->F, a->D, &a->f, &a->rho)) return rc;
+  if (seed_dev)
+    if (int rc = slot_semantics_ok("small_batch", a)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->node_off && a->code_off && a->S && a->lut && (a->Y || a->Ysum),
                "small_batch: null x / code / offsets / S / lut / outputs");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_batch: null weights");
@@ -900,14 +1009,38 @@ extern "C" int gnan_small_batch_fwd(const gnan_small_batch_args* a, gnan_stream_
   bp.node_off = a->node_off; bp.code_off = a->code_off;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(static_cast<unsigned>(a->F) + 1, static_cast<unsigned>(a->n_graphs));
+  constexpr size_t lds = small_cols_floats(2) * sizeof(float);
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
+    if (a->max_nodes <= 64) {
+      hipLaunchKernelGGL(small_graph_batch_drop_kernel<1>, grid, dim3(kWaves * kWave), small_cols_floats(1) * sizeof(float), st, bp, drop,
+                         seed_dev);
+    } else {
+      if (int rc = raise_dyn_lds<&small_graph_batch_drop_kernel<2>>(lds, "small_batch")) return rc;
+      hipLaunchKernelGGL(small_graph_batch_drop_kernel<2>, grid, dim3(kWaves * kWave), lds, st, bp, drop, seed_dev);
+    }
+    return gnan::check_launch("small_graph_batch_drop_kernel");
+  }
   if (a->max_nodes <= 64) {
     hipLaunchKernelGGL(small_graph_batch_kernel<1>, grid, dim3(kWaves * kWave), small_cols_floats(1) * sizeof(float), st, bp);
   } else {
-    constexpr size_t lds = small_cols_floats(2) * sizeof(float);
     if (int rc = raise_dyn_lds<&small_graph_batch_kernel<2>>(lds, "small_batch")) return rc;
     hipLaunchKernelGGL(small_graph_batch_kernel<2>, grid, dim3(kWaves * kWave), lds, st, bp);
   }
   return gnan::check_launch("small_graph_batch_kernel");
+}
+}  // namespace
+
+extern "C" int gnan_small_batch_fwd(const gnan_small_batch_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch: null args");
+  return small_batch_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
+}
+
+extern "C" int gnan_small_batch_fwd_drop_dev(const gnan_small_batch_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("small_batch", d, &drop, &seed_dev)) return rc;
+  return small_batch_fwd(a, drop, seed_dev, stream);
 }
 
 namespace {
@@ -928,8 +1061,18 @@ int64_t slab_layout(const gnan_small_mlp* f, int F, const gnan_small_mlp* r, int
 }
 
 template <int C>
-int launch_small_batch_bwd(const BatchBwdParams& bp, int n_graphs, int max_nodes, hipStream_t st) {
+int launch_small_batch_bwd(const BatchBwdParams& bp, int n_graphs, int max_nodes, const gnan_bwd::Drop& drop, const uint64_t* seed_dev,
+                           hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(bp.base.F) + 1, static_cast<unsigned>(n_graphs));
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own, the others untouched)
+    if (max_nodes <= 64) {
+      hipLaunchKernelGGL((small_graph_batch_bwd_drop_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(false), st, bp, drop, seed_dev);
+    } else {
+      if (int rc = raise_dyn_lds<&small_graph_batch_bwd_drop_kernel<C, 2>>(small_bwd_dyn_bytes<2>(false), "small_batch_bwd")) return rc;
+      hipLaunchKernelGGL((small_graph_batch_bwd_drop_kernel<C, 2>), grid, dim3(256), small_bwd_dyn_bytes<2>(false), st, bp, drop, seed_dev);
+    }
+    return gnan::check_launch("small_graph_batch_bwd_drop_kernel");
+  }
   if (max_nodes <= 64) {
     hipLaunchKernelGGL((small_graph_batch_bwd_kernel<C, 1>), grid, dim3(256), small_bwd_dyn_bytes<1>(false), st, bp);
   } else {
@@ -946,8 +1089,9 @@ extern "C" size_t gnan_small_batch_bwd_workspace_bytes(const gnan_small_batch_bw
   return static_cast<size_t>(a->n_graphs) * static_cast<size_t>(slab_layout(&a->f, a->F, &a->rho, at)) * sizeof(float);
 }
 
-extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_stream_t stream) {
-  GNAN_REQUIRE(a != nullptr, "small_batch_bwd: null args");
+namespace {
+// THE launcher of gnan_small_batch_bwd (seed_dev == NULL) and gnan_small_batch_bwd_drop_dev
+int small_batch_bwd(const gnan_small_batch_bwd_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a->n_graphs >= 0 && a->F >= 1 && a->D >= 1 && a->total_nodes >= 0, "small_batch_bwd: bad sizes");
   GNAN_REQUIRE(grads_ok(&a->f, &a->df) && grads_ok(&a->rho, &a->drho),
                "small_batch_bwd: a gradient pointer for every weight, and for a bias exactly where there is one");
@@ -968,6 +1112,8 @@ extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_str
   if (a->max_nodes < 1)
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "small_batch_bwd: covers graphs of >= 1 node (got max_nodes=%d)", a->max_nodes);
   if (int rc = shape_ok("small_batch_bwd", kBatchBwdCover, a->max_nodes, a->F, a->D, &a->f, &a->rho)) return rc;
+  if (seed_dev)
+    if (int rc = slot_semantics_ok("small_batch_bwd", a)) return rc;
   GNAN_REQUIRE(a->x && a->code && a->node_off && a->code_off && a->S && a->lut && (a->dY || a->dYsum),
                "small_batch_bwd: null x / code / offsets / S / lut / output gradient");
   GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_batch_bwd: null weights");
@@ -999,7 +1145,7 @@ extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_str
   p.rho_raw = a->rho_raw_hops != 0; p.rest_zero = a->rest_zero != 0; p.rho_c = a->rho.C;
   bp.node_off = a->node_off; bp.code_off = a->code_off; bp.slab = slab; bp.dy_per_graph = a->dYsum != nullptr;
   const int rc = with_channels(a->f.C, [&](auto c) {
-    return launch_small_batch_bwd<decltype(c)::value>(bp, a->n_graphs, a->max_nodes, st);
+    return launch_small_batch_bwd<decltype(c)::value>(bp, a->n_graphs, a->max_nodes, drop, seed_dev, st);
   });
   if (rc != GNAN_OK || direct) return rc;
   ReduceSeg seg;
@@ -1009,6 +1155,33 @@ extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_str
   blocks = blocks > 4096 ? 4096 : blocks;
   hipLaunchKernelGGL(batch_grad_reduce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, slabs, slab, a->n_graphs, seg);
   return gnan::check_launch("batch_grad_reduce_kernel");
+}
+}  // namespace
+
+extern "C" int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch_bwd: null args");
+  return small_batch_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
+}
+
+extern "C" int gnan_small_batch_bwd_drop_dev(const gnan_small_batch_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch_bwd: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("small_batch_bwd", d, &drop, &seed_dev)) return rc;
+  return small_batch_bwd(a, drop, seed_dev, stream);
+}
+
+// The Dropout seed's device cell: one tiny launch stores `seed` there — on the stream of the replay that will read it, before that
+// replay (a kernel argument, not a copy from host memory: legal between replays whatever the host buffer's life, and captured
+// steps never see a host pointer).
+namespace {
+__global__ void dropout_seed_set_kernel(uint64_t* cell, uint64_t seed) { *cell = seed; }
+}  // namespace
+
+extern "C" int gnan_dropout_seed_set(uint64_t* cell, uint64_t seed, gnan_stream_t stream) {
+  GNAN_REQUIRE(cell != nullptr, "dropout_seed_set: null cell");
+  hipLaunchKernelGGL(dropout_seed_set_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), cell, seed);
+  return gnan::check_launch("dropout_seed_set_kernel");
 }
 
 // Per-graph hop matrices (batched_pyg_main.py:19-48: float hop counts, -1 = unreachable) -> the packed uint8 codes the

@@ -241,6 +241,17 @@ inline int drop_ok(const char* who, const gnan_small_dropout* d, gnan_bwd::Drop*
   return GNAN_OK;
 }
 
+// ... and of the *_drop_dev entry points, whose seed lives in a device cell (gnan_dropout_seed_set writes it; a captured step reads
+// a fresh one at every replay): the same refusals in the same order, then a NULL cell.  The kernels read *seed; out->seed stays 0.
+inline int drop_dev_ok(const char* who, const gnan_small_dropout_dev* d, gnan_bwd::Drop* out, const uint64_t** seed) {
+  GNAN_REQUIRE(d != nullptr, "%s: null dropout record", who);
+  const gnan_small_dropout by_value = {d->p, d->reserved, 0ull};
+  if (int rc = drop_ok(who, &by_value, out)) return rc;
+  GNAN_REQUIRE(d->seed != nullptr, "%s: null dropout seed cell", who);
+  *seed = d->seed;
+  return GNAN_OK;
+}
+
 // THE pointer test of a stack whose shape was accepted (L == 1: the NAM read-out's Linear(1, C), only its last layer exists)
 inline bool mlp_ptrs_ok(const gnan_small_mlp* m) { return m->w_last && (m->L == 1 || (m->w_first && (m->L == 2 || m->w_mid))); }
 

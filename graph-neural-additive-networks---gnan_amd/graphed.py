@@ -401,11 +401,17 @@ class GraphedStep:
     replay's results in static tensors."""
 
     @staticmethod
-    def supported(model, optimizer=None) -> bool:
+    def supported(model, optimizer=None, data=None) -> bool:
+        """``data``: what the step will forward.  A model under training-mode Dropout is captured only where every mask's seed can
+        be read from a device cell (``small_graph.dropout_capture_applies``: a graph in slots, a dense graph of up to 448 nodes)
+        — never without ``data`` (the full-batch node-task step: ``gnan_fmlp_fwd`` takes its seed by value)."""
         if not torch.cuda.is_available():
             return False
         if getattr(model, "_dropout_active", lambda: False)():
-            return False
+            from .small_graph import dropout_capture_applies
+            g = getattr(data, "gnan_graph", None)
+            if data is None or g is None or not dropout_capture_applies(model, data.x, g):
+                return False
         return optimizer is None or all("capturable" in g for g in optimizer.param_groups)
 
     def __init__(self, model, data, loss_of=None, optimizer=None, forward: Optional[Callable] = None, warmup: int = 0,
@@ -424,6 +430,14 @@ class GraphedStep:
         self.lrs = self.prepared.lrs if self.training else []
         self.outputs = self.loss = self.extras = None
         self.flat = None
+        # training-mode Dropout (`supported` let this step through): the captured kernels read the masks' seed from this cell,
+        # `replay` writes a fresh one before every replay
+        self.cell = None
+        if getattr(model, "_dropout_active", lambda: False)():
+            if forward is not None or not GraphedStep.supported(model, None, data):
+                raise CaptureFailed("training-mode Dropout is captured on the one-launch graph routes only")
+            from .small_graph import seed_cell
+            self.cell = seed_cell(data.x.device)
 
         # Guarded steps: instead of building the tables of the current weights BEFORE every replay (one more table build, a
         # read-back and a host synchronisation: 0.14 ms of a 0.7-ms arxiv-shaped epoch, 0.5 of 2.1 ms on the Cora shape) the
@@ -483,17 +497,21 @@ class GraphedStep:
         if self.training and self.flat is None:
             self.guard = None                     # the optimizer's own update cannot be skipped on the device: check before replaying
         try:
+            if self.cell is not None:
+                object.__setattr__(model, "_dropout_cell", self.cell)      # (model._dropout_record() hands it to the kernels)
             self.graph = GraphedCallable(step, warmup=0, before_capture=clear, guard=self.guard)
         except CaptureFailed as e:
             if self._own_prepared:
                 self.prepared.restore()
             e.warmup_result = self.warmup_result      # warm-up steps were REAL steps: the caller must not step this input again
             raise
+        finally:
+            model.__dict__.pop("_dropout_cell", None)
         self.outputs, self.loss, self.extras = self.graph.out
         self._probes = _probe_params(model)
         self._params = [p.data_ptr() for p in self._probes]
         self._groups = _group_signature(optimizer) if self.training else None
-        self._mode = model.training
+        self._mode = (model.training, getattr(model, "dropout", None))
 
     def release(self, restore_optimizer: bool = True) -> None:
         """Free the captured graph (and its private memory pool) and drop what the step kept alive; with
@@ -513,8 +531,9 @@ class GraphedStep:
 
     def stale(self) -> bool:
         """Something the graph froze has changed: parameter storage (``.to()``, ``load_state_dict`` into new tensors),
-        optimizer hyper-parameters other than the learning rate, train/eval mode."""
-        if [p.data_ptr() for p in self._probes] != self._params or self.model.training != self._mode:
+        optimizer hyper-parameters other than the learning rate, train/eval mode, the Dropout probability."""
+        if ([p.data_ptr() for p in self._probes] != self._params
+                or (self.model.training, getattr(self.model, "dropout", None)) != self._mode):
             return True
         if self.training and self.flat is not None and not self.flat.intact(self.optimizer):
             return True
@@ -534,6 +553,10 @@ class GraphedStep:
             if group["lr"] is not static:                     # a scheduler wrote a float: keep the tensor, take the value
                 static.fill_(float(group["lr"]))
                 group["lr"] = static
+        if self.cell is not None:                             # this step's ONE seed draw, as the eager forward draws it
+            from .functional import draw_dropout_seed
+            from .small_graph import seed_cell_set
+            seed_cell_set(self.cell, draw_dropout_seed())
         self.graph.replay()
         if guarded and (tripped() if tripped is not None else bool(self.guard.item())):
             # the tables of these weights outgrew the captured look-up: its outputs are not the model's, and the update was

@@ -15,8 +15,9 @@ every later epoch replays a hipGraph of the whole step (forward, mask, loss, bac
 ``gnan_amd/graphed.py``) instead of re-issuing ~70 launches from Python: same arithmetic, same kernels, no host in the
 loop.  Graph-level tasks (a different small graph per step, batch_size = 1) get one captured step per graph SHAPE
 (nodes, features, shells): the third graph of a shape captures it over static buffers and every later graph of that shape
-is copied into them and replayed (``SlottedGraphStep``).  ``GNAN_GRAPHED_STEPS=0`` switches it off; anything a capture cannot hold (training-mode Dropout, an optimizer
-without a capturable mode, a loader that uploads fresh tensors per epoch) silently keeps the eager loop.
+is copied into them and replayed (``SlottedGraphStep``).  ``GNAN_GRAPHED_STEPS=0`` switches it off; anything a capture cannot hold (training-mode Dropout — unless
+``small_graph.CAPTURE_DROPOUT`` is on and the step is a graph-task step whose kernels can read the seed from a device cell,
+``small_graph.dropout_capture_applies`` —, an optimizer without a capturable mode, a loader that uploads fresh tensors per epoch) silently keeps the eager loop.
 
 The loss step itself — rows of the task mask, ``nn.BCEWithLogitsLoss()`` / ``nn.CrossEntropyLoss()`` at their default options,
 the gradient w.r.t. the logits, the hit count and the epoch's running totals — is one launch (``losses.loss_step`` ->
@@ -371,6 +372,12 @@ class _GraphTaskSteps:
             if self.slot_calls < SLOT_AFTER:
                 self.slot_calls += 1
                 return False
+            if model._dropout_active():                 # (eager as before, silently, where the slot kernels cannot take it)
+                from .small_graph import SlotGraph, dropout_capture_applies
+                probe = SlotGraph(int(data.x.shape[1]), data.x.device, use_cnt=use_cnt, max_nodes=tier[0], n_codes=tier[1])
+                if not dropout_capture_applies(model, probe.x, probe):
+                    self.slot_dead = True
+                    return False
             try:
                 if self.prepared is None and self.training:
                     from .graphed import prepare_optimizer
@@ -447,6 +454,11 @@ class _GraphTaskSteps:
             if rec["calls"] < GRAPH_AFTER or self.captured >= GRAPH_TASK_MAX_SHAPES:
                 rec["calls"] += 1
                 return False
+            if model._dropout_active():
+                from .small_graph import dropout_capture_applies
+                if not dropout_capture_applies(model, data.x, graph):
+                    rec["dead"] = True                  # (eager as before, silently)
+                    return False
             loss_of = self._loss_closure()
             try:
                 if self.prepared is None and self.training:
@@ -499,7 +511,10 @@ def _run(model, loader, loss_fn, device, optimizer, classify, label_index, compu
     if (GRAPHED_STEPS and is_graph_task and (optimizer is not None or not torch.is_grad_enabled()) and not compute_auc
             and torch.device(device).type == "cuda" and hasattr(model, "hop_graph")):
         from .graphed import GraphedStep
-        if GraphedStep.supported(model, optimizer):
+        from . import small_graph as sg
+        # (under training-mode Dropout the steps decide graph by graph: small_graph.dropout_capture_applies)
+        drop = getattr(model, "_dropout_active", lambda: False)()
+        if (sg.CAPTURE_DROPOUT and GraphedStep.supported(None, optimizer)) if drop else GraphedStep.supported(model, optimizer):
             replayer = _graph_task_steps(model, optimizer, loss_fn, classify, device)
             if replayer is not None:
                 replayer.total_loss.zero_()

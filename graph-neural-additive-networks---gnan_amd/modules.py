@@ -383,8 +383,9 @@ class _PathBase(nn.Module):
         reference only trains with Dropout in its first epoch: it never leaves eval mode again after ``trainer.py:97``);
         a one-time note says so.  Dense-coded graphs of up to 448 nodes keep their one-launch routes under Dropout
         (``small_graph.SMALL_GRAPH_DROPOUT``: ``gnan_small_graph_fwd_drop`` / ``gnan_mid_graph_fwd_drop`` and their backward
-        passes hash the same coordinates, so a seed gives the same masks on either route); the NAM read-out, the batched and
-        slot routes and captured steps do not."""
+        passes hash the same coordinates, so a seed gives the same masks on either route); the NAM read-out and the batched
+        route do not.  Captured and replayed steps take such forwards only behind ``small_graph.CAPTURE_DROPOUT`` (their kernels
+        then read the seed from a device cell: ``small_graph.dropout_capture_applies``)."""
         if self._dropout_active() and not getattr(self, "_dropout_noted", False):
             import warnings
             warnings.warn("gnan_amd: training-mode Dropout (p=%g) is active: the shape functions run through the direct "
@@ -395,9 +396,18 @@ class _PathBase(nn.Module):
         return bool(self.training and self.dropout and self.dropout > 0)
 
     def _dropout_record(self):
-        """``(p, seed)`` of this forward's masks: the ONE seed draw of the forward."""
+        """``(p, seed)`` of this forward's masks: the ONE seed draw of the forward — or ``(p, cell)`` while a captured step lends
+        this model its seed cell (``_dropout_cell``: replay.py / graphed.py, which draw the seed and write the cell before every
+        replay; nothing is drawn here then)."""
+        cell = self.__dict__.get("_dropout_cell")
+        if cell is not None:
+            return (float(self.dropout), cell)
         from .functional import draw_dropout_seed
         return (float(self.dropout), draw_dropout_seed())
+
+    def _small_route(self, node_ids=None):
+        """``(use_cnt, graph_sum)`` with which ``_forward`` tries :meth:`_small_graph`, or None where it does not."""
+        return None
 
     def _features(self, x, name, mlps, sum_features: bool, pad_ok: bool = False, want_total: bool = False,
                   out_dtype=torch.float32, room_rows: int = 0):
@@ -473,16 +483,19 @@ class _PathBase(nn.Module):
         from .small_graph import (MID_GRAPH_MAX_NODES, SMALL_GRAPH_MAX_NODES, SlotGraph, mid_graph_applies, mid_graph_forward,
                                   slot_graph_applies, slot_graph_forward, small_graph_applies, small_graph_forward)
         drop = self._dropout_active()
-        if drop and (not sg.SMALL_GRAPH_DROPOUT or isinstance(g, SlotGraph) or torch.cuda.is_current_stream_capturing()):
-            return None                                  # the general Dropout route, as before (slots and captures: a captured
-                                                         # seed would freeze the masks; graphed.py / harness.py refuse such steps)
+        if drop and not sg.SMALL_GRAPH_DROPOUT:
+            return None                                  # the general Dropout route, as before
+        if drop and (isinstance(g, SlotGraph) or torch.cuda.is_current_stream_capturing()) and not (
+                self.__dict__.get("_dropout_cell") is not None and sg.dropout_capture_applies(self, x, g)):
+            return None                                  # slots and captures take a seed from a device cell or none: a captured
+                                                         # by-value seed would freeze the masks (replay.py / graphed.py lend the cell)
         if isinstance(g, SlotGraph):
             # a captured step of a batch-size-1 loop: the graph sits in slots, its size is the device's to know
             f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
             if use_cnt == "pre" or not graph_sum or not slot_graph_applies(g, f, rho):
                 raise _lib.GnanHipError("graph slots serve graph-level read-outs with post-rho (or no) normalisation, a one-channel "
                                         "rho and at most 8 output channels")
-            return slot_graph_forward(g, f, rho, bool(use_cnt))
+            return slot_graph_forward(g, f, rho, bool(use_cnt), dropout=self._dropout_record() if drop else None)
         if not g.is_dense or x.shape[0] > MID_GRAPH_MAX_NODES:
             return None
         f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
@@ -548,13 +561,16 @@ class StandaloneTensorGNAN(_PathBase):
             return cpu_route.forward_standalone_tensor(self, inputs)
         return replay.run(self, inputs)               # the launches below, or — third call on the same inputs — their hipGraphs
 
+    def _small_route(self, node_ids=None):
+        return ("pre" if self.normalize_rho else False, bool(self.is_graph_task))
+
     def _forward(self, inputs):
         self._check_dropout()
         x = inputs.x
         _lib.require_device(x)
         self._mark("start")
         g = self._graph(inputs, want_norm=bool(self.normalize_rho))
-        small = self._small_graph(x, g, "pre" if self.normalize_rho else False, bool(self.is_graph_task))
+        small = self._small_graph(x, g, *self._small_route())
         if small is not None:
             return small
         lut = None if self.normalize_rho else self._lut_global(g)
@@ -608,6 +624,9 @@ class _GNANCore(_PathBase):
             return cpu_route.forward_gnan(self, inputs, node_ids)
         return replay.run(self, inputs, node_ids)
 
+    def _small_route(self, node_ids=None):
+        return None if node_ids is not None else (bool(self.normalize_rho), False)
+
     def _forward(self, inputs, node_ids=None):
         self._check_dropout()
         x = inputs.x
@@ -615,7 +634,7 @@ class _GNANCore(_PathBase):
         self._mark("start")
         g = self._graph(inputs, want_norm=True)            # GNAN.py:161 reads it unconditionally
         if node_ids is None:
-            small = self._small_graph(x, g, bool(self.normalize_rho), False)
+            small = self._small_graph(x, g, *self._small_route())
             if small is not None:
                 return small
         lut = self._lut_global(g)
@@ -710,6 +729,11 @@ class TensorGNAN(_PathBase):
             return cpu_route.forward_models_tensor(self, inputs)
         return replay.run(self, inputs)
 
+    def _small_route(self, node_ids=None):
+        if (self.is_graph_task and self.readout_n_layers > 0) or self.aggregation_order == "reference":
+            return None
+        return (bool(self.normalize_rho), bool(self.is_graph_task))
+
     def _forward(self, inputs):
         self._check_dropout()
         x = inputs.x
@@ -717,8 +741,9 @@ class TensorGNAN(_PathBase):
         self._mark("start")
         g = self._graph(inputs, want_norm=bool(self.normalize_rho))
         with_readout = self.is_graph_task and self.readout_n_layers > 0
-        if not with_readout and self.aggregation_order != "reference":
-            small = self._small_graph(x, g, bool(self.normalize_rho), bool(self.is_graph_task))
+        route = self._small_route()
+        if route is not None:
+            small = self._small_graph(x, g, *route)
             if small is not None:
                 return small
         use_cnt = bool(self.normalize_rho)

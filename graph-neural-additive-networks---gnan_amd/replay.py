@@ -18,7 +18,10 @@ What a plan freezes and how it is kept honest: the input tensors (key), the para
 modules' switches (key); the sizes of the shape-function tables — the captured look-up checks the tables its own build
 produced (``gnan_pwl_check_fit`` -> the plan's guard flag), the flag is read right after the forward replay, and a tripped plan
 is dropped and the forward runs eagerly (the look-up then sizes itself); a second forward replay before the backward of the
-first would overwrite what that backward reads — refused loudly.  Not captured: training-mode Dropout, ``node_ids``,
+first would overwrite what that backward reads — refused loudly.  Training-mode Dropout is captured where every mask's seed can
+be read from a device cell (``small_graph.dropout_capture_applies``: the one-launch routes, 1-448 nodes): the plan owns the cell,
+the host draws a seed per forward and writes it there before the replay, the backward graph reads the same cell.  Not captured:
+every other forward under Dropout, ``node_ids``,
 ``x.requires_grad``, anything while a capture is already running (``harness`` capturing a whole step).  Anomaly mode is switched off DURING the capture
 (its NaN checks read the device) and nowhere else.
 
@@ -75,6 +78,12 @@ class _Plan:
         if grad and any(st._occupied(name) for st in stores for name in st.buf):
             raise _NotNow()                             # gradients waiting to be added to: the capture would freeze "assign"
         self.guard = torch.zeros(1, dtype=torch.float32, device=dev)
+        # A forward under training-mode Dropout (small_graph.dropout_capture_applies let it through): its kernels, forward and
+        # backward, read the masks' seed from this cell, which `_fresh_seed` rewrites before every forward replay
+        self.cell = None
+        if module._dropout_active():
+            from .small_graph import seed_cell
+            self.cell = seed_cell(dev)
         # The gradient state as the caller left it — flat gradients (None after the zero_grad of an optimizer over
         # model.parameters(); still standing after one over the per-layer Parameters) and whether the per-layer views are linked
         # — is put back when the plan is built.  In between the flat gradients are None: the captured backward pass must
@@ -98,8 +107,11 @@ class _Plan:
                 st.pending.clear()
         blank()
         try:
+            if self.cell is not None:
+                object.__setattr__(module, "_dropout_cell", self.cell)       # (module._dropout_record() hands it to the kernels)
             self._capture(module, inputs, grad, stores, blank)
         finally:
+            module.__dict__.pop("_dropout_cell", None)
             restore()
         self.ptrs = [st.flat[name].data_ptr() for st in stores for name in st.buf]
         self.anchor = next((st.flat[name] for st in stores for name in st.buf if st.flat[name].requires_grad), None)
@@ -148,6 +160,15 @@ class _Plan:
 
 class _NotNow(Exception):
     pass
+
+
+def _fresh_seed(plan: "_Plan") -> None:
+    """Before a forward replay under Dropout: this forward's ONE seed draw (torch's CPU generator, as the eager forward draws it —
+    ``torch.manual_seed`` fixes the masks on either path) goes into the plan's cell, one tiny launch on the replay's stream."""
+    if plan.cell is not None:
+        from .functional import draw_dropout_seed
+        from .small_graph import seed_cell_set
+        seed_cell_set(plan.cell, draw_dropout_seed())
 
 
 def _refused(rec) -> None:
@@ -291,7 +312,8 @@ def _key(module, inputs, grad: bool):
     fields = ("node_distances", "normalization_matrix", "gnan_rowptr", "gnan_col", "gnan_code", "gnan_cnt")
     src = (x,) + tuple(t if torch.is_tensor(t) else None for t in (getattr(inputs, f, None) for f in fields))
     flags = tuple(bool(st.flat[name].requires_grad) for st in _stores_of(module) for name in st.buf)
-    extra = (grad, bool(module.training), None if g is None else id(g), getattr(module, "aggregation_order", None),
+    drop_p = float(module.dropout) if module._dropout_active() else 0.0
+    extra = (grad, bool(module.training), drop_p, None if g is None else id(g), getattr(module, "aggregation_order", None),
              str(getattr(module, "operand_dtype", None)), bool(getattr(module, "normalize_rho", True)), flags,
              int(getattr(inputs, "gnan_n_codes", 0) or 0))
     return src, extra
@@ -323,7 +345,7 @@ def _run_small(module, inputs):
     """A graph-level forward of a SMALL dense graph (batch_size = 1: another graph object every step) through graph slots: the
     graph is copied into the slots of its (node, hop-code) tier — one launch — and the tier's plan, captured over the slots, is
     replayed: whatever graph comes, forward and backward are one graph launch each.  None: not for this route."""
-    from .small_graph import SlotGraph, slot_mode, slot_tier
+    from .small_graph import SlotGraph, dropout_capture_applies, slot_mode, slot_tier
     use_cnt = slot_mode(module)
     if use_cnt is None or inputs.x.dtype != torch.float32:
         return None
@@ -337,7 +359,9 @@ def _run_small(module, inputs):
     if book is None:
         book = _SlotBook()
         object.__setattr__(module, "_replay_slots", book)
-    key = (tier, grad, bool(module.training), tuple(bool(st.flat[name].requires_grad) for st in stores for name in st.buf))
+    drop = module._dropout_active()
+    key = (tier, grad, bool(module.training), float(module.dropout) if drop else 0.0,
+           tuple(bool(st.flat[name].requires_grad) for st in stores for name in st.buf))
     rec = book.plans.get(key)
     if rec is None:
         if book.calls < REPLAY_AFTER:
@@ -356,6 +380,9 @@ def _run_small(module, inputs):
             slot = SlotGraph(int(inputs.x.shape[1]), inputs.x.device, use_cnt=use_cnt, max_nodes=tier[0], n_codes=tier[1])
             if not slot.fits(g, inputs.x):
                 return None
+            if drop and not dropout_capture_applies(module, slot.x, slot):
+                rec["dead"] = True                     # (eager as before, silently: the general Dropout route)
+                return None
             slot.load(g, inputs.x)
             plan = _Plan(module, _SlotInputs(slot), grad)
             rec["plan"], rec["slot"] = plan, slot
@@ -370,6 +397,7 @@ def _run_small(module, inputs):
     if not rec["slot"].fits(g, inputs.x):              # (another feature count, a graph without the shell sizes the slot holds)
         return None
     rec["slot"].load(g, inputs.x)
+    _fresh_seed(plan)
     plan.gen += 1
     plan.fwd.replay()
     if plan.guarded and bool(plan.guard.item()):       # (a slot forward that builds tables: as in run())
@@ -384,8 +412,14 @@ def run(module, inputs, node_ids=None):
     x = getattr(inputs, "x", None)
     if (not REPLAY_FORWARD or node_ids is not None or not torch.is_tensor(x) or not x.is_cuda or x.requires_grad
             or x.dim() != 2 or getattr(module, "stage_hook", None) is not None
-            or module._dropout_active() or torch.cuda.is_current_stream_capturing()):
+            or torch.cuda.is_current_stream_capturing()):
         return module._forward(inputs) if node_ids is None else module._forward(inputs, node_ids)
+    if module._dropout_active():
+        # only where every mask's seed can come from a device cell (the slot route decides for itself, over its slots)
+        from . import small_graph as sg
+        if not sg.CAPTURE_DROPOUT or x.shape[0] > sg.MID_GRAPH_MAX_NODES or (
+                x.shape[0] >= REPLAY_MIN_NODES and not sg.dropout_capture_applies(module, x, module.hop_graph(inputs))):
+            return module._forward(inputs)
     if x.shape[0] < REPLAY_MIN_NODES:
         out = None
         if REPLAY_SMALL_GRAPHS and getattr(inputs, "gnan_graph", None) is None:
@@ -433,6 +467,7 @@ def run(module, inputs, node_ids=None):
             import warnings
             warnings.warn(f"gnan_amd.replay: this forward stays eager ({type(e).__name__}: {str(e)[:200]})")
             return module._forward(inputs)
+    _fresh_seed(plan)
     plan.gen += 1
     plan.fwd.replay()
     if plan.guarded and bool(plan.guard.item()):        # the tables of these weights outgrew the captured look-up: its output is void

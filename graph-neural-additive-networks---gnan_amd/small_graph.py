@@ -135,7 +135,9 @@ class _OneLaunch(torch.autograd.Function):
     ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67; the small route only).
     ``dropout``: None, or ``(p, seed)`` — training-mode Dropout behind every hidden ReLU of f (never of rho), masks hashed from
     the seed (csrc/dropout.hpp; node = row of ``x``, feature = its column): both launches go through the ``_drop`` entry points
-    with the same record, and so does ``gnan_fmlp_bwd`` where the general backward runs."""
+    with the same record, and so does ``gnan_fmlp_bwd`` where the general backward runs.  ``seed`` an int: by value, the eager
+    path.  A one-element device tensor: the seed's cell, read by the ``_drop_dev`` entry points (captured steps) — then the backward
+    is the one launch or an error, never the general backward."""
 
     @staticmethod
     def forward(ctx, route, x, g, use_cnt, graph_sum, fm, rm, dropout, *params):
@@ -174,6 +176,10 @@ class _OneLaunch(torch.autograd.Function):
             if pre_rho:
                 raise RuntimeError("the one-launch small-graph forward with pre-rho normalisation was taken where its backward "
                                    "does not apply (float32 parameters and output gradient expected)")
+            if ctx.dropout is not None and torch.is_tensor(ctx.dropout[1]):
+                raise RuntimeError("a one-launch forward under Dropout with its seed in a device cell was taken where the one-launch "
+                                   "backward does not apply (the gradients of both f and rho, one rho channel, at most 64 shells, "
+                                   "float32): the general backward takes its seed by value")
             return (None, *_general_backward(ctx, x, S, lut, params, d_out, need_f, need_r))
         # one launch: every workgroup forms the operand (or table) gradient it needs itself, then the small-batch MLP backward
         keep = _kept(params)
@@ -197,12 +203,28 @@ class _OneLaunch(torch.autograd.Function):
 
 
 def _launch(entry: str, a, dropout, on: torch.Tensor) -> None:
-    """``entry(a, stream)``, or — ``dropout = (p, seed)`` — ``entry_drop(a, record, stream)``."""
+    """``entry(a, stream)``, or — ``dropout = (p, seed)`` — ``entry_drop(a, record, stream)`` for a seed by value (an int: the eager
+    path) and ``entry_drop_dev`` for a seed cell (a one-element device tensor: what a capture may record)."""
     if dropout is None:
         _lib.check(getattr(_lib.lib(), entry)(a, _lib.stream_of(on)), entry)
         return
+    if torch.is_tensor(dropout[1]):
+        d = _lib.SmallDropoutDev(p=float(dropout[0]), reserved=0, seed=_lib.ptr(dropout[1]))
+        _lib.check(getattr(_lib.lib(), entry + "_drop_dev")(a, d, _lib.stream_of(on)), entry + "_drop_dev")
+        return
     d = _lib.SmallDropout(p=float(dropout[0]), reserved=0, seed=int(dropout[1]))
     _lib.check(getattr(_lib.lib(), entry + "_drop")(a, d, _lib.stream_of(on)), entry + "_drop")
+
+
+def seed_cell(device) -> torch.Tensor:
+    """A Dropout seed's device cell (one ``int64`` word, 0 until :func:`seed_cell_set` writes it)."""
+    return torch.zeros(1, dtype=torch.int64, device=device)
+
+
+def seed_cell_set(cell: torch.Tensor, seed: int) -> None:
+    """Store ``seed`` (its 64 bits) in ``cell`` — one tiny launch (``gnan_dropout_seed_set``) on the current stream."""
+    _lib.check(_lib.lib().gnan_dropout_seed_set(_lib.ptr(cell), int(seed) & ((1 << 64) - 1), _lib.stream_of(cell)),
+               "gnan_dropout_seed_set")
 
 
 def _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r):
@@ -229,13 +251,18 @@ def _general_backward(ctx, x, S, lut, params, d_out, need_f, need_r):
 
 
 def _dropout_record(dropout):
-    """``None`` or ``(p, seed)`` as :class:`_OneLaunch` takes it: p in [0, 1), the seed's 64 bits."""
+    """``None`` or ``(p, seed)`` as :class:`_OneLaunch` takes it: p in [0, 1), and the seed's 64 bits — or its cell, a
+    one-element ``int64`` / ``uint64`` device tensor (the ``_dev`` entry points)."""
     if dropout is None:
         return None
-    p, seed = float(dropout[0]), int(dropout[1])
+    p, seed = float(dropout[0]), dropout[1]
     if not 0.0 <= p < 1.0:
         raise ValueError("dropout p must be in [0, 1)")
-    return (p, seed & ((1 << 64) - 1))
+    if torch.is_tensor(seed):
+        if not (seed.is_cuda and seed.numel() == 1 and seed.dtype in (torch.int64, torch.uint64) and seed.is_contiguous()):
+            raise ValueError("a dropout seed cell is a one-element int64 / uint64 device tensor")
+        return (p, seed)
+    return (p, int(seed) & ((1 << 64) - 1))
 
 
 def small_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool, dropout=None):
@@ -455,12 +482,48 @@ def slot_graph_applies(slot: SlotGraph, f: StackedMLP, rho: StackedMLP) -> bool:
     return bool(f.F == slot.F and rho.F == 1 and _stack_ok(f) and _stack_ok(rho, max_c=1))
 
 
-def slot_graph_forward(slot: SlotGraph, f: StackedMLP, rho: StackedMLP, use_cnt: bool) -> torch.Tensor:
+CAPTURE_DROPOUT = False      # on: forwards under training-mode Dropout may be captured (replay.py, graphed.py): their kernels read the
+                             # seed from a device cell the host rewrites before every replay.  Off (the default): such forwards stay
+                             # eager, as before.  Ships off by the measured rule of DESIGN.md section 5: harness.train_epoch's captured
+                             # step is 1.7 to 7.6 times faster than the eager step, but the modules' own replay inside the unchanged
+                             # loop is not faster at 130 and 417 nodes in two of three processes, and one switch governs both
+
+
+def dropout_capture_applies(model, x: torch.Tensor, g, node_ids=None) -> bool:
+    """May this forward of ``model`` under active Dropout be captured into a hipGraph?  Only where every kernel that draws a mask
+    reads its seed from a device cell — the one-launch routes: a graph in slots (``gnan_small_batch_*_drop_dev``) or a dense graph
+    of up to 448 nodes (``gnan_small_graph_*_drop_dev`` / ``gnan_mid_graph_*_drop_dev``) — and where the backward is one of theirs
+    too (the gradients of all of f's and rho's parameters, or of none: the general backward takes its seed by value).  Everything
+    else under Dropout stays eager: the general route, the NAM read-out, ``batched.TensorGNAN``, CSR graphs, ``node_ids``."""
+    route = getattr(model, "_small_route", None)
+    if not (CAPTURE_DROPOUT and SMALL_GRAPH_DROPOUT and route is not None) or node_ids is not None or x.requires_grad:
+        return False
+    args = route(node_ids)
+    if args is None:
+        return False
+    use_cnt = args[0]
+    f, rho = model._stacked("fs", model.fs), model._stacked("rho", [model.rho])
+    wanted = [t.requires_grad for t in (*f[:6], *rho[:6]) if t is not None]
+    if any(wanted) and not all(wanted):
+        return False
+    if isinstance(g, SlotGraph):
+        return slot_mode(model) is not None and slot_graph_applies(g, f, rho)
+    if not (g.is_dense and SMALL_GRAPH_BACKWARD):
+        return False
+    if x.shape[0] > SMALL_GRAPH_MAX_NODES:
+        return mid_graph_applies(x, g, f, rho, use_cnt)         # (one rho channel, at most 64 shells: its backward's cover too)
+    # (... which the small route's forward exceeds: a device-seed backward is the one launch or nothing)
+    return small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre") and rho.C == 1 and g.n_codes <= _ONE_LAUNCH_CODES
+
+
+def slot_graph_forward(slot: SlotGraph, f: StackedMLP, rho: StackedMLP, use_cnt: bool, dropout=None) -> torch.Tensor:
     """The graph read-out ``[C, 1]`` (GNAN.py:75-79 / models.py:383-384) of the graph in the slots: one launch forward, two
-    backward (``gnan_small_batch_bwd`` + the slab reduction)."""
+    backward (``gnan_small_batch_bwd`` + the slab reduction).  ``dropout = (p, seed cell)``: training-mode Dropout of f
+    (``gnan_small_batch_fwd_drop_dev``; a slot's graph sits at row 0: the masks of ``gnan_small_graph_fwd_drop``)."""
     from .batched import _BatchedGraphs
     if use_cnt and slot.cnt is None:
         raise _lib.GnanHipError("these slots were laid out without shell sizes")
     fm, rm = (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C)
-    out = _BatchedGraphs.apply(slot.x, slot.blocks, True, fm, rm, slot.cnt if use_cnt else None, False, *f[:6], *rho[:6])   # [1, C]
+    out = _BatchedGraphs.apply(slot.x, slot.blocks, True, fm, rm, slot.cnt if use_cnt else None, False, _dropout_record(dropout),
+                               *f[:6], *rho[:6])   # [1, C]
     return out.reshape(-1, 1)

@@ -1368,6 +1368,8 @@ int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream);
  * p > 0 launches Dropout instances of the kernels (kernels of their own); p == 0 launches the plain entry point's kernel, bit
  * for bit.  Refused on the host, before any HIP call: a NULL record, p outside [0, 1) (NaN included), reserved != 0
  * (GNAN_ERR_BAD_ARG); shapes outside the routes' cover stay GNAN_ERR_UNSUPPORTED with the plain entry points' messages.
+ * The seed here is a by-value kernel argument — right for eager launches, frozen by a capture: captured steps take the
+ * *_drop_dev twins further down (gnan_small_dropout_dev), which read it from a device cell.
  * ------------------------------------------------------------------------------------------- */
 typedef struct gnan_small_dropout {
   float p;                   /* in [0, 1); 0 = no Dropout: the plain entry point's kernel, bit for bit */
@@ -1413,6 +1415,43 @@ typedef struct gnan_small_batch_bwd_args {
 } gnan_small_batch_bwd_args;
 size_t gnan_small_batch_bwd_workspace_bytes(const gnan_small_batch_bwd_args* a);
 int gnan_small_batch_bwd(const gnan_small_batch_bwd_args* a, gnan_stream_t stream);
+
+/* -------------------------------------------------------------------------------------------
+ * Dropout of the shape functions in CAPTURED steps: the seed in a device cell (added under ABI 51: one new struct, seven new
+ * entry points, no existing struct changed, the number did not move).  gnan_small_dropout.seed is a by-value kernel argument: a
+ * hipGraph captured over it would replay the same masks for ever.  These twins of the *_drop entry points read the seed from
+ * device memory instead — `seed` points to one uint64_t cell — and the host writes a fresh seed into the cell before every
+ * replay with gnan_dropout_seed_set, on the replay's stream.
+ *   gnan_dropout_seed_set        one tiny launch that stores `seed` at `cell` (a kernel: the value travels as its argument, no host
+ *                                buffer has to outlive the call).  A NULL cell: GNAN_ERR_BAD_ARG before any HIP call.
+ *   gnan_small_graph_*_drop_dev,
+ *   gnan_mid_graph_*_drop_dev    arguments, covers, workspaces, masks and results of gnan_small_graph_*_drop / gnan_mid_graph_*_drop:
+ *                                a cell that holds s gives the bits of the by-value call with seed s (the same kernels: they
+ *                                take the cell's address beside the record, NULL from the by-value entry points).
+ *   gnan_small_batch_*_drop_dev  Dropout on the batched kernels (gnan_small_batch_fwd / _bwd; kernels of their own), for the
+ *                                semantics of graph slots only: rho_raw_hops == 0, rest_zero == 0 and a one-channel rho inside the
+ *                                plain entry points' covers, anything else GNAN_ERR_UNSUPPORTED naming limit and value (the batched
+ *                                script's own rho carries a per-pair Dropout these kernels do not have).  The masks' node
+ *                                coordinate is the row of the PACKED x, node_off[g] + the local row; feature, layer and unit as
+ *                                above.  So a batch of one graph (a slot: node_off = [0, n]) draws the masks of
+ *                                gnan_small_graph_fwd_drop for the same seed, the graphs of a batch draw different masks, and
+ *                                gnan_dropout_mask(seed, p, total_nodes, ...) is the batch's mask tensor.  Only f's workgroups are
+ *                                masked, never rho's.
+ * Refused on the host before any HIP call, in this order: a NULL record, p outside [0, 1) (NaN included), reserved != 0, a NULL
+ * seed (GNAN_ERR_BAD_ARG).  p == 0 launches the plain kernel, bit for bit, and never reads the cell.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_small_dropout_dev {
+  float p;                   /* in [0, 1); 0 = no Dropout: the plain entry point's kernel, bit for bit */
+  int32_t reserved;          /* 0 */
+  const uint64_t* seed;      /* device memory: the cell gnan_dropout_seed_set writes */
+} gnan_small_dropout_dev;
+int gnan_dropout_seed_set(uint64_t* cell, uint64_t seed, gnan_stream_t stream);
+int gnan_small_graph_fwd_drop_dev(const gnan_small_graph_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+int gnan_small_graph_bwd_drop_dev(const gnan_small_graph_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+int gnan_mid_graph_fwd_drop_dev(const gnan_mid_graph_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+int gnan_mid_graph_bwd_drop_dev(const gnan_mid_graph_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+int gnan_small_batch_fwd_drop_dev(const gnan_small_batch_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+int gnan_small_batch_bwd_drop_dev(const gnan_small_batch_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
 
 /* The same small graph-level task with a NAM read-out over the per-feature aggregates (models.py:358-384 with is_graph_task
  * and readout_n_layers > 0; models.py:259-300 for the read-out):
