@@ -538,6 +538,8 @@ SYMBOLS = {
     "gnan_mid_graph_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gnan_mid_graph_bwd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gnan_mid_graph_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MidGraphInfo)]),
+    "gnan_mid_graph_pre_bwd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gnan_mid_graph_pre_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MidGraphInfo)]),
     "gnan_mid_graph_fwd": (C.c_int, [C.POINTER(MidGraphArgs), C.c_void_p]),
     "gnan_mid_graph_bwd": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.c_void_p]),
     "gnan_small_graph_fwd_drop": (C.c_int, [C.POINTER(SmallGraphArgs), C.POINTER(SmallDropout), C.c_void_p]),

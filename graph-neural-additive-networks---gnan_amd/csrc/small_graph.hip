@@ -382,7 +382,7 @@ struct BatchBwdParams {
 };
 
 constexpr int kBinStride = kWave + 1;
-constexpr int kRhoSlot = kMaxH * kMaxH + 5 * kMaxH, kRhoGroupsMax = 12;       // 12 slots = 207 KB: inside a captured step's 256-KB scratch
+constexpr int kRhoGroupsMax = 12;       // (kRhoSlot: small_graph_body.hpp)  12 slots = 207 KB: inside a captured step's 256-KB scratch
 
 // NB as in small_graph_kernel (2: n <= 128 — hop codes and the row-weight / bin area take 50 KB: dynamic LDS).
 // fdrop: the forward's Dropout of the shape functions (thresh 0: none) — the feature workgroups recompute its masks; rho has none.

@@ -153,6 +153,11 @@ __device__ __forceinline__ void mlp_block(const Mlp& m, const MlpLds& w, float x
   __syncthreads();                                   // the columns are free for the next node block
 }
 
+// Pre-rho backward (small_graph.hip, mid_graph.hip): rho's arguments are split by rows over workgroups, each of which leaves its
+// share of rho's gradients in a slot of the workspace — W2's 64 x 64 (H x H, compact), then five vectors of 64: w_first, b_first,
+// b_mid, w_last, b_last — and the last to arrive adds the slots in group order.
+constexpr int kRhoSlot = kMaxH * kMaxH + 5 * kMaxH;
+
 constexpr int small_cols_floats(int nb) {
   const int nodes = 64 * nb;
   const int tables = 2 * nodes * kMaxC + 256 * kMaxC + nodes * kWave + nodes * nodes / 4;

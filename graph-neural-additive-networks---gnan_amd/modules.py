@@ -481,7 +481,8 @@ class _PathBase(nn.Module):
         GNAN.py:65-67), else None."""
         from . import small_graph as sg
         from .small_graph import (MID_GRAPH_MAX_NODES, SMALL_GRAPH_MAX_NODES, SlotGraph, mid_graph_applies, mid_graph_forward,
-                                  slot_graph_applies, slot_graph_forward, small_graph_applies, small_graph_forward)
+                                  mid_graph_pre_rho_applies, slot_graph_applies, slot_graph_forward, small_graph_applies,
+                                  small_graph_forward)
         drop = self._dropout_active()
         if drop and not sg.SMALL_GRAPH_DROPOUT:
             return None                                  # the general Dropout route, as before
@@ -500,7 +501,11 @@ class _PathBase(nn.Module):
             return None
         f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
         mid = x.shape[0] > SMALL_GRAPH_MAX_NODES        # 129 to 448 nodes: the same by tiles of 64 rows (gnan_mid_graph_fwd)
-        if not (mid_graph_applies(x, g, f, rho, use_cnt) if mid else small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre")):
+        if mid:
+            takes = mid_graph_pre_rho_applies(x, g, f, rho) if use_cnt == "pre" else mid_graph_applies(x, g, f, rho, use_cnt)
+        else:
+            takes = small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre")
+        if not takes:
             return None
         # (the forward's ONE seed draw: only once the route is taken — a forward that goes on to the general route draws its own)
         kw = {"dropout": self._dropout_record()} if drop else {}

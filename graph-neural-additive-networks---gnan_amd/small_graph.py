@@ -5,7 +5,7 @@
 * :func:`small_graph_forward` — features summed per node, rho on the distinct distances (or, ``use_cnt="pre"``, on the n x D
   normalised distances of GNAN.py:65-67), the normalised aggregation and the graph read-out: GNAN.py:55-79 / 146-172,
   models.py:358-384 with ``readout_n_layers == 0``;
-* :func:`mid_graph_forward` — the same for graphs of 129 to 448 nodes, over tiles of 64 rows;
+* :func:`mid_graph_forward` — the same for graphs of 129 to 448 nodes, over tiles of 64 rows (pre-rho: behind ``MID_GRAPH_PRE_RHO``);
 * :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381).
 
 All are autograd nodes whose backward pass is one launch as well (the first two are ONE node, :class:`_OneLaunch`, told its route).
@@ -119,12 +119,15 @@ class _Route(NamedTuple):
     name: str            # the library's entry points ``<name>_fwd`` / ``_bwd`` and ``<name>_workspace_bytes`` / ``_bwd_workspace_bytes``
     args: type           # ... and their argument structs
     bwd_args: type
-    flag: str            # the struct field that says pre-rho (``reserved``, always 0, where the route has no pre-rho)
+    flag: str            # the struct field that says pre-rho (the mid route's ``reserved``: 1 = ``GNAN_MID_PRE_RHO``)
     bwd_borrows: bool    # the backward always takes a workspace (else only under pre-rho)
+    pre_bwd_ws: str      # the query of the backward's workspace under pre-rho (rho's partial gradients in slots)
 
 
-_SMALL = _Route("gnan_small_graph", _lib.SmallGraphArgs, _lib.SmallGraphBwdArgs, "pre_rho", False)
-_MID = _Route("gnan_mid_graph", _lib.MidGraphArgs, _lib.MidGraphBwdArgs, "reserved", True)
+_SMALL = _Route("gnan_small_graph", _lib.SmallGraphArgs, _lib.SmallGraphBwdArgs, "pre_rho", False,
+                "gnan_small_graph_bwd_workspace_bytes")
+_MID = _Route("gnan_mid_graph", _lib.MidGraphArgs, _lib.MidGraphBwdArgs, "reserved", True,
+              "gnan_mid_graph_pre_bwd_workspace_bytes")
 
 
 class _OneLaunch(torch.autograd.Function):
@@ -132,7 +135,8 @@ class _OneLaunch(torch.autograd.Function):
     launch too (``gnan_small_graph_bwd`` / ``gnan_mid_graph_bwd``: one rho channel, <= 64 shells, the gradients of both f and rho
     wanted — or pre-rho), else the general path's kernels on the saved node sums and rho table — transposed aggregation, table
     gradient, the two small-batch MLP backward launches (their gradients land in the flat gradient buffers directly).
-    ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67; the small route only).
+    ``use_cnt``: False / True (post-rho shell normalisation) / ``"pre"`` (GNAN.py:65-67: the rows' table ``[n, D]`` is saved, and the
+    backward is the one launch or an error).
     ``dropout``: None, or ``(p, seed)`` — training-mode Dropout behind every hidden ReLU of f (never of rho), masks hashed from
     the seed (csrc/dropout.hpp; node = row of ``x``, feature = its column): both launches go through the ``_drop`` entry points
     with the same record, and so does ``gnan_fmlp_bwd`` where the general backward runs.  ``seed`` an int: by value, the eager
@@ -170,11 +174,11 @@ class _OneLaunch(torch.autograd.Function):
         Lr, Hr, Cr = ctx.rm
         n, D = x.shape[0], ctx.g.n_codes
         need_f, need_r = any(ctx.needs_input_grad[8:14]), any(ctx.needs_input_grad[14:])      # (eight arguments, then f's six, rho's six)
-        pre_rho = ctx.use_cnt == "pre"          # (small_graph_applies admitted it only where the one launch below covers it)
+        pre_rho = ctx.use_cnt == "pre"          # (the ``*_applies`` predicates admitted it only where the one launch below covers it)
         if not ((SMALL_GRAPH_BACKWARD and Cr == 1 and D <= _ONE_LAUNCH_CODES and d_out.dtype == torch.float32
                  and all(t is None or t.dtype == torch.float32 for t in params)) and ((need_f and need_r) or pre_rho)):
             if pre_rho:
-                raise RuntimeError("the one-launch small-graph forward with pre-rho normalisation was taken where its backward "
+                raise RuntimeError("the one-launch graph forward with pre-rho normalisation was taken where its backward "
                                    "does not apply (float32 parameters and output gradient expected)")
             if ctx.dropout is not None and torch.is_tensor(ctx.dropout[1]):
                 raise RuntimeError("a one-launch forward under Dropout with its seed in a device cell was taken where the one-launch "
@@ -187,7 +191,8 @@ class _OneLaunch(torch.autograd.Function):
         g_out = d_out.detach().contiguous()
         ws = None
         if route.bwd_borrows or pre_rho:
-            ws = _workspace(x.device, getattr(_lib.lib(), route.name + "_bwd_workspace_bytes")(n, D))
+            query = route.pre_bwd_ws if pre_rho else route.name + "_bwd_workspace_bytes"
+            ws = _workspace(x.device, getattr(_lib.lib(), query)(n, D))
         a = route.bwd_args(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, Cf),
                            rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(ctx.g.code), D=D, **{route.flag: int(pre_rho)},
                            **_cnt_pair(ctx.g.cnt if ctx.use_cnt else None), S=_lib.ptr(S), lut=_lib.ptr(lut),
@@ -291,12 +296,26 @@ def mid_graph_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedM
                 and x.shape[1] == f.F and rho.F == 1 and _stack_ok(f) and _stack_ok(rho, max_c=1))
 
 
+MID_GRAPH_PRE_RHO = True      # pre-rho normalisation (GNAN.py:65-67, the stand-alone class's default) on this route: ``reserved =
+                              # GNAN_MID_PRE_RHO``.  On by the measured rule of DESIGN.md section 5: the replayed one-launch step beats the
+                              # general route's at 130, 200 and 417 nodes by far more than the latter's spread (5 kernels against 25)
+
+
+def mid_graph_pre_rho_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP) -> bool:
+    """Can ``gnan_mid_graph_fwd`` / ``_bwd`` with ``reserved = GNAN_MID_PRE_RHO`` take this forward AND its backward: what
+    :func:`mid_graph_applies` asks of graph and stacks, the shell sizes, a one-channel rho, the one-launch backward (a pre-rho forward
+    has no other) and the route's switch?"""
+    return bool(MID_GRAPH_PRE_RHO and MID_GRAPH and SMALL_GRAPH_FORWARD and SMALL_GRAPH_BACKWARD and g.cnt is not None
+                and _graph_ok(x, g, MID_GRAPH_MIN_NODES, MID_GRAPH_MAX_NODES, _ONE_LAUNCH_CODES) and x.shape[1] == f.F and rho.F == 1
+                and rho.C == 1 and _stack_ok(f) and _stack_ok(rho, max_c=1))
+
+
 def mid_graph_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, use_cnt, graph_sum: bool, dropout=None):
     """:func:`small_graph_forward` for a dense-coded graph of 129 to 448 nodes (``gnan_mid_graph_fwd`` / ``_fwd_drop``): ``[n, C]``
-    node outputs, or ``[C, 1]`` with ``graph_sum``."""
+    node outputs, or ``[C, 1]`` with ``graph_sum``.  ``use_cnt="pre"``: GNAN.py:65-67 (:func:`mid_graph_pre_rho_applies`)."""
     _lib.require_device(x, f.w_last, rho.w_last, g.code)
-    return _OneLaunch.apply(_MID, x, g, bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C),
-                            _dropout_record(dropout), *f[:6], *rho[:6])
+    return _OneLaunch.apply(_MID, x, g, "pre" if use_cnt == "pre" else bool(use_cnt), bool(graph_sum), (f.L, f.H, f.C, f.F),
+                            (rho.L, rho.H, rho.C), _dropout_record(dropout), *f[:6], *rho[:6])
 
 
 # =============================================================================
@@ -510,8 +529,8 @@ def dropout_capture_applies(model, x: torch.Tensor, g, node_ids=None) -> bool:
         return slot_mode(model) is not None and slot_graph_applies(g, f, rho)
     if not (g.is_dense and SMALL_GRAPH_BACKWARD):
         return False
-    if x.shape[0] > SMALL_GRAPH_MAX_NODES:
-        return mid_graph_applies(x, g, f, rho, use_cnt)         # (one rho channel, at most 64 shells: its backward's cover too)
+    if x.shape[0] > SMALL_GRAPH_MAX_NODES:                      # (one rho channel, at most 64 shells: its backward's cover too)
+        return mid_graph_pre_rho_applies(x, g, f, rho) if use_cnt == "pre" else mid_graph_applies(x, g, f, rho, use_cnt)
     # (... which the small route's forward exceeds: a device-seed backward is the one launch or nothing)
     return small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre") and rho.C == 1 and g.n_codes <= _ONE_LAUNCH_CODES
 

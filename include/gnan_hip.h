@@ -1295,7 +1295,22 @@ int gnan_small_graph_bwd(const gnan_small_graph_bwd_args* a, gnan_stream_t strea
  * Backward: workgroup k < F forms dS over the row tiles itself and runs gnan_fmlp_bwd's body on feature k; the table gradient's
  * rows are split over ceil(n / 32) rho workgroups that leave float64 partials in the workspace, and the last of them to arrive
  * adds the partials in group order and runs the same body on rho.  No workgroup waits for another.
+ *
+ * Pre-rho normalisation (GNAN.py:65-67; no struct changed, the number did not move): `reserved` == GNAN_MID_PRE_RHO on any of the
+ * six entry points (gnan_mid_graph_fwd / _bwd and their _drop / _drop_dev twins) makes the weight of pair (i, j)
+ * rho(u_d / max(cnt[i, d], 1)) — rho after the IEEE float32 division, gnan_small_graph_fwd's pre_rho, with its arithmetic and
+ * orders: a graph both cover gets the same bits from both.  `reserved` == 0 is the behaviour above, bit for bit; any other value is
+ * GNAN_ERR_BAD_ARG naming it.  The cover is the one above and needs cnt != NULL (GNAN_ERR_UNSUPPORTED without, as
+ * gnan_small_graph_fwd refuses it).  lut is then the ROWS' table [n, D] = rho(u_d / max(cnt[i, d], 1)): n * D floats the forward
+ * writes and the backward reads.  Kernels of their own.  Forward: rho's n * D arguments go in passes of 64 (argument e = i * D + d
+ * in lane e % 64) to R = ceil(ceil(n D / 64) / ceil(n / 64)) rho workgroups of at most ceil(n / 64) passes each (the grid is
+ * F + R), and the last workgroup's tiles take their row weights from lut.  Backward: every (row, shell) is an argument of rho of
+ * its own; rho group g (rows 32 g .. 32 g + 31) leaves its share of rho's gradients in its slot of the workspace and the last
+ * group to arrive adds the slots in group order — no float atomics, the same bits every run.  That workspace is larger:
+ * gnan_mid_graph_pre_bwd_workspace_bytes(n, D) = 16 + ceil(n / 32) * 4416 * 4 bytes (247 312 at 448 nodes), 8-byte aligned, the
+ * first 16 zero as above; GNAN_ERR_WORKSPACE below it.  gnan_mid_graph_pre_describe is gnan_mid_graph_describe for these launches.
  * ------------------------------------------------------------------------------------------- */
+#define GNAN_MID_PRE_RHO 1   /* gnan_mid_graph_args.reserved / gnan_mid_graph_bwd_args.reserved: pre-rho normalisation */
 typedef struct gnan_mid_graph_args {
   const float* x;            /* [n, F], row stride x_stride */
   int64_t x_stride;
@@ -1304,11 +1319,11 @@ typedef struct gnan_mid_graph_args {
   gnan_small_mlp rho;        /* one scalar MLP, C == 1 */
   const uint8_t* code;       /* [n, n] hop codes (gnan_dense_to_code) */
   int32_t D;
-  int32_t reserved;          /* 0 */
-  const int32_t* cnt;        /* optional [n, cnt_stride] shell sizes */
+  int32_t reserved;          /* 0, or GNAN_MID_PRE_RHO */
+  const int32_t* cnt;        /* optional [n, cnt_stride] shell sizes (required under GNAN_MID_PRE_RHO) */
   int64_t cnt_stride;
   float* S;                  /* [n, f.C] */
-  float* lut;                /* [D] */
+  float* lut;                /* [D]; under GNAN_MID_PRE_RHO the rows' table [n, D] */
   float* Y;                  /* optional [n, f.C] */
   float* Ysum;               /* optional [f.C] */
   void* workspace;
@@ -1322,11 +1337,11 @@ typedef struct gnan_mid_graph_bwd_args {
   gnan_small_mlp rho;
   const uint8_t* code;
   int32_t D;
-  int32_t reserved;          /* 0 */
+  int32_t reserved;          /* 0, or GNAN_MID_PRE_RHO: as the forward's */
   const int32_t* cnt;
   int64_t cnt_stride;
   const float* S;            /* [n, f.C] node sums of the forward */
-  const float* lut;          /* [D] rho table of the forward */
+  const float* lut;          /* [D] rho table of the forward ([n, D] under GNAN_MID_PRE_RHO) */
   const float* dY;           /* [n, f.C] or NULL */
   const float* dYsum;        /* [f.C] or NULL (used when dY is NULL) */
   gnan_small_mlp_grads df;
@@ -1348,6 +1363,10 @@ typedef struct gnan_mid_graph_info {
 size_t gnan_mid_graph_workspace_bytes(int32_t n, int32_t F, int32_t C);
 size_t gnan_mid_graph_bwd_workspace_bytes(int32_t n, int32_t D);
 int gnan_mid_graph_describe(int32_t n, int32_t F, int32_t D, int32_t C, gnan_mid_graph_info* out);
+/* ... under GNAN_MID_PRE_RHO (host only): the backward's workspace, and the launches' look — fwd_grid = F + R, bwd_grid = F + rho_groups,
+ * the LDS of the pre-rho kernels, fwd_workspace_bytes = gnan_mid_graph_workspace_bytes, bwd_workspace_bytes = the query here */
+size_t gnan_mid_graph_pre_bwd_workspace_bytes(int32_t n, int32_t D);
+int gnan_mid_graph_pre_describe(int32_t n, int32_t F, int32_t D, int32_t C, gnan_mid_graph_info* out);
 int gnan_mid_graph_fwd(const gnan_mid_graph_args* a, gnan_stream_t stream);
 int gnan_mid_graph_bwd(const gnan_mid_graph_bwd_args* a, gnan_stream_t stream);
 

@@ -7,7 +7,12 @@ the harness's own per-shape captured step (forward + BCE loss + backward + Adam 
 captured in this one process and their replays are timed alternately: HIP events around ``REPLAYS`` replays, 30 samples after
 5 warm-ups, median / min / max in ms per step, and the kernel count of each captured step.  Prints one JSON line per route;
 ``faster`` says whether the new route's median lies below the general route's by more than the general route's own spread
-(max - min of its 30 samples)."""
+(max - min of its 30 samples).
+
+``--model standalone``: the stand-alone class ``gnan_amd.GNAN.TensorGNAN(15, 1, 3, hidden_channels = 64, is_graph_task)`` with its
+default pre-rho normalisation (GNAN.py:65-67) — the one-launch route behind ``small_graph.MID_GRAPH_PRE_RHO`` against the general
+kernels (the switch off: rho's row table, the operand, ``pre_rho_aggregate`` and their backward launches).  The same protocol."""
+import argparse
 import json
 import os
 import statistics
@@ -47,11 +52,20 @@ def graph_of(n, seed):
                 normalization_matrix=norm.to(DEV))
 
 
+MODEL = "models"              # --model: "models" (models.TensorGNAN, post-rho) or "standalone" (GNAN.TensorGNAN, pre-rho)
+
+
 def captured_step(data, mid):
     """-> (the model, its captured per-shape step) with the route frozen into the capture."""
-    small_graph.MID_GRAPH = mid
+    switch = "MID_GRAPH" if MODEL == "models" else "MID_GRAPH_PRE_RHO"
+    shipped = getattr(small_graph, switch)
+    setattr(small_graph, switch, mid)
     torch.manual_seed(0)
-    m = mb.TensorGNAN(F, 1, 3, hidden_channels=H, is_graph_task=True, readout_n_layers=0, device=DEV)
+    if MODEL == "models":
+        m = mb.TensorGNAN(F, 1, 3, hidden_channels=H, is_graph_task=True, readout_n_layers=0, device=DEV)
+    else:
+        from gnan_amd import GNAN as standalone
+        m = standalone.TensorGNAN(F, 1, 3, hidden_channels=H, is_graph_task=True, device=DEV)
     mb.redraw(m)
     m = m.to(DEV).eval()
     opt = torch.optim.Adam(gnan_amd.optim_params(m), lr=1e-3)
@@ -61,7 +75,7 @@ def captured_step(data, mid):
         harness.train_epoch(m, [data], loss_fn, opt, DEV, classify=True, is_graph_task=True)
         recs = [r for r in harness._steps_of(m).graph.buckets.values() if r["step"] is not None]
         if recs:
-            small_graph.MID_GRAPH = True
+            setattr(small_graph, switch, shipped)
             return m, keep, recs[0]["step"].step
     raise SystemExit("mid_graph_time.py: the per-shape step was not captured")
 
@@ -88,7 +102,7 @@ def measure(n):
     out = []
     for name, (_, _, step) in routes.items():
         ts = times[name]
-        out.append({"what": "mid_graph_time", "route": name, "nodes": n, "F": F, "H": H, "shells": int(step.model.hop_graph(data).n_codes),
+        out.append({"what": "mid_graph_time", "model": MODEL, "route": name, "nodes": n, "F": F, "H": H, "shells": int(step.model.hop_graph(data).n_codes),
                     "kernels": step.graph.kernel_nodes, "median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts),
                     "replays_per_sample": REPLAYS, "samples": SAMPLES})
     old, new = out
@@ -97,6 +111,9 @@ def measure(n):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--model", choices=("models", "standalone"), default="models")
+    MODEL = ap.parse_args().model
     if not torch.cuda.is_available():
         sys.exit("mid_graph_time.py measures on the GPU: no device visible")
     for n in SIZES:
