@@ -385,6 +385,18 @@ class MidGraphInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class SmallBatchPreInfo(C.Structure):
+    """What the two launches of ``gnan_small_batch_pre_fwd`` / ``_bwd`` look like for a shape (``gnan_small_batch_pre_info``)."""
+    _fields_ = [
+        ("node_blocks", C.c_int32), ("rho_workgroups", C.c_int32), ("rho_groups", C.c_int32), ("fwd_grid", C.c_int32),
+        ("bwd_grid", C.c_int32), ("fwd_lds_bytes", C.c_int32), ("bwd_lds_bytes", C.c_int32), ("reserved", C.c_int32),
+        ("fwd_graph_bytes", C.c_int64), ("fwd_node_bytes", C.c_int64), ("bwd_graph_bytes", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SmallDropout(C.Structure):
     """Training-mode Dropout of the shape functions on the one-launch routes (``gnan_small_dropout``): ``p`` in [0, 1), the
     64-bit seed of the hash masks (csrc/dropout.hpp)."""
@@ -560,6 +572,13 @@ SYMBOLS = {
     "gnan_mid_graph_bwd_drop_dev": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
     "gnan_small_batch_fwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
     "gnan_small_batch_bwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_small_batch_pre_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "gnan_small_batch_pre_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmallBatchBwdArgs)]),
+    "gnan_small_batch_pre_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmallBatchPreInfo)]),
+    "gnan_small_batch_pre_fwd": (C.c_int, [C.POINTER(SmallBatchArgs), C.c_void_p]),
+    "gnan_small_batch_pre_bwd": (C.c_int, [C.POINTER(SmallBatchBwdArgs), C.c_void_p]),
+    "gnan_small_batch_pre_fwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_small_batch_pre_bwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
     "gnan_hops_to_code": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnan_dense_blocks_to_code": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),

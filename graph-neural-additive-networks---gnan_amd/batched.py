@@ -326,6 +326,83 @@ class _BatchedGraphs(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None, *pg_f, *pg_r)
 
 
+class _BatchedGraphsPre(torch.autograd.Function):
+    """:class:`_BatchedGraphs` under PRE-rho normalisation (GNAN.py:65-67: pair (i, j) weighs ``rho(u_d / cnt[i, d])``) — the slots'
+    semantics with the shell sizes, a one-channel rho and at most 64 hop codes: ``gnan_small_batch_pre_fwd`` forward (the rows' table
+    ``[N * D, 1]`` is saved), ``gnan_small_batch_pre_bwd`` backward — its two launches or a :class:`GnanHipError`, never the general
+    kernels: a pre-rho forward has no other backward.  ``dropout``: None, or ``(p, seed cell)`` (the ``_drop_dev`` twins)."""
+
+    @staticmethod
+    def forward(ctx, x, blocks: HopBlocks, graph_sum, fm, rm, cnt, dropout, *params):
+        if dropout is not None and not torch.is_tensor(dropout[1]):
+            raise _lib.GnanHipError("Dropout on the batched kernels: the seed in a device cell")
+        from . import functional as Fn
+        Lf, Hf, Cf, F = fm
+        Lr, Hr, Cr = rm
+        G, N, D = blocks.n_graphs, blocks.total_nodes, blocks.n_codes
+        if cnt is None or Cr != 1 or D > 64 or blocks.min_nodes < 1 or G > 65535:
+            raise _lib.GnanHipError("pre-rho normalisation on the batched kernels needs the shell sizes, a one-channel rho, at most 64 "
+                                    f"hop codes, a node in every graph and at most 65535 graphs (got rho.C={Cr}, D={D}, "
+                                    f"min_nodes={blocks.min_nodes}, n_graphs={G})")
+        xk = Fn._rows(x.detach().float())
+        dev = xk.device
+        keep = _kept(params)
+        S = torch.empty((N, Cf), dtype=torch.float32, device=dev)
+        lut = torch.empty((N * D, 1), dtype=torch.float32, device=dev)
+        Y = None if graph_sum else torch.empty((N, Cf), dtype=torch.float32, device=dev)
+        Ysum = torch.empty((G, Cf), dtype=torch.float32, device=dev) if graph_sum else None
+        need = _lib.lib().gnan_small_batch_pre_workspace_bytes(G, N, F, Cf)
+        ws = torch.empty(need // 4 + 1, dtype=torch.int32, device=dev)
+        ws[: 32 * G].zero_()                                                 # the graphs' arrival counters (a 128-byte line each)
+        a = _lib.SmallBatchArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), total_nodes=N, F=F, n_graphs=G,
+                                max_nodes=blocks.max_nodes, f=_small_mlp(keep[:6], Lf, Hf, Cf),
+                                rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(blocks.code),
+                                node_off=_lib.ptr(blocks.node_off), code_off=_lib.ptr(blocks.code_off), D=D,
+                                rho_raw_hops=0, rest_zero=0, S=_lib.ptr(S), lut=_lib.ptr(lut),
+                                Y=_lib.ptr(Y), Ysum=_lib.ptr(Ysum), workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4,
+                                **_cnt_pair(cnt))
+        _launch("gnan_small_batch_pre_fwd", a, dropout, xk)
+        ctx.blocks, ctx.graph_sum, ctx.fm, ctx.rm, ctx.dropout, ctx.cnt = blocks, graph_sum, fm, rm, dropout, cnt
+        _save(ctx, (xk, S, lut), params)
+        return Ysum if graph_sum else Y
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from . import functional as Fn
+        (x, S, lut), params = _saved(ctx, 3)
+        Lf, Hf, Cf, F = ctx.fm
+        Lr, Hr, Cr = ctx.rm
+        need_f, need_r = any(ctx.needs_input_grad[7:13]), any(ctx.needs_input_grad[13:])      # (seven arguments, then f's six, rho's six)
+        blocks = ctx.blocks
+        if not (BATCH_BACKWARD_KERNEL and d_out.dtype == torch.float32 and all(t is None or t.dtype == torch.float32 for t in params)):
+            raise _lib.GnanHipError("gnan_small_batch_pre_bwd does not cover this step (float32 parameters and output gradient, "
+                                    "BATCH_BACKWARD_KERNEL on): a pre-rho forward has no other backward")
+        keep = _kept(params)
+        outs_f, outs_r = Fn._grad_outputs(keep[:6], ctx.dests[:6]), Fn._grad_outputs(keep[6:], ctx.dests[6:])
+        g_out = d_out.detach().contiguous()
+        a = _lib.SmallBatchBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), total_nodes=blocks.total_nodes, F=F,
+                                   n_graphs=blocks.n_graphs, max_nodes=blocks.max_nodes, f=_small_mlp(keep[:6], Lf, Hf, Cf),
+                                   rho=_small_mlp(keep[6:], Lr, Hr, Cr), code=_lib.ptr(blocks.code),
+                                   node_off=_lib.ptr(blocks.node_off), code_off=_lib.ptr(blocks.code_off), D=blocks.n_codes,
+                                   rho_raw_hops=0, rest_zero=0, S=_lib.ptr(S), lut=_lib.ptr(lut), **_cnt_pair(ctx.cnt),
+                                   dY=None if ctx.graph_sum else _lib.ptr(g_out),
+                                   dYsum=_lib.ptr(g_out) if ctx.graph_sum else None, df=_mlp_grads(outs_f), drho=_mlp_grads(outs_r),
+                                   workspace=None, workspace_bytes=0)
+        need = _lib.lib().gnan_small_batch_pre_bwd_workspace_bytes(a)
+        if need > BATCH_BACKWARD_MAX_WORKSPACE:
+            raise _lib.GnanHipError(f"gnan_small_batch_pre_bwd needs a workspace of {need} bytes, above BATCH_BACKWARD_MAX_WORKSPACE = "
+                                    f"{BATCH_BACKWARD_MAX_WORKSPACE}: a pre-rho forward has no other backward")
+        ws = torch.empty(need // 4 + 1, dtype=torch.float32, device=x.device)
+        G, info = blocks.n_graphs, _lib.SmallBatchPreInfo()
+        _lib.check(_lib.lib().gnan_small_batch_pre_describe(blocks.max_nodes, F, blocks.n_codes, Cf, info), "gnan_small_batch_pre_describe")
+        lines = (need - G * info.bwd_graph_bytes) // 4                       # behind the slabs: a counter line per graph, zero
+        ws[lines: lines + 32 * G].zero_()
+        a.workspace, a.workspace_bytes = _lib.ptr(ws), ws.numel() * 4
+        _launch("gnan_small_batch_pre_bwd", a, ctx.dropout, x)
+        return (None, None, None, None, None, None, None, *[o if need_f else None for o in outs_f],
+                *[o if need_r else None for o in outs_r])
+
+
 class TensorGNAN(_PathBase):
     """``TensorGNAN`` of the batched script — constructor batched_pyg_main.py:99-131, forward :133-184.
     The shape functions and rho are always two layers deep there (``n_layers`` is accepted and unused).

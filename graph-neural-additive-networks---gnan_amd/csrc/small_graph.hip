@@ -55,7 +55,9 @@ struct BatchParams {
 // DROP: the shape functions' workgroups mask their hidden activations (mlp_block<true>; node = the row of x, feature = k); the
 // Dropout-free instances are the code they were.  node_base: the mask's node coordinate of this graph's row 0 — 0 for a graph of
 // its own, node_off[g] for graph g of a batch (the row of the packed x), so the graphs of a batch draw different masks.
-template <int NB, bool DROP = false>
+// BATCH_PRE: pre-rho on a graph of a batch (small_graph_batch_pre_kernel): the grid's rho workgroups are sized on the host for the
+// LARGEST graph, so those whose 64 arguments all lie beyond this graph's n * D stage nothing and evaluate nothing — they only arrive.
+template <int NB, bool DROP = false, bool BATCH_PRE = false>
 __device__ __forceinline__ void small_graph_body(const SmallParams& p, float* cols, gnan_bwd::Drop drop = gnan_bwd::Drop{0u, 1.f, 0ull},
                                                  int64_t node_base = 0) {
   constexpr int kNodes = 64 * NB;
@@ -113,6 +115,8 @@ __device__ __forceinline__ void small_graph_body(const SmallParams& p, float* co
           for (int c = 0; c < p.f.C; ++c) p.part[(static_cast<int64_t>(k) * p.n + j) * p.f.C + c] = out[c];
       }
     }
+  } else if (BATCH_PRE && (k - p.F) * kWave >= p.n * p.D) {
+    // (nothing of this graph's for this workgroup)
   } else if (p.pre_rho) {
     // rho at the n * D normalised distances (GNAN.py:66: torch.div(node_distances, normalization_matrix), IEEE division): this
     // workgroup's 64 of them
@@ -330,6 +334,37 @@ __global__ __launch_bounds__(256) void small_graph_batch_drop_kernel(const Batch
   SmallParams p;
   const int64_t node_base = graph_of_batch(bp, blockIdx.y, p);
   small_graph_body<NB, true>(p, cols, drop, node_base);
+}
+
+// Pre-rho normalisation (GNAN.py:65-67) on the graphs of a batch (gnan_small_batch_pre_fwd): small_graph_batch_drop_kernel's lines
+// with the rows' table — lut is [total_nodes, D], graph g's rows start at node_off[g] * D — and gridDim.x = F + ceil(max_nodes D / 64):
+// rho workgroup r takes arguments 64 r .. 64 r + 63 of ITS graph's n_g * D (BATCH_PRE above); all gridDim.x workgroups of a graph
+// arrive at its counter, the last one aggregates with the row weights read back from lut.  A graph without nodes is left alone.
+__device__ __forceinline__ int64_t graph_of_batch_pre(const BatchParams& bp, int g, SmallParams& p) {
+  const int64_t o = graph_of_batch(bp, g, p);
+  p.lut = bp.base.lut + o * p.D;
+  p.pre_rho = 1; p.rho_raw = 0; p.rest_zero = 0; p.r.C = 1;          // (what the launcher set, as constants: the body's other paths fold away)
+  return o;
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void small_graph_batch_pre_kernel(const BatchParams bp) {
+  extern __shared__ __attribute__((aligned(16))) float cols[];
+  SmallParams p;
+  graph_of_batch_pre(bp, blockIdx.y, p);
+  if (p.n < 1) return;                                 // (uniform over the graph's workgroups)
+  small_graph_body<NB, false, true>(p, cols);
+}
+
+// ... under Dropout of the shape functions (gnan_small_batch_pre_fwd_drop_dev with p > 0): small_graph_batch_drop_kernel's masks
+template <int NB>
+__global__ __launch_bounds__(256) void small_graph_batch_pre_drop_kernel(const BatchParams bp, gnan_bwd::Drop drop, const uint64_t* seed_dev) {
+  extern __shared__ __attribute__((aligned(16))) float cols[];
+  drop.seed = *seed_dev;
+  SmallParams p;
+  const int64_t node_base = graph_of_batch_pre(bp, blockIdx.y, p);
+  if (p.n < 1) return;
+  small_graph_body<NB, true, true>(p, cols, drop, node_base);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -787,6 +822,47 @@ __global__ __launch_bounds__(256) void small_graph_batch_bwd_drop_kernel(const B
   small_graph_bwd_body<C, NB>(p, dyn, drop, node_base);
 }
 
+// The backward of small_graph_batch_pre_kernel (gnan_small_batch_pre_bwd): small_graph_batch_bwd_drop_kernel's lines with the rows'
+// table and gridDim.x = F + min(D, kRhoGroupsMax).  The host knows the largest graph only, so every graph derives small_bwd's split
+// of rho's arguments from its OWN n_g here; rho workgroups beyond its rho_groups leave at once and are not counted in the join.  The
+// groups' partial gradients go to the graph's own kRhoGroupsMax slots (bp.base.part), the last group to arrive at the graph's counter
+// line (bp.base.counter, 128 bytes per graph) adds them in group order into the graph's slab.  False: nothing to do here.
+template <int C>
+__device__ __forceinline__ bool graph_of_batch_pre(const BatchBwdParams& bp, int g, SmallBwdParams& p, int64_t& node_base) {
+  node_base = graph_of_batch<C>(bp, g, p);
+  if (p.n < 1) return false;
+  p.lut = bp.base.lut + node_base * p.D;
+  p.pre_rho = 1; p.rho_raw = 0; p.rest_zero = 0; p.rho_c = 1;        // (what the launcher set, as constants: the body's other paths fold away)
+  const int cap = static_cast<int>(gridDim.x) - p.F;                 // min(D, kRhoGroupsMax)
+  const int groups = cap < p.n ? cap : p.n;
+  p.rows_per = (p.n + groups - 1) / groups;
+  p.rho_groups = (p.n + p.rows_per - 1) / p.rows_per;
+  p.counter = bp.base.counter + 32 * g;
+  p.part = bp.base.part + static_cast<int64_t>(g) * kRhoGroupsMax * kRhoSlot;
+  return static_cast<int>(blockIdx.x) < p.F + p.rho_groups;
+}
+
+template <int C, int NB>
+__global__ __launch_bounds__(256) void small_graph_batch_pre_bwd_kernel(const BatchBwdParams bp) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  SmallBwdParams p;
+  int64_t node_base;
+  if (!graph_of_batch_pre<C>(bp, blockIdx.y, p, node_base)) return;
+  small_graph_bwd_body<C, NB>(p, dyn);
+}
+
+// ... of a forward under Dropout (gnan_small_batch_pre_bwd_drop_dev with p > 0): the masks of small_graph_batch_pre_drop_kernel
+template <int C, int NB>
+__global__ __launch_bounds__(256) void small_graph_batch_pre_bwd_drop_kernel(const BatchBwdParams bp, gnan_bwd::Drop drop,
+                                                                             const uint64_t* seed_dev) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  drop.seed = *seed_dev;
+  SmallBwdParams p;
+  int64_t node_base;
+  if (!graph_of_batch_pre<C>(bp, blockIdx.y, p, node_base)) return;
+  small_graph_bwd_body<C, NB>(p, dyn, drop, node_base);
+}
+
 // out[e] = sum_g slabs[g][e], graphs in order, eight graphs' terms requested together; the slab is the twelve gradient tensors
 // back to back and `dst` lists where each lives (offsets ascending, a NULL destination = a tensor that does not exist)
 struct ReduceSeg { int64_t at[13]; float* dst[12]; };
@@ -1169,6 +1245,235 @@ extern "C" int gnan_small_batch_bwd_drop_dev(const gnan_small_batch_bwd_args* a,
   const uint64_t* seed_dev = nullptr;
   if (int rc = drop_dev_ok("small_batch_bwd", d, &drop, &seed_dev)) return rc;
   return small_batch_bwd(a, drop, seed_dev, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pre-rho normalisation on the batched kernels (gnan_small_batch_pre_*): what a default stand-alone model in graph slots runs.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// the cover: the batch kernels' with shell sizes (D <= 64, a one-channel rho) — plus, below, the shell sizes themselves and the
+// slots' semantics
+constexpr RouteLimits kBatchPreCover = {kMaxNodes, kWave, kMaxC, false};
+constexpr int kBatchMaxGraphs = 65535;                 // blockIdx.y
+
+constexpr size_t kPreFwdStaticBytes = kWeightFloats * sizeof(float) + 16;                              // weight image + the arrival slot
+template <int NB>
+constexpr size_t pre_bwd_static_bytes() {              // red | dY, S, dS [n, C] | the waves' float64 partials | the rho groups' arrival slot
+  return sizeof(gnan_bwd::RedBuffer) + 3 * static_cast<size_t>(64 * NB) * kMaxC * sizeof(float) + kWaves * kWave * sizeof(double) + 16;
+}
+constexpr size_t kLdsBytes = 160 * 1024;
+static_assert(small_cols_floats(2) * sizeof(float) + kPreFwdStaticBytes <= kLdsBytes &&
+              small_bwd_dyn_bytes<2>(true) + pre_bwd_static_bytes<2>() <= kLdsBytes, "a workgroup's LDS fits the compute unit's");
+
+inline unsigned pre_rho_workgroups(int max_nodes, int D) { return static_cast<unsigned>((max_nodes * D + kWave - 1) / kWave); }
+inline int pre_rho_group_cap(int D) { return D < kRhoGroupsMax ? D : kRhoGroupsMax; }
+
+// the backward's workspace: slabs (whole 128-byte lines) | a counter line per graph | the graphs' rho slots
+inline size_t pre_slab_bytes(int n_graphs, int64_t slab) {
+  return (static_cast<size_t>(n_graphs) * static_cast<size_t>(slab) * sizeof(float) + 127) / 128 * 128;
+}
+constexpr size_t kPreBwdGraphBytes = 128 + static_cast<size_t>(kRhoGroupsMax) * kRhoSlot * sizeof(float);
+
+// what both launchers refuse beyond sizes and MLP shapes: the rest of the cover (GNAN_ERR_UNSUPPORTED naming limit and value)
+template <class A>
+int batch_pre_cover_ok(const char* who, const A* a) {
+  if (a->max_nodes < 1) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers graphs of >= 1 node (got max_nodes=%d)", who, a->max_nodes);
+  if (int rc = shape_ok(who, kBatchPreCover, a->max_nodes, a->F, a->D, &a->f, &a->rho)) return rc;
+  if (a->n_graphs > kBatchMaxGraphs)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: covers n_graphs <= %d graphs per launch (got n_graphs=%d)", who, kBatchMaxGraphs, a->n_graphs);
+  if (a->cnt == nullptr)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: pre-rho normalisation needs the shell sizes (got cnt=%p)", who, static_cast<const void*>(a->cnt));
+  if (a->rho_raw_hops != 0)
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: pre-rho covers rho_raw_hops == 0 (got rho_raw_hops=%d)", who, a->rho_raw_hops);
+  if (a->rest_zero != 0) return gnan::fail(GNAN_ERR_UNSUPPORTED, "%s: pre-rho covers rest_zero == 0 (got rest_zero=%d)", who, a->rest_zero);
+  return GNAN_OK;
+}
+}  // namespace
+
+extern "C" size_t gnan_small_batch_pre_workspace_bytes(int32_t n_graphs, int64_t total_nodes, int32_t F, int32_t C) {
+  return gnan_small_batch_workspace_bytes(n_graphs, total_nodes, F, C);          // counters (a line each) | part
+}
+
+extern "C" size_t gnan_small_batch_pre_bwd_workspace_bytes(const gnan_small_batch_bwd_args* a) {
+  if (a == nullptr) return 0;
+  int64_t at[13];
+  return pre_slab_bytes(a->n_graphs, slab_layout(&a->f, a->F, &a->rho, at)) + static_cast<size_t>(a->n_graphs) * kPreBwdGraphBytes;
+}
+
+extern "C" int gnan_small_batch_pre_describe(int32_t max_nodes, int32_t F, int32_t D, int32_t C, gnan_small_batch_pre_info* out) {
+  GNAN_REQUIRE(out != nullptr, "small_batch_pre_describe: null out");
+  gnan_small_mlp f{};
+  f.L = 3; f.H = 1; f.C = C;
+  if (int rc = shape_ok("small_batch_pre_describe", kBatchPreCover, max_nodes, F, D, &f, nullptr)) return rc;
+  const bool two = max_nodes > 64;
+  out->node_blocks = two ? 2 : 1;
+  out->rho_workgroups = static_cast<int32_t>(pre_rho_workgroups(max_nodes, D));
+  out->rho_groups = pre_rho_group_cap(D);
+  out->fwd_grid = F + out->rho_workgroups;
+  out->bwd_grid = F + out->rho_groups;
+  out->fwd_lds_bytes = static_cast<int32_t>(small_cols_floats(two ? 2 : 1) * sizeof(float) + kPreFwdStaticBytes);
+  out->bwd_lds_bytes = static_cast<int32_t>(two ? small_bwd_dyn_bytes<2>(true) + pre_bwd_static_bytes<2>()
+                                                : small_bwd_dyn_bytes<1>(true) + pre_bwd_static_bytes<1>());
+  out->reserved = 0;
+  out->fwd_graph_bytes = 128;
+  out->fwd_node_bytes = static_cast<int64_t>(F) * C * static_cast<int64_t>(sizeof(float));
+  out->bwd_graph_bytes = static_cast<int64_t>(kPreBwdGraphBytes);
+  return GNAN_OK;
+}
+
+namespace {
+// THE launcher of gnan_small_batch_pre_fwd (seed_dev == NULL) and gnan_small_batch_pre_fwd_drop_dev
+int small_batch_pre_fwd(const gnan_small_batch_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
+  GNAN_REQUIRE(a->n_graphs >= 0 && a->F >= 1 && a->D >= 1 && a->total_nodes >= 0, "small_batch_pre: bad sizes");
+  if (a->n_graphs == 0) return GNAN_OK;
+  if (int rc = batch_pre_cover_ok("small_batch_pre", a)) return rc;
+  GNAN_REQUIRE(a->x && a->code && a->node_off && a->code_off && a->S && a->lut && (a->Y || a->Ysum),
+               "small_batch_pre: null x / code / offsets / S / lut / outputs");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_batch_pre: null weights");
+  if (int rc = strides_ok("small_batch_pre", a)) return rc;
+  if (int rc = workspace_ok("small_batch_pre", a, gnan_small_batch_pre_workspace_bytes(a->n_graphs, a->total_nodes, a->F, a->f.C))) return rc;
+  BatchParams bp;
+  SmallParams& p = bp.base;
+  fwd_fields(p, a, 0);
+  p.S = a->S; p.lut = a->lut; p.Y = a->Y; p.Ysum = a->Ysum;
+  p.counter = static_cast<unsigned*>(a->workspace);
+  p.part = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + static_cast<size_t>(a->n_graphs) * 128);
+  p.rho_raw = 0; p.rest_zero = 0; p.pre_rho = 1;
+  bp.node_off = a->node_off; bp.code_off = a->code_off;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>(a->F) + pre_rho_workgroups(a->max_nodes, a->D), static_cast<unsigned>(a->n_graphs));
+  const dim3 block(kWaves * kWave);
+  constexpr size_t lds1 = small_cols_floats(1) * sizeof(float), lds2 = small_cols_floats(2) * sizeof(float);
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own)
+    if (a->max_nodes <= 64) {
+      hipLaunchKernelGGL(small_graph_batch_pre_drop_kernel<1>, grid, block, lds1, st, bp, drop, seed_dev);
+    } else {
+      if (int rc = raise_dyn_lds<&small_graph_batch_pre_drop_kernel<2>>(lds2, "small_batch_pre")) return rc;
+      hipLaunchKernelGGL(small_graph_batch_pre_drop_kernel<2>, grid, block, lds2, st, bp, drop, seed_dev);
+    }
+    return gnan::check_launch("small_graph_batch_pre_drop_kernel");
+  }
+  if (a->max_nodes <= 64) {
+    hipLaunchKernelGGL(small_graph_batch_pre_kernel<1>, grid, block, lds1, st, bp);
+  } else {
+    if (int rc = raise_dyn_lds<&small_graph_batch_pre_kernel<2>>(lds2, "small_batch_pre")) return rc;
+    hipLaunchKernelGGL(small_graph_batch_pre_kernel<2>, grid, block, lds2, st, bp);
+  }
+  return gnan::check_launch("small_graph_batch_pre_kernel");
+}
+
+template <int C>
+int launch_small_batch_pre_bwd(const BatchBwdParams& bp, int n_graphs, int max_nodes, const gnan_bwd::Drop& drop, const uint64_t* seed_dev,
+                               hipStream_t st) {
+  const dim3 grid(static_cast<unsigned>(bp.base.F + pre_rho_group_cap(bp.base.D)), static_cast<unsigned>(n_graphs));
+  constexpr size_t lds1 = small_bwd_dyn_bytes<1>(true), lds2 = small_bwd_dyn_bytes<2>(true);
+  if (drop.thresh != 0u) {                             // (the Dropout instances: kernels of their own)
+    if (max_nodes <= 64) {
+      hipLaunchKernelGGL((small_graph_batch_pre_bwd_drop_kernel<C, 1>), grid, dim3(256), lds1, st, bp, drop, seed_dev);
+    } else {
+      if (int rc = raise_dyn_lds<&small_graph_batch_pre_bwd_drop_kernel<C, 2>>(lds2, "small_batch_pre_bwd")) return rc;
+      hipLaunchKernelGGL((small_graph_batch_pre_bwd_drop_kernel<C, 2>), grid, dim3(256), lds2, st, bp, drop, seed_dev);
+    }
+    return gnan::check_launch("small_graph_batch_pre_bwd_drop_kernel");
+  }
+  if (max_nodes <= 64) {
+    hipLaunchKernelGGL((small_graph_batch_pre_bwd_kernel<C, 1>), grid, dim3(256), lds1, st, bp);
+  } else {
+    if (int rc = raise_dyn_lds<&small_graph_batch_pre_bwd_kernel<C, 2>>(lds2, "small_batch_pre_bwd")) return rc;
+    hipLaunchKernelGGL((small_graph_batch_pre_bwd_kernel<C, 2>), grid, dim3(256), lds2, st, bp);
+  }
+  return gnan::check_launch("small_graph_batch_pre_bwd_kernel");
+}
+
+// THE launcher of gnan_small_batch_pre_bwd (seed_dev == NULL) and gnan_small_batch_pre_bwd_drop_dev: small_batch_bwd's steps — a slab
+// of gradients per graph, batch_grad_reduce_kernel over the slabs (one graph: the caller's tensors, no reduction) — with a counter
+// line and kRhoGroupsMax slots per graph behind the slabs
+int small_batch_pre_bwd(const gnan_small_batch_bwd_args* a, const gnan_bwd::Drop& drop, const uint64_t* seed_dev, gnan_stream_t stream) {
+  GNAN_REQUIRE(a->n_graphs >= 0 && a->F >= 1 && a->D >= 1 && a->total_nodes >= 0, "small_batch_pre_bwd: bad sizes");
+  if (a->n_graphs > 0)                                 // (the cover first: grads_ok reads the depth of stacks the cover may not admit)
+    if (int rc = batch_pre_cover_ok("small_batch_pre_bwd", a)) return rc;
+  GNAN_REQUIRE(grads_ok(&a->f, &a->df) && grads_ok(&a->rho, &a->drho),
+               "small_batch_pre_bwd: a gradient pointer for every weight, and for a bias exactly where there is one");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int64_t at[13];
+  const int64_t slab = slab_layout(&a->f, a->F, &a->rho, at);
+  float* const dst[12] = {a->df.w_first, a->df.b_first, a->f.L == 3 ? a->df.w_mid : nullptr, a->f.L == 3 ? a->df.b_mid : nullptr,
+                          a->df.w_last, a->df.b_last, a->drho.w_first, a->drho.b_first, a->rho.L == 3 ? a->drho.w_mid : nullptr,
+                          a->rho.L == 3 ? a->drho.b_mid : nullptr, a->drho.w_last, a->drho.b_last};
+  if (a->n_graphs == 0) {                              // nothing contributes: the gradients are zero
+    for (int t = 0; t < 12; ++t)
+      if (dst[t] && at[t + 1] > at[t]) {
+        hipError_t e = hipMemsetAsync(dst[t], 0, static_cast<size_t>(at[t + 1] - at[t]) * sizeof(float), st);
+        if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "small_batch_pre_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
+      }
+    return GNAN_OK;
+  }
+  GNAN_REQUIRE(a->x && a->code && a->node_off && a->code_off && a->S && a->lut && (a->dY || a->dYsum),
+               "small_batch_pre_bwd: null x / code / offsets / S / lut / output gradient");
+  GNAN_REQUIRE(mlp_ptrs_ok(&a->f) && mlp_ptrs_ok(&a->rho), "small_batch_pre_bwd: null weights");
+  if (int rc = strides_ok("small_batch_pre_bwd", a)) return rc;
+  if (int rc = workspace_ok("small_batch_pre_bwd", a, gnan_small_batch_pre_bwd_workspace_bytes(a))) return rc;
+  GNAN_REQUIRE(reinterpret_cast<uintptr_t>(a->workspace) % 16 == 0, "small_batch_pre_bwd: workspace must be 16-byte aligned (got %p)",
+               a->workspace);
+  const bool direct = a->n_graphs == 1;                // ONE graph (a slot): its share IS the gradient, as in small_batch_bwd
+  float* slabs = static_cast<float*>(a->workspace);
+  gnan_small_mlp_grads gf = {slabs + at[0], a->f.b_first ? slabs + at[1] : nullptr, slabs + at[2],
+                             (a->f.L == 3 && a->f.b_mid) ? slabs + at[3] : nullptr, slabs + at[4], a->f.b_last ? slabs + at[5] : nullptr};
+  gnan_small_mlp_grads gr = {slabs + at[6], a->rho.b_first ? slabs + at[7] : nullptr, slabs + at[8],
+                             (a->rho.L == 3 && a->rho.b_mid) ? slabs + at[9] : nullptr, slabs + at[10],
+                             a->rho.b_last ? slabs + at[11] : nullptr};
+  if (direct) { gf = a->df; gr = a->drho; }
+  BatchBwdParams bp;
+  SmallBwdParams& p = bp.base;
+  bwd_fields(p, a, 0, &gf, &gr);
+  if (a->f.L != 3) { p.f.d_w_mid = nullptr; p.f.d_b_mid = nullptr; }
+  if (a->rho.L != 3) { p.r.d_w_mid = nullptr; p.r.d_b_mid = nullptr; }
+  p.S = a->S; p.lut = a->lut; p.dY = a->dYsum ? nullptr : a->dY; p.dYsum = a->dYsum; p.pre_rho = 1;
+  p.rho_groups = 1; p.rows_per = 0;                    // (every graph's own: graph_of_batch_pre)
+  char* behind = static_cast<char*>(a->workspace) + pre_slab_bytes(a->n_graphs, slab);
+  p.counter = reinterpret_cast<unsigned*>(behind);
+  p.part = reinterpret_cast<float*>(behind + static_cast<size_t>(a->n_graphs) * 128);
+  p.rho_raw = 0; p.rest_zero = 0; p.rho_c = 1;
+  bp.node_off = a->node_off; bp.code_off = a->code_off; bp.slab = slab; bp.dy_per_graph = a->dYsum != nullptr;
+  const int rc = with_channels(a->f.C, [&](auto c) {
+    return launch_small_batch_pre_bwd<decltype(c)::value>(bp, a->n_graphs, a->max_nodes, drop, seed_dev, st);
+  });
+  if (rc != GNAN_OK || direct) return rc;
+  ReduceSeg seg;
+  for (int t = 0; t < 13; ++t) seg.at[t] = at[t];
+  for (int t = 0; t < 12; ++t) seg.dst[t] = (at[t + 1] > at[t]) ? dst[t] : nullptr;
+  int64_t blocks = (slab + 255) / 256;
+  blocks = blocks > 4096 ? 4096 : blocks;
+  hipLaunchKernelGGL(batch_grad_reduce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, slabs, slab, a->n_graphs, seg);
+  return gnan::check_launch("batch_grad_reduce_kernel");
+}
+}  // namespace
+
+extern "C" int gnan_small_batch_pre_fwd(const gnan_small_batch_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch_pre: null args");
+  return small_batch_pre_fwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
+}
+
+extern "C" int gnan_small_batch_pre_fwd_drop_dev(const gnan_small_batch_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch_pre: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("small_batch_pre", d, &drop, &seed_dev)) return rc;
+  return small_batch_pre_fwd(a, drop, seed_dev, stream);
+}
+
+extern "C" int gnan_small_batch_pre_bwd(const gnan_small_batch_bwd_args* a, gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch_pre_bwd: null args");
+  return small_batch_pre_bwd(a, gnan_bwd::Drop{0u, 1.f, 0ull}, nullptr, stream);
+}
+
+extern "C" int gnan_small_batch_pre_bwd_drop_dev(const gnan_small_batch_bwd_args* a, const gnan_small_dropout_dev* d,
+                                                 gnan_stream_t stream) {
+  GNAN_REQUIRE(a != nullptr, "small_batch_pre_bwd: null args");
+  gnan_bwd::Drop drop;
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = drop_dev_ok("small_batch_pre_bwd", d, &drop, &seed_dev)) return rc;
+  return small_batch_pre_bwd(a, drop, seed_dev, stream);
 }
 
 // The Dropout seed's device cell: one tiny launch stores `seed` there — on the stream of the replay that will read it, before that

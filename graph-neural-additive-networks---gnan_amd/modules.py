@@ -493,10 +493,12 @@ class _PathBase(nn.Module):
         if isinstance(g, SlotGraph):
             # a captured step of a batch-size-1 loop: the graph sits in slots, its size is the device's to know
             f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])
-            if use_cnt == "pre" or not graph_sum or not slot_graph_applies(g, f, rho):
+            # (pre-rho, GNAN.py:65-67: exactly where slot_mode says so — small_graph.SLOT_PRE_RHO)
+            if (use_cnt == "pre" and sg.slot_mode(self) != "pre") or not graph_sum or not slot_graph_applies(g, f, rho):
                 raise _lib.GnanHipError("graph slots serve graph-level read-outs with post-rho (or no) normalisation, a one-channel "
                                         "rho and at most 8 output channels")
-            return slot_graph_forward(g, f, rho, bool(use_cnt), dropout=self._dropout_record() if drop else None)
+            return slot_graph_forward(g, f, rho, "pre" if use_cnt == "pre" else bool(use_cnt),
+                                      dropout=self._dropout_record() if drop else None)
         if not g.is_dense or x.shape[0] > MID_GRAPH_MAX_NODES:
             return None
         f, rho = self._stacked("fs", self.fs), self._stacked("rho", [self.rho])

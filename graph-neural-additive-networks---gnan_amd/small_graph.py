@@ -469,23 +469,35 @@ class SlotGraph:
             d.copy_(sr)
 
 
+SLOT_PRE_RHO = True          # on: the stand-alone class with its default pre-rho normalisation (GNAN.py:65-67) runs graph-level tasks through
+                             # graph slots too (gnan_small_batch_pre_fwd / _bwd).  Off: such a model takes a captured step per graph shape,
+                             # as before.  On by the measured rule of DESIGN.md section 5: the 4337-graph epoch's first two epochs are 20
+                             # times shorter than the parent's, 4 captured steps instead of 451, 0.12 GB reserved instead of 2.06
+
+
 def slot_mode(model):
-    """``use_cnt`` (True / False) of the slot forward this model can run, or None: the read-out of a graph-level task with
-    post-rho (or no) normalisation, a one-channel rho, features summed per node — ``models.TensorGNAN`` without a NAM read-out
-    in its default order, the stand-alone class without normalisation.  Decided once per model."""
+    """``use_cnt`` (True / False / ``"pre"``) of the slot forward this model can run, or None: the read-out of a graph-level task, a
+    one-channel rho, features summed per node — ``models.TensorGNAN`` without a NAM read-out in its default order (post-rho
+    normalisation or none), the stand-alone class without normalisation, and — ``"pre"``, behind ``SLOT_PRE_RHO`` and with the
+    one-launch backward on (a pre-rho forward has no other) — the stand-alone class with it.  The model's side is decided once per
+    model; the switches are read at every call."""
     mode = model.__dict__.get("_slot_mode", "?")
     if mode == "?":
         import types
         from . import modules
         mode = None
+        pre = isinstance(model, modules.StandaloneTensorGNAN) and bool(model.normalize_rho)
+        if pre and not (SLOT_PRE_RHO and SMALL_GRAPH_BACKWARD):
+            return None                                  # (nothing decided, nothing touched: as before the switch)
         if (isinstance(model, (modules.TensorGNAN, modules.StandaloneTensorGNAN)) and model.is_graph_task
-                and not (isinstance(model, modules.TensorGNAN) and (model.readout_n_layers > 0 or model.aggregation_order == "reference"))
-                and not (isinstance(model, modules.StandaloneTensorGNAN) and model.normalize_rho)):
+                and not (isinstance(model, modules.TensorGNAN) and (model.readout_n_layers > 0 or model.aggregation_order == "reference"))):
             with torch.no_grad():
                 f, rho = model._stacked("fs", model.fs), model._stacked("rho", [model.rho])
             if slot_graph_applies(types.SimpleNamespace(F=f.F), f, rho):
-                mode = bool(model.normalize_rho)
+                mode = "pre" if pre else bool(model.normalize_rho)
         object.__setattr__(model, "_slot_mode", mode)
+    if mode == "pre" and not (SLOT_PRE_RHO and SMALL_GRAPH_BACKWARD):
+        return None
     return mode
 
 
@@ -535,14 +547,18 @@ def dropout_capture_applies(model, x: torch.Tensor, g, node_ids=None) -> bool:
     return small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre") and rho.C == 1 and g.n_codes <= _ONE_LAUNCH_CODES
 
 
-def slot_graph_forward(slot: SlotGraph, f: StackedMLP, rho: StackedMLP, use_cnt: bool, dropout=None) -> torch.Tensor:
+def slot_graph_forward(slot: SlotGraph, f: StackedMLP, rho: StackedMLP, use_cnt, dropout=None) -> torch.Tensor:
     """The graph read-out ``[C, 1]`` (GNAN.py:75-79 / models.py:383-384) of the graph in the slots: one launch forward, two
-    backward (``gnan_small_batch_bwd`` + the slab reduction).  ``dropout = (p, seed cell)``: training-mode Dropout of f
+    backward (``gnan_small_batch_bwd`` + the slab reduction).  ``use_cnt="pre"``: pre-rho normalisation (GNAN.py:65-67;
+    ``gnan_small_batch_pre_fwd`` / ``_bwd``).  ``dropout = (p, seed cell)``: training-mode Dropout of f
     (``gnan_small_batch_fwd_drop_dev``; a slot's graph sits at row 0: the masks of ``gnan_small_graph_fwd_drop``)."""
-    from .batched import _BatchedGraphs
+    from .batched import _BatchedGraphs, _BatchedGraphsPre
     if use_cnt and slot.cnt is None:
         raise _lib.GnanHipError("these slots were laid out without shell sizes")
     fm, rm = (f.L, f.H, f.C, f.F), (rho.L, rho.H, rho.C)
+    if use_cnt == "pre":
+        out = _BatchedGraphsPre.apply(slot.x, slot.blocks, True, fm, rm, slot.cnt, _dropout_record(dropout), *f[:6], *rho[:6])
+        return out.reshape(-1, 1)
     out = _BatchedGraphs.apply(slot.x, slot.blocks, True, fm, rm, slot.cnt if use_cnt else None, False, _dropout_record(dropout),
                                *f[:6], *rho[:6])   # [1, C]
     return out.reshape(-1, 1)

@@ -1472,6 +1472,58 @@ int gnan_mid_graph_bwd_drop_dev(const gnan_mid_graph_bwd_args* a, const gnan_sma
 int gnan_small_batch_fwd_drop_dev(const gnan_small_batch_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
 int gnan_small_batch_bwd_drop_dev(const gnan_small_batch_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
 
+/* -------------------------------------------------------------------------------------------
+ * PRE-RHO normalisation on the batched kernels (GNAN.py:65-67, the stand-alone class's default; added under ABI 51: one new
+ * struct for the host-only query, seven new entry points, no existing struct changed, the number did not move).  They take the
+ * records of gnan_small_batch_fwd / _bwd and gnan_small_dropout_dev as they are.  Pair (i, j) of graph g weighs
+ *   rho(u_d / float(max(cnt[i, d], 1))),   d = min(code(i, j), D - 1),   u_d = float32(1 / (1 + d)) for d < D - 1,   u_{D-1} = 0
+ * — rho AFTER the IEEE float32 division, the expression and the orders of gnan_small_graph_fwd with pre_rho = 1.  lut is then
+ * the ROWS' table [total_nodes, D]: graph g's rows start at node_off[g] * D; the forward writes it, the backward reads it.
+ * Cover: graphs of 1 <= n_g <= max_nodes <= 128 nodes (every graph has a node), D <= 64, rho.C == 1, L in {2, 3}, H <= 64,
+ * f.C <= 8, n_graphs <= 65535, and cnt != NULL, rho_raw_hops == 0, rest_zero == 0 (the slots' semantics): anything else is
+ * GNAN_ERR_UNSUPPORTED naming the limit and the value; null pointers and short strides GNAN_ERR_BAD_ARG, a short workspace
+ * GNAN_ERR_WORKSPACE — all on the host, before any HIP call.
+ *   forward   one launch, grid (F + R, n_graphs), R = ceil(max_nodes * D / 64): the host sizes rho's workgroups for the largest
+ *             graph, workgroup r evaluates arguments 64 r .. 64 r + 63 of ITS graph's n_g * D (none: it only arrives); the last
+ *             of the F + R workgroups of a graph to arrive aggregates with the row weights read back from lut.  Workspace:
+ *             gnan_small_batch_pre_workspace_bytes(...) = that of gnan_small_batch_fwd, its first 128 * n_graphs bytes ZERO
+ *             before the first launch (left zero).
+ *   backward  two launches: grid (F + G, n_graphs), G = min(D, 12) — every graph splits rho's arguments by rows over
+ *             rho_groups = ceil(n_g / ceil(n_g / min(G, n_g))) workgroups, derived on the device from its own n_g (the split of
+ *             gnan_small_graph_bwd with a lent workspace); the groups leave partial gradients in the graph's own 12 slots of
+ *             4416 floats, the last to arrive adds them in group order into the graph's slab — then the slabs' sum in graph
+ *             order (gnan_small_batch_bwd's second launch; one graph: straight into df / drho, no second launch).  No float
+ *             atomics, no workgroup waits for another: two runs give the same bits.  Workspace:
+ *             gnan_small_batch_pre_bwd_workspace_bytes(args) = the slabs (whole 128-byte lines) | a 128-byte counter line per
+ *             graph, ZERO before the first launch (left zero) | 12 * 4416 * 4 bytes of slots per graph; 16-byte aligned.
+ *   *_drop_dev  the device-seed Dropout twins (refusals and order of gnan_small_batch_*_drop_dev; masks: node = the row of the
+ *             packed x; rho is never masked).  p == 0 launches the plain pre-rho kernel, bit for bit.
+ * A batch of ONE graph (node_off = [0, n]) gives the bits of gnan_small_graph_fwd / _bwd with pre_rho = 1 (and a lent
+ * workspace) — outputs, S, lut and gradients — and under Dropout those of gnan_small_graph_*_drop for the same seed.
+ * gnan_small_batch_pre_describe (host only, no HIP call): what the two launches of a shape look like.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_small_batch_pre_info {
+  int32_t node_blocks;       /* the kernels' build: 1 (max_nodes <= 64) or 2 */
+  int32_t rho_workgroups;    /* R = ceil(max_nodes * D / 64) */
+  int32_t rho_groups;        /* G = min(D, 12): the most rho groups a graph's backward uses */
+  int32_t fwd_grid;          /* workgroups of 256 threads per graph: F + R */
+  int32_t bwd_grid;          /* F + G */
+  int32_t fwd_lds_bytes;     /* dynamic + static LDS of a forward workgroup */
+  int32_t bwd_lds_bytes;     /* ... of a backward workgroup */
+  int32_t reserved;          /* 0 */
+  int64_t fwd_graph_bytes;   /* forward workspace = n_graphs * fwd_graph_bytes + total_nodes * fwd_node_bytes */
+  int64_t fwd_node_bytes;
+  int64_t bwd_graph_bytes;   /* backward workspace = the slabs (gnan_small_batch_bwd_workspace_bytes, rounded up to whole 128-byte
+                                lines) + n_graphs * bwd_graph_bytes */
+} gnan_small_batch_pre_info;
+size_t gnan_small_batch_pre_workspace_bytes(int32_t n_graphs, int64_t total_nodes, int32_t F, int32_t C);
+size_t gnan_small_batch_pre_bwd_workspace_bytes(const gnan_small_batch_bwd_args* a);
+int gnan_small_batch_pre_describe(int32_t max_nodes, int32_t F, int32_t D, int32_t C, gnan_small_batch_pre_info* out);
+int gnan_small_batch_pre_fwd(const gnan_small_batch_args* a, gnan_stream_t stream);
+int gnan_small_batch_pre_bwd(const gnan_small_batch_bwd_args* a, gnan_stream_t stream);
+int gnan_small_batch_pre_fwd_drop_dev(const gnan_small_batch_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+int gnan_small_batch_pre_bwd_drop_dev(const gnan_small_batch_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
+
 /* The same small graph-level task with a NAM read-out over the per-feature aggregates (models.py:358-384 with is_graph_task
  * and readout_n_layers > 0; models.py:259-300 for the read-out):
  *   out[c] = sum_k nam_k(hidden[k])[c],   hidden[k] = sum_i sum_j w(i, j) f_k(x[j, k]),

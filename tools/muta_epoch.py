@@ -36,6 +36,14 @@ class Data:
 def main():
     count = int(sys.argv[1]) if len(sys.argv) > 1 else 4337
     variant = sys.argv[2] if len(sys.argv) > 2 else "models"
+    switches = {}
+    for word in sys.argv[3:]:                      # NAME=0|1: a switch of gnan_amd.small_graph for this run (SLOT_PRE_RHO=1)
+        from gnan_amd import small_graph
+        name, value = word.split("=")
+        if not isinstance(getattr(small_graph, name), bool):
+            raise SystemExit(f"{name} is no switch of gnan_amd.small_graph")
+        setattr(small_graph, name, bool(int(value)))
+        switches[name] = bool(int(value))
     graphs = []
     for ei, x, y in syn.mutagenicity_shaped_graphs(count, seed=0):
         n = x.shape[0]
@@ -100,7 +108,10 @@ def main():
                steps_replayed_from_a_captured_step=replayed, share_replayed=round(replayed / count, 4),
                steps_of_at_most_six_kernels=six, share_at_most_six_kernels=round(six / count, 4),
                kernels_per_step_histogram={str(k): v for k, v in sorted(kernel_hist.items())},
-               eager_step_node_counts=sorted(eager_sizes)[-20:], reserved_GB=round(torch.cuda.memory_reserved() / 2 ** 30, 2))
+               eager_step_node_counts=sorted(eager_sizes)[-20:], reserved_GB=round(torch.cuda.memory_reserved() / 2 ** 30, 2),
+               # the captured steps that serve graphs of at most 128 nodes (slot steps and per-shape steps alike), and the raw figure
+               captured_steps_up_to_128_nodes=len(slots) + sum(r["step"] is not None and k[0] <= 128 for k, r in st.buckets.items()),
+               reserved_bytes=int(torch.cuda.memory_reserved()), switches=switches)
     print(json.dumps(out), flush=True)
 
 
