@@ -428,6 +428,37 @@ class SmallGraphNamBwdArgs(C.Structure):
     ]
 
 
+class SmallSlotNamArgs(C.Structure):
+    """``gnan_small_slot_nam_args``: the one-graph record with ``n`` replaced by the slots' capacity and ``node_off``, ``fx`` strided."""
+    _fields_ = [
+        ("x", C.c_void_p), ("x_stride", C.c_int64), ("max_nodes", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
+        ("nam", SmallMlp), ("code", C.c_void_p), ("D", C.c_int32), ("reserved", C.c_int32), ("cnt", C.c_void_p),
+        ("cnt_stride", C.c_int64), ("node_off", C.c_void_p), ("fx", C.c_void_p), ("fx_stride", C.c_int64), ("lut", C.c_void_p),
+        ("hidden", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class SmallSlotNamBwdArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("x_stride", C.c_int64), ("max_nodes", C.c_int32), ("F", C.c_int32), ("f", SmallMlp), ("rho", SmallMlp),
+        ("nam", SmallMlp), ("code", C.c_void_p), ("D", C.c_int32), ("reserved", C.c_int32), ("cnt", C.c_void_p),
+        ("cnt_stride", C.c_int64), ("node_off", C.c_void_p), ("fx", C.c_void_p), ("fx_stride", C.c_int64), ("lut", C.c_void_p),
+        ("hidden", C.c_void_p), ("d_out", C.c_void_p), ("df", SmallMlpGrads), ("drho", SmallMlpGrads), ("dnam", SmallMlpGrads),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class SmallSlotNamInfo(C.Structure):
+    """What the two launches of ``gnan_small_slot_nam_fwd`` / ``_bwd`` look like for a shape (``gnan_small_slot_nam_info``)."""
+    _fields_ = [
+        ("fwd_grid", C.c_int32), ("bwd_grid", C.c_int32), ("fwd_lds_bytes", C.c_int32), ("bwd_lds_bytes", C.c_int32),
+        ("fwd_workspace_bytes", C.c_int64), ("bwd_workspace_bytes", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class LossArgs(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("n_rows", C.c_int64), ("C", C.c_int32), ("kind", C.c_int32), ("stride", C.c_int64),
@@ -561,6 +592,10 @@ SYMBOLS = {
     "gnan_small_graph_nam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gnan_small_graph_nam_fwd": (C.c_int, [C.POINTER(SmallGraphNamArgs), C.c_void_p]),
     "gnan_small_graph_nam_bwd": (C.c_int, [C.POINTER(SmallGraphNamBwdArgs), C.c_void_p]),
+    "gnan_small_slot_nam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gnan_small_slot_nam_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmallSlotNamInfo)]),
+    "gnan_small_slot_nam_fwd": (C.c_int, [C.POINTER(SmallSlotNamArgs), C.c_void_p]),
+    "gnan_small_slot_nam_bwd": (C.c_int, [C.POINTER(SmallSlotNamBwdArgs), C.c_void_p]),
     "gnan_small_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "gnan_small_batch_fwd": (C.c_int, [C.POINTER(SmallBatchArgs), C.c_void_p]),
     "gnan_small_batch_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmallBatchBwdArgs)]),

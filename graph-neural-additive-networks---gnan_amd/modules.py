@@ -756,6 +756,19 @@ class TensorGNAN(_PathBase):
         use_cnt = bool(self.normalize_rho)
         rest = not g.is_dense                 # a CSR lists some pairs only: the others weigh rho(0) on the column sums
         if with_readout:
+            from . import small_graph as sg
+            if isinstance(g, sg.SlotGraph):
+                # a captured step of a batch-size-1 loop: the graph sits in slots (gnan_small_slot_nam_fwd / _bwd) exactly where
+                # slot_mode says so — small_graph.SLOT_NAM_READOUT; their kernels draw no Dropout masks
+                mode = sg.slot_mode(self)
+                if not isinstance(mode, sg.SlotNamMode) or self._dropout_active() or self.readout_nam._dropout_active():
+                    raise _lib.GnanHipError("graph slots serve a NAM read-out only where small_graph.slot_mode says so, and never "
+                                            "under training-mode Dropout")
+                out = sg.slot_graph_nam_forward(g, self._stacked("fs", self.fs), self._stacked("rho", [self.rho]),
+                                                self.readout_nam._stacked("fs", self.readout_nam.fs), mode)
+                for name in ("fmlp", "spmm"):
+                    self._mark(name)
+                return out
             if not self._dropout_active() and not self.readout_nam._dropout_active() and g.is_dense:
                 # a small graph: shape functions, rho, aggregation and the NAM read-out in ONE launch (csrc/small_graph_nam.hip)
                 from .small_graph import small_graph_nam_applies, small_graph_nam_forward

@@ -1580,6 +1580,85 @@ size_t gnan_small_graph_nam_workspace_bytes(int32_t F, int32_t C);
 int gnan_small_graph_nam_fwd(const gnan_small_graph_nam_args* a, gnan_stream_t stream);
 int gnan_small_graph_nam_bwd(const gnan_small_graph_nam_bwd_args* a, gnan_stream_t stream);
 
+/* ... for ONE graph held in device SLOTS whose size only the device knows (added under ABI 51: three new structs, four new entry
+ * points, no existing struct changed, the number did not move): what a captured step of a batch-size-1 loop over a read-out model
+ * launches, whatever graph the slots hold.  The records are gnan_small_graph_nam_args / _bwd_args with n replaced by
+ *   max_nodes   the slots' capacity, 64 or 128, and
+ *   node_off    a device pair [0, n]: the kernels read n = node_off[1] - node_off[0] and CLAMP it into [1, max_nodes] before anything
+ *               is indexed — a size outside that range reads and writes inside the slots and computes something meaningless, never
+ *               out of bounds; whether a graph fits is the caller's test (small_graph.SlotGraph.fits),
+ * and with fx in the fixed layout [F, fx_stride], fx_stride >= max_nodes (columns 0 .. n-1 of a row are written and read).
+ * x is the slots' [max_nodes, F]; code the slots' bytes with the graph's [n, n] packed at their start; D (2 <= D <= 64) the slots'
+ * hop-code capacity; cnt (optional) the slots' [max_nodes, D]: a listed hop of the graph in its own column, the graph's rest bucket
+ * in column D - 1, ones between (rows 0 .. n-1 are read); lut [D] accordingly: lut[d] = rho(1 / (1 + d)) for d < D - 1, lut[D-1] = rho(0).
+ * Cover otherwise that of gnan_small_graph_nam_fwd, but ANY F >= 1 in the backward: GNAN_ERR_UNSUPPORTED naming limit and value,
+ * GNAN_ERR_BAD_ARG for null pointers (a null weight included) and short strides, GNAN_ERR_WORKSPACE — all on the host, before any HIP
+ * call.  workspace: gnan_small_slot_nam_workspace_bytes(F, nam.C), first 16 bytes ZERO before the first launch (left zero).
+ *   forward   ONE launch of F workgroups, the arithmetic and orders of gnan_small_graph_nam_fwd: slots that hold graph G (D_G codes)
+ *             give its bits — out, hidden, fx[:, :n], lut[d] for the listed hops d < D_G - 1 (and lut[D-1] = its lut[D_G-1]).
+ *   backward  ONE launch of F workgroups, none of which waits for another: workgroup k leaves nam_k's and f_k's gradients, publishes
+ *             d hidden_k and arrives on the counter; the last to arrive then takes rho's part — T, the binned table gradient over the
+ *             graph's own D_G = (largest listed hop in the codes) + 2 shells, rho's gradients — in fixed orders: two runs give the same
+ *             bits whichever workgroup arrives last, and they are the bits of gnan_small_graph_nam_bwd on G.
+ * gnan_small_slot_nam_describe (host only, no HIP call): what the two launches of a shape look like. */
+typedef struct gnan_small_slot_nam_args {
+  const float* x;            /* [max_nodes, F], row stride x_stride */
+  int64_t x_stride;
+  int32_t max_nodes, F;
+  gnan_small_mlp f;          /* C == 1 */
+  gnan_small_mlp rho;        /* C == 1 */
+  gnan_small_mlp nam;
+  const uint8_t* code;       /* [n, n] at the start of the slots' max_nodes * max_nodes bytes */
+  int32_t D;                 /* the slots' hop-code capacity */
+  int32_t reserved;          /* 0 */
+  const int32_t* cnt;        /* optional [max_nodes, cnt_stride] */
+  int64_t cnt_stride;
+  const int32_t* node_off;   /* device [2]: 0, n */
+  float* fx;                 /* [F, fx_stride] */
+  int64_t fx_stride;
+  float* lut;                /* [D] */
+  float* hidden;             /* [F] */
+  float* out;                /* [nam.C] */
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_small_slot_nam_args;
+typedef struct gnan_small_slot_nam_bwd_args {
+  const float* x;
+  int64_t x_stride;
+  int32_t max_nodes, F;
+  gnan_small_mlp f;
+  gnan_small_mlp rho;
+  gnan_small_mlp nam;
+  const uint8_t* code;
+  int32_t D;
+  int32_t reserved;
+  const int32_t* cnt;
+  int64_t cnt_stride;
+  const int32_t* node_off;
+  const float* fx;           /* what the forward left */
+  int64_t fx_stride;
+  const float* lut;
+  const float* hidden;
+  const float* d_out;        /* [nam.C] */
+  gnan_small_mlp_grads df;
+  gnan_small_mlp_grads drho;
+  gnan_small_mlp_grads dnam;
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_small_slot_nam_bwd_args;
+typedef struct gnan_small_slot_nam_info {
+  int32_t fwd_grid;          /* workgroups of 256 threads: F */
+  int32_t bwd_grid;          /* F (no workgroup of rho's own: the last to arrive takes its part) */
+  int32_t fwd_lds_bytes;     /* dynamic + static LDS of a forward workgroup (one build serves both capacities) */
+  int32_t bwd_lds_bytes;     /* ... of a backward workgroup */
+  int64_t fwd_workspace_bytes; /* the forward's share: the counter's 16 bytes | part [F, C] */
+  int64_t bwd_workspace_bytes; /* the backward's: the counter's 16 bytes | d hidden [F]; the query returns the larger */
+} gnan_small_slot_nam_info;
+size_t gnan_small_slot_nam_workspace_bytes(int32_t F, int32_t C);
+int gnan_small_slot_nam_describe(int32_t max_nodes, int32_t F, int32_t D, int32_t C, gnan_small_slot_nam_info* out);
+int gnan_small_slot_nam_fwd(const gnan_small_slot_nam_args* a, gnan_stream_t stream);
+int gnan_small_slot_nam_bwd(const gnan_small_slot_nam_bwd_args* a, gnan_stream_t stream);
+
 /* Up to eight small device-to-device copies in one launch (host arrays of `count` device pointers and byte counts; ranges
  * must not overlap): the input slots of a captured graph-task step are refilled with it. */
 int gnan_multi_copy(int32_t count, const void* const* src, void* const* dst, const int64_t* bytes, gnan_stream_t stream);

@@ -5,8 +5,10 @@ models.TensorGNAN(is_graph_task=True).  Epochs 1-2 run eagerly (and capture), la
 shape.  Prints ms per graph by epoch, how many of the epoch's steps were replayed from a captured step (6 kernels: slot
 refill, forward, loss, backward, step counters, Adam — tools/graphed_timeline.sh; counted per captured step with
 gnan_graph_node_count) and the node counts of those that were not.
-  python tools/muta_epoch.py [graphs] [models|standalone|nam]     models: models.TensorGNAN as main.py builds it (post-rho);
-  standalone: the stand-alone file's TensorGNAN (pre-rho, GNAN.py:65-67); nam: models.TensorGNAN with a 2-layer NAM read-out."""
+  python tools/muta_epoch.py [graphs] [models|standalone|nam|readout] [SWITCH=0|1 ...]
+  models: models.TensorGNAN as main.py builds it (post-rho, readout_n_layers=0); standalone: the stand-alone file's TensorGNAN
+  (pre-rho, GNAN.py:65-67); nam: models.TensorGNAN with a 2-layer NAM read-out; readout: models.TensorGNAN with the read-out the
+  class itself defaults to (readout_n_layers=1, models.py:305) — graph slots behind small_graph.SLOT_NAM_READOUT."""
 import json
 import os
 import sys
@@ -59,7 +61,8 @@ def main():
         from gnan_amd.GNAN import TensorGNAN as Standalone
         m = Standalone(15, 1, 3, hidden_channels=64, is_graph_task=True, device=DEV)
     else:
-        m = TensorGNAN(15, 1, 3, hidden_channels=64, is_graph_task=True, readout_n_layers=2 if variant == "nam" else 0, device=DEV)
+        m = TensorGNAN(15, 1, 3, hidden_channels=64, is_graph_task=True, readout_n_layers={"nam": 2, "readout": 1}.get(variant, 0),
+                       device=DEV)
     with torch.no_grad():
         for _, p in m.named_parameters():
             torch.nn.init.xavier_normal_(p, gain=1.0) if p.dim() == 2 else p.normal_(0.0, 0.5)
