@@ -547,6 +547,10 @@ SYMBOLS = {
     "gnan_fmlp_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(FmlpBwdArgs)]),
     "gnan_fmlp_bwd": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p]),
     "gnan_dropout_mask": (C.c_int, [C.c_uint64, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gnan_dropout_mask_window": (C.c_int, [C.c_uint64, C.c_float, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p]),
+    "gnan_fmlp_bwd_mfma_workspace_bytes": (C.c_size_t, [C.POINTER(FmlpBwdArgs)]),
+    "gnan_fmlp_bwd_mfma": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p]),
     "gnan_pwl_build_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gnan_pwl_build": (C.c_int, [C.POINTER(PwlBuildArgs), C.c_void_p]),
     "gnan_pwl_check_fit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -43,7 +43,7 @@ struct Params {
   // features (Cora: 2.7k x 1434) still fill the chip; with sum_features the chunks meet in `sum_partial`
   int feat_chunk;
   float* sum_partial;  // [chunks, n, C] or nullptr (single chunk)
-  // training-mode Dropout (lane kernel): keep iff hash(seed, node, feature, layer, unit) >= drop_thresh, scale 1 / (1 - p)
+  // training-mode Dropout (lane kernel, DROP instances of the matrix-core kernel): keep iff hash(seed, node, feature, layer, unit) >= drop_thresh, scale 1 / (1 - p)
   uint32_t drop_thresh;
   float drop_scale;
   uint64_t drop_seed;
@@ -245,7 +245,15 @@ __global__ __launch_bounds__(256) void fmlp_pack_kernel(const Params p, float* _
   }
 }
 
-template <int HT, int NMID, int CT, bool SUM, int NT>
+// DROP: training-mode Dropout behind every hidden ReLU, with the lane kernel's coordinates (gnan_dropout_mask is the mask
+// tensor of both): after layer 1, B[s] of lane half `half` is hidden unit kperm(s, half) of hidden layer 0; after mid layer m,
+// acc[t][r] is unit 32 t + drow(r, half) of hidden layer m + 1; the node is node[nt].  One drop_base per (tile, feature), one
+// further mix per unit.  Units >= H (padding up to 32 HT) are hashed like the rest and need no care: their w1 / b1 and their
+// rows of the mid layers and biases are packed as zeros, so the ReLU hands 0 to the mask and 0 * drop_scale is 0 whether the
+// hash keeps them or not — and the next layer's columns and w_last are zero there as well.  Rows past n (valid[nt] false)
+// compute on x = 0 and are never stored.  Every DROP statement sits under `if constexpr`: the DROP = false instances are the
+// kernel as it was (DESIGN section 4.8 has the register lines of both).
+template <int HT, int NMID, int CT, bool SUM, int NT, bool DROP>
 __global__ __launch_bounds__(256, 2) void fmlp_mfma_kernel(const Params p, const float* __restrict__ packed) {
   constexpr int HP = 32 * HT, KS = 16 * HT, KS4 = 4 * HT;
   constexpr int MIDF = NMID * HP * HP;
@@ -297,10 +305,13 @@ __global__ __launch_bounds__(256, 2) void fmlp_mfma_kernel(const Params p, const
       // layer 1 straight into the B operand (K order = accumulator order)
       float B[KS];
       const float xv = xcur[nt];
+      uint32_t dbase = 0u;
+      if constexpr (DROP) dbase = gnan::drop_base(p.drop_seed, node[nt], k);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const float2 wb = *reinterpret_cast<const float2*>(vec + (s * 2 + half) * 2);
         B[s] = fmaxf(fmaf(xv, wb.x, wb.y), 0.f);
+        if constexpr (DROP) B[s] = gnan::drop_keep(dbase, 0, kperm(s, 0) + 4 * half, p.drop_thresh) ? B[s] * p.drop_scale : 0.f;
       }
       // hidden layers on the matrix cores; accumulators start at the bias
 #pragma unroll
@@ -330,7 +341,11 @@ __global__ __launch_bounds__(256, 2) void fmlp_mfma_kernel(const Params p, const
 #pragma unroll
         for (int t = 0; t < HT; ++t)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) B[16 * t + r] = fmaxf(acc[t][r], 0.f);
+          for (int r = 0; r < 16; ++r) {
+            B[16 * t + r] = fmaxf(acc[t][r], 0.f);
+            if constexpr (DROP)
+              B[16 * t + r] = gnan::drop_keep(dbase, m + 1, 32 * t + drow(r, 0) + 4 * half, p.drop_thresh) ? B[16 * t + r] * p.drop_scale : 0.f;
+          }
       }
       // last layer: C dot products over this lane's hidden units (the other half's units are added below)
       const float* wl = vec + 64 * HT + NMID * HP;
@@ -443,8 +458,9 @@ int launch_mfma(const Params& p, const float* packed, hipStream_t st) {
                        p, packed);
     return gnan::check_launch("fmlp_mfma_kernel");
   };
-  if (!p.sum_features) return go(fmlp_mfma_kernel<HT, NMID, CT, false, kNT>);
-  if (int rc = go(fmlp_mfma_kernel<HT, NMID, CT, true, kNT>)) return rc;
+  const bool drop = p.drop_thresh != 0u;              // p == 0: the plain instance, which never hashes
+  if (!p.sum_features) return drop ? go(fmlp_mfma_kernel<HT, NMID, CT, false, kNT, true>) : go(fmlp_mfma_kernel<HT, NMID, CT, false, kNT, false>);
+  if (int rc = drop ? go(fmlp_mfma_kernel<HT, NMID, CT, true, kNT, true>) : go(fmlp_mfma_kernel<HT, NMID, CT, true, kNT, false>)) return rc;
   if (p.sum_partial) {
     const int64_t total = p.n * p.C;
     hipLaunchKernelGGL(fmlp_chunk_sum_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, p,
@@ -509,7 +525,7 @@ extern "C" size_t gnan_fmlp_fwd_workspace_bytes(const gnan_fmlp_args* a) {
   if (!a || a->algo == GNAN_FMLP_LANE || point_route(a)) return 0;
   const Params p = make_params(a);
   MfmaShape s;
-  if (!mfma_shape(p, &s) || p.drop_thresh != 0u) return 0;
+  if (!mfma_shape(p, &s) || (p.drop_thresh != 0u && a->algo != GNAN_FMLP_MFMA)) return 0;   // Dropout under AUTO: lane kernel
   size_t bytes = packed_bytes(p, s);
   if (p.sum_features) {                               // room for the per-chunk partial sums (upper bound)
     const int chunks = feature_chunks(p.n, p.F);
@@ -538,9 +554,8 @@ extern "C" int gnan_fmlp_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
     return gnan::check_launch("fmlp_point_kernel");
   }
   MfmaShape shape;
-  const bool can_mfma = mfma_shape(p, &shape) && p.drop_thresh == 0u;        // Dropout: lane kernel
-  if (a->algo == GNAN_FMLP_MFMA && p.drop_thresh != 0u)
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fmlp: training-mode Dropout runs on the lane kernel (algo AUTO or LANE)");
+  // Dropout: the lane kernel unless the caller asks for the matrix-core kernel by name (its DROP instances)
+  const bool can_mfma = mfma_shape(p, &shape) && (p.drop_thresh == 0u || a->algo == GNAN_FMLP_MFMA);
   if (a->algo == GNAN_FMLP_MFMA && !can_mfma)
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "fmlp: MFMA path covers 3 <= L <= 4, H <= 64, C <= 8 (got L=%d H=%d C=%d)",
                       p.L, p.H, p.C);
@@ -573,28 +588,39 @@ extern "C" int gnan_fmlp_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
 
 
 namespace {
-__global__ __launch_bounds__(256) void dropout_mask_kernel(uint64_t seed, uint32_t thresh, int64_t n, int F, int LH, int H,
-                                                           uint8_t* __restrict__ mask) {
+__global__ __launch_bounds__(256) void dropout_mask_kernel(uint64_t seed, uint32_t thresh, int64_t node_lo, int64_t n, int F, int LH,
+                                                           int H, uint8_t* __restrict__ mask) {
   const int64_t total = n * F * LH * H;
   for (int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; e < total; e += static_cast<int64_t>(gridDim.x) * 256) {
     const int j = static_cast<int>(e % H);
     const int l = static_cast<int>((e / H) % LH);
     const int k = static_cast<int>((e / (static_cast<int64_t>(H) * LH)) % F);
-    const int64_t node = e / (static_cast<int64_t>(H) * LH * F);
+    const int64_t node = node_lo + e / (static_cast<int64_t>(H) * LH * F);     // the hash takes the global node index
     mask[e] = gnan::drop_keep(gnan::drop_base(seed, node, k), l, j, thresh) ? 1 : 0;
   }
 }
 }  // namespace
 
-extern "C" int gnan_dropout_mask(uint64_t seed, float p, int64_t n_nodes, int32_t F, int32_t n_hidden_layers, int32_t H,
-                                 uint8_t* mask, gnan_stream_t stream) {
-  GNAN_REQUIRE(p >= 0.f && p < 1.f && n_nodes >= 0 && F >= 1 && n_hidden_layers >= 1 && H >= 1, "dropout_mask: bad arguments");
+// rows [node_lo, node_lo + n_nodes) of the mask tensor: mask[i] is node node_lo + i
+static int dropout_mask_rows(const char* who, uint64_t seed, float p, int64_t node_lo, int64_t n_nodes, int32_t F, int32_t n_hidden_layers,
+                             int32_t H, uint8_t* mask, gnan_stream_t stream) {
+  GNAN_REQUIRE(p >= 0.f && p < 1.f && node_lo >= 0 && n_nodes >= 0 && F >= 1 && n_hidden_layers >= 1 && H >= 1, "%s: bad arguments", who);
   if (n_nodes == 0) return GNAN_OK;
-  GNAN_REQUIRE(mask != nullptr, "dropout_mask: null output");
+  GNAN_REQUIRE(mask != nullptr, "%s: null output", who);
   const int64_t total = n_nodes * F * n_hidden_layers * H;
   int64_t blocks = (total + 255) / 256;
   blocks = blocks > 65536 ? 65536 : blocks;
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
-                     gnan::drop_threshold(p), n_nodes, F, n_hidden_layers, H, mask);
+                     gnan::drop_threshold(p), node_lo, n_nodes, F, n_hidden_layers, H, mask);
   return gnan::check_launch("dropout_mask_kernel");
+}
+
+extern "C" int gnan_dropout_mask(uint64_t seed, float p, int64_t n_nodes, int32_t F, int32_t n_hidden_layers, int32_t H,
+                                 uint8_t* mask, gnan_stream_t stream) {
+  return dropout_mask_rows("dropout_mask", seed, p, 0, n_nodes, F, n_hidden_layers, H, mask, stream);
+}
+
+extern "C" int gnan_dropout_mask_window(uint64_t seed, float p, int64_t node_lo, int64_t n_nodes, int32_t F, int32_t n_hidden_layers,
+                                        int32_t H, uint8_t* mask, gnan_stream_t stream) {
+  return dropout_mask_rows("dropout_mask_window", seed, p, node_lo, n_nodes, F, n_hidden_layers, H, mask, stream);
 }

@@ -59,7 +59,8 @@ __global__ __launch_bounds__(kWaves * kWave) void fmlp_bwd_kernel(const BwdParam
 }
 
 // out[i] = sum over the splits of partial[s * stride + i], in split order — all six gradient tensors in ONE launch (a launch per
-// tensor was six launches behind a 15-us kernel on a few hundred inputs)
+// tensor was six launches behind a 15-us kernel on a few hundred inputs).  csrc/fmlp_bwd_mfma.hip keeps a copy
+// (fmlp_bwd_mfma_reduce_kernel): change the two together.
 struct ReduceOuts {
   float* out[6];
   int64_t off[6];       // start of the tensor inside a split's block; off[t + 1] - off[t] elements (off[6] = block size)

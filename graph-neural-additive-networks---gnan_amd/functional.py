@@ -715,8 +715,9 @@ HIP_SMALL_BACKWARD = True
 HIP_SMALL_BACKWARD_MAX_WORK = 1 << 23
 
 
-def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=None, dests=None):
-    """``gnan_fmlp_bwd``: gradients of the six stacked parameter tensors (None where a bias is absent), in their order."""
+def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=None, dests=None, mfma=False):
+    """``gnan_fmlp_bwd`` (``mfma``: ``gnan_fmlp_bwd_mfma``, the matrix-core kernel of large batches, same record): gradients of
+    the six stacked parameter tensors (None where a bias is absent), in their order."""
     xd = x.detach().float()
     xd = _rows(xd)
     g = grad_out.detach().float()
@@ -735,11 +736,15 @@ def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout
                          d_b_mid=_lib.ptr(d_b_mid), d_w_last=_lib.ptr(outs[4]), d_b_last=_lib.ptr(outs[5]))
     if dropout is not None:
         a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1])
-    need = _lib.lib().gnan_fmlp_bwd_workspace_bytes(a)
+    lib = _lib.lib()
+    need = lib.gnan_fmlp_bwd_mfma_workspace_bytes(a) if mfma else lib.gnan_fmlp_bwd_workspace_bytes(a)
     if need:
         ws = torch.empty(need // 4, dtype=torch.float32, device=xd.device)
         a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    _lib.check(_lib.lib().gnan_fmlp_bwd(a, _lib.stream_of(xd)), "gnan_fmlp_bwd")
+    if mfma:
+        _lib.check(lib.gnan_fmlp_bwd_mfma(a, _lib.stream_of(xd)), "gnan_fmlp_bwd_mfma")
+    else:
+        _lib.check(lib.gnan_fmlp_bwd(a, _lib.stream_of(xd)), "gnan_fmlp_bwd")
     return outs
 
 
@@ -783,31 +788,108 @@ def dropout_masks(seed: int, p: float, n: int, F: int, n_hidden: int, H: int, de
     return m
 
 
-def _fmlp_eager_masked(x: torch.Tensor, p: StackedMLP, sum_features: bool, masks: torch.Tensor, drop_p: float) -> torch.Tensor:
+# uint8 mask elements one launch of the restatement's backward may write out (2 GiB).  A batch whose whole mask tensor
+# [n, F, L - 1, H] fits is drawn once (gnan_dropout_mask); beyond, the masks are drawn window by window of at most this many
+# elements (gnan_dropout_mask_window) and multiplied in as they come — the products are element-wise, so the windows' size
+# does not show in a single bit of the result.
+DROPOUT_MASK_MAX_ELEMS = 1 << 31
+
+
+def dropout_mask_window(seed: int, p: float, node_lo: int, n: int, F: int, n_hidden: int, H: int, device) -> torch.Tensor:
+    """Rows ``[node_lo, node_lo + n)`` of :func:`dropout_masks`' tensor (``gnan_dropout_mask_window``: the hash takes the global
+    node index): uint8 ``[n, F, n_hidden, H]``."""
+    m = torch.empty((n, F, n_hidden, H), dtype=torch.uint8, device=device)
+    _lib.check(_lib.lib().gnan_dropout_mask_window(int(seed), float(p), int(node_lo), n, F, n_hidden, H, _lib.ptr(m),
+                                                   _lib.stream_of(m)), "gnan_dropout_mask_window")
+    return m
+
+
+class _MaskRows(torch.autograd.Function):
+    """``h * (keep * 1 / (1 - p))`` for ``h [F, rows, H]`` of hidden layer ``layer``, rows = nodes ``node_lo ...``, the keep
+    bits drawn in windows of ``window`` nodes: what ``_fmlp_eager_masked`` multiplies in from the whole mask tensor, element by
+    element (forward and backward), without ever holding more than a window of it."""
+
+    @staticmethod
+    def _scaled(g, meta):
+        seed, drop_p, node_lo, layer, n_hidden, window = meta
+        F, rows, H = g.shape
+        scale = 1.0 / (1.0 - drop_p)
+        out = torch.empty_like(g)
+        for lo in range(0, rows, window):
+            hi = min(rows, lo + window)
+            m = dropout_mask_window(seed, drop_p, node_lo + lo, hi - lo, F, n_hidden, H, g.device)
+            out[:, lo:hi] = g[:, lo:hi] * (m[:, :, layer].permute(1, 0, 2).to(g.dtype) * scale)
+        return out
+
+    @staticmethod
+    def forward(ctx, h, seed, drop_p, node_lo, layer, n_hidden, window):
+        ctx.meta = (seed, drop_p, node_lo, layer, n_hidden, window)
+        return _MaskRows._scaled(h, ctx.meta)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return (_MaskRows._scaled(grad, ctx.meta),) + (None,) * 6
+
+
+def _fmlp_eager_masked(x: torch.Tensor, p: StackedMLP, sum_features: bool, masks, drop_p: float) -> torch.Tensor:
     """:func:`_fmlp_eager` with the kernels' Dropout masks (``dropout_masks``): the backward route of shapes
     ``gnan_fmlp_bwd`` does not cover (deeper / wider than the reference's defaults) under training-mode Dropout."""
     scale = 1.0 / (1.0 - drop_p)
+    if torch.is_tensor(masks):
+        drop = lambda h, l: torch.relu(h) * (masks[:, :, l].permute(1, 0, 2).to(h.dtype) * scale)   # noqa: E731
+    else:                               # (seed, first node of x, nodes per window): drawn as they are used (_MaskRows)
+        seed, node_lo, window = masks
+        drop = lambda h, l: _MaskRows.apply(torch.relu(h), seed, drop_p, node_lo, l, p.L - 1, window)   # noqa: E731
     xt = x.t().unsqueeze(-1)                                            # [F, n, 1]
     h = xt * p.w_first.unsqueeze(1)
     if p.b_first is not None:
         h = h + p.b_first.unsqueeze(1)
-    h = torch.relu(h) * (masks[:, :, 0].permute(1, 0, 2).to(h.dtype) * scale)
+    h = drop(h, 0)
     for l in range(p.L - 2):
         h = torch.bmm(h, p.w_mid[l].transpose(1, 2))
         if p.b_mid is not None:
             h = h + p.b_mid[l].unsqueeze(1)
-        h = torch.relu(h) * (masks[:, :, l + 1].permute(1, 0, 2).to(h.dtype) * scale)
+        h = drop(h, l + 1)
     h = torch.bmm(h, p.w_last.transpose(1, 2))
     if p.b_last is not None:
         h = h + p.b_last.unsqueeze(1)
     return h.sum(0) if sum_features else h.permute(1, 0, 2).reshape(x.shape[0], -1)
 
 
+# Large batches under Dropout on the matrix cores: the forward asks gnan_fmlp_fwd for GNAN_FMLP_MFMA (its Dropout instances),
+# the backward calls gnan_fmlp_bwd_mfma, each behind its own switch, from DROPOUT_MFMA_MIN_WORK node-features on.  The
+# switches and the threshold follow from profiles/r26_dropout_mfma.jsonl (tools/dropout_mfma_time.py --drive) by the rule of
+# DESIGN section 5: a switch is on only if its pass beat the lane route at both full shapes by more than the lane route's
+# spread — the forward did (arxiv shape 32.3 -> 2.95 ms, Cora shape 117 -> 2.87 ms), the backward did (23.2 -> 9.72 ms,
+# 3.01 -> 1.63 ms); in the sweep at F = 64 the forward is ahead from 2^16 node-features on, the backward from 2^18 (at 2^16
+# gnan_fmlp_bwd's 0.068 ms beat 0.13 ms), so 2^18 it is.  The threshold never lies below DROPOUT_MFMA_CLAMP: smaller batches
+# keep the lane route and its bits whatever was measured.
+DROPOUT_MFMA_CLAMP = 1 << 16
+DROPOUT_MFMA = True
+DROPOUT_MFMA_BACKWARD = True
+DROPOUT_MFMA_MIN_WORK = max(1 << 18, DROPOUT_MFMA_CLAMP)
+
+
+def dropout_mfma_routes(n: int, F: int, L: int, H: int, C: int, x_grad: bool = False, forward_on=None, backward_on=None,
+                        min_work=None):
+    """``(forward on the matrix cores, backward on the matrix cores)`` of one :func:`feature_mlps_dropout` call: pure, the
+    module's switches and threshold unless given.  Forward cover: ``3 <= L <= 4, H <= 64, C <= 8`` (``gnan_fmlp_fwd``'s);
+    backward cover: ``L == 3, H <= 64, C <= 8`` and no ``x.grad`` (``gnan_fmlp_bwd_mfma``'s)."""
+    forward_on = DROPOUT_MFMA if forward_on is None else forward_on
+    backward_on = DROPOUT_MFMA_BACKWARD if backward_on is None else backward_on
+    min_work = DROPOUT_MFMA_MIN_WORK if min_work is None else min_work
+    big = n * F >= min_work
+    inside = 1 <= H <= 64 and 1 <= C <= 8
+    return (bool(forward_on and big and inside and 3 <= L <= 4),
+            bool(backward_on and big and inside and L == 3 and not x_grad))
+
+
 class _DropoutMLPs(torch.autograd.Function):
     """The shape functions with training-mode Dropout behind every hidden ReLU (GNAN.py:28,32; run.sh trains with p = 0.6),
-    in the kernels: forward ``gnan_fmlp_fwd`` (lane kernel), backward ``gnan_fmlp_bwd`` — both recompute the masks from
-    ``(p, seed)`` (csrc/dropout.hpp), no mask or activation tensor is formed.  Shapes the backward kernel does not cover
-    (L > 3, H > 64, C > 8) back-propagate through the batched restatement in chunks of nodes, with the kernels' masks."""
+    in the kernels: forward ``gnan_fmlp_fwd`` (lane kernel; the matrix-core kernel where :func:`dropout_mfma_routes` says so),
+    backward ``gnan_fmlp_bwd`` (``gnan_fmlp_bwd_mfma`` likewise) — all recompute the masks from ``(p, seed)``
+    (csrc/dropout.hpp), no mask or activation tensor is formed.  Shapes the backward kernels do not cover (L > 3, H > 64,
+    C > 8) back-propagate through the batched restatement in chunks of nodes, with the kernels' masks."""
 
     @staticmethod
     def forward(ctx, x, sum_features, drop_p, seed, L, H, C, F, *params):
@@ -815,7 +897,8 @@ class _DropoutMLPs(torch.autograd.Function):
         ctx.meta = (sum_features, float(drop_p), int(seed), L, H, C, F)
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(x, *[t for t in params if t is not None])
-        return _fmlp_launch(x, p, sum_features, _lib.FMLP_LANE, dropout=(drop_p, seed))
+        mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[0]
+        return _fmlp_launch(x, p, sum_features, _lib.FMLP_MFMA if mfma else _lib.FMLP_LANE, dropout=(drop_p, seed))
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -824,7 +907,8 @@ class _DropoutMLPs(torch.autograd.Function):
         x = saved.pop(0)
         params = [saved.pop(0) if present else None for present in ctx.present]
         if L in (2, 3) and 1 <= H <= 64 and C <= 8 and not ctx.needs_input_grad[0]:
-            pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed))
+            mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[1]
+            pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed), mfma=mfma)
             return (None,) * 8 + tuple(pg)
         leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
         p = StackedMLP(*leaves, L, H, C, F)
@@ -834,15 +918,16 @@ class _DropoutMLPs(torch.autograd.Function):
         chunk = max(1, _BWD_CHUNK_ELEMS // max(1, F * max(H, C) * 2))
         xd = x.detach().float()
         gx = torch.zeros_like(xd) if ctx.needs_input_grad[0] else None
-        masks = dropout_masks(seed, drop_p, n, F, L - 1, H, x.device) if n * F * (L - 1) * H <= (1 << 31) else None
+        per_node = F * (L - 1) * H
+        masks = dropout_masks(seed, drop_p, n, F, L - 1, H, x.device) if n * per_node <= DROPOUT_MASK_MAX_ELEMS else None
         for lo in range(0, n, chunk):
             xs = xd[lo:lo + chunk]
             if gx is not None:
                 xs = xs.clone().requires_grad_(True)
             if masks is not None:
                 mk = masks[lo:lo + chunk]
-            else:                       # (the hash takes the global node index: a chunk's masks are cut from a window's)
-                raise _lib.GnanHipError("training-mode Dropout: this shape's backward needs more than 2 GiB of masks")
+            else:                       # (the hash takes the global node index: the chunk's masks come in windows from lo on)
+                mk = (seed, lo, max(1, DROPOUT_MASK_MAX_ELEMS // per_node))
             with torch.enable_grad():
                 out = _fmlp_eager_masked(xs, p, sum_features, mk, drop_p)
             got = torch.autograd.grad(out, live + ([xs] if gx is not None else []), grad_out[lo:lo + chunk])

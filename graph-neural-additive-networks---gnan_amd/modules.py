@@ -376,7 +376,9 @@ class _PathBase(nn.Module):
 
     def _check_dropout(self):
         """Training-mode Dropout (GNAN.py:28,32; run.sh trains with 0.6) runs in the kernels: ``gnan_fmlp_fwd`` /
-        ``gnan_fmlp_bwd`` apply a keep-mask that is a counter-based hash of (seed, node, feature, layer, unit), the seed
+        ``gnan_fmlp_bwd`` — and, for large batches behind ``functional.DROPOUT_MFMA`` / ``DROPOUT_MFMA_BACKWARD``, the
+        matrix-core kernels (``GNAN_FMLP_MFMA`` / ``gnan_fmlp_bwd_mfma``: ``functional.dropout_mfma_routes``) — apply a
+        keep-mask that is a counter-based hash of (seed, node, feature, layer, unit), the seed
         drawn from torch's generator once per forward (``functional.draw_dropout_seed``).  Same distribution as
         ``nn.Dropout``, not torch's Bernoulli stream — which depends on the order of the reference's Python loop and is not
         part of any contract.  The table path cannot hold per-node masks, so these steps use the direct kernels (the

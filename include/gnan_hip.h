@@ -58,7 +58,7 @@ const char* gnan_last_error(void);
  *            w_mid [L-2, F, H, H] (out, in), b_mid [L-2, F, H]    Linear(H, H)
  *            w_last [F, C, H], b_last [F, C]                      Linear(H, C)
  * Bias pointers may be NULL (bias=False).  ReLU after every layer but the last; training-mode Dropout
- * (GNAN.py:28,32) runs inside the lane kernel when dropout_p > 0 (see the struct), else none is applied.
+ * (GNAN.py:28,32) runs inside the kernels when dropout_p > 0 (see the struct), else none is applied.
  *
  * sum_features == 0 : out[n, k*C + c]               ("reference order", fx of GNAN.py:57)
  * sum_features == 1 : out[n, c] = sum_k fx[n, k, c]  (f_sums of GNAN.py:157)
@@ -83,7 +83,8 @@ typedef struct gnan_fmlp_args {
   size_t workspace_bytes;
   float dropout_p;       /* > 0: training-mode Dropout behind every hidden ReLU (GNAN.py:28,32), kept units scaled by    */
   uint64_t dropout_seed; /* 1 / (1 - p); the mask is a counter-based hash of (seed, node, feature, layer, unit) —        */
-                         /* gnan_dropout_mask writes it out.  Lane kernel only (algo AUTO picks it; MFMA is refused)     */
+                         /* gnan_dropout_mask writes it out.  AUTO and LANE: the lane kernel, no workspace; MFMA: the     */
+                         /* matrix-core kernel's Dropout instances (3 <= L <= 4, H <= 64, C <= 8), same masks            */
 } gnan_fmlp_args;
 
 enum gnan_fmlp_algo { GNAN_FMLP_AUTO = 0, GNAN_FMLP_LANE = 1, GNAN_FMLP_MFMA = 2 };
@@ -132,6 +133,19 @@ int gnan_fmlp_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream);
  * For tests and for callers that evaluate a shape outside the kernels' coverage with the same masks. */
 int gnan_dropout_mask(uint64_t seed, float p, int64_t n_nodes, int32_t F, int32_t n_hidden_layers, int32_t H, uint8_t* mask,
                       gnan_stream_t stream);
+/* Rows [node_lo, node_lo + n_nodes) of that tensor (the hash takes the global node index): mask is [n_nodes, F,
+ * n_hidden_layers, H], mask[0] belongs to node node_lo.  For callers that walk a large batch in chunks of nodes. */
+int gnan_dropout_mask_window(uint64_t seed, float p, int64_t node_lo, int64_t n_nodes, int32_t F, int32_t n_hidden_layers,
+                             int32_t H, uint8_t* mask, gnan_stream_t stream);
+
+/* gnan_fmlp_bwd's gradients on the matrix cores, for batches past the reach of its wave-per-node kernel (added under ABI 51:
+ * two new entry points on the existing record, the number did not move).  Covers L == 3, 1 <= H <= 64, 1 <= C <= 8, both
+ * sum_features, biases present or absent, dropout_p in [0, 1) (the forward's masks are recomputed from the seed; nothing of
+ * size [n, F, H] is written); GNAN_ERR_UNSUPPORTED otherwise.  Arguments, refusals and their order as gnan_fmlp_bwd; the
+ * workspace is this entry point's own size (partial gradients of the node ranges, added in range order: no atomics, the same
+ * bits on every run).  Agrees with gnan_fmlp_bwd to rounding (another order of summation), not bit for bit. */
+size_t gnan_fmlp_bwd_mfma_workspace_bytes(const gnan_fmlp_bwd_args* a);
+int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Shape functions by exact piecewise-linear table look-up — same outputs as gnan_fmlp_fwd.
