@@ -99,6 +99,10 @@ PAIR_STREAM_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs (
 PAIR_STREAM_MIN_PAIRS = 5          # ... rows of this many pairs up to the hub threshold (HopGraph.pair_stream_plan), in place of the
 PAIR_STREAM_BLOCKS = 2             # ... classed rows; ranked blocks of BLOCKED_HUB_BLOCK_BYTES per class, and
 PAIR_STREAM_CHUNK_PAIRS = 32       # ... entries a lane group takes (a multiple of 16); swept on C4: DESIGN.md 4.1
+# What spmm_stream_combine_kernel is compiled with (kCombineRows, kCombineCap in csrc/spmm_stream.hip): stated here for the tests, which
+# build plans that meet every shape of its tile walk; not a switch (tests/test_stream_combine_blocks.py holds the two against the source)
+PAIR_STREAM_COMBINE_ROWS = 256     # stream rows per workgroup
+PAIR_STREAM_COMBINE_CAP = 4096     # row_seg entries per LDS tile
 
 
 def append_hot_rows(S: torch.Tensor, hot: torch.Tensor, group: int = 1, room: Optional[torch.Tensor] = None) -> torch.Tensor:

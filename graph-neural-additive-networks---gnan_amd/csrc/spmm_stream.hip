@@ -8,12 +8,18 @@
 // applied once per row, in the combine).  A segment is a maximal run of one row inside a chunk; the entry that ends one carries bit 31,
 // and there the group reduces its accumulators to ONE float.  The floats lie in QUEUE order — segment s of the plan's enumeration at
 // partial[s], chunk t's k-th at partial[chunk_first_seg[t] + k] — so a class's partials form one region that its XCD writes nearly
-// sequentially: lane kr of the group keeps the round's kr-th float and the round ends with one store of all of them.  The combine finds
-// a row's floats through row_seg (the row's segments, in queue order).  The gathers of a batch are issued whatever segment they belong
-// to, so they stay in flight across segment ends.
+// sequentially: lane kr of the group keeps the round's kr-th float and the round ends with one store of all of them.  The gathers of a
+// batch are issued whatever segment they belong to, so they stay in flight across segment ends.
 // Workgroup b takes class b & 7 (the XCD's L2 then holds one eighth of the hot operand rows) and its lane groups consecutive chunks, so
 // a class's queue runs in popularity-block order, most listed first.  A code object of its own: the aggregation's other kernels keep
 // their registers.  No LDS, no barrier, no atomics.
+//
+// The combine finds a row's floats through row_seg (the row's segments, in queue order).  A workgroup takes kCombineRows consecutive
+// stream rows: their entries of row_seg are ONE range, which the workgroup walks in entry order, kCombineCap entries a tile — row_seg
+// read coalesced, partial[row_seg[s]] gathered into the entry's place of an LDS tile.  A block's gathers fall into its few (class,
+// block) windows of partial and are issued together, so a line is fetched once (a thread per row walking its own run touched the
+// same lines again many iterations later, after other waves' traffic: 1.9 times the bytes).  Behind a barrier thread i adds its row's
+// floats from the tile in row_seg order, keeping its sum and its place across tiles.  No atomics, nothing between workgroups.
 #include "spmm_common.hpp"
 
 namespace {
@@ -119,19 +125,56 @@ void spmm_stream_kernel(const StreamParams p) {
   }
 }
 
-// combine: one thread per stream row r — the floats of its segments row_seg[row_slot_ptr[r] .. row_slot_ptr[r + 1]) in that order (the
-// queue's: the chain the row-major slots gave), the one weight, the rest and self terms as spmm_seg_combine_kernel
-// forms them:   Y[row] = fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, (w_code - w_rest) * (((p_0 + p_1) + p_2) + ...)))
-// One fixed shape per row: bit-reproducible.
+// combine: workgroup b takes the stream rows [b * kCombineRows, (b + 1) * kCombineRows), thread i row b * kCombineRows + i — the floats of
+// its segments row_seg[row_slot_ptr[r] .. row_slot_ptr[r + 1]) in that order (the queue's: the chain the row-major slots gave), the one
+// weight, the rest and self terms as spmm_seg_combine_kernel forms them:
+//   Y[row] =fmaf(w_0 - w_rest, a_i, fmaf(w_rest, T, (w_code - w_rest) * (((p_0 + p_1) + p_2) + ...)))
+// The block's entries [row_slot_ptr[r0], row_slot_ptr[r0 + rows)) pass through the LDS tile kCombineCap at a time, staged in entry order
+// by all 256 threads (entry j of the tile by thread j & 255); a row may straddle a tile's edge, and a row of 512 pairs alone can list
+// more entries than a tile holds.  Both barriers of a tile are reached by every thread (the trip count is the block's).
+// One fixed shape per row, decided by the plan alone: bit-reproducible.
+constexpr int kCombineRows = 256;    // stream rows per workgroup (at most the 256 threads)
+constexpr int kCombineCap = 4096;    // entries per LDS tile (16 KB)
+
 __global__ __launch_bounds__(256) void spmm_stream_combine_kernel(const Params p, const StreamParams sp) {
-  const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (r >= sp.n_rows) return;
-  const int64_t q = sp.q_lo + r;
+  static_assert(kCombineRows <= 256 && kCombineCap % 256 == 0, "a thread per row, whole passes of the workgroup over a tile");
+  constexpr int FLY = 4;    // gathers in flight per thread
+  __shared__ float tile[kCombineCap];
+  const int t = static_cast<int>(threadIdx.x);
+  const int r0 = static_cast<int>(blockIdx.x) * kCombineRows;
+  const int rows = sp.n_rows - r0 < kCombineRows ? sp.n_rows - r0 : kCombineRows;    // (the last block may be short)
+  const bool mine = t < rows;
+  const int64_t q = sp.q_lo + r0 + (mine ? t : 0);
   const int64_t o = out_row(p, q, q);
-  const int s0 = sp.row_slot_ptr[r], s1 = sp.row_slot_ptr[r + 1];
+  int s = 0, s1 = 0;    // the row's next entry and its end; a thread without a row adds nothing
+  if (mine) { s = sp.row_slot_ptr[r0 + t]; s1 = sp.row_slot_ptr[r0 + t + 1]; }
+  const int e0 = sp.row_slot_ptr[r0], e1 = sp.row_slot_ptr[r0 + rows];
   float y = 0.f;
-  for (int s = s0; s < s1; ++s) y += sp.partial[sp.row_seg[s]];
-  combine_store<true>(p, q, o, y, sp.code);
+  for (int base = e0; base < e1; base += kCombineCap) {
+    const int m = e1 - base < kCombineCap ? e1 - base : kCombineCap;
+    const int32_t* seg = sp.row_seg + base;
+    for (int j0 = t; j0 < m; j0 += 256 * FLY) {
+      int sg[FLY];
+      float v[FLY];
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) {   // no branch around a load: a slot past the end reads the tile's last entry again, dropped below
+        const int j = j0 + 256 * u;
+        sg[u] = seg[j < m ? j : m - 1];
+      }
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) v[u] = sp.partial[sg[u]];
+#pragma unroll
+      for (int u = 0; u < FLY; ++u) {
+        const int j = j0 + 256 * u;
+        if (j < m) tile[j] = v[u];
+      }
+    }
+    __syncthreads();
+    const int hi = s1 < base + m ? s1 : base + m;
+    for (; s < hi; ++s) y += tile[s - base];
+    __syncthreads();
+  }
+  if (mine) combine_store<true>(p, q, o, y, sp.code);
 }
 
 StreamParams stream_params(const gnan_spmm_args* a) {
@@ -172,6 +215,7 @@ int gnan::launch_stream_combine(const gnan_spmm_args* a, hipStream_t st) {
   if (a->stream_index == nullptr) return GNAN_OK;
   const Params p = make_params(a);
   const StreamParams sp = stream_params(a);
-  hipLaunchKernelGGL(spmm_stream_combine_kernel, dim3(static_cast<unsigned>((sp.n_rows + 255) / 256)), dim3(256), 0, st, p, sp);
+  const unsigned nb = static_cast<unsigned>((sp.n_rows + kCombineRows - 1) / kCombineRows);
+  hipLaunchKernelGGL(spmm_stream_combine_kernel, dim3(nb), dim3(256), 0, st, p, sp);
   return gnan::check_launch("spmm_stream_combine_kernel");
 }
