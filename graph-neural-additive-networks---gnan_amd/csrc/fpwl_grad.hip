@@ -33,6 +33,8 @@
 namespace {
 
 constexpr int kBI = 16;   // elements of a 4-lane split: ceil(64 / 4)
+constexpr size_t kLdsPerCu = 160 * 1024;      // gfx950
+constexpr size_t kWideStaticLds = 128;        // n_live and wave_live of the wide instance, rounded up
 
 struct GradParams {
   const int32_t* off;
@@ -109,7 +111,7 @@ __device__ __forceinline__ void list_live_pieces(const GradParams& p, int base, 
   if (tid == 0) *n_live = running;
 }
 
-// ---- L == 3, H <= 64: NG groups of 256 threads walk the pieces NG at a time; in a group thread (j, ib) = (unit of
+// ---- L == 3, H <= kW: NG groups of 4 kW (kW = 64: 256) threads walk the pieces NG at a time; in a group thread (j, ib) = (unit of
 // layer 2, quarter of the layer-1 units).  One group per workgroup needed 110 us on the arxiv shape (129 features x ~130
 // pieces, two barriers per piece, 129 workgroups on 256 CUs); several groups share the weights in LDS and a piece's
 // latency, the live pieces are listed by ballots and a piece's moments, anchor and inner point are requested a round
@@ -118,8 +120,18 @@ __device__ __forceinline__ void list_live_pieces(const GradParams& p, int base, 
 // CQ = ceil(C / 4) channel accumulators per thread: a template parameter so that the common one-channel case does not pay
 // 32 registers for them.  1024 threads leave 128 VGPRs per lane: W2 is read from its padded LDS copy (conflict-free: row
 // stride H + 1) rather than kept in 16 registers, which spilled 86 at four groups; CQ = 16 spills 120 there and runs two.
-template <int kNG, int CQ>
-__global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams p) {
+//
+// kW = 128 is the wide instance, 64 < H <= 128: the same code with a group of 4 kW = 512 threads (a quad per unit still) and
+// kW / 4 = 32 float64 dW2 accumulators per thread (64 VGPRs), so the quad split, the butterfly and the in-order group add — the
+// rounding order — are those of kW = 64.  ONE group for every channel count: 512 threads are two waves per SIMD, 256 VGPRs per
+// lane, of which CQ = 1 / 2 / 4 / 16 take 177 / 179 / 183 / 207; two groups (1024 threads, 128 VGPRs) spill 53-63 registers to
+// scratch, and still 25-38 with the mat-vec loops unrolled by four only (compiler's resource report).  The
+// padded W2 copy alone is 66 KB at H = 128: every wide launch raises the dynamic LDS limit, and gnan_fpwl_param_grads refuses
+// what would not fit a CU.  The sweep kernel below (two [H][H + 1] float64 forms: 264 KB at H = 128) does not serve kW = 128.
+template <int kW, int kNG, int CQ>
+__global__ __launch_bounds__(4 * kW * kNG) void fpwl_grad3_kernel(const GradParams p) {
+  constexpr int kGT = 4 * kW;          // threads of a group: a quad per unit
+  constexpr int kQ = kW / 4;           // elements of a 4-lane split: ceil(kW / 4)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int H = p.H, C = p.C, HS = H + 1;
   float* w1 = reinterpret_cast<float*>(smem_raw);
@@ -129,31 +141,31 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
   float* Wl = W2s + H * HS;            // [C][H]
   double* vec = reinterpret_cast<double*>(smem_raw + (((3 * H + H * HS + C * H) * sizeof(float) + 7) & ~size_t(7)));
   const int tid = threadIdx.x, k = blockIdx.x;
-  const int grp = tid >> 8, lt = tid & 255;
+  const int grp = tid / kGT, lt = tid % kGT;
   double* h1i = vec + grp * (5 * H + 2 * C);      // per group: h1i | h1a | h1p | e0 | e1 | Mv[2C]
   double* h1a = h1i + H;
   double* h1p = h1a + H;
   double* e0 = h1p + H;
   double* e1 = e0 + H;
   double* Mv = e1 + H;
-  double* red = vec + kNG * (5 * H + 2 * C);      // [kNG - 1][256]: one accumulator of every thread of groups 1.. at a time
-  int* live = reinterpret_cast<int*>(red + (kNG - 1) * 256);   // [P]: the pieces that hold at least one node, ascending
+  double* red = vec + kNG * (5 * H + 2 * C);      // [kNG - 1][kGT]: one accumulator of every thread of groups 1.. at a time
+  int* live = reinterpret_cast<int*>(red + (kNG - 1) * kGT);   // [P]: the pieces that hold at least one node, ascending
   __shared__ int n_live;
-  __shared__ int wave_live[4 * kNG];
+  __shared__ int wave_live[kGT / 64 * kNG];
   const int j = lt >> 2, ib = lt & 3;
   const int BI = (H + 3) >> 2;
   const int64_t kH = static_cast<int64_t>(k) * H;
 
-  for (int i = tid; i < H; i += 256 * kNG) {
+  for (int i = tid; i < H; i += kGT * kNG) {
     w1[i] = p.w1[kH + i];
     b1[i] = p.b1 ? p.b1[kH + i] : 0.f;
     b2[i] = p.b2 ? p.b2[kH + i] : 0.f;
   }
-  for (int i = tid; i < H * H; i += 256 * kNG) W2s[(i / H) * HS + i % H] = p.W2[kH * H + i];
-  for (int i = tid; i < C * H; i += 256 * kNG) Wl[i] = p.Wl[kH * C + i];
-  double dW2[kBI], dW3[CQ];
+  for (int i = tid; i < H * H; i += kGT * kNG) W2s[(i / H) * HS + i % H] = p.W2[kH * H + i];
+  for (int i = tid; i < C * H; i += kGT * kNG) Wl[i] = p.Wl[kH * C + i];
+  double dW2[kQ], dW3[CQ];
 #pragma unroll
-  for (int r = 0; r < kBI; ++r) dW2[r] = 0.0;
+  for (int r = 0; r < kQ; ++r) dW2[r] = 0.0;
 #pragma unroll
   for (int r = 0; r < CQ; ++r) dW3[r] = 0.0;
   double db2 = 0.0, dw1 = 0.0, db1 = 0.0, db3 = 0.0;
@@ -162,7 +174,7 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
   // Most pieces hold no node (the kinks of a feature spread far beyond the range of its values): list the others first —
   // one parallel pass over the moments instead of a dependent global read and a barrier per piece (the kernel spent its
   // time there: 110 us on the arxiv shape with ~130 pieces of which ~25 are live).
-  list_live_pieces<256 * kNG>(p, base, P, inv0, inv1, live, wave_live, &n_live);
+  list_live_pieces<kGT * kNG>(p, base, P, inv0, inv1, live, wave_live, &n_live);
   __syncthreads();
   const int nl = n_live;
   double mval = 0.0;                                // this thread's moment of the group's NEXT piece, requested a round ahead
@@ -196,7 +208,7 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
     if (j < H) {
       double si = 0.0, sa = 0.0, sp = 0.0;
 #pragma unroll
-      for (int r = 0; r < kBI; ++r) {
+      for (int r = 0; r < kQ; ++r) {
         const int i = ib * BI + r;
         if (r < BI && i < H) {
           const double w = static_cast<double>(W2s[j * HS + i]);
@@ -218,7 +230,7 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
       p0 = quad_sum(p0); p1 = quad_sum(p1);
       const double e0v = on2 ? p0 : 0.0, e1v = on2 ? p1 : 0.0;
 #pragma unroll
-      for (int r = 0; r < kBI; ++r) {
+      for (int r = 0; r < kQ; ++r) {
         const int i = ib * BI + r;
         if (r < BI && i < H) dW2[r] = fma(e0v, h1a[i], fma(e1v, h1p[i], dW2[r]));
       }
@@ -239,7 +251,7 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
       const int i = j;
       double q0 = 0.0, q1 = 0.0;
 #pragma unroll
-      for (int r = 0; r < kBI; ++r) {
+      for (int r = 0; r < kQ; ++r) {
         const int jj = ib * BI + r;
         if (r < BI && jj < H) {
           const double w = static_cast<double>(W2s[jj * HS + i]);
@@ -259,15 +271,15 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
   // groups 1 .. NG-1 hand their accumulators to group 0, one value per thread at a time; group 0 adds them in group order
   auto gather = [&](double& v) {
     __syncthreads();
-    if (grp > 0) red[(grp - 1) * 256 + lt] = v;
+    if (grp > 0) red[(grp - 1) * kGT + lt] = v;
     __syncthreads();
     if (grp == 0) {
 #pragma unroll
-      for (int g = 1; g < kNG; ++g) v += red[(g - 1) * 256 + lt];
+      for (int g = 1; g < kNG; ++g) v += red[(g - 1) * kGT + lt];
     }
   };
 #pragma unroll
-  for (int r = 0; r < kBI; ++r)
+  for (int r = 0; r < kQ; ++r)
     if (r < BI) gather(dW2[r]);
 #pragma unroll
   for (int r = 0; r < CQ; ++r)
@@ -277,7 +289,7 @@ __global__ __launch_bounds__(256 * kNG) void fpwl_grad3_kernel(const GradParams 
 
   if (j < H) {
 #pragma unroll
-    for (int r = 0; r < kBI; ++r) {
+    for (int r = 0; r < kQ; ++r) {
       const int i = ib * BI + r;
       if (r < BI && i < H) p.d_W2[(kH + j) * H + i] = static_cast<float>(dW2[r]);
     }
@@ -955,8 +967,8 @@ extern "C" int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t
   GNAN_REQUIRE(a != nullptr, "fpwl_param_grads: null args");
   GNAN_REQUIRE(a->F >= 1 && a->H >= 1 && a->C >= 1, "fpwl_param_grads: bad sizes");
   if (a->L < 2 || a->L > 4) return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: kernel covers L in {2, 3, 4} (got %d)", a->L);
-  if (a->C > 64 || a->H > (a->L >= 3 ? 64 : 128))
-    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: H <= %d and C <= 64 (got H=%d, C=%d)", a->L >= 3 ? 64 : 128, a->H, a->C);
+  if (a->C > 64 || a->H > (a->L == 4 ? 64 : 128))
+    return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: H <= %d and C <= 64 (got H=%d, C=%d)", a->L == 4 ? 64 : 128, a->H, a->C);
   GNAN_REQUIRE(a->off && a->anchor && a->w_first && a->w_last && a->d_w_first && a->d_w_last, "fpwl_param_grads: null pointer");
   GNAN_REQUIRE(a->max_pieces >= 1 && a->max_pieces <= 8192, "fpwl_param_grads: max_pieces must be in [1, 8192] (got %d)", a->max_pieces);
   GNAN_REQUIRE((a->moments != nullptr) != (a->moments_fixed != nullptr), "fpwl_param_grads: exactly one of moments / moments_fixed");
@@ -992,6 +1004,28 @@ extern "C" int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t
     else hipLaunchKernelGGL((fpwl_grad4_kernel<ng, 16>), grid, block, lds, st, p);
     return gnan::check_launch("fpwl_grad4_kernel");
   }
+  if (a->L == 3 && a->H > 64) {
+    // wide instance: ONE group of 512 threads for every channel count — two (1024 threads, 128 VGPRs) spill 53-63 registers
+    // (LDS: 139 296 bytes at H = 128, C = 64, max_pieces = 8192, the largest shape the checks above admit)
+    const size_t H = a->H, C = a->C;
+    const size_t lds = (((3 * H + H * (H + 1) + C * H) * sizeof(float) + 7) & ~size_t(7)) + (5 * H + 2 * C) * sizeof(double) +
+                       (static_cast<size_t>(a->max_pieces) + 8) * sizeof(int);
+    if (lds + kWideStaticLds > kLdsPerCu)
+      return gnan::fail(GNAN_ERR_UNSUPPORTED, "fpwl_param_grads: H=%d, C=%d, max_pieces=%d need %zu bytes of LDS, a CU has %zu",
+                        a->H, a->C, a->max_pieces, lds + kWideStaticLds, kLdsPerCu);
+    const void* fn = C <= 4 ? reinterpret_cast<const void*>(fpwl_grad3_kernel<128, 1, 1>)
+                     : C <= 8 ? reinterpret_cast<const void*>(fpwl_grad3_kernel<128, 1, 2>)
+                     : C <= 16 ? reinterpret_cast<const void*>(fpwl_grad3_kernel<128, 1, 4>)
+                               : reinterpret_cast<const void*>(fpwl_grad3_kernel<128, 1, 16>);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return gnan::fail(GNAN_ERR_HIP, "fpwl_param_grads: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const dim3 grid(a->F), block(512);
+    if (C <= 4) hipLaunchKernelGGL((fpwl_grad3_kernel<128, 1, 1>), grid, block, lds, st, p);
+    else if (C <= 8) hipLaunchKernelGGL((fpwl_grad3_kernel<128, 1, 2>), grid, block, lds, st, p);
+    else if (C <= 16) hipLaunchKernelGGL((fpwl_grad3_kernel<128, 1, 4>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((fpwl_grad3_kernel<128, 1, 16>), grid, block, lds, st, p);
+    return gnan::check_launch("fpwl_grad3_kernel (wide)");
+  }
   if (a->L == 3) {
     const size_t H = a->H, C = a->C;
     size_t lds = ((3 * H + H * (H + 1) + C * H) * sizeof(float) + 7) & ~size_t(7);
@@ -1013,10 +1047,10 @@ extern "C" int gnan_fpwl_param_grads(const gnan_fpwl_grad_args* a, gnan_stream_t
     const int ng = C <= 4 ? 4 : 2;
     lds += (ng * (5 * H + 2 * C) + (ng - 1) * 256) * sizeof(double) + (static_cast<size_t>(a->max_pieces) + 8) * sizeof(int);   // + live pieces
     const dim3 grid(a->F), block(256 * ng);
-    if (C <= 4) hipLaunchKernelGGL((fpwl_grad3_kernel<4, 1>), grid, block, lds, st, p);
-    else if (C <= 8) hipLaunchKernelGGL((fpwl_grad3_kernel<2, 2>), grid, block, lds, st, p);
-    else if (C <= 16) hipLaunchKernelGGL((fpwl_grad3_kernel<2, 4>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((fpwl_grad3_kernel<2, 16>), grid, block, lds, st, p);
+    if (C <= 4) hipLaunchKernelGGL((fpwl_grad3_kernel<64, 4, 1>), grid, block, lds, st, p);
+    else if (C <= 8) hipLaunchKernelGGL((fpwl_grad3_kernel<64, 2, 2>), grid, block, lds, st, p);
+    else if (C <= 16) hipLaunchKernelGGL((fpwl_grad3_kernel<64, 2, 4>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((fpwl_grad3_kernel<64, 2, 16>), grid, block, lds, st, p);
     return gnan::check_launch("fpwl_grad3_kernel");
   }
   hipLaunchKernelGGL(fpwl_grad2_kernel, dim3(a->F), dim3(512), (static_cast<size_t>(a->max_pieces) + 8) * sizeof(int), st, p);

@@ -602,6 +602,15 @@ def _table_grads_applies(L: int, H: int, C: int) -> bool:
     return HIP_TABLE_GRADS and C <= 4096 and ((L in (3, 4) and H <= 64) or (L == 2 and H <= 128))
 
 
+WIDE_TABLE_GRADS = True   # ... of three-layer nets of 65-128 hidden units as well (fpwl_grad3_kernel's wide instance)
+
+
+def _wide_table_grads_applies(L: int, H: int, C: int) -> bool:
+    """Parameter gradients only: ``x.grad`` at these widths has no table route (:func:`_input_grad_applies` and
+    ``aggregate.reference_order_applies`` ask :func:`_table_grads_applies`)."""
+    return HIP_TABLE_GRADS and WIDE_TABLE_GRADS and L == 3 and 64 < H <= 128 and C <= 4096
+
+
 def _grad_outputs(keep, dests):
     """Output tensors of a parameter-gradient kernel: the caller's destinations (``FlatMLPStore.grad_dest`` — the kernel then
     writes straight into the flat gradient buffer the Parameters' ``.grad`` views are cut from, no copy) where they fit."""
@@ -1038,7 +1047,7 @@ def _shape_function_grads(x, params, present, tables, grad_out, sum_features, L,
         # table path: one streaming pass bins the upstream gradient per piece (HIP), then the exact
         # parameter gradients follow from 2 probe points per piece through the tiny batched MLP
         from .pwl import parameter_grads_from_moments
-        if _table_grads_applies(L, H, C) and x.is_cuda:
+        if (_table_grads_applies(L, H, C) or _wide_table_grads_applies(L, H, C)) and x.is_cuda:
             # ... exactly, in one kernel: one reverse pass for the value and one for the slope of every non-empty piece
             M = _fpwl_moments(x, tables, grad_out, sum_features, x_abs_max, raw=True, located=located)
             return None, _fpwl_param_grads_launch(params, tables, M, L, H, C, F, dests=dests)
@@ -1102,7 +1111,7 @@ def _rho_param_grads(arg: torch.Tensor, dlut: torch.Tensor, tables, params, pres
     x = arg.reshape(-1, 1)
     g = dlut.reshape(-1, C)
     x_abs_max = x.abs().max().double() if x.numel() else None
-    if _table_grads_applies(L, H, C):
+    if _table_grads_applies(L, H, C) or _wide_table_grads_applies(L, H, C):
         M = _fpwl_moments(x, tables, g, False, x_abs_max, raw=True)
         return tuple(_fpwl_param_grads_launch(params, tables, M, L, H, C, 1))
     from .pwl import parameter_grads_from_moments

@@ -363,8 +363,11 @@ int gnan_fpwl_moment_scales(const gnan_moment_scales_args* a, gnan_stream_t stre
  * one workgroup per feature, no atomics (bit-reproducible).  Moments as gnan_fpwl_moments wrote them (`moments`) or in
  * fixed point (`moments_fixed` + the `scales` they were accumulated with); tables as gnan_pwl_build wrote them (only
  * off / anchor are read).  Weight and gradient layouts as gnan_fmlp_bwd_args, the mid layers stacked as in gnan_fmlp_args:
- * w_mid / d_w_mid [L-2, F, H, H], b_mid / d_b_mid [L-2, F, H].  Covers L == 2 with H <= 128 and L in {3, 4} with H <= 64 (L == 4:
- * ABI 51), C <= 64; anything else is GNAN_ERR_UNSUPPORTED before a launch. */
+ * w_mid / d_w_mid [L-2, F, H, H], b_mid / d_b_mid [L-2, F, H].  Covers L in {2, 3} with H <= 128 and L == 4 with H <= 64 (L == 4:
+ * ABI 51; L == 3 with 64 < H <= 128 was added under ABI 51 too: no symbol or struct changed), C <= 64; anything else is
+ * GNAN_ERR_UNSUPPORTED before a launch.  L == 3 with H > 64 keeps its weights, one group's vectors and the list of live pieces in
+ * up to 139 296 bytes of LDS (H = 128, C = 64, max_pieces = 8192); a shape that would not fit a CU's 160 KiB is refused likewise,
+ * naming the bytes. */
 typedef struct gnan_fpwl_grad_args {
   const int32_t* off;           /* [F+1] */
   const float* anchor;          /* [T] */
