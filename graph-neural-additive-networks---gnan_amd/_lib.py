@@ -551,6 +551,10 @@ SYMBOLS = {
                                            C.c_void_p]),
     "gnan_fmlp_bwd_mfma_workspace_bytes": (C.c_size_t, [C.POINTER(FmlpBwdArgs)]),
     "gnan_fmlp_bwd_mfma": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p]),
+    "gnan_fmlp_mc_fwd_workspace_bytes": (C.c_size_t, [C.POINTER(FmlpArgs)]),
+    "gnan_fmlp_mc_fwd": (C.c_int, [C.POINTER(FmlpArgs), C.c_void_p]),
+    "gnan_fmlp_mc_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(FmlpBwdArgs)]),
+    "gnan_fmlp_mc_bwd": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p]),
     "gnan_pwl_build_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gnan_pwl_build": (C.c_int, [C.POINTER(PwlBuildArgs), C.c_void_p]),
     "gnan_pwl_check_fit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -12,6 +12,7 @@
 // loop.  Per node and wave: 3 H^2 fmas (z2, dW2 += dz2 x h1, dh1 = W2^T dz2).  The four waves' partial sums meet in LDS
 // in wave order at the end.
 #include "fmlp_bwd_body.hpp"
+#include "fmlp_split_reduce.hpp"
 
 namespace {
 
@@ -58,26 +59,8 @@ __global__ __launch_bounds__(kWaves * kWave) void fmlp_bwd_kernel(const BwdParam
       [&](int64_t node, int c) { return p.grad[node * p.grad_stride + goff + c]; }, red);
 }
 
-// out[i] = sum over the splits of partial[s * stride + i], in split order — all six gradient tensors in ONE launch (a launch per
-// tensor was six launches behind a 15-us kernel on a few hundred inputs).  csrc/fmlp_bwd_mfma.hip keeps a copy
-// (fmlp_bwd_mfma_reduce_kernel): change the two together.
-struct ReduceOuts {
-  float* out[6];
-  int64_t off[6];       // start of the tensor inside a split's block; off[t + 1] - off[t] elements (off[6] = block size)
-  int64_t end;
-};
-
-__global__ __launch_bounds__(256) void fmlp_bwd_reduce_kernel(const float* __restrict__ partial, int64_t stride, int splits,
-                                                              const ReduceOuts r) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= r.end) return;
-  float a = partial[i];
-  for (int s = 1; s < splits; ++s) a += partial[static_cast<int64_t>(s) * stride + i];
-  int t = 0;
-#pragma unroll
-  for (int u = 1; u < 6; ++u) t = i >= r.off[u] ? u : t;
-  if (r.out[t]) r.out[t][i - r.off[t]] = a;
-}
+// the splits' blocks meet in split order: gnan::fmlp_split_reduce_kernel (csrc/fmlp_split_reduce.hpp)
+using ReduceOuts = gnan::SplitReduceOuts;
 
 // How many node ranges a feature's nodes are cut into: enough workgroups to fill the chip twice over, at least 256 nodes each.
 int node_splits(int64_t n, int F) {
@@ -176,8 +159,8 @@ extern "C" int gnan_fmlp_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) 
   r.out[3] = a->L == 3 ? a->d_b_mid : nullptr; r.out[4] = a->d_w_last; r.out[5] = a->d_b_last;
   r.off[0] = 0; r.off[1] = off_b1; r.off[2] = off_w2; r.off[3] = off_b2; r.off[4] = off_w3; r.off[5] = off_b3;
   r.end = blk;
-  hipLaunchKernelGGL(fmlp_bwd_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st, ws, blk, splits, r);
-  return gnan::check_launch("fmlp_bwd_reduce_kernel");
+  hipLaunchKernelGGL(gnan::fmlp_split_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st, ws, blk, splits, r);
+  return gnan::check_launch("fmlp_split_reduce_kernel");
 }
 
 extern "C" size_t gnan_fmlp_bwd_workspace_bytes(const gnan_fmlp_bwd_args* a) {

@@ -16,10 +16,11 @@
 //   tiles through a private LDS slab (written lane = node, read lane = unit) and runs them as MFMA with K = node; dW2 stays in
 //   HT^2 x 16 accumulator registers over all tiles of the split, dW3 (g padded to one 32-row tile) in HT x 16.
 //   dw1, db1, db2, db3 are lane sums, reduced over the lanes once at the end (fixed butterfly).
-// The four waves' sums meet in LDS in wave order, the splits' in fmlp_bwd_reduce_kernel in split order: no atomics, the same
+// The four waves' sums meet in LDS in wave order, the splits' in gnan::fmlp_split_reduce_kernel in split order: no atomics, the same
 // bits on every run.  Rows past the split's end take x = 0 and g = 0: every product they enter is exactly 0.
 #include "common.hpp"
 #include "dropout.hpp"
+#include "fmlp_split_reduce.hpp"
 
 namespace {
 
@@ -355,25 +356,8 @@ __global__ __launch_bounds__(256) void fmlp_bwd_mfma_kernel(const Params p) {
   }
 }
 
-// out[i] = sum over the splits of partial[s * stride + i], in split order — all six gradient tensors in one launch.  A copy of
-// fmlp_bwd_reduce_kernel of csrc/fmlp_bwd.hip (file-local there): change the two together.
-struct ReduceOuts {
-  float* out[6];
-  int64_t off[6];
-  int64_t end;
-};
-
-__global__ __launch_bounds__(256) void fmlp_bwd_mfma_reduce_kernel(const float* __restrict__ partial, int64_t stride, int splits,
-                                                                   const ReduceOuts r) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= r.end) return;
-  float a = partial[i];
-  for (int s = 1; s < splits; ++s) a += partial[static_cast<int64_t>(s) * stride + i];
-  int t = 0;
-#pragma unroll
-  for (int u = 1; u < 6; ++u) t = i >= r.off[u] ? u : t;
-  if (r.out[t]) r.out[t][i - r.off[t]] = a;
-}
+// the splits' blocks meet in split order: gnan::fmlp_split_reduce_kernel (csrc/fmlp_split_reduce.hpp)
+using ReduceOuts = gnan::SplitReduceOuts;
 
 // Node ranges per feature: enough workgroups to fill the chip twice over (one workgroup per CU: the LDS), at least one
 // 32-node tile per wave each.
@@ -469,9 +453,9 @@ extern "C" int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t str
   r.out[5] = a->d_b_last;
   r.off[0] = 0; r.off[1] = off_b1; r.off[2] = off_w2; r.off[3] = off_b2; r.off[4] = off_w3; r.off[5] = off_b3;
   r.end = blk;
-  hipLaunchKernelGGL(fmlp_bwd_mfma_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st,
+  hipLaunchKernelGGL(gnan::fmlp_split_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st,
                      static_cast<const float*>(a->workspace), blk, splits, r);
-  return gnan::check_launch("fmlp_bwd_mfma_reduce_kernel");
+  return gnan::check_launch("fmlp_split_reduce_kernel");
 }
 
 extern "C" size_t gnan_fmlp_bwd_mfma_workspace_bytes(const gnan_fmlp_bwd_args* a) {

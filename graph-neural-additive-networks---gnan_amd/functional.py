@@ -524,7 +524,8 @@ def _fmlp_forward(x: torch.Tensor, p: "StackedMLP", sum_features: bool, want_tot
     return _fmlp_launch(x, p, sum_features, _lib.FMLP_AUTO if algo == _lib.FMLP_PWL else algo), None, None
 
 
-def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int = 0, dropout=None) -> torch.Tensor:
+def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int = 0, dropout=None, mc: bool = False) -> torch.Tensor:
+    """``gnan_fmlp_fwd`` (``mc``: ``gnan_fmlp_mc_fwd``, the many-channel matrix-core kernel, same record; ``algo`` is not read)."""
     x = x.detach().float()
     x = _rows(x)
     n = x.shape[0]
@@ -537,11 +538,15 @@ def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int =
                       sum_features=int(sum_features), out=_lib.ptr(out), out_stride=out.stride(0), algo=algo)
     if dropout is not None:
         a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1])
-    need = _lib.lib().gnan_fmlp_fwd_workspace_bytes(a)
+    lib = _lib.lib()
+    need = lib.gnan_fmlp_mc_fwd_workspace_bytes(a) if mc else lib.gnan_fmlp_fwd_workspace_bytes(a)
     if need:
         ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)   # packed weights (caching allocator)
         a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    _lib.check(_lib.lib().gnan_fmlp_fwd(a, _lib.stream_of(x)), "gnan_fmlp_fwd")
+    if mc:
+        _lib.check(lib.gnan_fmlp_mc_fwd(a, _lib.stream_of(x)), "gnan_fmlp_mc_fwd")
+    else:
+        _lib.check(lib.gnan_fmlp_fwd(a, _lib.stream_of(x)), "gnan_fmlp_fwd")
     return out
 
 
@@ -724,9 +729,10 @@ HIP_SMALL_BACKWARD = True
 HIP_SMALL_BACKWARD_MAX_WORK = 1 << 23
 
 
-def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=None, dests=None, mfma=False):
-    """``gnan_fmlp_bwd`` (``mfma``: ``gnan_fmlp_bwd_mfma``, the matrix-core kernel of large batches, same record): gradients of
-    the six stacked parameter tensors (None where a bias is absent), in their order."""
+def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=None, dests=None, mfma=False, mc=False):
+    """``gnan_fmlp_bwd`` (``mfma``: ``gnan_fmlp_bwd_mfma``, the matrix-core kernel of large batches; ``mc``: ``gnan_fmlp_mc_bwd``,
+    the many-channel one; same record): gradients of the six stacked parameter tensors (None where a bias is absent), in their
+    order."""
     xd = x.detach().float()
     xd = _rows(xd)
     g = grad_out.detach().float()
@@ -746,11 +752,16 @@ def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout
     if dropout is not None:
         a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1])
     lib = _lib.lib()
-    need = lib.gnan_fmlp_bwd_mfma_workspace_bytes(a) if mfma else lib.gnan_fmlp_bwd_workspace_bytes(a)
+    if mc:
+        need = lib.gnan_fmlp_mc_bwd_workspace_bytes(a)
+    else:
+        need = lib.gnan_fmlp_bwd_mfma_workspace_bytes(a) if mfma else lib.gnan_fmlp_bwd_workspace_bytes(a)
     if need:
         ws = torch.empty(need // 4, dtype=torch.float32, device=xd.device)
         a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    if mfma:
+    if mc:
+        _lib.check(lib.gnan_fmlp_mc_bwd(a, _lib.stream_of(xd)), "gnan_fmlp_mc_bwd")
+    elif mfma:
         _lib.check(lib.gnan_fmlp_bwd_mfma(a, _lib.stream_of(xd)), "gnan_fmlp_bwd_mfma")
     else:
         _lib.check(lib.gnan_fmlp_bwd(a, _lib.stream_of(xd)), "gnan_fmlp_bwd")
@@ -893,12 +904,44 @@ def dropout_mfma_routes(n: int, F: int, L: int, H: int, C: int, x_grad: bool = F
             bool(backward_on and big and inside and L == 3 and not x_grad))
 
 
+# Many output channels (9 <= C <= 64: the 40-class arxiv model) under Dropout on the matrix cores: the forward calls
+# gnan_fmlp_mc_fwd, the backward gnan_fmlp_mc_bwd (csrc/fmlp_mc.hip: the last layer is a matrix product too), each behind its own
+# switch, from DROPOUT_MC_MIN_WORK node-features on.  Switches and threshold follow from profiles/r29_dropout_mc.jsonl
+# (tools/dropout_mc_time.py --drive) by the rule of DESIGN section 5: a pass ships on only if at the arxiv shape with C = 40 its
+# slowest process beat the parent's fastest by more than the parent's spread — the forward did (58.6 -> 4.42-4.46 ms), the backward
+# did (131.9 -> 15.9 ms); in the sweep at F = 64 both are ahead from the smallest size, 2^16 node-features (7.33 -> 0.105 ms,
+# 0.385 -> 0.179 ms).  The threshold is a name of its own and never lies below DROPOUT_MFMA_CLAMP, so smaller batches keep the lane
+# forward and the restatement's backward, and their bits, whatever was measured.
+DROPOUT_MC = True
+DROPOUT_MC_BACKWARD = True
+DROPOUT_MC_MEASURED_MIN_WORK = 1 << 16
+DROPOUT_MC_MIN_WORK = max(DROPOUT_MC_MEASURED_MIN_WORK, DROPOUT_MFMA_CLAMP)
+DROPOUT_MC_CMAX = 64              # gnan_fmlp_mc_fwd's and gnan_fmlp_mc_bwd's channel cover
+
+
+def dropout_mc_routes(n: int, F: int, L: int, H: int, C: int, x_grad: bool = False, forward_on=None, backward_on=None,
+                      min_work=None):
+    """``(forward on gnan_fmlp_mc_fwd, backward on gnan_fmlp_mc_bwd)`` of one :func:`feature_mlps_dropout` call, asked after
+    :func:`dropout_mfma_routes` (which owns ``C <= 8``): pure, the module's switches and threshold unless given.  Forward cover:
+    ``3 <= L <= 4, H <= 64, 9 <= C <= 64``; backward cover: ``L == 3``, the same ``H`` and ``C``, and no ``x.grad``.  The
+    module's own threshold never lies below ``DROPOUT_MFMA_CLAMP``."""
+    forward_on = DROPOUT_MC if forward_on is None else forward_on
+    backward_on = DROPOUT_MC_BACKWARD if backward_on is None else backward_on
+    min_work = DROPOUT_MC_MIN_WORK if min_work is None else min_work
+    big = n * F >= min_work
+    inside = 1 <= H <= 64 and 9 <= C <= DROPOUT_MC_CMAX
+    return (bool(forward_on and big and inside and 3 <= L <= 4),
+            bool(backward_on and big and inside and L == 3 and not x_grad))
+
+
 class _DropoutMLPs(torch.autograd.Function):
     """The shape functions with training-mode Dropout behind every hidden ReLU (GNAN.py:28,32; run.sh trains with p = 0.6),
     in the kernels: forward ``gnan_fmlp_fwd`` (lane kernel; the matrix-core kernel where :func:`dropout_mfma_routes` says so),
     backward ``gnan_fmlp_bwd`` (``gnan_fmlp_bwd_mfma`` likewise) — all recompute the masks from ``(p, seed)``
-    (csrc/dropout.hpp), no mask or activation tensor is formed.  Shapes the backward kernels do not cover (L > 3, H > 64,
-    C > 8) back-propagate through the batched restatement in chunks of nodes, with the kernels' masks."""
+    (csrc/dropout.hpp), no mask or activation tensor is formed.  ``9 <= C <= 64`` goes to ``gnan_fmlp_mc_fwd`` /
+    ``gnan_fmlp_mc_bwd`` where :func:`dropout_mc_routes` says so.  Shapes no backward kernel covers (L > 3, H > 64, C > 64,
+    C > 8 below the many-channel threshold, ``x.grad`` at C > 8) back-propagate through the batched restatement in chunks of
+    nodes, with the kernels' masks."""
 
     @staticmethod
     def forward(ctx, x, sum_features, drop_p, seed, L, H, C, F, *params):
@@ -907,6 +950,8 @@ class _DropoutMLPs(torch.autograd.Function):
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(x, *[t for t in params if t is not None])
         mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[0]
+        if not mfma and dropout_mc_routes(x.shape[0], F, L, H, C)[0]:
+            return _fmlp_launch(x, p, sum_features, dropout=(drop_p, seed), mc=True)
         return _fmlp_launch(x, p, sum_features, _lib.FMLP_MFMA if mfma else _lib.FMLP_LANE, dropout=(drop_p, seed))
 
     @staticmethod
@@ -918,6 +963,9 @@ class _DropoutMLPs(torch.autograd.Function):
         if L in (2, 3) and 1 <= H <= 64 and C <= 8 and not ctx.needs_input_grad[0]:
             mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[1]
             pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed), mfma=mfma)
+            return (None,) * 8 + tuple(pg)
+        if dropout_mc_routes(x.shape[0], F, L, H, C, x_grad=ctx.needs_input_grad[0])[1]:
+            pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed), mc=True)
             return (None,) * 8 + tuple(pg)
         leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
         p = StackedMLP(*leaves, L, H, C, F)

@@ -147,6 +147,23 @@ int gnan_dropout_mask_window(uint64_t seed, float p, int64_t node_lo, int64_t n_
 size_t gnan_fmlp_bwd_mfma_workspace_bytes(const gnan_fmlp_bwd_args* a);
 int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t stream);
 
+/* The shape functions with MANY output channels on the matrix cores: the last layer is a matrix product too (channel tiles
+ * of 32 rows), where gnan_fmlp_fwd(GNAN_FMLP_MFMA) and gnan_fmlp_bwd_mfma stop at C = 8 (added under ABI 51: four new entry
+ * points on the two existing records, the number did not move; `algo` is not read).
+ *   gnan_fmlp_mc_fwd: gnan_fmlp_fwd's outputs for 3 <= L <= 4, 1 <= H <= 64, 1 <= C <= 64, both sum_features, dropout_p in
+ *     [0, 1) with gnan_dropout_mask's masks.  The workspace (packed weights, plus per-chunk partial sums with sum_features) is
+ *     always needed, 16-byte aligned.
+ *   gnan_fmlp_mc_bwd: gnan_fmlp_bwd_mfma's gradients for L == 3, 1 <= H <= 64, 1 <= C <= 64; workspace as there (partial
+ *     gradients of the node ranges, added in range order: no atomics, the same bits on every run).
+ * Refusals, in this order and all before any HIP call: NULL record or n < 0 or F < 1 -> GNAN_ERR_BAD_ARG; outside the cover ->
+ * GNAN_ERR_UNSUPPORTED (the message names the limits and the values); pointers, strides, dropout_p -> GNAN_ERR_BAD_ARG; workspace
+ * -> GNAN_ERR_WORKSPACE (both byte counts).  The forward returns GNAN_OK for n == 0 once the cover is checked.  Both agree with
+ * the C <= 8 kernels to rounding (another order of summation in the last layer), not bit for bit. */
+size_t gnan_fmlp_mc_fwd_workspace_bytes(const gnan_fmlp_args* a);
+int gnan_fmlp_mc_fwd(const gnan_fmlp_args* a, gnan_stream_t stream);
+size_t gnan_fmlp_mc_bwd_workspace_bytes(const gnan_fmlp_bwd_args* a);
+int gnan_fmlp_mc_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Shape functions by exact piecewise-linear table look-up — same outputs as gnan_fmlp_fwd.
  * Each f_k (a ReLU MLP of a scalar, GNAN.py:24-34) is exactly piecewise linear; the caller tabulates it
