@@ -615,6 +615,11 @@ SYMBOLS = {
     "gnan_mid_graph_bwd_drop_dev": (C.c_int, [C.POINTER(MidGraphBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
     "gnan_small_batch_fwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
     "gnan_small_batch_bwd_drop_dev": (C.c_int, [C.POINTER(SmallBatchBwdArgs), C.POINTER(SmallDropoutDev), C.c_void_p]),
+    "gnan_fmlp_fwd_dev": (C.c_int, [C.POINTER(FmlpArgs), C.c_void_p, C.c_void_p]),
+    "gnan_fmlp_bwd_dev": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p, C.c_void_p]),
+    "gnan_fmlp_bwd_mfma_dev": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p, C.c_void_p]),
+    "gnan_fmlp_mc_fwd_dev": (C.c_int, [C.POINTER(FmlpArgs), C.c_void_p, C.c_void_p]),
+    "gnan_fmlp_mc_bwd_dev": (C.c_int, [C.POINTER(FmlpBwdArgs), C.c_void_p, C.c_void_p]),
     "gnan_small_batch_pre_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "gnan_small_batch_pre_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmallBatchBwdArgs)]),
     "gnan_small_batch_pre_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmallBatchPreInfo)]),

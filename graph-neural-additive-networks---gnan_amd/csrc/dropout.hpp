@@ -10,6 +10,8 @@
 #pragma once
 #include <cstdint>
 
+#include "common.hpp"
+
 namespace gnan {
 
 __host__ __device__ __forceinline__ uint32_t mix32(uint32_t h) {      // murmur3's finaliser
@@ -32,6 +34,22 @@ __host__ __device__ __forceinline__ bool drop_keep(uint32_t base, int layer, int
 __host__ __forceinline__ uint32_t drop_threshold(float p) {
   const double t = static_cast<double>(p) * 4294967296.0;
   return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 4294967295u : static_cast<uint32_t>(t));
+}
+
+// The *_dev twins of the direct kernels' entry points (gnan_fmlp_fwd_dev, gnan_fmlp_bwd_dev, gnan_fmlp_bwd_mfma_dev,
+// gnan_fmlp_mc_fwd_dev, gnan_fmlp_mc_bwd_dev): the seed lives in a device cell (gnan_dropout_seed_set writes it; a captured step
+// reads a fresh one at every replay).  Checked on the host before anything else of theirs, in drop_dev_ok's order: p outside
+// [0, 1) (NaN included), a non-zero by-value seed in the record (the cell is the seed), then a NULL cell under p > 0.
+// *seed_dev: the cell the kernel reads, NULL for p == 0 (the plain kernel, which never reads it).
+template <class A>
+inline int seed_cell_ok(const char* who, const A* a, const uint64_t* cell, const uint64_t** seed_dev) {
+  GNAN_REQUIRE(a != nullptr, "%s: null args", who);
+  GNAN_REQUIRE(a->dropout_p >= 0.f && a->dropout_p < 1.f, "%s: dropout_p must be in [0, 1) (got p=%g)", who, static_cast<double>(a->dropout_p));
+  GNAN_REQUIRE(a->dropout_seed == 0, "%s: dropout_seed must be 0, the cell holds the seed (got dropout_seed=%llu)", who,
+               static_cast<unsigned long long>(a->dropout_seed));
+  GNAN_REQUIRE(cell != nullptr || !(a->dropout_p > 0.f), "%s: null dropout seed cell", who);
+  *seed_dev = a->dropout_p > 0.f ? cell : nullptr;
+  return GNAN_OK;
 }
 
 }  // namespace gnan

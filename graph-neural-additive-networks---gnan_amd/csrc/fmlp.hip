@@ -47,6 +47,7 @@ struct Params {
   uint32_t drop_thresh;
   float drop_scale;
   uint64_t drop_seed;
+  const uint64_t* seed_dev;   // NULL (drop_seed came by value), or the device cell the seed is read from (the *_dev entry points); NULL whenever drop_thresh == 0
 };
 
 constexpr int JB = 8;
@@ -86,6 +87,7 @@ __global__ __launch_bounds__(256) void fmlp_lane_kernel(const Params p) {
   float* sacc = buf_b + H * kWave;
   const int64_t node = (static_cast<int64_t>(blockIdx.x) * waves + wave) * kWave + lane;
   const bool valid = node < p.n;
+  const uint64_t seed = p.seed_dev ? *p.seed_dev : p.drop_seed;      // one wave-uniform load (gnan_fmlp_fwd_dev: the seed's device cell)
   if (p.sum_features)
     for (int c = 0; c < C; ++c) sacc[c * kWave] = 0.f;
 
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void fmlp_lane_kernel(const Params p) {
       continue;
     }
     const bool drop = p.drop_thresh != 0u;
-    const uint32_t dbase = drop ? gnan::drop_base(p.drop_seed, node, k) : 0u;
+    const uint32_t dbase = drop ? gnan::drop_base(seed, node, k) : 0u;
     for (int j = 0; j < H; ++j) {
       const float b = p.b_first ? p.b_first[k * H + j] : 0.f;
       float h = fmaxf(fmaf(xv, p.w_first[k * H + j], b), 0.f);
@@ -263,6 +265,8 @@ __global__ __launch_bounds__(256, 2) void fmlp_mfma_kernel(const Params p, const
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   const int half = lane >> 5, nl = lane & 31;
+  uint64_t seed = 0;
+  if constexpr (DROP) seed = p.seed_dev ? *p.seed_dev : p.drop_seed;   // one wave-uniform load (gnan_fmlp_fwd_dev: the seed's device cell)
   const int64_t tile0 = (static_cast<int64_t>(blockIdx.x) * 4 + wave) * NT;
   int64_t node[NT];
   bool valid[NT];
@@ -306,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void fmlp_mfma_kernel(const Params p, const
       float B[KS];
       const float xv = xcur[nt];
       uint32_t dbase = 0u;
-      if constexpr (DROP) dbase = gnan::drop_base(p.drop_seed, node[nt], k);
+      if constexpr (DROP) dbase = gnan::drop_base(seed, node[nt], k);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const float2 wb = *reinterpret_cast<const float2*>(vec + (s * 2 + half) * 2);
@@ -510,6 +514,7 @@ Params make_params(const gnan_fmlp_args* a) {
   p.drop_thresh = drop ? gnan::drop_threshold(a->dropout_p) : 0u;
   p.drop_scale = drop ? 1.f / (1.f - a->dropout_p) : 1.f;
   p.drop_seed = a->dropout_seed;
+  p.seed_dev = nullptr;
   return p;
 }
 
@@ -534,7 +539,8 @@ extern "C" size_t gnan_fmlp_fwd_workspace_bytes(const gnan_fmlp_args* a) {
   return bytes;
 }
 
-extern "C" int gnan_fmlp_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
+// THE launcher of gnan_fmlp_fwd (seed_dev == NULL) and gnan_fmlp_fwd_dev (seed_dev: the seed's device cell, NULL for p == 0)
+static int fmlp_fwd(const gnan_fmlp_args* a, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fmlp: null args");
   GNAN_REQUIRE(a->n >= 0 && a->F >= 1 && a->L >= 1 && a->C >= 1, "fmlp: bad sizes n=%lld F=%d L=%d C=%d",
                static_cast<long long>(a->n), a->F, a->L, a->C);
@@ -547,7 +553,8 @@ extern "C" int gnan_fmlp_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
   GNAN_REQUIRE(a->out_stride >= ow, "fmlp: out row stride smaller than the output width");
 
   GNAN_REQUIRE(a->dropout_p >= 0.f && a->dropout_p < 1.f, "fmlp: dropout_p must be in [0, 1)");
-  const Params p = make_params(a);
+  Params p = make_params(a);
+  p.seed_dev = p.drop_thresh != 0u ? seed_dev : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (point_route(a)) {
     hipLaunchKernelGGL(fmlp_point_kernel, dim3(static_cast<unsigned>(a->n * a->F)), dim3(64), 0, st, p);
@@ -584,6 +591,14 @@ extern "C" int gnan_fmlp_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
   }
   hipLaunchKernelGGL(fmlp_lane_kernel, dim3(static_cast<unsigned>(blocks)), dim3(waves * gnan::kWave), lds, st, p);
   return gnan::check_launch("fmlp_lane_kernel");
+}
+
+extern "C" int gnan_fmlp_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) { return fmlp_fwd(a, nullptr, stream); }
+
+extern "C" int gnan_fmlp_fwd_dev(const gnan_fmlp_args* a, const uint64_t* seed_cell, gnan_stream_t stream) {
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = gnan::seed_cell_ok("fmlp_fwd_dev", a, seed_cell, &seed_dev)) return rc;
+  return fmlp_fwd(a, seed_dev, stream);
 }
 
 

@@ -35,6 +35,7 @@ struct BwdParams {
   uint32_t drop_thresh;      // training-mode Dropout of the forward pass (csrc/dropout.hpp); 0 = none
   float drop_scale;
   uint64_t drop_seed;
+  const uint64_t* seed_dev;   // NULL (drop_seed came by value), or the device cell the seed is read from (the *_dev entry points); NULL whenever drop_thresh == 0
 };
 
 // One 256-thread workgroup per feature (and node range), nothing crosses workgroups (no atomics: the result does not depend on
@@ -49,7 +50,8 @@ __global__ __launch_bounds__(kWaves * kWave) void fmlp_bwd_kernel(const BwdParam
   w.w_first = p.w_first; w.b_first = p.b_first; w.w_mid = p.w_mid; w.b_mid = p.b_mid; w.w_last = p.w_last; w.b_last = p.b_last;
   w.d_w_first = p.d_w_first; w.d_b_first = p.d_b_first; w.d_w_mid = p.d_w_mid; w.d_b_mid = p.d_b_mid;
   w.d_w_last = p.d_w_last; w.d_b_last = p.d_b_last;
-  const gnan_bwd::Drop drop{p.drop_thresh, p.drop_scale, p.drop_seed};
+  // (gnan_fmlp_bwd_dev: the seed's device cell, one wave-uniform load)
+  const gnan_bwd::Drop drop{p.drop_thresh, p.drop_scale, p.seed_dev ? *p.seed_dev : p.drop_seed};
   const int64_t n_lo = static_cast<int64_t>(blockIdx.y) * p.nodes_per_split;
   const int64_t n_hi = n_lo + p.nodes_per_split < p.n ? n_lo + p.nodes_per_split : p.n;
   const int64_t so = static_cast<int64_t>(blockIdx.y) * p.split_stride;     // this split's block of partial gradients
@@ -90,7 +92,8 @@ int launch_bwd(const BwdParams& p, unsigned splits, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int gnan_fmlp_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) {
+// THE launcher of gnan_fmlp_bwd (seed_dev == NULL) and gnan_fmlp_bwd_dev (seed_dev: the seed's device cell, NULL for p == 0)
+static int fmlp_bwd(const gnan_fmlp_bwd_args* a, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fmlp_bwd: null args");
   GNAN_REQUIRE(a->n >= 0 && a->F >= 1, "fmlp_bwd: bad sizes");
   if ((a->L != 2 && a->L != 3) || a->H < 1 || a->H > kH || a->C < 1 || a->C > kCmax)
@@ -116,6 +119,7 @@ extern "C" int gnan_fmlp_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) 
   p.drop_thresh = a->dropout_p > 0.f ? gnan::drop_threshold(a->dropout_p) : 0u;
   p.drop_scale = a->dropout_p > 0.f ? 1.f / (1.f - a->dropout_p) : 1.f;
   p.drop_seed = a->dropout_seed;
+  p.seed_dev = p.drop_thresh != 0u ? seed_dev : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // few features and many nodes: a feature's nodes are cut into ranges, one workgroup each; the ranges' gradients land in
   // the workspace and are added in range order (still no atomics)
@@ -161,6 +165,14 @@ extern "C" int gnan_fmlp_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) 
   r.end = blk;
   hipLaunchKernelGGL(gnan::fmlp_split_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st, ws, blk, splits, r);
   return gnan::check_launch("fmlp_split_reduce_kernel");
+}
+
+extern "C" int gnan_fmlp_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) { return fmlp_bwd(a, nullptr, stream); }
+
+extern "C" int gnan_fmlp_bwd_dev(const gnan_fmlp_bwd_args* a, const uint64_t* seed_cell, gnan_stream_t stream) {
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = gnan::seed_cell_ok("fmlp_bwd_dev", a, seed_cell, &seed_dev)) return rc;
+  return fmlp_bwd(a, seed_dev, stream);
 }
 
 extern "C" size_t gnan_fmlp_bwd_workspace_bytes(const gnan_fmlp_bwd_args* a) {

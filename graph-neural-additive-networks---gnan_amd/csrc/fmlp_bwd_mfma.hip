@@ -48,6 +48,7 @@ struct Params {
   uint32_t drop_thresh;
   float drop_scale;
   uint64_t drop_seed;
+  const uint64_t* seed_dev;   // NULL (drop_seed came by value), or the device cell the seed is read from (the *_dev entry points); NULL whenever drop_thresh == 0
 };
 
 __host__ __device__ constexpr int slab_floats(int HP) { return 2 * HP * kST + kCmax * kST; }          // per wave
@@ -79,6 +80,8 @@ __global__ __launch_bounds__(256) void fmlp_bwd_mfma_kernel(const Params p) {
   float* slab_g = slab_b + HP * kST;                     // [8][kST]:  g
   const int k = blockIdx.x;
   const int H = p.H, C = p.C;
+  uint64_t seed = 0;
+  if constexpr (DROP) seed = p.seed_dev ? *p.seed_dev : p.drop_seed;   // one wave-uniform load (gnan_fmlp_bwd_mfma_dev: the seed's device cell)
 
   // the feature's weights into LDS, in fmlp_pack_kernel's order
   {
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(256) void fmlp_bwd_mfma_kernel(const Params p) {
 #pragma unroll
     for (int c = 0; c < CT; ++c) g[c] = (valid && c < C) ? p.grad[node * p.grad_stride + goff + c] : 0.f;
     uint32_t dbase = 0u;
-    if constexpr (DROP) dbase = gnan::drop_base(p.drop_seed, node, k);
+    if constexpr (DROP) dbase = gnan::drop_base(seed, node, k);
 
     // ---- forward: h1 into the B operand, z2 on the matrix cores, h2
     float h1[KS];
@@ -400,7 +403,8 @@ int launch_ct(const Params& p, unsigned splits, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) {
+// THE launcher of gnan_fmlp_bwd_mfma (seed_dev == NULL) and gnan_fmlp_bwd_mfma_dev (seed_dev: the seed's device cell, NULL for p == 0)
+static int fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fmlp_bwd_mfma: null args");
   GNAN_REQUIRE(a->n >= 0 && a->F >= 1, "fmlp_bwd_mfma: bad sizes");
   if (a->L != 3 || a->H < 1 || a->H > 64 || a->C < 1 || a->C > kCmax)
@@ -423,6 +427,7 @@ extern "C" int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t str
   p.drop_thresh = a->dropout_p > 0.f ? gnan::drop_threshold(a->dropout_p) : 0u;
   p.drop_scale = a->dropout_p > 0.f ? 1.f / (1.f - a->dropout_p) : 1.f;
   p.drop_seed = a->dropout_seed;
+  p.seed_dev = p.drop_thresh != 0u ? seed_dev : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int splits = a->n > 0 ? node_splits(a->n, a->F) : 1;
   const int64_t blk = block_floats(a);
@@ -456,6 +461,14 @@ extern "C" int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t str
   hipLaunchKernelGGL(gnan::fmlp_split_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st,
                      static_cast<const float*>(a->workspace), blk, splits, r);
   return gnan::check_launch("fmlp_split_reduce_kernel");
+}
+
+extern "C" int gnan_fmlp_bwd_mfma(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) { return fmlp_bwd_mfma(a, nullptr, stream); }
+
+extern "C" int gnan_fmlp_bwd_mfma_dev(const gnan_fmlp_bwd_args* a, const uint64_t* seed_cell, gnan_stream_t stream) {
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = gnan::seed_cell_ok("fmlp_bwd_mfma_dev", a, seed_cell, &seed_dev)) return rc;
+  return fmlp_bwd_mfma(a, seed_dev, stream);
 }
 
 extern "C" size_t gnan_fmlp_bwd_mfma_workspace_bytes(const gnan_fmlp_bwd_args* a) {

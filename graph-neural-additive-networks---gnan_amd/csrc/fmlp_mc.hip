@@ -56,6 +56,7 @@ struct FwdParams {
   uint32_t drop_thresh;
   float drop_scale;
   uint64_t drop_seed;
+  const uint64_t* seed_dev;   // NULL (drop_seed came by value), or the device cell the seed is read from (the *_dev entry points); NULL whenever drop_thresh == 0
 };
 
 // floats per feature in the packed stream: mid layers | W3 | {w1, b1} | b_mid | b_last, padded to whole 1-KiB pieces per wave
@@ -142,6 +143,8 @@ __global__ __launch_bounds__(256, 4 * sizeof(float) * fwd_feature_floats(HT, NMI
   const int wave = threadIdx.x / kWave;
   const int half = lane >> 5, nl = lane & 31;
   const int C = p.C;
+  uint64_t seed = 0;
+  if constexpr (DROP) seed = p.seed_dev ? *p.seed_dev : p.drop_seed;   // one wave-uniform load (gnan_fmlp_mc_fwd_dev: the seed's device cell)
   const int64_t tile0 = (static_cast<int64_t>(blockIdx.x) * 4 + wave) * NT;
   int64_t node[NT];
   bool valid[NT];
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(256, 4 * sizeof(float) * fwd_feature_floats(HT, NMI
       float B[KS];
       const float xv = xcur[nt];
       uint32_t dbase = 0u;
-      if constexpr (DROP) dbase = gnan::drop_base(p.drop_seed, node[nt], k);
+      if constexpr (DROP) dbase = gnan::drop_base(seed, node[nt], k);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const float2 wb = *reinterpret_cast<const float2*>(vec + (s * 2 + half) * 2);
@@ -380,6 +383,7 @@ struct BwdParams {
   uint32_t drop_thresh;
   float drop_scale;
   uint64_t drop_seed;
+  const uint64_t* seed_dev;   // NULL (drop_seed came by value), or the device cell the seed is read from (the *_dev entry points); NULL whenever drop_thresh == 0
 };
 
 __host__ __device__ constexpr int slab_floats(int HP, int CP) { return (2 * HP + CP) * kST; }                  // per wave
@@ -425,6 +429,8 @@ __global__ __launch_bounds__(256) void fmlp_mc_bwd_kernel(const BwdParams p) {
   float* slab_g = slab_b + HP * kST;                     // [CP][kST]: g, channel-major
   const int k = blockIdx.x;
   const int H = p.H, C = p.C;
+  uint64_t seed = 0;
+  if constexpr (DROP) seed = p.seed_dev ? *p.seed_dev : p.drop_seed;   // one wave-uniform load (gnan_fmlp_mc_bwd_dev: the seed's device cell)
 
   {
     const float* W2 = p.w_mid + static_cast<int64_t>(k) * H * H;
@@ -502,7 +508,7 @@ __global__ __launch_bounds__(256) void fmlp_mc_bwd_kernel(const BwdParams p) {
       }
     }
     uint32_t dbase = 0u;
-    if constexpr (DROP) dbase = gnan::drop_base(p.drop_seed, node, k);
+    if constexpr (DROP) dbase = gnan::drop_base(seed, node, k);
 
     // ---- forward: h1 into the B operand, z2 on the matrix cores, h2 into the slab (its sign bits stay)
     float h1[KS];
@@ -777,7 +783,8 @@ extern "C" size_t gnan_fmlp_mc_fwd_workspace_bytes(const gnan_fmlp_args* a) {
   return bytes;
 }
 
-extern "C" int gnan_fmlp_mc_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
+// THE launcher of gnan_fmlp_mc_fwd (seed_dev == NULL) and gnan_fmlp_mc_fwd_dev (seed_dev: the seed's device cell, NULL for p == 0)
+static int fmlp_mc_fwd(const gnan_fmlp_args* a, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fmlp_mc_fwd: null args");
   GNAN_REQUIRE(a->n >= 0 && a->F >= 1, "fmlp_mc_fwd: bad sizes");
   if (!fwd_cover(a))
@@ -805,6 +812,7 @@ extern "C" int gnan_fmlp_mc_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
   p.drop_thresh = drop ? gnan::drop_threshold(a->dropout_p) : 0u;
   p.drop_scale = drop ? 1.f / (1.f - a->dropout_p) : 1.f;
   p.drop_seed = a->dropout_seed;
+  p.seed_dev = p.drop_thresh != 0u ? seed_dev : nullptr;
   const int chunks = feature_chunks(p.n, p.F, p.H);
   p.feat_chunk = (p.F + chunks - 1) / chunks;
   p.feat_chunk += p.feat_chunk & 1;                  // even: chunks start on a double-buffer pair boundary
@@ -821,13 +829,22 @@ extern "C" int gnan_fmlp_mc_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) {
   return NMID == 1 ? launch_fwd_ct<2, 1>(p, packed, st) : launch_fwd_ct<2, 2>(p, packed, st);
 }
 
+extern "C" int gnan_fmlp_mc_fwd(const gnan_fmlp_args* a, gnan_stream_t stream) { return fmlp_mc_fwd(a, nullptr, stream); }
+
+extern "C" int gnan_fmlp_mc_fwd_dev(const gnan_fmlp_args* a, const uint64_t* seed_cell, gnan_stream_t stream) {
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = gnan::seed_cell_ok("fmlp_mc_fwd_dev", a, seed_cell, &seed_dev)) return rc;
+  return fmlp_mc_fwd(a, seed_dev, stream);
+}
+
 extern "C" size_t gnan_fmlp_mc_bwd_workspace_bytes(const gnan_fmlp_bwd_args* a) {
   if (!a || a->n <= 0 || a->F < 1 || !bwd_cover(a)) return 0;
   const int splits = node_splits(a->n, a->F);
   return splits > 1 ? static_cast<size_t>(splits) * block_floats(a) * sizeof(float) : 0;
 }
 
-extern "C" int gnan_fmlp_mc_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) {
+// THE launcher of gnan_fmlp_mc_bwd (seed_dev == NULL) and gnan_fmlp_mc_bwd_dev (seed_dev: the seed's device cell, NULL for p == 0)
+static int fmlp_mc_bwd(const gnan_fmlp_bwd_args* a, const uint64_t* seed_dev, gnan_stream_t stream) {
   GNAN_REQUIRE(a != nullptr, "fmlp_mc_bwd: null args");
   GNAN_REQUIRE(a->n >= 0 && a->F >= 1, "fmlp_mc_bwd: bad sizes");
   if (!bwd_cover(a))
@@ -853,6 +870,7 @@ extern "C" int gnan_fmlp_mc_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t strea
   p.drop_thresh = a->dropout_p > 0.f ? gnan::drop_threshold(a->dropout_p) : 0u;
   p.drop_scale = a->dropout_p > 0.f ? 1.f / (1.f - a->dropout_p) : 1.f;
   p.drop_seed = a->dropout_seed;
+  p.seed_dev = p.drop_thresh != 0u ? seed_dev : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int splits = a->n > 0 ? node_splits(a->n, a->F) : 1;
   const int64_t blk = block_floats(a);
@@ -887,4 +905,12 @@ extern "C" int gnan_fmlp_mc_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t strea
   hipLaunchKernelGGL(gnan::fmlp_split_reduce_kernel, dim3(static_cast<unsigned>((blk + 255) / 256)), dim3(256), 0, st,
                      static_cast<const float*>(a->workspace), blk, splits, r);
   return gnan::check_launch("fmlp_split_reduce_kernel");
+}
+
+extern "C" int gnan_fmlp_mc_bwd(const gnan_fmlp_bwd_args* a, gnan_stream_t stream) { return fmlp_mc_bwd(a, nullptr, stream); }
+
+extern "C" int gnan_fmlp_mc_bwd_dev(const gnan_fmlp_bwd_args* a, const uint64_t* seed_cell, gnan_stream_t stream) {
+  const uint64_t* seed_dev = nullptr;
+  if (int rc = gnan::seed_cell_ok("fmlp_mc_bwd_dev", a, seed_cell, &seed_dev)) return rc;
+  return fmlp_mc_bwd(a, seed_dev, stream);
 }

@@ -525,7 +525,9 @@ def _fmlp_forward(x: torch.Tensor, p: "StackedMLP", sum_features: bool, want_tot
 
 
 def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int = 0, dropout=None, mc: bool = False) -> torch.Tensor:
-    """``gnan_fmlp_fwd`` (``mc``: ``gnan_fmlp_mc_fwd``, the many-channel matrix-core kernel, same record; ``algo`` is not read)."""
+    """``gnan_fmlp_fwd`` (``mc``: ``gnan_fmlp_mc_fwd``, the many-channel matrix-core kernel, same record; ``algo`` is not read).
+    ``dropout = (p, seed)``: an int travels by value in the record, a seed cell (:func:`_seed_cell_of`) goes to the ``_dev`` twin
+    of the same entry point — what a capture may record."""
     x = x.detach().float()
     x = _rows(x)
     n = x.shape[0]
@@ -536,18 +538,40 @@ def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int =
                       w_first=_lib.ptr(keep[0]), b_first=_lib.ptr(keep[1]), w_mid=_lib.ptr(keep[2]),
                       b_mid=_lib.ptr(keep[3]), w_last=_lib.ptr(keep[4]), b_last=_lib.ptr(keep[5]),
                       sum_features=int(sum_features), out=_lib.ptr(out), out_stride=out.stride(0), algo=algo)
-    if dropout is not None:
-        a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1])
+    cell = _seed_into(a, dropout)
     lib = _lib.lib()
     need = lib.gnan_fmlp_mc_fwd_workspace_bytes(a) if mc else lib.gnan_fmlp_fwd_workspace_bytes(a)
     if need:
         ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)   # packed weights (caching allocator)
         a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    if mc:
-        _lib.check(lib.gnan_fmlp_mc_fwd(a, _lib.stream_of(x)), "gnan_fmlp_mc_fwd")
+    entry = "gnan_fmlp_mc_fwd" if mc else "gnan_fmlp_fwd"
+    if cell is not None:
+        _lib.check(getattr(lib, entry + "_dev")(a, _lib.ptr(cell), _lib.stream_of(x)), entry + "_dev")
     else:
-        _lib.check(lib.gnan_fmlp_fwd(a, _lib.stream_of(x)), "gnan_fmlp_fwd")
+        _lib.check(getattr(lib, entry)(a, _lib.stream_of(x)), entry)
     return out
+
+
+def _seed_cell_of(seed) -> Optional[torch.Tensor]:
+    """``seed`` if it is a Dropout seed's device cell (``small_graph.seed_cell``: a one-element ``int64`` / ``uint64`` device tensor
+    that ``gnan_dropout_seed_set`` writes), None for a seed by value."""
+    if not torch.is_tensor(seed):
+        return None
+    if not (seed.is_cuda and seed.numel() == 1 and seed.dtype in (torch.int64, torch.uint64) and seed.is_contiguous()):
+        raise ValueError("a dropout seed cell is a one-element int64 / uint64 device tensor")
+    return seed
+
+
+def _seed_into(a, dropout) -> Optional[torch.Tensor]:
+    """``dropout = (p, seed)`` into the record ``a`` of a direct kernel: p, and the seed where it travels by value.  Returns the
+    seed's device cell where it does not (the record's seed stays 0: the ``_dev`` entry points refuse anything else)."""
+    if dropout is None:
+        return None
+    a.dropout_p = float(dropout[0])
+    cell = _seed_cell_of(dropout[1])
+    if cell is None:
+        a.dropout_seed = int(dropout[1])
+    return cell
 
 
 class TablePrefetch:
@@ -732,7 +756,7 @@ HIP_SMALL_BACKWARD_MAX_WORK = 1 << 23
 def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=None, dests=None, mfma=False, mc=False):
     """``gnan_fmlp_bwd`` (``mfma``: ``gnan_fmlp_bwd_mfma``, the matrix-core kernel of large batches; ``mc``: ``gnan_fmlp_mc_bwd``,
     the many-channel one; same record): gradients of the six stacked parameter tensors (None where a bias is absent), in their
-    order."""
+    order.  ``dropout = (p, seed)`` as in :func:`_fmlp_launch`: a seed cell goes to the entry point's ``_dev`` twin."""
     xd = x.detach().float()
     xd = _rows(xd)
     g = grad_out.detach().float()
@@ -749,8 +773,7 @@ def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout
                          grad=_lib.ptr(g), grad_stride=g.stride(0),
                          d_w_first=_lib.ptr(outs[0]), d_b_first=_lib.ptr(outs[1]), d_w_mid=_lib.ptr(d_w_mid),
                          d_b_mid=_lib.ptr(d_b_mid), d_w_last=_lib.ptr(outs[4]), d_b_last=_lib.ptr(outs[5]))
-    if dropout is not None:
-        a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1])
+    cell = _seed_into(a, dropout)
     lib = _lib.lib()
     if mc:
         need = lib.gnan_fmlp_mc_bwd_workspace_bytes(a)
@@ -759,12 +782,11 @@ def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout
     if need:
         ws = torch.empty(need // 4, dtype=torch.float32, device=xd.device)
         a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    if mc:
-        _lib.check(lib.gnan_fmlp_mc_bwd(a, _lib.stream_of(xd)), "gnan_fmlp_mc_bwd")
-    elif mfma:
-        _lib.check(lib.gnan_fmlp_bwd_mfma(a, _lib.stream_of(xd)), "gnan_fmlp_bwd_mfma")
+    entry = "gnan_fmlp_mc_bwd" if mc else ("gnan_fmlp_bwd_mfma" if mfma else "gnan_fmlp_bwd")
+    if cell is not None:
+        _lib.check(getattr(lib, entry + "_dev")(a, _lib.ptr(cell), _lib.stream_of(xd)), entry + "_dev")
     else:
-        _lib.check(lib.gnan_fmlp_bwd(a, _lib.stream_of(xd)), "gnan_fmlp_bwd")
+        _lib.check(getattr(lib, entry)(a, _lib.stream_of(xd)), entry)
     return outs
 
 
@@ -934,6 +956,53 @@ def dropout_mc_routes(n: int, F: int, L: int, H: int, C: int, x_grad: bool = Fal
             bool(backward_on and big and inside and L == 3 and not x_grad))
 
 
+# Captured steps under Dropout on the DIRECT kernels (full-batch node tasks, CSR-coded graphs, dense graphs past the one-launch
+# routes): the step's owner (graphed.GraphedStep, replay.py) lends the model a seed cell, modules._features hands it to
+# feature_mlps_dropout, and forward and backward run the ``_dev`` twins of the same kernels, which read the seed when they run —
+# one gnan_dropout_seed_set per replay draws fresh masks.  Ships OFF: no time had been measured for the route when it was built
+# (tools/dropout_direct_capture_time.py records it), and tests/test_gpu_dropout_capture.py pins that with
+# small_graph.CAPTURE_DROPOUT alone a node-task step, a 449-node graph and a step that wants only f's gradients store no seed.
+CAPTURE_DROPOUT_DIRECT = False
+
+
+def dropout_direct_capture_applies(model, x, g, node_ids=None) -> bool:
+    """May this forward of ``model`` under active Dropout be captured with its seed in a device cell on the GENERAL route — the
+    shape functions through ``modules._features`` and the direct kernels' ``_dev`` entry points?  Pure.  True only where the switch
+    is on, the forward is the general route's (none of the one-launch routes takes it: ``small_graph.dropout_capture_applies`` is
+    their predicate; no graph in slots), ``node_ids`` is None, ``x`` is float32 and wants no gradient, the model is one of this
+    package's graph models (not ``batched.TensorGNAN``, whose rho draws a mask per pair) without a NAM read-out, and f's stack lies
+    inside a kernel backward's cover — L in {2, 3}, H <= 64, C <= 8 (``gnan_fmlp_bwd`` / ``gnan_fmlp_bwd_mfma``), or L = 3, H <= 64,
+    9 <= C <= 64 from ``DROPOUT_MC_MIN_WORK`` node-features on (``gnan_fmlp_mc_bwd``): anywhere else the backward is the batched
+    restatement, whose masks are by value.  Everything else under Dropout stays eager, as before."""
+    if not CAPTURE_DROPOUT_DIRECT or node_ids is not None:
+        return False
+    if x.dtype != torch.float32 or x.requires_grad:
+        return False
+    from . import modules
+    from . import small_graph as sg
+    if not isinstance(model, (modules.StandaloneTensorGNAN, modules._GNANCore, modules.TensorGNAN)):
+        return False
+    if isinstance(model, modules.TensorGNAN) and model.is_graph_task and model.readout_n_layers > 0:
+        return False
+    if isinstance(g, sg.SlotGraph):
+        return False
+    f = model._stacked("fs", model.fs)
+    n = int(x.shape[0])
+    route = model._small_route(None)
+    if route is not None and sg.SMALL_GRAPH_DROPOUT and g.is_dense and n <= sg.MID_GRAPH_MAX_NODES:
+        # (modules._small_graph's own order: an eager forward that a one-launch route takes is not the general route's)
+        rho, use_cnt = model._stacked("rho", [model.rho]), route[0]
+        if n > sg.SMALL_GRAPH_MAX_NODES:
+            takes = sg.mid_graph_pre_rho_applies(x, g, f, rho) if use_cnt == "pre" else sg.mid_graph_applies(x, g, f, rho, use_cnt)
+        else:
+            takes = sg.small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre")
+        if takes:
+            return False
+    if f.L in (2, 3) and 1 <= f.H <= 64 and 1 <= f.C <= 8:
+        return True
+    return bool(dropout_mc_routes(n, f.F, f.L, f.H, f.C)[1])
+
+
 class _DropoutMLPs(torch.autograd.Function):
     """The shape functions with training-mode Dropout behind every hidden ReLU (GNAN.py:28,32; run.sh trains with p = 0.6),
     in the kernels: forward ``gnan_fmlp_fwd`` (lane kernel; the matrix-core kernel where :func:`dropout_mfma_routes` says so),
@@ -941,12 +1010,14 @@ class _DropoutMLPs(torch.autograd.Function):
     (csrc/dropout.hpp), no mask or activation tensor is formed.  ``9 <= C <= 64`` goes to ``gnan_fmlp_mc_fwd`` /
     ``gnan_fmlp_mc_bwd`` where :func:`dropout_mc_routes` says so.  Shapes no backward kernel covers (L > 3, H > 64, C > 64,
     C > 8 below the many-channel threshold, ``x.grad`` at C > 8) back-propagate through the batched restatement in chunks of
-    nodes, with the kernels' masks."""
+    nodes, with the kernels' masks.  ``seed``: 64 bits by value, or the seed's device cell (a captured step's: the ``_dev`` entry
+    points of the same kernels) — the restatement draws its masks by value, so a cell that reaches it is refused loudly."""
 
     @staticmethod
     def forward(ctx, x, sum_features, drop_p, seed, L, H, C, F, *params):
         p = StackedMLP(*params, L, H, C, F)
-        ctx.meta = (sum_features, float(drop_p), int(seed), L, H, C, F)
+        seed = seed if _seed_cell_of(seed) is not None else int(seed)
+        ctx.meta = (sum_features, float(drop_p), seed, L, H, C, F)
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(x, *[t for t in params if t is not None])
         mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[0]
@@ -967,6 +1038,10 @@ class _DropoutMLPs(torch.autograd.Function):
         if dropout_mc_routes(x.shape[0], F, L, H, C, x_grad=ctx.needs_input_grad[0])[1]:
             pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed), mc=True)
             return (None,) * 8 + tuple(pg)
+        if torch.is_tensor(seed):
+            raise RuntimeError("shape functions under Dropout with their seed in a device cell were evaluated where no backward kernel "
+                               "applies (L in {2, 3}, H <= 64, C <= 8, or L = 3, H <= 64, 9 <= C <= 64 from DROPOUT_MC_MIN_WORK "
+                               "node-features on, and no x.grad): the batched restatement draws its masks by value")
         leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
         p = StackedMLP(*leaves, L, H, C, F)
         live = [t for t in leaves if t is not None]
@@ -1003,12 +1078,14 @@ def draw_dropout_seed() -> int:
     return int(torch.empty((), dtype=torch.int64).random_().item()) & ((1 << 63) - 1)
 
 
-def feature_mlps_dropout(x: torch.Tensor, p: StackedMLP, sum_features: bool, drop_p: float, seed: Optional[int] = None,
+def feature_mlps_dropout(x: torch.Tensor, p: StackedMLP, sum_features: bool, drop_p: float, seed=None,
                          return_total: bool = False):
     """:func:`feature_mlps` in training mode with Dropout ``drop_p`` behind every hidden ReLU (GNAN.py:28,32).  ``seed``:
     64 bits that fix the masks; by default drawn from torch's CPU generator (so ``torch.manual_seed`` makes a run
     repeatable, as it does for ``nn.Dropout``).  The masks are a function of (seed, node, feature, layer, unit) —
-    :func:`dropout_masks` — not torch's Bernoulli stream."""
+    :func:`dropout_masks` — not torch's Bernoulli stream.  ``seed`` may also be the seed's device cell (``small_graph.seed_cell``,
+    written by ``small_graph.seed_cell_set``): the kernels read it when they run, so a captured step draws fresh masks at every
+    replay; ``dropout_masks(s, ...)`` is the mask tensor of a cell that holds ``s``."""
     _lib.require_device(x, p.w_last)
     if x.shape[1] != p.F:
         raise ValueError(f"x has {x.shape[1]} feature columns, the model was built for {p.F}")
@@ -1018,7 +1095,8 @@ def feature_mlps_dropout(x: torch.Tensor, p: StackedMLP, sum_features: bool, dro
         return feature_mlps(x, p, sum_features, return_total=return_total)
     if seed is None:
         seed = draw_dropout_seed()
-    out = _DropoutMLPs.apply(x, sum_features, float(drop_p), int(seed) & ((1 << 63) - 1), p.L, p.H, p.C, p.F, *p[:6])
+    seed = seed if _seed_cell_of(seed) is not None else int(seed) & ((1 << 63) - 1)
+    out = _DropoutMLPs.apply(x, sum_features, float(drop_p), seed, p.L, p.H, p.C, p.F, *p[:6])
     return (out, column_sums(out)) if return_total else out
 
 

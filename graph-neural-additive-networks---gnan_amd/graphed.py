@@ -403,15 +403,22 @@ class GraphedStep:
     @staticmethod
     def supported(model, optimizer=None, data=None) -> bool:
         """``data``: what the step will forward.  A model under training-mode Dropout is captured only where every mask's seed can
-        be read from a device cell (``small_graph.dropout_capture_applies``: a graph in slots, a dense graph of up to 448 nodes)
-        — never without ``data`` (the full-batch node-task step: ``gnan_fmlp_fwd`` takes its seed by value)."""
+        be read from a device cell (``small_graph.dropout_capture_applies``: a graph in slots, a dense graph of up to 448 nodes;
+        behind ``functional.CAPTURE_DROPOUT_DIRECT`` also ``functional.dropout_direct_capture_applies``: the general route, whose
+        direct kernels have ``_dev`` entry points — the full-batch node-task step) — never without ``data``."""
         if not torch.cuda.is_available():
             return False
         if getattr(model, "_dropout_active", lambda: False)():
+            from . import functional as Fn
             from .small_graph import dropout_capture_applies
-            g = getattr(data, "gnan_graph", None)
-            if data is None or g is None or not dropout_capture_applies(model, data.x, g):
+            if data is None:
                 return False
+            g = getattr(data, "gnan_graph", None)
+            if g is None or not dropout_capture_applies(model, data.x, g):
+                if not (Fn.CAPTURE_DROPOUT_DIRECT and hasattr(model, "hop_graph")):
+                    return False
+                if not Fn.dropout_direct_capture_applies(model, data.x, model.hop_graph(data) if g is None else g):
+                    return False
         return optimizer is None or all("capturable" in g for g in optimizer.param_groups)
 
     def __init__(self, model, data, loss_of=None, optimizer=None, forward: Optional[Callable] = None, warmup: int = 0,
@@ -435,7 +442,7 @@ class GraphedStep:
         self.cell = None
         if getattr(model, "_dropout_active", lambda: False)():
             if forward is not None or not GraphedStep.supported(model, None, data):
-                raise CaptureFailed("training-mode Dropout is captured on the one-launch graph routes only")
+                raise CaptureFailed("training-mode Dropout is captured only where every mask's seed can be read from a device cell")
             from .small_graph import seed_cell
             self.cell = seed_cell(data.x.device)
 

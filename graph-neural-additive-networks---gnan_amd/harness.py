@@ -17,7 +17,8 @@ loop.  Graph-level tasks (a different small graph per step, batch_size = 1) get 
 (nodes, features, shells): the third graph of a shape captures it over static buffers and every later graph of that shape
 is copied into them and replayed (``SlottedGraphStep``).  ``GNAN_GRAPHED_STEPS=0`` switches it off; anything a capture cannot hold (training-mode Dropout — unless
 ``small_graph.CAPTURE_DROPOUT`` is on and the step is a graph-task step whose kernels can read the seed from a device cell,
-``small_graph.dropout_capture_applies`` —, an optimizer without a capturable mode, a loader that uploads fresh tensors per epoch) silently keeps the eager loop.
+``small_graph.dropout_capture_applies``, or ``functional.CAPTURE_DROPOUT_DIRECT`` is on and the step runs the general route's direct
+kernels, ``functional.dropout_direct_capture_applies``: the full-batch node-task step, larger graphs' per-shape steps —, an optimizer without a capturable mode, a loader that uploads fresh tensors per epoch) silently keeps the eager loop.
 
 The loss step itself — rows of the task mask, ``nn.BCEWithLogitsLoss()`` / ``nn.CrossEntropyLoss()`` at their default options,
 the gradient w.r.t. the logits, the hit count and the epoch's running totals — is one launch (``losses.loss_step`` ->
@@ -247,7 +248,14 @@ def _step_record(model, data, mask_name, label_index, loss_fn, optimizer, classi
 def _graphed_epoch(model, data, loss_fn, optimizer, classify, label_index, compute_auc, mask_name):
     """One epoch of a full-batch node task through a captured step; None if this epoch has to run eagerly."""
     from .graphed import CaptureFailed, GraphedStep
-    if not GraphedStep.supported(model, optimizer):
+    drop = getattr(model, "_dropout_active", lambda: False)()
+    if drop:
+        # a full-batch node task under training-mode Dropout: the general route's direct kernels, behind their own switch, or eager
+        from .functional import CAPTURE_DROPOUT_DIRECT, dropout_direct_capture_applies
+        if not (CAPTURE_DROPOUT_DIRECT and hasattr(model, "hop_graph") and torch.is_tensor(getattr(data, "x", None)) and data.x.is_cuda
+                and dropout_direct_capture_applies(model, data.x, model.hop_graph(data))):
+            return None
+    if not GraphedStep.supported(model, optimizer, data if drop else None):
         return None
     rec = _step_record(model, data, mask_name, label_index, loss_fn, optimizer, classify)
     if rec is None or rec["dead"]:
@@ -455,8 +463,10 @@ class _GraphTaskSteps:
                 rec["calls"] += 1
                 return False
             if model._dropout_active():
+                from .functional import dropout_direct_capture_applies
                 from .small_graph import dropout_capture_applies
-                if not dropout_capture_applies(model, data.x, graph):
+                # (a graph the one-launch routes refuse: the general route's direct kernels, behind their own switch)
+                if not dropout_capture_applies(model, data.x, graph) and not dropout_direct_capture_applies(model, data.x, graph):
                     rec["dead"] = True                  # (eager as before, silently)
                     return False
             loss_of = self._loss_closure()
@@ -511,10 +521,13 @@ def _run(model, loader, loss_fn, device, optimizer, classify, label_index, compu
     if (GRAPHED_STEPS and is_graph_task and (optimizer is not None or not torch.is_grad_enabled()) and not compute_auc
             and torch.device(device).type == "cuda" and hasattr(model, "hop_graph")):
         from .graphed import GraphedStep
+        from . import functional as Fn
         from . import small_graph as sg
-        # (under training-mode Dropout the steps decide graph by graph: small_graph.dropout_capture_applies)
+        # (under training-mode Dropout the steps decide graph by graph: small_graph.dropout_capture_applies, or — per-shape steps
+        # of graphs the one-launch routes refuse — functional.dropout_direct_capture_applies)
         drop = getattr(model, "_dropout_active", lambda: False)()
-        if (sg.CAPTURE_DROPOUT and GraphedStep.supported(None, optimizer)) if drop else GraphedStep.supported(model, optimizer):
+        if (((sg.CAPTURE_DROPOUT or Fn.CAPTURE_DROPOUT_DIRECT) and GraphedStep.supported(None, optimizer)) if drop
+                else GraphedStep.supported(model, optimizer)):
             replayer = _graph_task_steps(model, optimizer, loss_fn, classify, device)
             if replayer is not None:
                 replayer.total_loss.zero_()

@@ -419,7 +419,9 @@ class _PathBase(nn.Module):
         instead of a second pass over the rows (``rho_aggregate(s_total=...)`` accounts for it in its backward)."""
         if self._dropout_active():
             from .functional import feature_mlps_dropout
-            return feature_mlps_dropout(x, self._stacked(name, mlps), sum_features, float(self.dropout), return_total=want_total)
+            # (a captured step lends its seed cell — functional.dropout_direct_capture_applies let it through: nothing is drawn here)
+            return feature_mlps_dropout(x, self._stacked(name, mlps), sum_features, float(self.dropout),
+                                        seed=self.__dict__.get("_dropout_cell"), return_total=want_total)
         kw = {} if out_dtype == torch.float32 else {"out_dtype": out_dtype}
         if room_rows:
             kw["room_rows"] = room_rows

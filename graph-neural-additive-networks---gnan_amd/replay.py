@@ -78,7 +78,8 @@ class _Plan:
         if grad and any(st._occupied(name) for st in stores for name in st.buf):
             raise _NotNow()                             # gradients waiting to be added to: the capture would freeze "assign"
         self.guard = torch.zeros(1, dtype=torch.float32, device=dev)
-        # A forward under training-mode Dropout (small_graph.dropout_capture_applies let it through): its kernels, forward and
+        # A forward under training-mode Dropout (small_graph.dropout_capture_applies or, on the general route,
+        # functional.dropout_direct_capture_applies let it through): its kernels, forward and
         # backward, read the masks' seed from this cell, which `_fresh_seed` rewrites before every forward replay
         self.cell = None
         if module._dropout_active():
@@ -416,10 +417,14 @@ def run(module, inputs, node_ids=None):
         return module._forward(inputs) if node_ids is None else module._forward(inputs, node_ids)
     if module._dropout_active():
         # only where every mask's seed can come from a device cell (the slot route decides for itself, over its slots)
+        from . import functional as Fn
         from . import small_graph as sg
         if not sg.CAPTURE_DROPOUT or x.shape[0] > sg.MID_GRAPH_MAX_NODES or (
                 x.shape[0] >= REPLAY_MIN_NODES and not sg.dropout_capture_applies(module, x, module.hop_graph(inputs))):
-            return module._forward(inputs)
+            # ... or, behind functional.CAPTURE_DROPOUT_DIRECT, the general route's direct kernels do (their ``_dev`` entry points)
+            if not (Fn.CAPTURE_DROPOUT_DIRECT and x.shape[0] >= REPLAY_MIN_NODES
+                    and Fn.dropout_direct_capture_applies(module, x, module.hop_graph(inputs))):
+                return module._forward(inputs)
     if x.shape[0] < REPLAY_MIN_NODES:
         out = None
         if REPLAY_SMALL_GRAPHS and getattr(inputs, "gnan_graph", None) is None:

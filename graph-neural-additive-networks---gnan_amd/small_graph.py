@@ -567,7 +567,8 @@ def dropout_capture_applies(model, x: torch.Tensor, g, node_ids=None) -> bool:
     reads its seed from a device cell — the one-launch routes: a graph in slots (``gnan_small_batch_*_drop_dev``) or a dense graph
     of up to 448 nodes (``gnan_small_graph_*_drop_dev`` / ``gnan_mid_graph_*_drop_dev``) — and where the backward is one of theirs
     too (the gradients of all of f's and rho's parameters, or of none: the general backward takes its seed by value).  Everything
-    else under Dropout stays eager: the general route, the NAM read-out, ``batched.TensorGNAN``, CSR graphs, ``node_ids``."""
+    else under Dropout stays eager as far as THIS predicate goes: the general route (CSR graphs, larger graphs: it has a predicate
+    and a switch of its own, ``functional.dropout_direct_capture_applies``), the NAM read-out, ``batched.TensorGNAN``, ``node_ids``."""
     route = getattr(model, "_small_route", None)
     if not (CAPTURE_DROPOUT and SMALL_GRAPH_DROPOUT and route is not None) or node_ids is not None or x.requires_grad:
         return False

@@ -1506,6 +1506,29 @@ int gnan_mid_graph_bwd_drop_dev(const gnan_mid_graph_bwd_args* a, const gnan_sma
 int gnan_small_batch_fwd_drop_dev(const gnan_small_batch_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
 int gnan_small_batch_bwd_drop_dev(const gnan_small_batch_bwd_args* a, const gnan_small_dropout_dev* d, gnan_stream_t stream);
 
+/* ... and of the DIRECT kernels, for captured steps past the one-launch routes (full-batch node tasks, CSR-coded graphs, dense
+ * graphs beyond 448 nodes; added under ABI 51: five new entry points on the two existing records, no struct changed, the
+ * number did not move).  gnan_fmlp_args.dropout_seed / gnan_fmlp_bwd_args.dropout_seed are by-value kernel arguments like
+ * gnan_small_dropout.seed; these twins take the records as they are plus `seed_cell`, the device cell gnan_dropout_seed_set writes.
+ *   gnan_fmlp_fwd_dev       gnan_fmlp_fwd        (lane kernel; GNAN_FMLP_MFMA: the matrix-core kernel's Dropout instances)
+ *   gnan_fmlp_bwd_dev       gnan_fmlp_bwd
+ *   gnan_fmlp_bwd_mfma_dev  gnan_fmlp_bwd_mfma
+ *   gnan_fmlp_mc_fwd_dev    gnan_fmlp_mc_fwd
+ *   gnan_fmlp_mc_bwd_dev    gnan_fmlp_mc_bwd
+ * Arguments, covers, workspaces, workspace queries (gnan_fmlp_*_workspace_bytes), masks and results are those of the by-value
+ * entry point on the right: a cell that holds s gives the bits of the by-value call with dropout_seed = s, and
+ * gnan_dropout_mask(s, ...) is its mask tensor.  Each pair shares one launcher and one kernel instance (the kernels take the cell's
+ * address beside the by-value seed, NULL from the by-value entry points, and read it with one wave-uniform load at entry), so
+ * the eager warm-up of a step has raised the instance's dynamic-LDS limit before the step is captured.
+ * Refused on the host before any HIP call, in this order: a NULL record, dropout_p outside [0, 1) (NaN included), a non-zero
+ * dropout_seed in the record (the cell is the seed), a NULL cell with dropout_p > 0 (GNAN_ERR_BAD_ARG); then the by-value entry
+ * point's own refusals.  dropout_p == 0 launches the plain kernel, bit for bit, and never reads the cell (which may be NULL). */
+int gnan_fmlp_fwd_dev(const gnan_fmlp_args* a, const uint64_t* seed_cell, gnan_stream_t stream);
+int gnan_fmlp_bwd_dev(const gnan_fmlp_bwd_args* a, const uint64_t* seed_cell, gnan_stream_t stream);
+int gnan_fmlp_bwd_mfma_dev(const gnan_fmlp_bwd_args* a, const uint64_t* seed_cell, gnan_stream_t stream);
+int gnan_fmlp_mc_fwd_dev(const gnan_fmlp_args* a, const uint64_t* seed_cell, gnan_stream_t stream);
+int gnan_fmlp_mc_bwd_dev(const gnan_fmlp_bwd_args* a, const uint64_t* seed_cell, gnan_stream_t stream);
+
 /* -------------------------------------------------------------------------------------------
  * PRE-RHO normalisation on the batched kernels (GNAN.py:65-67, the stand-alone class's default; added under ABI 51: one new
  * struct for the host-only query, seven new entry points, no existing struct changed, the number did not move).  They take the
