@@ -459,6 +459,27 @@ class SmallSlotNamInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MidGraphNamArgs(C.Structure):
+    """``gnan_mid_graph_nam_args``: the one-graph record of the NAM read-out plus ``colw``, the column sums the forward leaves."""
+    _fields_ = SmallGraphNamArgs._fields_ + [("colw", C.c_void_p)]
+
+
+class MidGraphNamBwdArgs(C.Structure):
+    _fields_ = SmallGraphNamBwdArgs._fields_ + [("colw", C.c_void_p)]
+
+
+class MidGraphNamInfo(C.Structure):
+    """What the launches of ``gnan_mid_graph_nam_fwd`` / ``_bwd`` look like for a shape (``gnan_mid_graph_nam_info``)."""
+    _fields_ = [
+        ("row_tiles", C.c_int32), ("rho_groups", C.c_int32), ("fwd_grid", C.c_int32), ("bwd_feature_grid", C.c_int32),
+        ("bwd_rho_grid", C.c_int32), ("fwd_lds_bytes", C.c_int32), ("bwd_lds_bytes", C.c_int32), ("fwd_workspace_bytes", C.c_int64),
+        ("bwd_workspace_bytes", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class LossArgs(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("n_rows", C.c_int64), ("C", C.c_int32), ("kind", C.c_int32), ("stride", C.c_int64),
@@ -604,6 +625,10 @@ SYMBOLS = {
     "gnan_small_slot_nam_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmallSlotNamInfo)]),
     "gnan_small_slot_nam_fwd": (C.c_int, [C.POINTER(SmallSlotNamArgs), C.c_void_p]),
     "gnan_small_slot_nam_bwd": (C.c_int, [C.POINTER(SmallSlotNamBwdArgs), C.c_void_p]),
+    "gnan_mid_graph_nam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gnan_mid_graph_nam_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MidGraphNamInfo)]),
+    "gnan_mid_graph_nam_fwd": (C.c_int, [C.POINTER(MidGraphNamArgs), C.c_void_p]),
+    "gnan_mid_graph_nam_bwd": (C.c_int, [C.POINTER(MidGraphNamBwdArgs), C.c_void_p]),
     "gnan_small_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "gnan_small_batch_fwd": (C.c_int, [C.POINTER(SmallBatchArgs), C.c_void_p]),
     "gnan_small_batch_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(SmallBatchBwdArgs)]),

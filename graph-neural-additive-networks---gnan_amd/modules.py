@@ -783,6 +783,13 @@ class TensorGNAN(_PathBase):
                     for name in ("fmlp", "spmm"):
                         self._mark(name)
                     return out
+                # 129 to 448 nodes: the same in one launch forward and two backward, over tiles of 64 rows (csrc/mid_graph_nam.hip;
+                # small_graph.MID_GRAPH_NAM).  The reference order keeps the general route.
+                if self.aggregation_order != "reference" and sg.mid_graph_nam_applies(x, g, f, rho, nam, use_cnt):
+                    out = sg.mid_graph_nam_forward(x, g, f, rho, nam, use_cnt)
+                    for name in ("fmlp", "spmm"):
+                        self._mark(name)
+                    return out
             lut = self._lut_global(g)
             self._mark("lut")
             fx, total = self._operand(x, "fs", self.fs, False, rest, pad_ok=True)     # [N, F]   (f is 1-wide; + zero columns)

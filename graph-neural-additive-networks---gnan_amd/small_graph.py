@@ -1,14 +1,17 @@
 """One-launch forward and backward of SMALL dense-coded graphs (``csrc/small_graph.hip``, ``csrc/small_graph_nam.hip``,
-``csrc/mid_graph.hip``) — what a graph-level task feeds per step (trainer.py:23-86 with ``batch_size = 1``; SURVEY.md section 8d C2:
-30 nodes on average).
+``csrc/mid_graph.hip``, ``csrc/mid_graph_nam.hip``) — what a graph-level task feeds per step (trainer.py:23-86 with
+``batch_size = 1``; SURVEY.md section 8d C2: 30 nodes on average).
 
 * :func:`small_graph_forward` — features summed per node, rho on the distinct distances (or, ``use_cnt="pre"``, on the n x D
   normalised distances of GNAN.py:65-67), the normalised aggregation and the graph read-out: GNAN.py:55-79 / 146-172,
   models.py:358-384 with ``readout_n_layers == 0``;
 * :func:`mid_graph_forward` — the same for graphs of 129 to 448 nodes, over tiles of 64 rows (pre-rho: behind ``MID_GRAPH_PRE_RHO``);
-* :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381).
+* :func:`small_graph_nam_forward` — the NAM read-out over the per-feature aggregates (models.py:379-381) on graphs of up to 128 nodes;
+* :func:`mid_graph_nam_forward` — the same read-out for graphs of 129 to 448 nodes: one launch forward, two backward, over tiles of
+  64 rows, no workgroup waiting for another (behind ``MID_GRAPH_NAM``).
 
-All are autograd nodes whose backward pass is one launch as well (the first two are ONE node, :class:`_OneLaunch`, told its route).
+All are autograd nodes whose backward pass is one launch as well (the first two are ONE node, :class:`_OneLaunch`, told its route;
+the last one's backward is two launches in stream order).
 The general kernels (``functional``) take everything these do not cover; the ``*_applies`` predicates say which is which: each
 is the shared test of the graph (:func:`_graph_ok`) and of the MLP stacks (:func:`_stack_ok`) with the route's limits, which stand
 next to it.  The library's copy of the same limits: the ``RouteLimits`` next to each route's entry points.
@@ -395,6 +398,88 @@ def small_graph_nam_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: St
     _lib.require_device(x, f.w_last, rho.w_last, nam.w_last, g.code)
     return _SmallGraphNam.apply(x, g, bool(use_cnt), (f.L, f.H, f.F), (rho.L, rho.H), (nam.L, nam.H, nam.C),
                                 *f[:6], *rho[:6], *nam[:6])
+
+
+# =============================================================================
+# ... for graphs of 129 to 448 nodes: one launch forward, two backward, over tiles of 64 rows (csrc/mid_graph_nam.hip)
+# =============================================================================
+MID_GRAPH_NAM = True          # the route's switch, read at every call.  Off: such a forward takes the general kernels (table, operand,
+                              # rho_aggregate, gnan_colsum, the read-out's MLPs), as before.  On by the measured rule of DESIGN.md section
+                              # 5 (tools/mid_graph_nam_time.py): the replayed step beats the general route's at 130, 200 and 417 nodes by
+                              # 35 to 155 times the latter's spread (6 kernels against 28 with a one-layer read-out, 39 with two layers)
+
+
+def mid_graph_nam_applies(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, nam: StackedMLP, use_cnt=True) -> bool:
+    """Can ``gnan_mid_graph_nam_fwd`` / ``_bwd`` take this graph-level forward with a NAM read-out: a dense-coded graph of 129 to 448
+    nodes and at most 64 shells, one-wide f and rho, the read-out by the rules of :func:`small_graph_nam_applies` — and any number of
+    features: no workgroup of these kernels waits for another.  ``use_cnt`` without the graph's shell sizes does not apply."""
+    if use_cnt and g.cnt is None:
+        return False
+    return bool(MID_GRAPH_NAM and _graph_ok(x, g, MID_GRAPH_MIN_NODES, MID_GRAPH_MAX_NODES, _ONE_LAUNCH_CODES)
+                and x.shape[1] == f.F == nam.F and rho.F == 1 and _stack_ok(f, max_c=1) and _stack_ok(rho, max_c=1)
+                and _stack_ok(nam, depths=(1, 2, 3)))
+
+
+class _MidGraphNam(torch.autograd.Function):
+    """:class:`_SmallGraphNam` by ``gnan_mid_graph_nam_fwd`` (one launch) and ``gnan_mid_graph_nam_bwd`` (two launches, stream-ordered):
+    the forward also leaves ``colw [n]``, the column sums the backward reads."""
+
+    @staticmethod
+    def forward(ctx, x, g, use_cnt, fm, rm, nm, *params):
+        Lf, Hf, F = fm
+        Lr, Hr = rm
+        Ln, Hn, Cn = nm
+        xk = Fn._rows(x.detach())
+        n, D, dev = xk.shape[0], g.n_codes, xk.device
+        keep = _kept(params)
+        fx = torch.empty((F, n), dtype=torch.float32, device=dev)
+        lut = torch.empty(D, dtype=torch.float32, device=dev)
+        hidden = torch.empty(F, dtype=torch.float32, device=dev)
+        colw = torch.empty(n, dtype=torch.float32, device=dev)
+        out = torch.empty(Cn, dtype=torch.float32, device=dev)
+        ws = _workspace(dev, _lib.lib().gnan_mid_graph_nam_workspace_bytes(n, F, D, Cn))
+        a = _lib.MidGraphNamArgs(x=_lib.ptr(xk), x_stride=xk.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, 1),
+                                 rho=_small_mlp(keep[6:12], Lr, Hr, 1), nam=_nam_mlp(keep[12:], Ln, Hn, Cn),
+                                 code=_lib.ptr(g.code), D=D, reserved=0, **_cnt_pair(g.cnt if use_cnt else None), fx=_lib.ptr(fx),
+                                 lut=_lib.ptr(lut), hidden=_lib.ptr(hidden), out=_lib.ptr(out), workspace=_lib.ptr(ws),
+                                 workspace_bytes=ws.numel() * 4, colw=_lib.ptr(colw))
+        _lib.check(_lib.lib().gnan_mid_graph_nam_fwd(a, _lib.stream_of(xk)), "gnan_mid_graph_nam_fwd")
+        ctx.g, ctx.use_cnt, ctx.fm, ctx.rm, ctx.nm = g, use_cnt, fm, rm, nm
+        _save(ctx, (xk, fx, lut, hidden, colw), params)
+        return out.view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (x, fx, lut, hidden, colw), params = _saved(ctx, 5)
+        Lf, Hf, F = ctx.fm
+        Lr, Hr = ctx.rm
+        Ln, Hn, Cn = ctx.nm
+        n, D, dev = x.shape[0], ctx.g.n_codes, x.device
+        keep = _kept(params)
+        outs = [Fn._grad_outputs(keep[i:i + 6], ctx.dests[i:i + 6]) for i in (0, 6, 12)]
+        g_out = d_out.detach().to(torch.float32).contiguous().view(-1)
+        ws = _workspace(dev, _lib.lib().gnan_mid_graph_nam_workspace_bytes(n, F, D, Cn))
+        a = _lib.MidGraphNamBwdArgs(x=_lib.ptr(x), x_stride=x.stride(0), n=n, F=F, f=_small_mlp(keep[:6], Lf, Hf, 1),
+                                    rho=_small_mlp(keep[6:12], Lr, Hr, 1), nam=_nam_mlp(keep[12:], Ln, Hn, Cn),
+                                    code=_lib.ptr(ctx.g.code), D=D, reserved=0, **_cnt_pair(ctx.g.cnt if ctx.use_cnt else None),
+                                    fx=_lib.ptr(fx), lut=_lib.ptr(lut), hidden=_lib.ptr(hidden), d_out=_lib.ptr(g_out),
+                                    df=_mlp_grads(outs[0], Lf), drho=_mlp_grads(outs[1], Lr), dnam=_mlp_grads(outs[2], Ln),
+                                    workspace=_lib.ptr(ws), workspace_bytes=ws.numel() * 4, colw=_lib.ptr(colw))
+        _lib.check(_lib.lib().gnan_mid_graph_nam_bwd(a, _lib.stream_of(x)), "gnan_mid_graph_nam_bwd")
+        flat = []
+        for i, o in zip((0, 6, 12), outs):
+            need = ctx.needs_input_grad[6 + i:12 + i]      # (six arguments, then f's six, rho's six, the read-out's six)
+            flat += [v if nd else None for v, nd in zip(o, need)]
+        return (None, None, None, None, None, None, *flat)
+
+
+def mid_graph_nam_forward(x: torch.Tensor, g: HopGraph, f: StackedMLP, rho: StackedMLP, nam: StackedMLP, use_cnt: bool):
+    """:func:`small_graph_nam_forward` for a dense-coded graph of 129 to 448 nodes (:func:`mid_graph_nam_applies`): ``[C, 1]``."""
+    if use_cnt and g.cnt is None:
+        raise _lib.GnanHipError("shell normalisation was asked for on a graph without shell sizes")
+    _lib.require_device(x, f.w_last, rho.w_last, nam.w_last, g.code)
+    return _MidGraphNam.apply(x, g, bool(use_cnt), (f.L, f.H, f.F), (rho.L, rho.H), (nam.L, nam.H, nam.C),
+                              *f[:6], *rho[:6], *nam[:6])
 
 
 # =============================================================================

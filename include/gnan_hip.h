@@ -1716,6 +1716,89 @@ int gnan_small_slot_nam_describe(int32_t max_nodes, int32_t F, int32_t D, int32_
 int gnan_small_slot_nam_fwd(const gnan_small_slot_nam_args* a, gnan_stream_t stream);
 int gnan_small_slot_nam_bwd(const gnan_small_slot_nam_bwd_args* a, gnan_stream_t stream);
 
+/* ... for dense-coded graphs of up to 448 nodes, walked in tiles of 64 rows (csrc/mid_graph_nam.hip; added under ABI 51: three new
+ * structs, four new entry points, no existing struct changed, the number did not move).  The function, the arithmetic and the leftovers
+ * of gnan_small_graph_nam_fwd / _bwd (whose cover, n <= 128, stays what it was); the records are theirs plus
+ *   colw        [n] the column sums colw[j] = sum_i lut[d] / max(cnt[i, d], 1), d = min(code[i, j], D - 1): the forward writes them,
+ *               the backward reads them (no second walk over the graph).
+ * Cover: 1 <= n <= 448, 2 <= D <= 64, f.C == rho.C == 1, f and rho with L in {2, 3} and 1 <= H <= 64, nam with L in {1, 2, 3} (H <= 64
+ * when L > 1) and 1 <= C <= 8, ANY F >= 1 (no workgroup waits for another, so nothing has to be resident together), float32.  Anything
+ * else: GNAN_ERR_UNSUPPORTED naming the offending value (n=449, f.C=2, nam.C=9, ...).  GNAN_ERR_BAD_ARG for null pointers (a null weight
+ * included), short strides, a code pointer off a 4-byte boundary, a gradient pointer missing or one too many (a bias gradient exactly
+ * where there is a bias; the one-layer read-out: its last layer's only); GNAN_ERR_WORKSPACE, naming both sizes, below
+ * gnan_mid_graph_nam_workspace_bytes(n, F, D, nam.C) — ONE size for both directions, 8-byte aligned, whose first 16 bytes are ZERO before
+ * the first launch (every launch leaves them zero); one workspace per stream.  Every check runs on the host before the first HIP call.
+ *   forward   ONE launch of F workgroups, none of which waits: workgroup k evaluates rho on the D distances, forms colw over the row
+ *             tiles in ascending row order (the next tile's codes and shell sizes requested before the current one is consumed), f_k on
+ *             the nodes in blocks of 64 (fx [F, n]), hidden[k] = sum_j colw[j] fx[k, j] — lane l over j = l, l + 64, ... ascending, one
+ *             fma each, then the butterfly over the 64 lanes (xor 32 .. 1) — and nam_k; the last to arrive adds the features in feature
+ *             order into out [nam.C].  Workgroup 0 writes lut [D] and colw [n].
+ *   backward  TWO launches on the caller's stream, stream order their only dependency.  A, F workgroups: nam_k's gradients, d hidden[k]
+ *             (to the workspace), f_k's gradients from g[j] = colw[j] * d hidden[k].  B, ceil(n / 32) rho groups: each forms
+ *             T[j] = sum_k d hidden[k] fx[k, j] in feature order, bins it by hop code over its 32 rows (lane-private bins, float64 across
+ *             rows) and leaves float64 partials in the workspace; the last group to arrive adds them in group order and runs rho's
+ *             gradients on its D arguments.
+ * Fixed summation orders, no float atomics: two runs give the same bits.  gnan_mid_graph_nam_describe (host only, no HIP call): what the
+ * launches of a shape look like. */
+typedef struct gnan_mid_graph_nam_args {
+  const float* x;            /* [n, F], row stride x_stride */
+  int64_t x_stride;
+  int32_t n, F;
+  gnan_small_mlp f;          /* C == 1 */
+  gnan_small_mlp rho;        /* C == 1 */
+  gnan_small_mlp nam;        /* the read-out's F shape functions */
+  const uint8_t* code;       /* [n, n], 4-byte aligned */
+  int32_t D;
+  int32_t reserved;          /* 0 */
+  const int32_t* cnt;        /* optional [n, cnt_stride] */
+  int64_t cnt_stride;
+  float* fx;                 /* [F, n] */
+  float* lut;                /* [D] */
+  float* hidden;             /* [F] */
+  float* out;                /* [nam.C] */
+  void* workspace;
+  size_t workspace_bytes;
+  float* colw;               /* [n] */
+} gnan_mid_graph_nam_args;
+typedef struct gnan_mid_graph_nam_bwd_args {
+  const float* x;
+  int64_t x_stride;
+  int32_t n, F;
+  gnan_small_mlp f;
+  gnan_small_mlp rho;
+  gnan_small_mlp nam;
+  const uint8_t* code;
+  int32_t D;
+  int32_t reserved;
+  const int32_t* cnt;
+  int64_t cnt_stride;
+  const float* fx;           /* what the forward left */
+  const float* lut;
+  const float* hidden;
+  const float* d_out;        /* [nam.C] */
+  gnan_small_mlp_grads df;
+  gnan_small_mlp_grads drho;
+  gnan_small_mlp_grads dnam;
+  void* workspace;
+  size_t workspace_bytes;
+  const float* colw;         /* [n]: what the forward left */
+} gnan_mid_graph_nam_bwd_args;
+typedef struct gnan_mid_graph_nam_info {
+  int32_t row_tiles;         /* ceil(n / 64) */
+  int32_t rho_groups;        /* ceil(n / 32) */
+  int32_t fwd_grid;          /* workgroups of 256 threads: F */
+  int32_t bwd_feature_grid;  /* launch A: F */
+  int32_t bwd_rho_grid;      /* launch B: rho_groups */
+  int32_t fwd_lds_bytes;     /* dynamic + static LDS of a forward workgroup */
+  int32_t bwd_lds_bytes;     /* ... of a backward workgroup: the larger of the two kernels' */
+  int64_t fwd_workspace_bytes; /* gnan_mid_graph_nam_workspace_bytes: one size serves both directions */
+  int64_t bwd_workspace_bytes;
+} gnan_mid_graph_nam_info;
+size_t gnan_mid_graph_nam_workspace_bytes(int32_t n, int32_t F, int32_t D, int32_t C);
+int gnan_mid_graph_nam_describe(int32_t n, int32_t F, int32_t D, int32_t C, gnan_mid_graph_nam_info* out);
+int gnan_mid_graph_nam_fwd(const gnan_mid_graph_nam_args* a, gnan_stream_t stream);
+int gnan_mid_graph_nam_bwd(const gnan_mid_graph_nam_bwd_args* a, gnan_stream_t stream);
+
 /* Up to eight small device-to-device copies in one launch (host arrays of `count` device pointers and byte counts; ranges
  * must not overlap): the input slots of a captured graph-task step are refilled with it. */
 int gnan_multi_copy(int32_t count, const void* const* src, void* const* dst, const int64_t* bytes, gnan_stream_t stream);
