@@ -959,7 +959,7 @@ def reference_order_applies(x: torch.Tensor, p: StackedMLP, lut: torch.Tensor, g
     grads = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in p[:6])
     x_ok = not x.requires_grad or (x.is_cuda and Fn._table_grads_applies(p.L, p.H, p.C))
     return (grads and x_ok and lut.dim() == 2 and p.C in FUSABLE_READOUT and p.L >= 2 and not g.is_dense
-            and (Fn.FMLP_ALGO == _lib.FMLP_PWL or (Fn.FMLP_ALGO == _lib.FMLP_AUTO and x.shape[0] * p.F >= Fn.PWL_MIN_WORK_GRAD))
+            and Fn.table_route_applies(x.shape[0], p.F, True)
             and not torch.cuda.is_current_stream_capturing() and not (Fn.PAD_FEATURES and p.F % Fn.PAD_FEATURES and p.C == 1
                                                                       and x.shape[0] * p.F >= Fn.PAD_MIN_WORK))
 
@@ -993,8 +993,7 @@ def reference_order_inference_applies(x: torch.Tensor, p: Optional[StackedMLP], 
             and g.n_rows >= SELF_FROM_LOOKUP_MIN_ROWS and g.n_rows >= DEGREE_SORTED_COPY_MIN_ROWS and g.n_codes <= 4
             and DEGREE_SORTED_COPY and PACKED_INDEX and g.n_cols <= (1 << 29) and Fn.INDEX_LOOKUP and x.shape[0] >= Fn.INDEX_MIN_NODES):
         return False
-    if Fn.FMLP_ALGO not in (_lib.FMLP_PWL, _lib.FMLP_AUTO) or (Fn.FMLP_ALGO == _lib.FMLP_AUTO and (
-            x.shape[0] * F < Fn.PWL_MIN_WORK or x.shape[0] < Fn.PWL_MIN_NODES)):
+    if not Fn.table_route_applies(x.shape[0], F, False):
         return False
     if g._self_free is None and torch.cuda.is_current_stream_capturing():
         return False
@@ -1002,21 +1001,18 @@ def reference_order_inference_applies(x: torch.Tensor, p: Optional[StackedMLP], 
 
 
 def reference_order_inference(g: HopGraph, x: torch.Tensor, p: StackedMLP, lut: torch.Tensor, use_cnt: bool,
-                              mark=None) -> torch.Tensor:
+                              mark=None, operand: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``Y [N, 1]`` of the reference order at inference without a single self gather: the look-up stores the operand rows the
     self-free twin of ``g`` lists, hands out every row's feature sum (4 bytes per feature group and node) and the column sums;
     the aggregation walks the twin and adds ``(w(i, 0) - w_rest(i)) * a_i`` in its read-out's epilogue (``gnan_spmm_args.
-    self_sum``).  The ``[N, F]`` operand never leaves this function: its unlisted rows hold whatever was there and are never
-    read.  ``mark``: called between the two stages.  Check :func:`reference_order_inference_applies`."""
+    self_sum``).  The ``[N, F]`` operand never leaves this function — unless the caller lends it (``operand``: float32 rows
+    the look-up stores into): its unlisted rows hold whatever was there and are never read.  ``mark``: called between the two
+    stages.  Check :func:`reference_order_inference_applies`."""
     _lib.require_device(x, p.w_last, lut, g.code)
     plan = g.self_free_plan(strict=False)
-    req = Fn.SelfRequest(plan.listed, SELF_FROM_LOOKUP_SKIP_STORES)
-    Fn._SELF_REQUEST = req
-    try:
-        with torch.no_grad():
-            fx, _, total = Fn._fmlp_forward(x, p, False, True)
-    finally:
-        Fn._SELF_REQUEST = None
+    req = Fn.LookupRequest(out=operand, keep=plan.listed, skip_stores=SELF_FROM_LOOKUP_SKIP_STORES)
+    with torch.no_grad():
+        fx, _, total = Fn._fmlp_forward(x, p, False, True, request=req)
     if total is None:
         total = Fn.column_sums(fx)
     if mark is not None:

@@ -5,6 +5,14 @@ direct evaluation (``csrc/fmlp.hip``) and the exact piecewise-linear tables (``p
 wrappers of both, their autograd node and its backward (moments + analytic parameter gradients, or ``gnan_fmlp_bwd``), the
 pre-rho row table (``rho_row_lut``) and the row reductions of ``csrc/colsum.hip``.
 
+Which route a call takes is asked of pure functions: :func:`table_route_applies` (tables or a direct kernel),
+:func:`dropout_routes` (the forward and backward kernels under Dropout; composed of :func:`dropout_mfma_routes`,
+:func:`dropout_mc_routes` and the lane backward's cover).  What one call asks of its look-up beyond the rows — the caller's own
+rows, room behind them, the keep mask — and what that launch hands back travels in a :class:`LookupRequest` argument from
+:func:`feature_mlps` down to :func:`_fpwl_launch`; a look-up behind a build still in flight, captured or eager, is
+:func:`_look_up_pending`.  No parameter of a single call travels through module state; the capture context
+(``CAPTURED_BUILDS``, ``CAPTURE_PINS``, ``CAPTURE_GUARD``, ``CAPTURE_SCRATCH``) is set by ``graphed`` and spans a whole captured step.
+
 The package's other operators live next door: ``aggregate`` (:func:`~.aggregate.rho_aggregate`, the rho(distance)-weighted
 neighbourhood sum — GNAN.py:65-73 / models.py:368-376 and the per-node loop GNAN.py:159-170), ``small_graph`` (one-launch
 forward / backward of small graphs), ``losses`` (the epoch loops' loss step).  ``modules`` wires them into the reference's classes.
@@ -104,14 +112,16 @@ FPWL_ROWS_MIN_CHANNELS_LARGE = min(4, FPWL_ROWS_MIN_CHANNELS)       # from FPWL_
 FPWL_ROWS_LARGE = 262144
 
 
-def _fpwl_args(x: torch.Tensor, t, sum_features: bool, out=None) -> "_lib.FpwlArgs":
+def _fpwl_args(x: torch.Tensor, t, sum_features: bool, out=None, out_dtype=torch.float32) -> "_lib.FpwlArgs":
+    """The ``gnan_fpwl_args`` record of tables ``t`` over ``x``: what the look-up, the locate pass and the moment kernels share
+    (``out`` None for the passes that store no rows)."""
     n, F = x.shape
     return _lib.FpwlArgs(x=_lib.ptr(x), n=n, x_stride=x.stride(0), F=F, C=t.val.shape[1], off=_lib.ptr(t.off),
                          anchor=_lib.ptr(t.anchor), val=_lib.ptr(t.val), slope=_lib.ptr(t.slope),
                          max_pieces=t.max_pieces, features_per_group=t.features_per_group,
                          max_group_pieces=t.max_group_pieces, sum_features=int(sum_features),
-                         out=_lib.ptr(out), out_stride=0 if out is None else out.stride(0), out_dtype=_lib.GNAN_F32,
-                         flags=_fpwl_flags())
+                         out=_lib.ptr(out), out_stride=0 if out is None else out.stride(0),
+                         out_dtype=_lib.GNAN_BF16 if out_dtype == torch.bfloat16 else _lib.GNAN_F32, flags=_fpwl_flags())
 
 
 def _fpwl_rows_applies(n: int, C: int, t, bins: bool = True) -> bool:
@@ -165,12 +175,17 @@ def _feature_range(x: torch.Tensor) -> Optional[torch.Tensor]:
     return _pin_for_capture(_RANGE_CACHE.put((x,), None, rng))
 
 
+def _index_applies(C: int, x: torch.Tensor, t) -> bool:
+    """The direct-index look-up's cover: one channel, whole 16-feature groups, 16-byte aligned rows, pieces an int16 cell names."""
+    return (C == 1 and t.features_per_group == 16 and x.shape[1] % 16 == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+            and t.max_pieces <= 4096)
+
+
 def _fpwl_index(a: "_lib.FpwlArgs", x: torch.Tensor, t, x_range: torch.Tensor) -> Optional[list]:
     """Build the direct-index tables of ``t`` over ``x_range`` (``gnan_fpwl_index_build``: one small workgroup per feature,
     queued behind the table build) and attach them to the look-up's arguments; returns the tensors to keep alive."""
     n, F = x.shape
-    if (x_range is None or a.C != 1 or t.features_per_group != 16 or F % 16 or x.stride(0) % 4 or x.data_ptr() % 16
-            or t.max_pieces > 4096 or tuple(x_range.shape) != (F, 2)):
+    if x_range is None or not _index_applies(a.C, x, t) or tuple(x_range.shape) != (F, 2):
         return None
     table = torch.empty((F, INDEX_BUCKETS), dtype=torch.int16, device=x.device)
     key = torch.empty((F, 2), dtype=torch.float32, device=x.device)
@@ -182,13 +197,21 @@ def _fpwl_index(a: "_lib.FpwlArgs", x: torch.Tensor, t, x_range: torch.Tensor) -
     return [table, key]
 
 
-class SelfRequest:
-    """What ``aggregate.reference_order_inference`` asks of the per-feature look-up: ``keep`` (in) the bit mask of the rows to
-    store, ``skip_stores`` (in) whether to apply it; ``row_sum`` (out) ``[parts, n]`` the rows' feature sums, or None when the
-    direct-index look-up did not serve the call (the rows are then complete)."""
+class LookupRequest:
+    """What :func:`feature_mlps` / ``aggregate.reference_order_inference`` ask of ONE table look-up, handed down to
+    :func:`_fpwl_launch` as an argument, and what that launch reports back.  Asks: ``out`` the caller's rows to store into (used
+    only where they fit), ``room_rows`` rows of room behind an ``[n, C]`` feature sum, ``keep`` the bit mask of the rows to store —
+    it also asks for every row's feature sum — and ``skip_stores`` whether to apply it.  Outcome of the LAST launch that received
+    the record (cleared on receipt, filled once that launch is queued): ``row_sum [parts, n]``, or None when the direct-index
+    look-up did not serve the call (the rows are then complete); ``room`` the larger buffer the result heads, or None."""
 
-    def __init__(self, keep: torch.Tensor, skip_stores: bool):
-        self.keep, self.skip_stores, self.row_sum = keep, skip_stores, None
+    def __init__(self, out: Optional[torch.Tensor] = None, room_rows: int = 0, keep: Optional[torch.Tensor] = None,
+                 skip_stores: bool = False):
+        self.out, self.room_rows, self.keep, self.skip_stores = out, int(room_rows), keep, skip_stores
+        self.row_sum = self.room = None
+
+    def clear(self):
+        self.row_sum = self.room = None
 
 
 LOCATED_KEEP_MAX_BYTES = 2 << 30   # (piece, dx) of a forward are kept for its backward pass while they stay below 2 GiB
@@ -196,12 +219,14 @@ LOCATED_KEEP_MAX_BYTES = 2 << 30   # (piece, dx) of a forward are kept for its b
 
 def _fpwl_launch(x: torch.Tensor, t, sum_features: bool, want_total: bool = False, out_dtype=torch.float32,
                  total_rows: Optional[int] = None, located: Optional[list] = None, x_range: Optional[torch.Tensor] = None,
-                 index=None):
+                 index=None, request: Optional[LookupRequest] = None):
     """Evaluate pre-built piecewise-linear tables (``pwl.build_tables``) with ``gnan_fpwl_fwd``.
     With ``want_total`` returns ``(out, total)`` where ``total[w] = sum_n out[n, w]`` comes out of the same pass
-    when the kernel's fast path applies (one output channel, whole feature groups), else ``total`` is None."""
-    x = x.detach().float()
-    x = _rows(x)
+    when the kernel's fast path applies (one output channel, whole feature groups), else ``total`` is None.
+    ``request``: see :class:`LookupRequest`."""
+    req = request or LookupRequest()
+    req.clear()
+    x = _rows(x.detach().float())
     n, F = x.shape
     C = t.val.shape[1]
     if (sum_features and C > 1 and F >= 16 and n < SUM_VIA_FEATURES_MAX_NODES and n * F * C * 4 <= (1 << 30)
@@ -212,46 +237,38 @@ def _fpwl_launch(x: torch.Tensor, t, sum_features: bool, want_total: bool = Fals
         per = _fpwl_launch(x, t, False)
         out = per.view(n, F, C).sum(dim=1)
         return (out, None) if want_total else out
-    global _ROOM_RESULT
     width = C if sum_features else F * C
-    if (_OUT_BUFFER is not None and tuple(_OUT_BUFFER.shape) == (n, width) and _OUT_BUFFER.dtype == out_dtype
-            and _OUT_BUFFER.stride(1) == 1 and _OUT_BUFFER.device == x.device):
-        out = _OUT_BUFFER                          # the caller's rows (feature_mlps(out=...): one operand filled by several look-ups)
-    elif sum_features and _ROOM_REQUEST and out_dtype == torch.float32:
+    room = row_sum = None
+    if (req.out is not None and tuple(req.out.shape) == (n, width) and req.out.dtype == out_dtype
+            and req.out.stride(1) == 1 and req.out.device == x.device):
+        out = req.out                              # the caller's rows (feature_mlps(out=...): one operand filled by several look-ups)
+    elif sum_features and req.room_rows and out_dtype == torch.float32:
         # room behind the rows for the compact copy of the most listed nodes' rows (append_hot_rows): the aggregation then
         # gathers the copy into place instead of copying the whole operand into a larger buffer first (40 MB at 10M nodes)
-        room = torch.empty((n + _ROOM_REQUEST, C), dtype=out_dtype, device=x.device)
+        room = torch.empty((n + req.room_rows, C), dtype=out_dtype, device=x.device)
         out = room[:n]
-        _ROOM_RESULT = (out.data_ptr(), room)
     else:
-        out = torch.empty((n, C if sum_features else F * C), dtype=out_dtype, device=x.device)
+        out = torch.empty((n, width), dtype=out_dtype, device=x.device)
+    a = _fpwl_args(x, t, sum_features, out, out_dtype)
     if out_dtype == torch.float32 and _fpwl_rows_applies(n, C, t, bins=False):
-        a = _fpwl_args(x, t, sum_features, out)
         piece, dx = _fpwl_locate(x, t, a)
         _lib.check(_lib.lib().gnan_fpwl_rows_fwd(a, _lib.ptr(piece), _lib.ptr(dx), _lib.stream_of(x)), "gnan_fpwl_rows_fwd")
         if located is not None and 2 * piece.numel() * 4 <= LOCATED_KEEP_MAX_BYTES:
             located[:] = [piece, dx]                    # the backward pass bins the gradient by the same pieces
+        req.room = room
         return (out, None) if want_total else out
-    a = _lib.FpwlArgs(x=_lib.ptr(x), n=n, x_stride=x.stride(0), F=F, C=C, off=_lib.ptr(t.off),
-                      anchor=_lib.ptr(t.anchor), val=_lib.ptr(t.val), slope=_lib.ptr(t.slope),
-                      max_pieces=t.max_pieces, features_per_group=t.features_per_group,
-                      max_group_pieces=t.max_group_pieces, sum_features=int(sum_features),
-                      out=_lib.ptr(out), out_stride=out.stride(0),
-                      out_dtype=_lib.GNAN_BF16 if out_dtype == torch.bfloat16 else _lib.GNAN_F32, flags=_fpwl_flags())
-    if (index is not None and a.C == 1 and t.features_per_group == 16 and F % 16 == 0 and x.stride(0) % 4 == 0
-            and x.data_ptr() % 16 == 0 and t.max_pieces <= 4096):
+    if index is not None and _index_applies(C, x, t):
         # direct-index tables built ahead of time for THESE tables (TablePrefetch(x_range=...): on the side stream)
         a.index_table, a.index_key, a.index_buckets = _lib.ptr(index[0]), _lib.ptr(index[1]), int(index[0].shape[1])
     else:
         index_keep = _fpwl_index(a, x, t, x_range)      # noqa: F841  (alive until the look-up is queued)
-    req = _SELF_REQUEST
-    if req is not None and not sum_features and out_dtype == torch.float32 and a.index_table and n > 0:
+    if req.keep is not None and not sum_features and out_dtype == torch.float32 and a.index_table and n > 0:
         # the reference-order inference route (aggregate.reference_order_inference): the rows' feature sums out of the same pass,
         # and no store for the rows the self-free graph does not list (gnan_fpwl_args.row_sum / row_keep)
         parts = int(_lib.lib().gnan_fpwl_row_sum_parts(a))
         if parts > 0 and req.keep.numel() * 32 >= n:
-            req.row_sum = torch.empty((parts, n), dtype=torch.float32, device=x.device)
-            a.row_sum = _lib.ptr(req.row_sum)
+            row_sum = torch.empty((parts, n), dtype=torch.float32, device=x.device)
+            a.row_sum = _lib.ptr(row_sum)
             a.row_keep = _lib.ptr(req.keep) if req.skip_stores else None
     sum_ws = None
     if sum_features and a.index_table:
@@ -286,18 +303,16 @@ def _fpwl_launch(x: torch.Tensor, t, sum_features: bool, want_total: bool = Fals
         rc = _lib.lib().gnan_fpwl_fwd(a, _lib.stream_of(x))
         if rc == 0:
             located[:] = [piece8]
+            req.room = room
             return (out, total) if want_total else out
         if rc != _lib.ERR_UNSUPPORTED:                  # only "not this kernel's shape" is a reason to ask again: nothing was launched
             _lib.check(rc, "gnan_fpwl_fwd")
         a.piece_out = None                              # another kernel serves this shape: plain look-up
     _lib.check(_lib.lib().gnan_fpwl_fwd(a, _lib.stream_of(x)), "gnan_fpwl_fwd")
+    req.row_sum, req.room = row_sum, room               # the outcome of THIS launch, now that it is queued
     return (out, total) if want_total else out
 
 
-_SELF_REQUEST = None          # SelfRequest while aggregate.reference_order_inference runs its look-up
-_OUT_BUFFER = None            # feature_mlps(out=...): where the table look-up stores its result instead of a fresh tensor
-_ROOM_REQUEST = 0             # rows of room feature_mlps(room_rows=...) asks the table look-up to leave behind its [n, C] result
-_ROOM_RESULT = None           # (data_ptr of the result, the larger buffer it heads) of the last look-up that did
 CAPTURED_BUILDS = []          # (sizes a look-up was captured with, the stacked weights it tabulates) of the capture in progress
 CAPTURE_PINS = None           # list while graphed.GraphedCallable captures: cache-owned tensors the captured step reads
 CAPTURE_GUARD = None          # float32 [1] while a guarded step is captured: set to 1 by a look-up whose tables outgrew its sizes
@@ -345,6 +360,14 @@ def _abs_max_cached(x: torch.Tensor) -> torch.Tensor:
     return _pin_for_capture(hit)
 
 
+def _described(describe: Optional[list], info_type, entry: str, *args) -> None:
+    """Append the library's plan of a launch (``entry(*args, info)`` as a dict) to ``describe``; nothing is asked when it is None."""
+    if describe is not None:
+        info = info_type()
+        _lib.check(getattr(_lib.lib(), entry)(*args, info), entry)
+        describe.append(info.as_dict())
+
+
 def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
                   x_abs_max: Optional[torch.Tensor] = None, raw: bool = False, located=None, describe: Optional[list] = None):
     """Per-piece moments of the upstream gradient (``gnan_fpwl_moments[_fixed]``) -> ``[T, 2, C]`` float32; with ``raw``
@@ -359,18 +382,12 @@ def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
     ``describe``: a list that receives the route of the launch (``gnan_fpwl_moments_describe`` /
     ``gnan_fpwl_rows_moments_describe`` as a dict: kernel, tree depth, node blocks), asked of the library with the very
     arguments of the launch."""
-    x = x.detach().float()
-    x = _rows(x)
-    grad = grad.detach().float()
-    grad = _rows(grad)
+    x = _rows(x.detach().float())
+    grad = _rows(grad.detach().float())
     n, F = x.shape
     C = t.val.shape[1]
     T = t.anchor.numel()
-    a = _lib.FpwlArgs(x=_lib.ptr(x), n=n, x_stride=x.stride(0), F=F, C=C, off=_lib.ptr(t.off),
-                      anchor=_lib.ptr(t.anchor), val=_lib.ptr(t.val), slope=_lib.ptr(t.slope),
-                      max_pieces=t.max_pieces, features_per_group=t.features_per_group,
-                      max_group_pieces=t.max_group_pieces, sum_features=int(sum_features), out=None, out_stride=0,
-                      flags=_fpwl_flags())
+    a = _fpwl_args(x, t, sum_features)
     mgp = t.max_group_pieces
     rows = _fpwl_rows_applies(n, C, t)                  # several channels, large batch: per-feature bins, lane = channel
     if MOMENTS_FIXED_POINT and n > 0 and (rows or (mgp + 1) // 2 * 8 + mgp * (2 * C + 1 if C > 1 else 2) * 8 <= 150 * 1024):
@@ -392,128 +409,120 @@ def _fpwl_moments(x: torch.Tensor, t, grad: torch.Tensor, sum_features: bool,
         scales = scales[:2]
         if located and len(located) == 1 and not rows:          # one channel: the forward's pieces, one byte per look-up
             a.piece_in = _lib.ptr(located[0])
-        if describe is not None:
-            info = _lib.FpwlMomentsInfo()
-            if rows:
-                _lib.check(_lib.lib().gnan_fpwl_rows_moments_describe(a, grad.stride(0), info), "gnan_fpwl_rows_moments_describe")
-            else:
-                _lib.check(_lib.lib().gnan_fpwl_moments_describe(a, _lib.ptr(grad), grad.stride(0), 1, info), "gnan_fpwl_moments_describe")
-            describe.append(info.as_dict())
         if rows:
+            _described(describe, _lib.FpwlMomentsInfo, "gnan_fpwl_rows_moments_describe", a, grad.stride(0))
             piece, dx = located if (located and len(located) == 2) else _fpwl_locate(x, t, a)    # kept by the forward pass, or located again
             _lib.check(_lib.lib().gnan_fpwl_rows_moments_fixed(a, _lib.ptr(piece), _lib.ptr(dx), _lib.ptr(grad), grad.stride(0),
                                                                _lib.ptr(scales), _lib.ptr(Mi), _lib.stream_of(x)),
                        "gnan_fpwl_rows_moments_fixed")
         else:
+            _described(describe, _lib.FpwlMomentsInfo, "gnan_fpwl_moments_describe", a, _lib.ptr(grad), grad.stride(0), 1)
             _lib.check(_lib.lib().gnan_fpwl_moments_fixed(a, _lib.ptr(grad), grad.stride(0), _lib.ptr(scales), _lib.ptr(Mi),
                                                           _lib.stream_of(x)), "gnan_fpwl_moments_fixed")
         if raw:
             return Mi, scales
         return (Mi.double() / scales.view(1, 2, 1)).float()
-    if describe is not None:
-        info = _lib.FpwlMomentsInfo()
-        _lib.check(_lib.lib().gnan_fpwl_moments_describe(a, _lib.ptr(grad), grad.stride(0), 0, info), "gnan_fpwl_moments_describe")
-        describe.append(info.as_dict())
+    _described(describe, _lib.FpwlMomentsInfo, "gnan_fpwl_moments_describe", a, _lib.ptr(grad), grad.stride(0), 0)
     M = torch.zeros((T, 2, C), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().gnan_fpwl_moments(a, _lib.ptr(grad), grad.stride(0), _lib.ptr(M), _lib.stream_of(x)),
                "gnan_fpwl_moments")
     return M
 
 
+def table_route_applies(n: int, F: int, needs_grad: bool, min_work: Optional[int] = None) -> bool:
+    """Do ``n x F`` look-ups take the table route under ``FMLP_ALGO``?  ``FMLP_PWL`` always, the pinned direct kernels never;
+    AUTO from the thresholds above — ``min_work`` replaces both of them (rho's row table has one of its own and no node gate)."""
+    if FMLP_ALGO != _lib.FMLP_AUTO:
+        return FMLP_ALGO == _lib.FMLP_PWL
+    if min_work is not None:
+        return n * F >= min_work
+    return n * F >= (PWL_MIN_WORK_GRAD if needs_grad else PWL_MIN_WORK) and (needs_grad or n >= PWL_MIN_NODES)
+
+
+def _c_stack(p: StackedMLP) -> StackedMLP:
+    return StackedMLP(*[_c(t) for t in p[:6]], *p[6:])
+
+
+def _check_fit(pending_meta: torch.Tensor, F: int, guess, guard: torch.Tensor, stream) -> None:
+    """``gnan_pwl_check_fit``: ``guard`` is set on the device if the tables behind ``pending_meta`` outgrew ``guess``'s sizes."""
+    _lib.check(_lib.lib().gnan_pwl_check_fit(_lib.ptr(pending_meta), F, int(guess.features_per_group), int(guess.max_pieces),
+                                             int(guess.max_group_pieces), _lib.ptr(guard), stream), "gnan_pwl_check_fit")
+
+
+def _look_up_pending(pending, look_up, stacked: StackedMLP, capturing: bool, stream):
+    """Look up behind a pending build with its speculative sizes, then settle (see :func:`_fmlp_forward`): ``(out, tables,
+    total)``, or None when the tables have more pieces than the look-up kernel supports."""
+    guess = pending.speculative()
+    if capturing:
+        if guess is None:
+            raise _lib.GnanHipError("graph capture needs one eager forward of this model first (table sizes unknown)")
+        res = look_up(guess)
+        CAPTURED_BUILDS.append((guess, stacked))
+        if CAPTURE_GUARD is not None and not getattr(pending, "fit_checked", False):
+            # the step's guard: set on the device if the tables of the weights a REPLAY finds outgrew these sizes — the
+            # captured update is skipped then and the replayer re-runs the step eagerly (graphed.GraphedStep.replay)
+            _check_fit(pending.meta, stacked.F, guess, CAPTURE_GUARD, stream)
+        return res[0], guess, res[1]
+    from .pwl import covers
+    res = None
+    if guess is not None:
+        try:
+            res = look_up(guess)
+        except _lib.GnanHipError:          # a guess the kernel refuses is just a wrong guess
+            res = None
+    tables = pending.resolve()
+    if tables is None:
+        return None
+    if res is None or not covers(guess, tables):
+        res = look_up(tables)
+    return res[0], tables, res[1]
+
+
 def _fmlp_forward(x: torch.Tensor, p: "StackedMLP", sum_features: bool, want_total: bool = False,
                   needs_grad: bool = False, out_dtype=torch.float32, total_rows: Optional[int] = None, prebuilt=None,
-                  located: Optional[list] = None):
+                  located: Optional[list] = None, request: Optional[LookupRequest] = None):
     """Strategy choice: exact table look-up for large batches, matrix-core / lane kernel otherwise.
-    Returns ``(out, tables or None, total or None)``."""
+    Returns ``(out, tables or None, total or None)``.  ``request``: see :class:`LookupRequest`; its outcome is that of the
+    look-up whose rows are returned, and empty when a direct kernel served the call."""
     algo = FMLP_ALGO
     if out_dtype != torch.float32:                      # bf16 operand rows exist only on the table path
         algo = _lib.FMLP_PWL
-    threshold = PWL_MIN_WORK_GRAD if needs_grad else PWL_MIN_WORK
-    if algo == _lib.FMLP_PWL or (algo == _lib.FMLP_AUTO and x.shape[0] * p.F >= threshold
-                                 and (needs_grad or x.shape[0] >= PWL_MIN_NODES)):
-        from .pwl import build_tables, build_tables_lazy, covers, hip_build_applies
-        stacked = StackedMLP(*[_c(t) for t in p[:6]], *p[6:])
+    if algo == _lib.FMLP_PWL or table_route_applies(x.shape[0], p.F, needs_grad):
+        from .pwl import build_tables, build_tables_lazy, hip_build_applies
+        stacked = _c_stack(p)
 
         x_range = _feature_range(x) if p.C == 1 else None
         built = [getattr(prebuilt, "index", None) if prebuilt is not None else None]      # direct-index tables made with the tables
-        request = None if x_range is None else (x_range, INDEX_BUCKETS)
 
         def look_up(t):
-            return _fpwl_launch(x, t, sum_features, want_total=True, out_dtype=out_dtype, total_rows=total_rows,
-                                located=located, x_range=x_range, index=built[0]) \
-                if want_total else (_fpwl_launch(x, t, sum_features, out_dtype=out_dtype, located=located,
-                                                 x_range=x_range, index=built[0]), None)
+            res = _fpwl_launch(x, t, sum_features, want_total, out_dtype, total_rows, located=located, x_range=x_range,
+                               index=built[0], request=request)
+            return res if want_total else (res, None)
 
-        if prebuilt is not None and torch.cuda.is_current_stream_capturing():
-            # a captured inference step (distributed.SharePipeline): the tables sit in caller-owned buffers the PREVIOUS
-            # replay filled; sized like every captured look-up — from the last eager forward's counts — and guarded on the
-            # device (the replayer reads the guard, a tripped loop falls back to eager forwards)
-            guess = prebuilt.speculative()
-            if guess is None:
-                raise _lib.GnanHipError("graph capture needs one eager forward of this model first (table sizes unknown)")
-            res = look_up(guess)
-            CAPTURED_BUILDS.append((guess, stacked))
-            if CAPTURE_GUARD is not None and not getattr(prebuilt, "fit_checked", False):
-                _lib.check(_lib.lib().gnan_pwl_check_fit(_lib.ptr(prebuilt.meta), stacked.F, int(guess.features_per_group),
-                                                         int(guess.max_pieces), int(guess.max_group_pieces),
-                                                         _lib.ptr(CAPTURE_GUARD), _lib.stream_of(x)), "gnan_pwl_check_fit")
-            return res[0], guess, res[1]
+        capturing = torch.cuda.is_current_stream_capturing()
+        pending = prebuilt
         if prebuilt is not None:
-            # tables of THESE weights queued earlier, possibly on another stream (TablePrefetch): wait for that stream's
+            # captured (an inference step of distributed.SharePipeline): the tables sit in caller-owned buffers the PREVIOUS
+            # replay filled; sized like every captured look-up — from the last eager forward's counts — and guarded on the
+            # device (the replayer reads the guard, a tripped loop falls back to eager forwards).
+            # eager: tables of THESE weights queued earlier, possibly on another stream (TablePrefetch): wait for that stream's
             # build on the device, then look up as the speculative path does
-            prebuilt.join(torch.cuda.current_stream(x.device))
-            guess = prebuilt.speculative()
-            res = None
-            if guess is not None:
-                try:
-                    res = look_up(guess)
-                except _lib.GnanHipError:
-                    res = None
-            tables = prebuilt.resolve()
-            if tables is not None:
-                if res is None or not covers(guess, tables):
-                    res = look_up(tables)
-                return res[0], tables, res[1]
-            if algo == _lib.FMLP_PWL:
-                raise _lib.GnanHipError("shape functions need more pieces than the look-up kernel supports")
-            return _fmlp_launch(x, p, sum_features, _lib.FMLP_AUTO), None, None
-        if hip_build_applies(stacked) and torch.cuda.is_current_stream_capturing():
+            if not capturing:
+                prebuilt.join(torch.cuda.current_stream(x.device))
+        elif hip_build_applies(stacked) and (capturing or SPECULATIVE_LOOKUP):
             # hipGraph capture (gnan_amd/graphed.py): no device->host copy may happen here, so the look-up is sized like
             # the speculative one — from the piece counts of the LAST eager forward, with room — and whoever replays the
-            # graph checks before every replay that the tables of the current weights still fit (CAPTURED_BUILDS)
-            pending = build_tables_lazy(stacked, index_request=request)
-            built[0] = pending.index
-            guess = pending.speculative()
-            if guess is None:
-                raise _lib.GnanHipError("graph capture needs one eager forward of this model first (table sizes unknown)")
-            res = look_up(guess)
-            CAPTURED_BUILDS.append((guess, stacked))
-            if CAPTURE_GUARD is not None:
-                # the step's guard: set on the device if the tables of the weights a REPLAY finds outgrew these sizes — the
-                # captured update is skipped then and the replayer re-runs the step eagerly (graphed.GraphedStep.replay)
-                _lib.check(_lib.lib().gnan_pwl_check_fit(_lib.ptr(pending.meta), stacked.F, int(guess.features_per_group),
-                                                         int(guess.max_pieces), int(guess.max_group_pieces),
-                                                         _lib.ptr(CAPTURE_GUARD), _lib.stream_of(x)), "gnan_pwl_check_fit")
-            return res[0], guess, res[1]
-        if SPECULATIVE_LOOKUP and hip_build_applies(stacked) and not torch.cuda.is_current_stream_capturing():
-            # Sizing the look-up needs the tables' piece counts, i.e. a device->host copy between the table build and the
+            # graph checks before every replay that the tables of the current weights still fit (CAPTURED_BUILDS).
+            # eager: Sizing the look-up needs the tables' piece counts, i.e. a device->host copy between the table build and the
             # look-up during which the GPU idles (60-70 us: 1 % of the C4 forward, 6 % of a 1/8 share).  The look-up is
             # queued right behind the build with the sizes of the LAST forward plus some room; the counts are read
             # afterwards (they arrived long before) and the look-up is queued again in the rare case they outgrew the guess.
-            pending = build_tables_lazy(stacked, index_request=request)
+            pending = build_tables_lazy(stacked, index_request=None if x_range is None else (x_range, INDEX_BUCKETS))
             built[0] = pending.index
-            guess = pending.speculative()
-            res = None
-            if guess is not None:
-                try:
-                    res = look_up(guess)
-                except _lib.GnanHipError:          # a guess the kernel refuses is just a wrong guess
-                    res = None
-            tables = pending.resolve()
-            if tables is not None:
-                if res is None or not covers(guess, tables):
-                    res = look_up(tables)
-                return res[0], tables, res[1]
+        if pending is not None:
+            got = _look_up_pending(pending, look_up, stacked, capturing, _lib.stream_of(x))
+            if got is not None:
+                return got
         else:
             tables = build_tables(stacked)
             if tables is not None:
@@ -521,6 +530,8 @@ def _fmlp_forward(x: torch.Tensor, p: "StackedMLP", sum_features: bool, want_tot
                 return out, tables, total
         if algo == _lib.FMLP_PWL:
             raise _lib.GnanHipError("shape functions need more pieces than the look-up kernel supports")
+    if request is not None:
+        request.clear()                                 # (a guess may have been looked up before the tables proved too large)
     return _fmlp_launch(x, p, sum_features, _lib.FMLP_AUTO if algo == _lib.FMLP_PWL else algo), None, None
 
 
@@ -528,8 +539,7 @@ def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int =
     """``gnan_fmlp_fwd`` (``mc``: ``gnan_fmlp_mc_fwd``, the many-channel matrix-core kernel, same record; ``algo`` is not read).
     ``dropout = (p, seed)``: an int travels by value in the record, a seed cell (:func:`_seed_cell_of`) goes to the ``_dev`` twin
     of the same entry point — what a capture may record."""
-    x = x.detach().float()
-    x = _rows(x)
+    x = _rows(x.detach().float())
     n = x.shape[0]
     width = p.C if sum_features else p.F * p.C
     out = torch.empty((n, width), dtype=torch.float32, device=x.device)
@@ -538,18 +548,23 @@ def _fmlp_launch(x: torch.Tensor, p: StackedMLP, sum_features: bool, algo: int =
                       w_first=_lib.ptr(keep[0]), b_first=_lib.ptr(keep[1]), w_mid=_lib.ptr(keep[2]),
                       b_mid=_lib.ptr(keep[3]), w_last=_lib.ptr(keep[4]), b_last=_lib.ptr(keep[5]),
                       sum_features=int(sum_features), out=_lib.ptr(out), out_stride=out.stride(0), algo=algo)
+    _direct_call("gnan_fmlp_mc_fwd" if mc else "gnan_fmlp_fwd", a, dropout, x)
+    return out
+
+
+def _direct_call(entry: str, a, dropout, x: torch.Tensor) -> None:
+    """Queue the direct kernel ``entry`` with its record ``a`` on ``x``'s stream: the workspace ``entry + "_workspace_bytes"``
+    asks for, ``dropout = (p, seed)`` into the record, and the ``_dev`` twin of the entry point when the seed is a device cell."""
     cell = _seed_into(a, dropout)
     lib = _lib.lib()
-    need = lib.gnan_fmlp_mc_fwd_workspace_bytes(a) if mc else lib.gnan_fmlp_fwd_workspace_bytes(a)
+    need = getattr(lib, entry + "_workspace_bytes")(a)
     if need:
         ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)   # packed weights (caching allocator)
         a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    entry = "gnan_fmlp_mc_fwd" if mc else "gnan_fmlp_fwd"
     if cell is not None:
         _lib.check(getattr(lib, entry + "_dev")(a, _lib.ptr(cell), _lib.stream_of(x)), entry + "_dev")
     else:
         _lib.check(getattr(lib, entry)(a, _lib.stream_of(x)), entry)
-    return out
 
 
 def _seed_cell_of(seed) -> Optional[torch.Tensor]:
@@ -583,7 +598,7 @@ class TablePrefetch:
 
     def __init__(self, stacked: StackedMLP):
         from .pwl import hip_build_applies
-        self.stacked = StackedMLP(*[_c(t) for t in stacked[:6]], *stacked[6:])
+        self.stacked = _c_stack(stacked)
         self.applies = hip_build_applies(self.stacked)
         self.side = torch.cuda.Stream(device=self.stacked.w_last.device) if self.applies else None
 
@@ -616,9 +631,7 @@ class TablePrefetch:
             if guard is not None:
                 spec = pending.speculative()
                 if spec is not None:
-                    _lib.check(_lib.lib().gnan_pwl_check_fit(_lib.ptr(pending.meta), F, int(spec.features_per_group),
-                                                             int(spec.max_pieces), int(spec.max_group_pieces),
-                                                             _lib.ptr(guard), _lib.stream_of(guard)), "gnan_pwl_check_fit")
+                    _check_fit(pending.meta, F, spec, guard, _lib.stream_of(guard))
                     pending.fit_checked = True
         pending.owner_stream = self.side
         return pending
@@ -682,9 +695,9 @@ def _fpwl_param_grads_launch(params, t, moments, L, H, C, F, dests=None):
             if total[5] is not None:
                 total[5][:, c0:c1] = got[5]
         return total
-    keep = [None if q is None else q.detach().float().contiguous() for q in params]
+    keep = [_c(q) for q in params]
     outs = _grad_outputs(keep, dests)
-    M = None if fixed else moments.detach().float().contiguous()
+    M = None if fixed else _c(moments)
     a = _lib.FpwlGradArgs(
         off=_lib.ptr(t.off), anchor=_lib.ptr(t.anchor), moments=_lib.ptr(M),
         moments_fixed=_lib.ptr(moments[0]) if fixed else None, scales=_lib.ptr(moments[1]) if fixed else None,
@@ -710,7 +723,7 @@ def _input_grad_applies(tables, L: int, H: int, C: int, x: torch.Tensor) -> bool
 def _piece_dfdx_launch(params, t, L, H, C, F) -> torch.Tensor:
     """``gnan_pwl_piece_dfdx``: ``dfdx [T, C]`` float32, the input derivative of every piece of the stacked tables ``t`` at the
     point the parameter gradients take its masks at (``pwl.piece_derivatives_reference`` restates it)."""
-    keep = [None if q is None else q.detach().float().contiguous() for q in params]
+    keep = [_c(q) for q in params]
     T = t.anchor.numel()
     dfdx = torch.empty((T, C), dtype=torch.float32, device=t.anchor.device)
     a = _lib.PwlDfdxArgs(off=_lib.ptr(t.off), anchor=_lib.ptr(t.anchor), T=T, w_first=_lib.ptr(keep[0]), b_first=_lib.ptr(keep[1]),
@@ -733,10 +746,7 @@ def _fpwl_input_grad(x: torch.Tensor, t, dfdx: torch.Tensor, grad: torch.Tensor,
                                features_per_group=int(t.features_per_group), max_group_pieces=int(t.max_group_pieces),
                                sum_features=int(sum_features), grad=_lib.ptr(grad), grad_stride=grad.stride(0),
                                gx=_lib.ptr(gx), gx_stride=gx.stride(0))
-    if describe is not None:
-        info = _lib.FpwlInputGradInfo()
-        _lib.check(_lib.lib().gnan_fpwl_input_grad_describe(a, info), "gnan_fpwl_input_grad_describe")
-        describe.append(info.as_dict())
+    _described(describe, _lib.FpwlInputGradInfo, "gnan_fpwl_input_grad_describe", a)
     _lib.check(_lib.lib().gnan_fpwl_input_grad(a, _lib.stream_of(x)), "gnan_fpwl_input_grad")
     return gx
 
@@ -757,11 +767,8 @@ def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout
     """``gnan_fmlp_bwd`` (``mfma``: ``gnan_fmlp_bwd_mfma``, the matrix-core kernel of large batches; ``mc``: ``gnan_fmlp_mc_bwd``,
     the many-channel one; same record): gradients of the six stacked parameter tensors (None where a bias is absent), in their
     order.  ``dropout = (p, seed)`` as in :func:`_fmlp_launch`: a seed cell goes to the entry point's ``_dev`` twin."""
-    xd = x.detach().float()
-    xd = _rows(xd)
-    g = grad_out.detach().float()
-    g = _rows(g)
-    keep = [None if t is None else t.detach().float().contiguous() for t in params]
+    xd, g = _rows(x.detach().float()), _rows(grad_out.detach().float())
+    keep = [_c(t) for t in params]
     outs = _grad_outputs(keep, dests)
     w_mid = None if keep[2] is None else keep[2][0]              # [1, F, H, H] -> [F, H, H]   (absent for L == 2)
     d_w_mid = None if outs[2] is None else outs[2][0]
@@ -773,29 +780,22 @@ def _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout
                          grad=_lib.ptr(g), grad_stride=g.stride(0),
                          d_w_first=_lib.ptr(outs[0]), d_b_first=_lib.ptr(outs[1]), d_w_mid=_lib.ptr(d_w_mid),
                          d_b_mid=_lib.ptr(d_b_mid), d_w_last=_lib.ptr(outs[4]), d_b_last=_lib.ptr(outs[5]))
-    cell = _seed_into(a, dropout)
-    lib = _lib.lib()
-    if mc:
-        need = lib.gnan_fmlp_mc_bwd_workspace_bytes(a)
-    else:
-        need = lib.gnan_fmlp_bwd_mfma_workspace_bytes(a) if mfma else lib.gnan_fmlp_bwd_workspace_bytes(a)
-    if need:
-        ws = torch.empty(need // 4, dtype=torch.float32, device=xd.device)
-        a.workspace, a.workspace_bytes = _lib.ptr(ws), need
-    entry = "gnan_fmlp_mc_bwd" if mc else ("gnan_fmlp_bwd_mfma" if mfma else "gnan_fmlp_bwd")
-    if cell is not None:
-        _lib.check(getattr(lib, entry + "_dev")(a, _lib.ptr(cell), _lib.stream_of(xd)), entry + "_dev")
-    else:
-        _lib.check(getattr(lib, entry)(a, _lib.stream_of(xd)), entry)
+    _direct_call("gnan_fmlp_mc_bwd" if mc else ("gnan_fmlp_bwd_mfma" if mfma else "gnan_fmlp_bwd"), a, dropout, xd)
     return outs
 
 
-def _fmlp_eager(x: torch.Tensor, p: StackedMLP, sum_features: bool, dropout: float = 0.0) -> torch.Tensor:
+def _fmlp_eager(x: torch.Tensor, p: StackedMLP, sum_features: bool, dropout: float = 0.0, behind_relu=None) -> torch.Tensor:
     """Batched-GEMM restatement on the device.  Used (a) inside backward passes to obtain parameter gradients
     (recompute + torch autograd on small batches; two probe points per piece on the table path) and (b) as the
     forward while training-mode Dropout is active (``dropout > 0``: ``F.dropout`` after every hidden ReLU,
-    GNAN.py:28,32).  The eval-mode forward never comes here."""
-    drop = (lambda h: torch.nn.functional.dropout(h, dropout, training=True)) if dropout > 0 else (lambda h: h)
+    GNAN.py:28,32).  The eval-mode forward never comes here.  ``behind_relu(h, l)``: what stands behind the ReLU of hidden
+    layer ``l`` instead — the kernels' own Dropout masks (:func:`_kernel_masks`)."""
+    if behind_relu is not None:
+        drop = behind_relu
+    elif dropout > 0:
+        drop = lambda h, l: torch.nn.functional.dropout(h, dropout, training=True)   # noqa: E731
+    else:
+        drop = lambda h, l: h   # noqa: E731
     xt = x.t().unsqueeze(-1)                                            # [F, n, 1]
     if p.L == 1:
         h = xt * p.w_last.unsqueeze(1)                                  # [F, n, C]
@@ -805,12 +805,12 @@ def _fmlp_eager(x: torch.Tensor, p: StackedMLP, sum_features: bool, dropout: flo
         h = xt * p.w_first.unsqueeze(1)
         if p.b_first is not None:
             h = h + p.b_first.unsqueeze(1)
-        h = drop(torch.relu(h))                                         # [F, n, H]
+        h = drop(torch.relu(h), 0)                                      # [F, n, H]
         for l in range(p.L - 2):
             h = torch.bmm(h, p.w_mid[l].transpose(1, 2))
             if p.b_mid is not None:
                 h = h + p.b_mid[l].unsqueeze(1)
-            h = drop(torch.relu(h))
+            h = drop(torch.relu(h), l + 1)
         h = torch.bmm(h, p.w_last.transpose(1, 2))                      # [F, n, C]
         if p.b_last is not None:
             h = h + p.b_last.unsqueeze(1)
@@ -848,7 +848,7 @@ def dropout_mask_window(seed: int, p: float, node_lo: int, n: int, F: int, n_hid
 
 class _MaskRows(torch.autograd.Function):
     """``h * (keep * 1 / (1 - p))`` for ``h [F, rows, H]`` of hidden layer ``layer``, rows = nodes ``node_lo ...``, the keep
-    bits drawn in windows of ``window`` nodes: what ``_fmlp_eager_masked`` multiplies in from the whole mask tensor, element by
+    bits drawn in windows of ``window`` nodes: what ``_kernel_masks`` multiplies in from the whole mask tensor, element by
     element (forward and backward), without ever holding more than a window of it."""
 
     @staticmethod
@@ -873,29 +873,15 @@ class _MaskRows(torch.autograd.Function):
         return (_MaskRows._scaled(grad, ctx.meta),) + (None,) * 6
 
 
-def _fmlp_eager_masked(x: torch.Tensor, p: StackedMLP, sum_features: bool, masks, drop_p: float) -> torch.Tensor:
-    """:func:`_fmlp_eager` with the kernels' Dropout masks (``dropout_masks``): the backward route of shapes
-    ``gnan_fmlp_bwd`` does not cover (deeper / wider than the reference's defaults) under training-mode Dropout."""
-    scale = 1.0 / (1.0 - drop_p)
+def _kernel_masks(masks, drop_p: float, n_hidden: int):
+    """``behind_relu`` of :func:`_fmlp_eager` that multiplies in the kernels' Dropout masks: the backward route of shapes no
+    backward kernel covers (deeper / wider than the reference's defaults) under training-mode Dropout.  ``masks``: the rows'
+    slice of ``dropout_masks``' tensor, or ``(seed, first node, nodes per window)`` — drawn as they are used (_MaskRows)."""
     if torch.is_tensor(masks):
-        drop = lambda h, l: torch.relu(h) * (masks[:, :, l].permute(1, 0, 2).to(h.dtype) * scale)   # noqa: E731
-    else:                               # (seed, first node of x, nodes per window): drawn as they are used (_MaskRows)
-        seed, node_lo, window = masks
-        drop = lambda h, l: _MaskRows.apply(torch.relu(h), seed, drop_p, node_lo, l, p.L - 1, window)   # noqa: E731
-    xt = x.t().unsqueeze(-1)                                            # [F, n, 1]
-    h = xt * p.w_first.unsqueeze(1)
-    if p.b_first is not None:
-        h = h + p.b_first.unsqueeze(1)
-    h = drop(h, 0)
-    for l in range(p.L - 2):
-        h = torch.bmm(h, p.w_mid[l].transpose(1, 2))
-        if p.b_mid is not None:
-            h = h + p.b_mid[l].unsqueeze(1)
-        h = drop(h, l + 1)
-    h = torch.bmm(h, p.w_last.transpose(1, 2))
-    if p.b_last is not None:
-        h = h + p.b_last.unsqueeze(1)
-    return h.sum(0) if sum_features else h.permute(1, 0, 2).reshape(x.shape[0], -1)
+        scale = 1.0 / (1.0 - drop_p)
+        return lambda h, l: h * (masks[:, :, l].permute(1, 0, 2).to(h.dtype) * scale)
+    seed, node_lo, window = masks
+    return lambda h, l: _MaskRows.apply(h, seed, drop_p, node_lo, l, n_hidden, window)
 
 
 # Large batches under Dropout on the matrix cores: the forward asks gnan_fmlp_fwd for GNAN_FMLP_MFMA (its Dropout instances),
@@ -956,6 +942,29 @@ def dropout_mc_routes(n: int, F: int, L: int, H: int, C: int, x_grad: bool = Fal
             bool(backward_on and big and inside and L == 3 and not x_grad))
 
 
+def _lane_backward_applies(L: int, H: int, C: int) -> bool:
+    """The cover of ``gnan_fmlp_bwd`` (and, inside it, of ``gnan_fmlp_bwd_mfma``): parameter gradients only, no ``x.grad``."""
+    return L in (2, 3) and 1 <= H <= 64 and C <= 8
+
+
+DROPOUT_BACKWARD_COVER = ("L in {2, 3}, H <= 64, C <= 8, or L = 3, H <= 64, 9 <= C <= 64 from DROPOUT_MC_MIN_WORK node-features "
+                          "on, and no x.grad")      # what dropout_routes(...)[1] is not None means, for messages
+
+
+def dropout_routes(n: int, F: int, L: int, H: int, C: int, x_grad: bool = False):
+    """``(forward kernel, backward kernel)`` of one :func:`feature_mlps_dropout` call: pure, from the module's switches and
+    thresholds.  Forward: ``"mfma"`` (``gnan_fmlp_fwd`` on the matrix cores, :func:`dropout_mfma_routes`), ``"mc"``
+    (``gnan_fmlp_mc_fwd``, :func:`dropout_mc_routes`), else ``"lane"``.  Backward: inside :func:`_lane_backward_applies` and
+    without ``x.grad`` ``"mfma"`` (``gnan_fmlp_bwd_mfma``) or ``"lane"`` (``gnan_fmlp_bwd``); ``"mc"`` (``gnan_fmlp_mc_bwd``) where
+    :func:`dropout_mc_routes` says so; None anywhere else — the batched restatement with the kernels' masks."""
+    fwd_mfma, bwd_mfma = dropout_mfma_routes(n, F, L, H, C, x_grad)
+    fwd_mc, bwd_mc = dropout_mc_routes(n, F, L, H, C, x_grad)
+    forward = "mfma" if fwd_mfma else ("mc" if fwd_mc else "lane")
+    if _lane_backward_applies(L, H, C) and not x_grad:
+        return forward, ("mfma" if bwd_mfma else "lane")
+    return forward, ("mc" if bwd_mc else None)
+
+
 # Captured steps under Dropout on the DIRECT kernels (full-batch node tasks, CSR-coded graphs, dense graphs past the one-launch
 # routes): the step's owner (graphed.GraphedStep, replay.py) lends the model a seed cell, modules._features hands it to
 # feature_mlps_dropout, and forward and backward run the ``_dev`` twins of the same kernels, which read the seed when they run —
@@ -998,9 +1007,7 @@ def dropout_direct_capture_applies(model, x, g, node_ids=None) -> bool:
             takes = sg.small_graph_applies(x, g, f, rho, pre_rho=use_cnt == "pre")
         if takes:
             return False
-    if f.L in (2, 3) and 1 <= f.H <= 64 and 1 <= f.C <= 8:
-        return True
-    return bool(dropout_mc_routes(n, f.F, f.L, f.H, f.C)[1])
+    return dropout_routes(n, f.F, f.L, f.H, f.C)[1] is not None
 
 
 class _DropoutMLPs(torch.autograd.Function):
@@ -1020,10 +1027,10 @@ class _DropoutMLPs(torch.autograd.Function):
         ctx.meta = (sum_features, float(drop_p), seed, L, H, C, F)
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(x, *[t for t in params if t is not None])
-        mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[0]
-        if not mfma and dropout_mc_routes(x.shape[0], F, L, H, C)[0]:
+        kernel = dropout_routes(x.shape[0], F, L, H, C)[0]
+        if kernel == "mc":
             return _fmlp_launch(x, p, sum_features, dropout=(drop_p, seed), mc=True)
-        return _fmlp_launch(x, p, sum_features, _lib.FMLP_MFMA if mfma else _lib.FMLP_LANE, dropout=(drop_p, seed))
+        return _fmlp_launch(x, p, sum_features, _lib.FMLP_MFMA if kernel == "mfma" else _lib.FMLP_LANE, dropout=(drop_p, seed))
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -1031,44 +1038,26 @@ class _DropoutMLPs(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         x = saved.pop(0)
         params = [saved.pop(0) if present else None for present in ctx.present]
-        if L in (2, 3) and 1 <= H <= 64 and C <= 8 and not ctx.needs_input_grad[0]:
-            mfma = dropout_mfma_routes(x.shape[0], F, L, H, C)[1]
-            pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed), mfma=mfma)
-            return (None,) * 8 + tuple(pg)
-        if dropout_mc_routes(x.shape[0], F, L, H, C, x_grad=ctx.needs_input_grad[0])[1]:
-            pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed), mc=True)
+        n, x_grad = x.shape[0], ctx.needs_input_grad[0]
+        kernel = dropout_routes(n, F, L, H, C, x_grad)[1]
+        if kernel is not None:
+            pg = _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dropout=(drop_p, seed),
+                                       mfma=kernel == "mfma", mc=kernel == "mc")
             return (None,) * 8 + tuple(pg)
         if torch.is_tensor(seed):
             raise RuntimeError("shape functions under Dropout with their seed in a device cell were evaluated where no backward kernel "
-                               "applies (L in {2, 3}, H <= 64, C <= 8, or L = 3, H <= 64, 9 <= C <= 64 from DROPOUT_MC_MIN_WORK "
-                               "node-features on, and no x.grad): the batched restatement draws its masks by value")
-        leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
-        p = StackedMLP(*leaves, L, H, C, F)
-        live = [t for t in leaves if t is not None]
-        grads = [torch.zeros_like(t) for t in live]
-        n = x.shape[0]
-        chunk = max(1, _BWD_CHUNK_ELEMS // max(1, F * max(H, C) * 2))
-        xd = x.detach().float()
-        gx = torch.zeros_like(xd) if ctx.needs_input_grad[0] else None
+                               f"applies ({DROPOUT_BACKWARD_COVER}; dropout_routes({n}, {F}, {L}, {H}, {C}, x_grad={bool(x_grad)}) "
+                               "names none): the batched restatement draws its masks by value")
         per_node = F * (L - 1) * H
         masks = dropout_masks(seed, drop_p, n, F, L - 1, H, x.device) if n * per_node <= DROPOUT_MASK_MAX_ELEMS else None
-        for lo in range(0, n, chunk):
-            xs = xd[lo:lo + chunk]
-            if gx is not None:
-                xs = xs.clone().requires_grad_(True)
-            if masks is not None:
-                mk = masks[lo:lo + chunk]
-            else:                       # (the hash takes the global node index: the chunk's masks come in windows from lo on)
-                mk = (seed, lo, max(1, DROPOUT_MASK_MAX_ELEMS // per_node))
-            with torch.enable_grad():
-                out = _fmlp_eager_masked(xs, p, sum_features, mk, drop_p)
-            got = torch.autograd.grad(out, live + ([xs] if gx is not None else []), grad_out[lo:lo + chunk])
-            for g, d in zip(grads, got):
-                g += d
-            if gx is not None:
-                gx[lo:lo + chunk] = got[-1]
-        it = iter(grads)
-        pg = [next(it) if present else None for present in ctx.present]
+
+        def forward(xs, p, lo):
+            # (without the whole tensor the chunk's masks come in windows from lo on: the hash takes the global node index)
+            mk = masks[lo:lo + xs.shape[0]] if masks is not None else (seed, lo, max(1, DROPOUT_MASK_MAX_ELEMS // per_node))
+            return _fmlp_eager(xs, p, sum_features, behind_relu=_kernel_masks(mk, drop_p, L - 1))
+
+        chunk = max(1, _BWD_CHUNK_ELEMS // max(1, F * max(H, C) * 2))
+        gx, pg = _recompute_grads(x, params, ctx.present, grad_out, (L, H, C, F), x_grad, chunk, forward)
         return (gx, None, None, None, None, None, None, None, *pg)
 
 
@@ -1102,33 +1091,29 @@ def feature_mlps_dropout(x: torch.Tensor, p: StackedMLP, sum_features: bool, dro
 
 class _FeatureMLPs(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, sum_features, want_total, out_dtype, total_rows, L, H, C, F, *params):
+    def forward(ctx, x, sum_features, want_total, out_dtype, total_rows, request, L, H, C, F, *params):
         p = StackedMLP(*params, L, H, C, F)
         ctx.meta = (sum_features, L, H, C, F)
         ctx.save_for_backward(x, *[t for t in params if t is not None])
         ctx.present = [t is not None for t in params]
         ctx.grad_dests = _grad_dests_of(params)
         ctx.set_materialize_grads(False)      # (the non-differentiable column sums would get a zero-filled gradient: a launch)
-        if any(ctx.needs_input_grad[9:]) and not ctx.needs_input_grad[0] and out_dtype != torch.float32:
+        if any(ctx.needs_input_grad[10:]) and not ctx.needs_input_grad[0] and out_dtype != torch.float32:
             raise _lib.GnanHipError("bf16 operand storage is an inference format: no backward pass")
         # parameters or x need a gradient: the training thresholds, and the pieces are kept for the backward pass — x.grad is
         # a look-up in the same tables (_shape_function_grads)
-        needs_grad = (any(ctx.needs_input_grad[9:]) or ctx.needs_input_grad[0]) and out_dtype == torch.float32
+        needs_grad = (any(ctx.needs_input_grad[10:]) or ctx.needs_input_grad[0]) and out_dtype == torch.float32
         if total_rows is not None and not 0 <= total_rows <= x.shape[0]:
             raise ValueError(f"total_rows={total_rows} outside [0, {x.shape[0]}]")
-        fused_total = want_total and total_rows != 0           # 0 rows: the kernel reads that as "all", sum nothing instead
         ctx.located = [] if needs_grad else None
-        out, ctx.tables, total = _fmlp_forward(x, p, sum_features, fused_total, needs_grad, out_dtype, total_rows,
-                                               located=ctx.located)
+        out, ctx.tables, total = _fmlp_forward(x, p, sum_features, want_total and total_rows != 0, needs_grad, out_dtype,
+                                               total_rows, located=ctx.located, request=request)
         # max |x| scales the fixed-point moments of the backward pass; it is looked up here because this is where the
         # caller's own tensor object is in hand (backward sees a fresh unpacked copy of the saved tensor every time)
         ctx.x_abs_max = _abs_max_cached(x) if (needs_grad and ctx.tables is not None and x.numel()) else None
         if not want_total:
             return out
-        if total_rows == 0:
-            total = out.new_zeros(out.shape[1], dtype=torch.float32)
-        if total is None:
-            total = column_sums(out if total_rows is None else out[:total_rows])
+        total = _finish_total(out, total, total_rows)
         ctx.mark_non_differentiable(total)     # d total / d out is accounted for inside the aggregation's backward
         return out, total
 
@@ -1140,16 +1125,62 @@ class _FeatureMLPs(torch.autograd.Function):
         params = [saved.pop(0) if present else None for present in ctx.present]
         located, ctx.located = ctx.located, None
         if grad_out is None:                  # nothing downstream used the values
-            return (None,) * (9 + len(params))
+            return (None,) * (10 + len(params))
         gx, pg = _shape_function_grads(x, params, ctx.present, ctx.tables, grad_out, sum_features, L, H, C, F, ctx.x_abs_max,
                                        located, ctx.needs_input_grad[0], dests=ctx.grad_dests,
-                                       want_param_grads=any(ctx.needs_input_grad[9:]))
-        return (gx, None, None, None, None, None, None, None, None, *pg)
+                                       want_param_grads=any(ctx.needs_input_grad[10:]))
+        return (gx,) + (None,) * 9 + tuple(pg)
+
+
+def _finish_total(out: torch.Tensor, total: Optional[torch.Tensor], total_rows: Optional[int]) -> torch.Tensor:
+    """The column sums a forward with ``want_total`` hands back: the look-up's fused ``total`` where it produced one — it is asked
+    only when ``total_rows != 0``: 0 rows the kernel reads as "all", so nothing is summed instead — else ``gnan_colsum``."""
+    if total_rows == 0:
+        return out.new_zeros(out.shape[1], dtype=torch.float32)
+    if total is None:
+        total = column_sums(out if total_rows is None else out[:total_rows])
+    return total
 
 
 def _grad_dests_of(params):
     """Per stacked parameter tensor: the getter of its direct gradient destination (set by ``FlatMLPStore.stacked``) or None."""
     return [None if t is None else getattr(t, "gnan_grad_dest", None) for t in params]
+
+
+def _probe_param_grads(params, present, tables, M: torch.Tensor, L: int, H: int, C: int, F: int) -> list:
+    """The moments fallback where ``gnan_fpwl_param_grads`` does not apply: exact parameter gradients from two probe points per
+    piece through the tiny batched MLP in float64 (``pwl.parameter_grads_from_moments``), as float32, None where absent."""
+    from .pwl import parameter_grads_from_moments
+    leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
+    got = parameter_grads_from_moments(
+        StackedMLP(*leaves, L, H, C, F), tables, M,
+        lambda U, q: _fmlp_eager(U, StackedMLP(*[None if t is None else t.double() for t in q[:6]], *q[6:]), False))
+    it = iter(got)
+    return [next(it).to(torch.float32) if pr else None for pr in present]
+
+
+def _recompute_grads(x, params, present, grad_out, meta, want_x_grad: bool, chunk: int, forward):
+    """``(d x or None, parameter gradients)`` by recomputing ``forward(x rows, leaves as a StackedMLP, first row)`` — a batched
+    restatement — under torch autograd, ``chunk`` nodes at a time (the restatement materialises ``[F, n, H]`` activations)."""
+    leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
+    p = StackedMLP(*leaves, *meta)
+    live = [t for t in leaves if t is not None]
+    grads = [torch.zeros_like(t) for t in live]
+    xd = x.detach().float()
+    gx = torch.zeros_like(xd) if want_x_grad else None
+    for lo in range(0, x.shape[0], chunk):
+        xs = xd[lo:lo + chunk]
+        if gx is not None:
+            xs = xs.clone().requires_grad_(True)
+        with torch.enable_grad():
+            out = forward(xs, p, lo)
+        got = torch.autograd.grad(out, live + ([xs] if gx is not None else []), grad_out[lo:lo + chunk])
+        for g, d in zip(grads, got):
+            g += d
+        if gx is not None:
+            gx[lo:lo + chunk] = got[-1]
+    it = iter(grads)
+    return gx, [next(it) if pr else None for pr in present]
 
 
 def _shape_function_grads(x, params, present, tables, grad_out, sum_features, L, H, C, F, x_abs_max=None, located=None,
@@ -1166,48 +1197,24 @@ def _shape_function_grads(x, params, present, tables, grad_out, sum_features, L,
             M = _fpwl_moments(x, tables, grad_out, sum_features, x_abs_max, raw=True, located=located)
             pg = _fpwl_param_grads_launch(params, tables, M, L, H, C, F, dests=dests)
         return _table_input_grad(x, params, tables, grad_out, sum_features, L, H, C, F), pg
-    leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
-    p = StackedMLP(*leaves, L, H, C, F)
-    live = [t for t in leaves if t is not None]
     if tables is not None and not want_x_grad:
         # table path: one streaming pass bins the upstream gradient per piece (HIP), then the exact
         # parameter gradients follow from 2 probe points per piece through the tiny batched MLP
-        from .pwl import parameter_grads_from_moments
         if (_table_grads_applies(L, H, C) or _wide_table_grads_applies(L, H, C)) and x.is_cuda:
             # ... exactly, in one kernel: one reverse pass for the value and one for the slope of every non-empty piece
             M = _fpwl_moments(x, tables, grad_out, sum_features, x_abs_max, raw=True, located=located)
             return None, _fpwl_param_grads_launch(params, tables, M, L, H, C, F, dests=dests)
         M = _fpwl_moments(x, tables, grad_out, sum_features, x_abs_max, located=located)
-        got = parameter_grads_from_moments(
-            p, tables, M, lambda U, q: _fmlp_eager(U, StackedMLP(*[None if t is None else t.double()
-                                                                  for t in q[:6]], *q[6:]), False))
-        it = iter(got)
-        pg = [None if not pr else next(it) for pr in present]
-        return None, [None if g is None else g.to(torch.float32) for g in pg]
-    if (HIP_SMALL_BACKWARD and L in (2, 3) and 1 <= H <= 64 and C <= 8 and not want_x_grad and x.is_cuda
+        return None, _probe_param_grads(params, present, tables, M, L, H, C, F)
+    if (HIP_SMALL_BACKWARD and _lane_backward_applies(L, H, C) and not want_x_grad and x.is_cuda
             and 0 < x.shape[0] * F <= HIP_SMALL_BACKWARD_MAX_WORK):
         # small batches (the forward evaluated the MLPs directly): one workgroup per feature recomputes the
         # activations node by node and accumulates every parameter gradient in registers (gnan_fmlp_bwd) — the torch
         # restatement below materialises [F, n, H] activations for the same sums (Cora-shaped: 1 GB per layer)
         return None, _fmlp_backward_launch(x, params, grad_out, sum_features, L, H, C, F, dests=dests)
-    grads = [torch.zeros_like(t) for t in live]
-    n = x.shape[0]
     chunk = max(1, _BWD_CHUNK_ELEMS // max(1, F * max(H, C)))
-    xd = x.detach().float()
-    gx = torch.zeros_like(xd) if want_x_grad else None
-    for lo in range(0, n, chunk):
-        xs = xd[lo:lo + chunk]
-        if gx is not None:
-            xs = xs.clone().requires_grad_(True)
-        with torch.enable_grad():
-            out = _fmlp_eager(xs, p, sum_features)
-        got = torch.autograd.grad(out, live + ([xs] if gx is not None else []), grad_out[lo:lo + chunk])
-        for g, d in zip(grads, got):
-            g += d
-        if gx is not None:
-            gx[lo:lo + chunk] = got[-1]
-    it = iter(grads)
-    return gx, [next(it) if pr else None for pr in present]
+    return _recompute_grads(x, params, present, grad_out, (L, H, C, F), want_x_grad, chunk,
+                            lambda xs, p, lo: _fmlp_eager(xs, p, sum_features))
 
 
 # =============================================================================
@@ -1240,15 +1247,7 @@ def _rho_param_grads(arg: torch.Tensor, dlut: torch.Tensor, tables, params, pres
     if _table_grads_applies(L, H, C) or _wide_table_grads_applies(L, H, C):
         M = _fpwl_moments(x, tables, g, False, x_abs_max, raw=True)
         return tuple(_fpwl_param_grads_launch(params, tables, M, L, H, C, 1))
-    from .pwl import parameter_grads_from_moments
-    M = _fpwl_moments(x, tables, g, False, x_abs_max)
-    leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
-    got = parameter_grads_from_moments(
-        StackedMLP(*leaves, L, H, C, 1), tables, M,
-        lambda U, q: _fmlp_eager(U, StackedMLP(*[None if t is None else t.double() for t in q[:6]], *q[6:]), False))
-    it = iter(got)
-    pg = [None if not pr else next(it) for pr in present]
-    return tuple(None if t is None else t.to(torch.float32) for t in pg)
+    return tuple(_probe_param_grads(params, present, tables, _fpwl_moments(x, tables, g, False, x_abs_max), L, H, C, 1))
 
 
 class _RhoRowLut(torch.autograd.Function):
@@ -1275,10 +1274,9 @@ class _RhoRowLut(torch.autograd.Function):
 
 def _rho_tables(p: StackedMLP, n_lookups: int):
     """rho's piecewise-linear table when the table route applies to ``n_lookups`` (row, hop code) pairs, else None."""
-    if (FMLP_ALGO == _lib.FMLP_PWL or (FMLP_ALGO == _lib.FMLP_AUTO and n_lookups >= PRE_RHO_TABLE_MIN)) \
-            and not torch.cuda.is_current_stream_capturing():
+    if table_route_applies(n_lookups, 1, True, min_work=PRE_RHO_TABLE_MIN) and not torch.cuda.is_current_stream_capturing():
         from .pwl import build_tables
-        return build_tables(StackedMLP(*[_c(t) for t in p[:6]], *p[6:]))
+        return build_tables(_c_stack(p))
     return None
 
 
@@ -1335,29 +1333,20 @@ def feature_mlps(x: torch.Tensor, p: StackedMLP, sum_features: bool, return_tota
     most listed nodes' rows instead of copying the operand (``append_hot_rows``).  ``out`` (inference, table path): rows of a
     caller-owned operand the look-up writes into — the result IS ``out`` when the look-up could use it (same shape and dtype),
     a fresh tensor otherwise (the caller checks ``res is out``)."""
-    global _ROOM_REQUEST, _ROOM_RESULT, _OUT_BUFFER
     if out is not None:
-        _OUT_BUFFER = out
-        try:
-            return _feature_mlps(x, p, sum_features, return_total, out_dtype, total_rows, pad_ok, tables)
-        finally:
-            _OUT_BUFFER = None
+        return _feature_mlps(x, p, sum_features, return_total, out_dtype, total_rows, pad_ok, tables, LookupRequest(out=out))
     if not (room_rows and sum_features):
         return _feature_mlps(x, p, sum_features, return_total, out_dtype, total_rows, pad_ok, tables)
-    _ROOM_REQUEST, _ROOM_RESULT = int(room_rows), None
-    try:
-        res = _feature_mlps(x, p, sum_features, return_total, out_dtype, total_rows, pad_ok, tables)
-    finally:
-        _ROOM_REQUEST = 0
-    out = res[0] if return_total else res
-    if _ROOM_RESULT is not None and _ROOM_RESULT[0] == out.data_ptr() and out.shape[0] + room_rows == _ROOM_RESULT[1].shape[0]:
-        out.gnan_room = _ROOM_RESULT[1]
-    _ROOM_RESULT = None
+    req = LookupRequest(room_rows=room_rows)
+    res = _feature_mlps(x, p, sum_features, return_total, out_dtype, total_rows, pad_ok, tables, req)
+    if req.room is not None:                            # (set only by the look-up whose rows these are)
+        (res[0] if return_total else res).gnan_room = req.room
     return res
 
 
 def _feature_mlps(x: torch.Tensor, p: StackedMLP, sum_features: bool, return_total: bool = False,
-                  out_dtype=torch.float32, total_rows: Optional[int] = None, pad_ok: bool = False, tables=None):
+                  out_dtype=torch.float32, total_rows: Optional[int] = None, pad_ok: bool = False, tables=None,
+                  request: Optional[LookupRequest] = None):
     """``fx[n, k*C + c] = f_k(x[n, k])[c]`` or, with ``sum_features``, ``sum_k f_k(x[n, k])`` — GNAN.py:57-62,157.
     ``return_total`` additionally returns the column sums of the result (the aggregation's rest-bucket operand),
     fused into the look-up kernel where possible.  ``out_dtype=torch.bfloat16`` stores the per-feature rows in bf16
@@ -1373,15 +1362,9 @@ def _feature_mlps(x: torch.Tensor, p: StackedMLP, sum_features: bool, return_tot
     if tables is not None and not (PAD_FEATURES and p.F % PAD_FEATURES and p.C == 1):
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in p[:6]):
             raise _lib.GnanHipError("prefetched tables are an inference feature: run under torch.no_grad()")
-        fused_total = return_total and total_rows != 0
-        out, _, total = _fmlp_forward(x, p, sum_features, fused_total, False, out_dtype, total_rows, prebuilt=tables)
-        if not return_total:
-            return out
-        if total_rows == 0:
-            total = out.new_zeros(out.shape[1], dtype=torch.float32)
-        if total is None:
-            total = column_sums(out if total_rows is None else out[:total_rows])
-        return out, total
+        out, _, total = _fmlp_forward(x, p, sum_features, return_total and total_rows != 0, False, out_dtype, total_rows,
+                                      prebuilt=tables, request=request)
+        return (out, _finish_total(out, total, total_rows)) if return_total else out
     twin = getattr(p.w_last, "gnan_padded", None)           # modules.FlatMLPStore: the padded problem without the concatenations
     if (PAD_FEATURES and p.F % PAD_FEATURES and p.C == 1 and p.L >= 2
             and x.shape[0] * p.F >= (PAD_MIN_WORK_STORE if twin is not None else PAD_MIN_WORK)):
@@ -1392,13 +1375,13 @@ def _feature_mlps(x: torch.Tensor, p: StackedMLP, sum_features: bool, return_tot
         # feature matrix, the stacked weights per call (a few tiny concatenations autograd sees through).
         Fp = (p.F + PAD_FEATURES - 1) // PAD_FEATURES * PAD_FEATURES
         padded = twin if (twin is not None and twin.F == Fp) else _padded_stack(p, Fp)
-        res = _feature_mlps(_padded_x(x, Fp), padded, sum_features, return_total, out_dtype, total_rows)
+        res = _feature_mlps(_padded_x(x, Fp), padded, sum_features, return_total, out_dtype, total_rows, request=request)
         if sum_features or pad_ok:              # [n, C] either way; or the caller takes the zero columns along
             return res
         if return_total:
             return res[0][:, :p.F], res[1][:p.F]
         return res[:, :p.F]
-    return _FeatureMLPs.apply(x, sum_features, return_total, out_dtype, total_rows, p.L, p.H, p.C, p.F,
+    return _FeatureMLPs.apply(x, sum_features, return_total, out_dtype, total_rows, request, p.L, p.H, p.C, p.F,
                               p.w_first, p.b_first, p.w_mid, p.b_mid, p.w_last, p.b_last)
 
 

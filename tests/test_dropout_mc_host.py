@@ -197,3 +197,49 @@ def test_the_routing_predicate_over_the_covers_edges_the_switches_and_the_clamp(
     assert functional.dropout_mfma_routes(n, F, 3, 64, 9, **on) == (False, False)
     assert functional.dropout_mfma_routes(1 << 20, 64, 3, 64, 9) == (False, False)
     assert functional.DROPOUT_MFMA_MIN_WORK == max(1 << 18, functional.DROPOUT_MFMA_CLAMP)
+
+
+def _documented_routes(n, F, L, H, C, x_grad, mfma_fwd, mfma_bwd, mc_fwd, mc_bwd):
+    """The truth table of a Dropout call's kernels, written out from the covers the kernels document: ``gnan_fmlp_fwd`` on the matrix
+    cores 3 <= L <= 4, H <= 64, C <= 8; ``gnan_fmlp_mc_fwd`` the same with 9 <= C <= 64; ``gnan_fmlp_bwd`` L in {2, 3}, H <= 64,
+    C <= 8; ``gnan_fmlp_bwd_mfma`` L = 3 inside that; ``gnan_fmlp_mc_bwd`` L = 3, H <= 64, 9 <= C <= 64; no backward kernel hands out
+    x.grad; the matrix-core kernels start at their thresholds."""
+    work, narrow, wide = n * F, 1 <= C <= 8, 9 <= C <= 64
+    forward = "lane"
+    if L in (3, 4) and 1 <= H <= 64:
+        if narrow and mfma_fwd and work >= functional.DROPOUT_MFMA_MIN_WORK:
+            forward = "mfma"
+        if wide and mc_fwd and work >= functional.DROPOUT_MC_MIN_WORK:
+            forward = "mc"
+    backward = None
+    if not x_grad and 1 <= H <= 64:
+        if narrow and L == 2:
+            backward = "lane"
+        if narrow and L == 3:
+            backward = "mfma" if mfma_bwd and work >= functional.DROPOUT_MFMA_MIN_WORK else "lane"
+        if wide and L == 3 and mc_bwd and work >= functional.DROPOUT_MC_MIN_WORK:
+            backward = "mc"
+    return forward, backward
+
+
+def test_the_combined_route_function_agrees_with_the_documented_truth_table(monkeypatch):
+    F = 4
+    assert functional.DROPOUT_MC_MIN_WORK < functional.DROPOUT_MFMA_MIN_WORK and functional.DROPOUT_MC_MIN_WORK % F == 0
+    sizes = [functional.DROPOUT_MC_MIN_WORK // F - 1, functional.DROPOUT_MC_MIN_WORK // F,
+             functional.DROPOUT_MFMA_MIN_WORK // F - 1, functional.DROPOUT_MFMA_MIN_WORK // F]
+    seen = set()
+    for bits in range(16):
+        switches = [bool(bits >> k & 1) for k in range(4)]
+        for name, on in zip(("DROPOUT_MFMA", "DROPOUT_MFMA_BACKWARD", "DROPOUT_MC", "DROPOUT_MC_BACKWARD"), switches):
+            monkeypatch.setattr(functional, name, on)
+        for L in (1, 2, 3, 4, 5):
+            for H in (1, 64, 65):
+                for C in (1, 8, 9, 64, 65):
+                    for n in sizes:
+                        for x_grad in (False, True):
+                            want = _documented_routes(n, F, L, H, C, x_grad, *switches)
+                            assert functional.dropout_routes(n, F, L, H, C, x_grad) == want, (switches, n, L, H, C, x_grad)
+                            seen.add(want)
+    # the grid reaches every pair the covers allow (C <= 8 and C >= 9 never share a call)
+    assert seen == {("lane", None), ("lane", "lane"), ("lane", "mfma"), ("lane", "mc"), ("mfma", None), ("mfma", "lane"),
+                    ("mfma", "mfma"), ("mc", None), ("mc", "mc")}

@@ -79,12 +79,8 @@ def test_lookup_stores_listed_rows_only_and_hands_out_every_rows_sum(F, parts, m
     with torch.no_grad():
         fx0, tables, tot0 = Fn._fmlp_forward(x, st, False, True)
         buf = torch.full((N, F), float("nan"), device=DEV)
-        req = Fn.SelfRequest(plan.listed, True)
-        monkeypatch.setattr(Fn, "_OUT_BUFFER", buf)
-        monkeypatch.setattr(Fn, "_SELF_REQUEST", req)
-        fx1, _, tot1 = Fn._fmlp_forward(x, st, False, True)
-        monkeypatch.setattr(Fn, "_SELF_REQUEST", None)
-        monkeypatch.setattr(Fn, "_OUT_BUFFER", None)
+        req = Fn.LookupRequest(out=buf, keep=plan.listed, skip_stores=True)
+        fx1, _, tot1 = Fn._fmlp_forward(x, st, False, True, request=req)
     torch.cuda.synchronize()
     assert fx1 is buf and tables is not None and tot0 is not None
     assert req.row_sum is not None and tuple(req.row_sum.shape) == (parts, N)
@@ -111,6 +107,54 @@ def test_lookup_stores_listed_rows_only_and_hands_out_every_rows_sum(F, parts, m
         assert rc == _lib.ERR_UNSUPPORTED, (mode, rc)
         assert bool(torch.isnan(out.float()).all()), mode
         assert _lib.lib().gnan_fpwl_row_sum_parts(a) == 0
+
+
+def test_one_request_reports_the_launch_that_received_it_last(monkeypatch):
+    """One request handed to two look-ups in a row: the first has the feature range and is served by the direct index (row sums,
+    listed rows only), the second has none and is not — its outcome is "no row sums, complete rows", not the first launch's buffer."""
+    from gnan_amd import functional as Fn
+    _lower(monkeypatch)
+    F = 32
+    rowptr, col, code = _csr()
+    plan = _plan(_graph(rowptr, col, code, N, 3))
+    st = _stack(_mlp_state(F, 3, 16, 1, True, seed=F), F, 3, 16, 1, True)
+    x = torch.randn(N, F, generator=torch.Generator().manual_seed(F)).to(DEV)
+    with torch.no_grad():
+        _, tables, _ = Fn._fmlp_forward(x, st, False, True)
+        plain = Fn._fpwl_launch(x, tables, False)
+        buf = torch.full((N, F), float("nan"), device=DEV)
+        req = Fn.LookupRequest(out=buf, keep=plan.listed, skip_stores=True)
+        first = Fn._fpwl_launch(x, tables, False, x_range=Fn._feature_range(x), request=req)
+        served = req.row_sum
+        holes = bool(torch.isnan(buf).any())
+        second = Fn._fpwl_launch(x, tables, False, x_range=None, request=req)
+    torch.cuda.synchronize()
+    assert first is buf and served is not None and tuple(served.shape) == (1, N) and holes
+    assert req.row_sum is None and req.room is None
+    assert second is buf and torch.equal(second.view(torch.int32), plain.view(torch.int32))
+
+
+def test_out_rows_of_the_wrong_shape_are_left_alone(monkeypatch):
+    """``feature_mlps(out=buf)``: rows that do not fit the result are not written and a fresh tensor comes back; rows that fit ARE
+    the result; the next plain call allocates its own rows — nothing of the request outlives its call."""
+    from gnan_amd import _lib
+    from gnan_amd import functional as Fn
+    monkeypatch.setattr(Fn, "FMLP_ALGO", _lib.FMLP_PWL)
+    n, F = 300, 16
+    st = _stack(_mlp_state(F, 3, 16, 1, True, seed=3), F, 3, 16, 1, True)
+    x = torch.randn(n, F, generator=torch.Generator().manual_seed(3)).to(DEV)
+    with torch.no_grad():
+        want = Fn.feature_mlps(x, st, False)
+        wrong = torch.full((n + 1, F), float("nan"), device=DEV)
+        got = Fn.feature_mlps(x, st, False, out=wrong)
+        fits = torch.full((n, F), float("nan"), device=DEV)
+        into = Fn.feature_mlps(x, st, False, out=fits)
+        after = Fn.feature_mlps(x, st, False)
+    torch.cuda.synchronize()
+    assert got.data_ptr() != wrong.data_ptr() and bool(torch.isnan(wrong).all())
+    assert into.data_ptr() == fits.data_ptr() and after.data_ptr() not in (wrong.data_ptr(), fits.data_ptr())
+    for rows in (got, fits, after):
+        assert torch.equal(rows.view(torch.int32), want.view(torch.int32))
 
 
 # ---- the aggregation ----------------------------------------------------------------------------------------------------------------
@@ -206,11 +250,9 @@ def test_route_never_gathers_an_unlisted_row(F, monkeypatch):
     assert aggregate.reference_order_inference_applies(x, st, lut, g)
     with torch.no_grad():
         fx, _, tot = Fn._fmlp_forward(x, st, False, True)
-        buf = torch.full((N, F), float("nan"), device=DEV)
-        monkeypatch.setattr(Fn, "_OUT_BUFFER", buf)                    # the route's operand buffer: NaN where nothing is stored
+        buf = torch.full((N, F), float("nan"), device=DEV)             # the route's operand buffer: NaN where nothing is stored
         marks = []
-        y = aggregate.reference_order_inference(g, x, st, lut, True, mark=lambda: marks.append(1))
-        monkeypatch.setattr(Fn, "_OUT_BUFFER", None)
+        y = aggregate.reference_order_inference(g, x, st, lut, True, mark=lambda: marks.append(1), operand=buf)
         monkeypatch.setattr(aggregate, "SELF_FROM_LOOKUP_SKIP_STORES", False)
         full = aggregate.reference_order_inference(g, x, st, lut, True)
     torch.cuda.synchronize()

@@ -303,3 +303,40 @@ def test_bench_refuses_to_time_fewer_ranks_than_asked():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
+
+
+def test_table_route_applies_at_its_thresholds_and_the_reference_order_flips_with_it(monkeypatch):
+    """AUTO tabulates from ``PWL_MIN_WORK`` look-ups on ``PWL_MIN_NODES`` nodes at inference and from ``PWL_MIN_WORK_GRAD`` when a
+    backward follows; PWL always, a pinned direct kernel never; ``min_work`` is rho's own threshold.  The reference-order training
+    route asks the same function."""
+    from gnan_amd import _lib
+    route = functional.table_route_applies
+    work, grad, nodes = functional.PWL_MIN_WORK, functional.PWL_MIN_WORK_GRAD, functional.PWL_MIN_NODES
+    assert (work, grad, nodes) == (1 << 24, 1 << 18, 1 << 14) and functional.FMLP_ALGO == _lib.FMLP_AUTO
+    assert [route(n, 1, False) for n in (work - 1, work, work + 1)] == [False, True, True]
+    assert [route(n, 1, True) for n in (grad - 1, grad, grad + 1)] == [False, True, True]
+    assert [route(n, work // nodes + 1, False) for n in (nodes - 1, nodes, nodes + 1)] == [False, True, True]
+    assert route(nodes - 1, grad, True)                                    # no node gate when a backward follows
+    assert route(grad // 4, 4, True) and not route(grad // 4 - 1, 4, True) and not route(work // 4 - 1, 4, False)
+    assert [route(n, 1, True, min_work=functional.PRE_RHO_TABLE_MIN) for n in (functional.PRE_RHO_TABLE_MIN - 1,
+                                                                                 functional.PRE_RHO_TABLE_MIN)] == [False, True]
+
+    class NotDense:
+        is_dense = False
+
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)      # (asked last; needs a device)
+
+    def stack(F):
+        w = [torch.zeros(F, 4, requires_grad=True), None, None, None, torch.zeros(F, 1, 4, requires_grad=True), None]
+        return StackedMLP(*w, 2, 4, 1, F)
+
+    def ref_order(n, F=1):
+        return aggregate.reference_order_applies(torch.empty(n, F), stack(F), torch.zeros(3, 1), NotDense())
+
+    assert [ref_order(n) for n in (grad - 1, grad, grad + 1)] == [False, True, True]
+    assert ref_order(grad // 4, 4) and not ref_order(grad // 4 - 1, 4)
+    for algo, want in ((_lib.FMLP_PWL, True), (_lib.FMLP_LANE, False), (_lib.FMLP_MFMA, False)):
+        monkeypatch.setattr(functional, "FMLP_ALGO", algo)
+        assert route(1, 1, False) is want and route(work, nodes, False) is want and route(work, 1, True) is want
+        assert route(1, 1, True, min_work=functional.PRE_RHO_TABLE_MIN) is want
+        assert ref_order(grad - 1) is want and ref_order(grad) is want
