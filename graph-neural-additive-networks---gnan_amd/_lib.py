@@ -557,6 +557,29 @@ class SmallBatchBwdArgs(C.Structure):
     ]
 
 
+class AttrArgs(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.c_void_p), ("rowptr_is64", C.c_int32),
+        ("col", C.c_void_p), ("code", C.c_void_p), ("row_ids", C.c_void_p),
+        ("S", C.c_void_p), ("W", C.c_int32), ("s_stride", C.c_int64),
+        ("lut", C.c_void_p), ("lut_row_stride", C.c_int64), ("D", C.c_int32), ("Cw", C.c_int32),
+        ("cnt", C.c_void_p), ("cnt_stride", C.c_int64), ("s_total", C.c_void_p),
+        ("A", C.c_void_p), ("a_stride", C.c_int64), ("nnz", C.c_int64), ("max_row_pairs", C.c_int64),
+        ("item_ptr", C.c_void_p), ("n_items", C.c_int64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AttrInfo(C.Structure):
+    _fields_ = [
+        ("col_tiles", C.c_int32), ("shell_passes", C.c_int32), ("chunk_pairs", C.c_int32), ("pair_slots", C.c_int32),
+        ("block_size", C.c_int32), ("launches", C.c_int32), ("lds_bytes", C.c_int32), ("max_row_chunks", C.c_int64),
+        ("n_items", C.c_int64), ("workspace_bytes", C.c_size_t),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 _lib: Optional[C.CDLL] = None
 
 # every symbol include/gnan_hip.h declares: (name, restype, argtypes)
@@ -714,6 +737,9 @@ SYMBOLS = {
                                    C.c_void_p]),
     "gnan_dense_to_code": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnan_attr_rows_workspace_bytes": (C.c_size_t, [C.POINTER(AttrArgs)]),
+    "gnan_attr_rows_describe": (C.c_int, [C.POINTER(AttrArgs), C.POINTER(AttrInfo)]),
+    "gnan_attr_rows": (C.c_int, [C.POINTER(AttrArgs), C.c_void_p]),
 }
 
 

@@ -10,7 +10,8 @@ torch so that autograd differentiates it —
   or on the N x D distinct quotients ``u_d / |shell|`` (pre-rho, GNAN.py:65-67), never on N^2 pairs;
 * the per-feature networks run as batched matrix products over chunks of features (GNAN.py:57-62 without the Python loop);
 * the aggregation is one gather of the per-(row, shell) weights and one matrix product (dense inputs), or an ``index_add`` over the
-  listed pairs plus the rest-bucket term (hop-coded CSR inputs).
+  listed pairs plus the rest-bucket term (hop-coded CSR inputs);
+* ``shell_attributions`` keeps that aggregation's terms apart by shell — what ``interpret.explain`` returns for such a module.
 
 Nothing here imports ``oracle/`` (test infrastructure) and nothing under ``tests -m gpu``, ``bench.py``'s timed region or
 ``__graft_entry__.smoke()`` reaches this file.  It is also an independent restatement the HIP kernels can be compared with
@@ -177,6 +178,36 @@ def aggregate(g: HopGraph, S: torch.Tensor, wt: torch.Tensor, rows: Optional[tor
     Y = torch.zeros((g.n_rows, W), dtype=S.dtype).index_add(0, row_of, (w_e - w_rest[row_of]) * gathered)
     Y = Y + w_rest * S.sum(dim=0, keepdim=True)
     return Y if rows is None else Y[rows]
+
+
+def shell_attributions(g: HopGraph, S: torch.Tensor, wt: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                       with_rest: Optional[bool] = None) -> torch.Tensor:
+    """The terms :func:`aggregate` sums, kept apart by shell: ``A[q, d, w] = wt[i_q, d, w % C_rho] * sum of S[j, w] over the
+    nodes j in shell d of row i_q``, ``[n_out, D, W]`` — an ``index_add`` of the gathered rows over (row, shell); the rest shell
+    of a CSR is the column sums minus the listed pairs' rows.  ``A.sum(1)`` is :func:`aggregate`'s row."""
+    D, cw = g.n_codes, wt.shape[-1]
+    W = S.shape[1]
+    if W % cw:
+        raise ValueError("operand width must be a multiple of the weight-channel count")
+    if with_rest is None:
+        with_rest = not g.is_dense
+    ids = torch.arange(g.n_rows) if rows is None else torch.as_tensor(rows, dtype=torch.int64).view(-1)
+    R = ids.numel()
+    if g.is_dense:
+        shell = g.code.long().clamp(max=D - 1)[ids]                           # [R, N]; 255 (unreachable) -> the rest shell
+        slot = (torch.arange(R).unsqueeze(1) * D + shell).reshape(-1)
+        src = torch.arange(g.n_cols).repeat(R)
+    else:
+        rowptr = g.rowptr.long()
+        lo, deg = rowptr[ids], rowptr[ids + 1] - rowptr[ids]
+        q_of = torch.repeat_interleave(torch.arange(R), deg)
+        pair = torch.arange(int(deg.sum())) - torch.repeat_interleave(torch.cumsum(deg, 0) - deg, deg) + lo[q_of]
+        slot = q_of * D + g.code.long()[pair].clamp(max=D - 1)
+        src = g.col.long()[pair]
+    Z = torch.zeros((R * D, W), dtype=S.dtype).index_add_(0, slot, S[src]).view(R, D, W)
+    if with_rest:
+        Z[:, D - 1] = S.sum(dim=0, keepdim=True) - Z[:, : D - 1].sum(dim=1)
+    return wt[ids].repeat(1, 1, W // cw) * Z
 
 
 def _rho_lut(module, g: HopGraph) -> torch.Tensor:

@@ -5,9 +5,14 @@ Everything here is read off the tables the fast path evaluates the model with: `
 rho EXACTLY (they are ReLU MLPs of a scalar, hence piecewise linear: breakpoints, values, slopes), and the curves are
 ``gnan_fpwl_fwd`` look-ups of a grid in those tables — the same kernels, the same numbers the forward pass uses.
 :func:`shape_function_tables` / :func:`rho_table` hand out the tables themselves: the breakpoints are where a plot of f_k
-bends, which a value grid can only approximate.  Device tensors in, device tensors out; no CPU path."""
+bends, which a value grid can only approximate.  Device tensors in, device tensors out; no CPU path.
+
+:func:`explain` goes from the global curves to one prediction: every term ``(feature k, distance d)`` of the sum that IS the
+model's output for a node of a graph (``gnan_attr_rows`` on the HIP path, ``cpu_route.shell_attributions`` for a module that
+lives on the CPU)."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -75,3 +80,77 @@ def contribution_heatmap(model, max_hop: int, value: float = 1.0) -> torch.Tenso
     f = shape_functions(model, torch.tensor([value]))[:, 0]          # [F, C]
     r = rho_curve(model, max_hop)[: max_hop + 1]                     # [D, C_rho]
     return f.unsqueeze(1) * r.unsqueeze(0)
+
+
+# =============================================================================
+# per-prediction explanations: the (feature, distance) terms of rows
+# =============================================================================
+@dataclass
+class Explanation:
+    """The exact decomposition of the outputs of ``rows``: ``by_feature_distance[q, k, d, c]`` is what feature ``k`` of the nodes
+    at hop ``hops[d]`` from node ``rows[q]`` adds to its channel ``c`` (``hops[-1] = inf``: every node beyond the listed hops).
+    ``output[q] = by_feature_distance[q].sum((0, 1))`` — the model's output for the node.  Graph tasks (all rows requested) also
+    carry the sum over the nodes, ``graph_by_feature_distance [F, D, C]``; a NAM read-out on top of it has ``hidden [F]`` (that sum
+    over the distances) and ``readout_by_feature[k] = g_k(hidden[k])``, whose sum over ``k`` is the model's output."""
+    rows: torch.Tensor
+    by_feature_distance: torch.Tensor
+    hops: torch.Tensor
+    output: torch.Tensor
+    graph_by_feature_distance: Optional[torch.Tensor] = None
+    hidden: Optional[torch.Tensor] = None
+    readout_by_feature: Optional[torch.Tensor] = None
+
+
+@torch.no_grad()
+def explain(model, data, rows=None, node_ids=None) -> Explanation:
+    """Attributions of ``model``'s outputs for ``rows`` (``node_ids``: the same, under ``GNAN.forward``'s name; default: every
+    node) on ``data`` — the model in ``eval()`` mode.  A module on the GPU runs ``gnan_attr_rows`` (device inputs only, as the
+    forward); a module that lives on the CPU, called with CPU inputs, runs the plain-torch restatement of ``cpu_route``.
+    The result's bytes grow as ``R * F * D * C``: ``attribution.ATTR_MAX_BYTES`` bounds them, pass ``rows`` in batches beyond."""
+    from . import attribution, cpu_route
+    from .functional import column_sums
+    from .modules import NAM, StandaloneTensorGNAN, TensorGNAN, _GNANCore
+    if model.training:
+        raise _lib.GnanHipError("explain() describes the model in eval() mode (training-mode Dropout has no fixed decomposition)")
+    if rows is None:
+        rows = node_ids
+    x = data if torch.is_tensor(data) else data.x
+    cpu = cpu_route.applies(model, x)
+    if not cpu:
+        _lib.require_device(x)
+    dev = x.device
+    if rows is not None:
+        rows = torch.as_tensor(list(rows) if not torch.is_tensor(rows) else rows).to(device=dev, dtype=torch.int64).view(-1)
+    f = model._stacked("fs", model.fs)
+    fx = cpu_route.shape_functions(x, f, False) if cpu else feature_mlps(x, f, sum_features=False)      # [N, F * C]
+    F, C = x.shape[1], fx.shape[1] // x.shape[1]
+    ids = torch.arange(x.shape[0], device=dev) if rows is None else rows
+    if isinstance(model, NAM):                                                # no graph: one "distance", the node itself
+        bfd = fx.float()[ids].view(-1, F, 1, C).contiguous()
+        return Explanation(ids, bfd, torch.zeros(1, device=dev), bfd.sum(dim=2).sum(dim=1))
+    pre = isinstance(model, StandaloneTensorGNAN) and bool(model.normalize_rho)
+    use_cnt = (not isinstance(model, StandaloneTensorGNAN)) and bool(model.normalize_rho)
+    if cpu:
+        want = True if isinstance(model, _GNANCore) else bool(model.normalize_rho)
+        g = cpu_route.graph_of(model, data, want_norm=want)
+        wt = cpu_route._pre_rho_weights(model, g) if pre else cpu_route.shell_weights(g, cpu_route._rho_lut(model, g), use_cnt)
+        A = cpu_route.shell_attributions(g, fx, wt, rows)
+    else:
+        g = model.hop_graph(data)
+        lut = model._lut_pre_rho(g) if pre else model._lut_global(g)
+        A = attribution.shell_attributions(g, fx, lut, use_cnt, rows, None if g.is_dense else column_sums(fx))
+    D = g.n_codes
+    bfd = A.view(-1, D, F, C).permute(0, 2, 1, 3).contiguous()                # [R, F, D, C]
+    hops = torch.arange(D, dtype=torch.float32, device=dev)
+    hops[D - 1] = float("inf")
+    out = Explanation(ids, bfd, hops, bfd.sum(dim=2).sum(dim=1))
+    if getattr(model, "is_graph_task", False) and rows is None:
+        out.graph_by_feature_distance = bfd.sum(dim=0)                        # [F, D, C]  (framework arithmetic: DESIGN.md section 6)
+        if isinstance(model, TensorGNAN) and model.readout_n_layers > 0:
+            nam = model.readout_nam
+            out.hidden = out.graph_by_feature_distance.sum(dim=1).view(-1)    # [F]  models.py:379
+            h = out.hidden.view(1, -1)
+            gk = cpu_route.shape_functions(h, nam._stacked("fs", nam.fs), False) if cpu \
+                else feature_mlps(h.contiguous(), nam._stacked("fs", nam.fs), sum_features=False)
+            out.readout_by_feature = gk.view(F, -1)                           # [F, out_channels]  models.py:380-381
+    return out

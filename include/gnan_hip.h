@@ -2050,6 +2050,73 @@ typedef struct gnan_shell_counts_blocks_args {
 int gnan_shell_counts_blocks(const gnan_shell_counts_blocks_args* a, gnan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-row attributions (added under ABI 51; csrc/attr_rows.hip, gnan_amd.attribution): the terms gnan_spmm_fwd sums away.
+ * For output row q (adjacency row i = row_ids ? row_ids[q] : q), shell d and operand column w:
+ *
+ *   Z[q, d, w]   = sum of S[col_l, w] over the listed pairs l of row i with min(code_l, D-1) == d            d < D-1
+ *   Z[q, D-1, w] = the same sum over the pairs coded >= D-1                                  (s_total == NULL: dense layouts)
+ *   Z[q, D-1, w] = s_total[w] - sum of S[col_l, w] over the listed pairs with code_l < D-1   (s_total given: a CSR's rest bucket)
+ *   A[q, d, w]   = wt(i, d, w % Cw) * Z[q, d, w],   wt as in gnan_spmm_args (lut, lut_row_stride, cnt)
+ *
+ * so that sum_d A[q, d, w] is what gnan_spmm_fwd returns for column w.  A is [n_rows, D, W] fp32 with a_stride floats between
+ * rows.  Adjacency, row_ids (unordered, may repeat), operand, lut, cnt and s_total follow gnan_spmm_args; S is fp32.  A listed
+ * code >= D-1 counts for the rest shell and never indexes past it.  Cover: 2 <= D <= GNAN_MAX_CODES (GNAN_ERR_UNSUPPORTED
+ * beyond, naming limit and value), any W >= 1, any row length.  Null pointers, a NULL col beside a rowptr, W < 1, Cw not
+ * dividing W and short strides are GNAN_ERR_BAD_ARG, a short workspace GNAN_ERR_WORKSPACE — all before any HIP call.
+ *
+ * Work items: a row is walked in chunks of gnan_attr_info.chunk_pairs pairs, one workgroup per (chunk, tile of 64 columns);
+ * rows of more than one chunk keep raw partial sums in `workspace`, added in chunk order by the second launch.  With
+ * item_ptr == NULL every row gets the chunks of the longest one (max_row_pairs; the dense layout: n_cols).  item_ptr
+ * [n_rows + 1] int32 (device) is the prefix sum of max(1, ceil(pairs of row q / chunk_pairs)) and n_items its last entry:
+ * what to pass when row lengths differ widely.  A row's last chunk always runs to the row's end.  No atomics; a row's bits
+ * do not depend on the launch, on the other rows requested, or on their order.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_attr_args {
+  int64_t n_rows;            /* requested (output) rows */
+  int64_t n_cols;            /* rows of S */
+  const void* rowptr;        /* NULL => dense layout */
+  int32_t rowptr_is64;
+  const int32_t* col;
+  const uint8_t* code;
+  const int32_t* row_ids;    /* optional [n_rows] */
+  const float* S;            /* [n_cols, W] */
+  int32_t W;
+  int64_t s_stride;
+  const float* lut;          /* [D, Cw] or [n_adj_rows, D, Cw] */
+  int64_t lut_row_stride;    /* 0 => one table */
+  int32_t D;
+  int32_t Cw;
+  const int32_t* cnt;        /* optional [n_adj_rows, cnt_stride] */
+  int64_t cnt_stride;
+  const float* s_total;      /* optional [W] */
+  float* A;                  /* [n_rows, D, W] */
+  int64_t a_stride;          /* >= D * W */
+  int64_t nnz;               /* listed pairs (CSR) where known; 0 = unknown */
+  int64_t max_row_pairs;     /* CSR: pairs of the longest requested row (item_ptr == NULL: sizes every row's chunk list) */
+  const int32_t* item_ptr;   /* optional [n_rows + 1] */
+  int64_t n_items;
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_attr_args;
+
+typedef struct gnan_attr_info {
+  int32_t col_tiles;         /* tiles of 64 operand columns */
+  int32_t shell_passes;      /* walks of a chunk: ceil(D / 64) */
+  int32_t chunk_pairs;       /* pairs per work item */
+  int32_t pair_slots;        /* pairs a wave takes per step (W < 64: 64 / next power of two >= W) */
+  int32_t block_size;
+  int32_t launches;
+  int32_t lds_bytes;
+  int64_t max_row_chunks;    /* chunks of the longest row (max_row_pairs, or n_cols for the dense layout) */
+  int64_t n_items;           /* workgroups of the first launch per column tile */
+  size_t workspace_bytes;
+} gnan_attr_info;
+
+size_t gnan_attr_rows_workspace_bytes(const gnan_attr_args* a);
+int gnan_attr_rows_describe(const gnan_attr_args* a, gnan_attr_info* out);
+int gnan_attr_rows(const gnan_attr_args* a, gnan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph hygiene for captured steps (gnan_amd/graphed.py; nothing comparable in the reference, which issues every
  * epoch's launches from Python, trainer.py:23-86).  `graph` is a hipGraph_t obtained by stream capture and not yet
  * instantiated: every memset node is replaced by a kernel node performing the same fill, with the same dependencies
