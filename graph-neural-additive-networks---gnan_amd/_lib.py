@@ -182,6 +182,7 @@ class SpmmArgs(C.Structure):
         ("stream_q_lo", C.c_int64), ("stream_q_hi", C.c_int64), ("stream_chunk", C.c_int32), ("stream_code", C.c_int32),
         ("n_stream_seg", C.c_int32), ("stream_max_chunks_per_class", C.c_int32),
         ("stream_row_seg", C.c_void_p),         # every row's segments in queue order: partial[s] is segment s's float (stream_seg_slot: not read)
+        ("q_hub", C.c_int64),                   # first hub row of a pair stream that ends with the hub rows (0 or stream_q_hi: none)
     ]
 
 

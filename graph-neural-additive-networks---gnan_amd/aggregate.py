@@ -99,6 +99,11 @@ PAIR_STREAM_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs (
 PAIR_STREAM_MIN_PAIRS = 5          # ... rows of this many pairs up to the hub threshold (HopGraph.pair_stream_plan), in place of the
 PAIR_STREAM_BLOCKS = 2             # ... classed rows; ranked blocks of BLOCKED_HUB_BLOCK_BYTES per class, and
 PAIR_STREAM_CHUNK_PAIRS = 32       # ... entries a lane group takes (a multiple of 16); swept on C4: DESIGN.md 4.1
+HUB_STREAM = True              # ... and the hub rows through the same stream: one queue per class to the last row, tried first
+HUB_STREAM_MIN_NNZ = 1 << 24       # ... on graphs of at least this many pairs (its own gate)
+HUB_STREAM_BLOCKS = 4              # ... the hub rows' ranked blocks of BLOCKED_HUB_BLOCK_BYTES per class (the other rows keep PAIR_STREAM_BLOCKS), and
+HUB_STREAM_CHUNK_PAIRS = 32        # ... entries a lane group takes: the route is taken only while this is PAIR_STREAM_CHUNK_PAIRS (one launch, one
+                                   # chunk; another would re-cut the rows in front of the hubs) and PAIR_STREAM is on; swept on C4: DESIGN.md 4.1
 # What spmm_stream_combine_kernel is compiled with (kCombineRows, kCombineCap in csrc/spmm_stream.hip): stated here for the tests, which
 # build plans that meet every shape of its tile walk; not a switch (tests/test_stream_combine_blocks.py holds the two against the source)
 PAIR_STREAM_COMBINE_ROWS = 256     # stream rows per workgroup
@@ -249,17 +254,27 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         # with a rest total, the default hub threshold.  Each plan adds its switch, its size gate and its own terms
         if (scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1 and s_total is not None
                 and S.dtype == torch.float32 and (plan is None or plan.threshold == LONG_ROW_THRESHOLD)):
-            W, lo, rows, hubs = S.shape[1], SHORT_ROW_LMAX + 1, None, None
+            W, lo, rows, hubs, both = S.shape[1], SHORT_ROW_LMAX + 1, None, None, None
             block_rows = max(1, BLOCKED_HUB_BLOCK_BYTES // (W * 4)) if W else 0      # operand rows of one (class, block): one XCD's L2
-            if PAIR_STREAM and g.nnz >= PAIR_STREAM_MIN_NNZ and 32 < W <= 256:      # None for two hop codes: the classed rows then
-                rows = g.pair_stream_plan(max(PAIR_STREAM_MIN_PAIRS, lo), block_rows, PAIR_STREAM_BLOCKS, PAIR_STREAM_CHUNK_PAIRS)
-            if rows is None and CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ:
-                rows = g.classed_row_plan(max(CLASSED_ROWS_MIN_PAIRS, lo))
-            if BLOCKED_HUBS and g.nnz >= BLOCKED_HUBS_MIN_NNZ and plan is not None and plan.n_long > 0:
-                hubs = g.blocked_hub_plan(block_rows, BLOCKED_HUB_BLOCKS, BLOCKED_HUB_SEG_PAIRS)
-            for wide in (rows, hubs):                     # (in this order: the hubs' bind takes the hub rows out of the slice plan)
-                if wide is not None:
-                    wide.bind(a)
+            if (HUB_STREAM and PAIR_STREAM and HUB_STREAM_CHUNK_PAIRS == PAIR_STREAM_CHUNK_PAIRS and g.nnz >= HUB_STREAM_MIN_NNZ
+                    and 32 < W <= 256 and plan is not None and plan.n_long > 0):
+                # one stream to the last row, the hub rows at its end (None for two hop codes or without a stream row: the routes below).
+                # It IS the pair stream, extended: PAIR_STREAM = False switches it off too, and one launch has one chunk — with another
+                # chunk than the pair stream's the rows in front of the hubs would be cut anew and change their bits, so the routes below take such a call
+                both = g.pair_stream_plan(max(PAIR_STREAM_MIN_PAIRS, lo), block_rows, PAIR_STREAM_BLOCKS, HUB_STREAM_CHUNK_PAIRS, None,
+                                          HUB_STREAM_BLOCKS)
+            if both is not None:
+                both.bind(a)                              # (takes the hub rows out of the slice plan; no BlockedHubPlan is built)
+            else:
+                if PAIR_STREAM and g.nnz >= PAIR_STREAM_MIN_NNZ and 32 < W <= 256:      # None for two hop codes: the classed rows then
+                    rows = g.pair_stream_plan(max(PAIR_STREAM_MIN_PAIRS, lo), block_rows, PAIR_STREAM_BLOCKS, PAIR_STREAM_CHUNK_PAIRS)
+                if rows is None and CLASSED_ROWS and g.nnz >= CLASSED_ROWS_MIN_NNZ:
+                    rows = g.classed_row_plan(max(CLASSED_ROWS_MIN_PAIRS, lo))
+                if BLOCKED_HUBS and g.nnz >= BLOCKED_HUBS_MIN_NNZ and plan is not None and plan.n_long > 0:
+                    hubs = g.blocked_hub_plan(block_rows, BLOCKED_HUB_BLOCKS, BLOCKED_HUB_SEG_PAIRS)
+                for wide in (rows, hubs):                     # (in this order: the hubs' bind takes the hub rows out of the slice plan)
+                    if wide is not None:
+                        wide.bind(a)
     need = _lib.lib().gnan_spmm_fwd_workspace_bytes(a)
     ws = None
     if need:

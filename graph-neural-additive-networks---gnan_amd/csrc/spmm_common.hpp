@@ -376,6 +376,9 @@ constexpr int kHotLdsFloats = 16384;   // 64 KB of hot operand rows per workgrou
 // the self_sum route as the classed rows, the blocked hubs and the pair stream need it: short-row runs declared, s_total set
 inline bool self_route_with_tiles(const gnan_spmm_args* a) { return a->self_sum && a->s_total && a->short_lmax > 0; }
 
+// does the pair stream end with hub rows (gnan_spmm_args.q_hub: rows [q_hub, stream_q_hi), a combine pass of their own)?
+inline bool stream_takes_hubs(const gnan_spmm_args* a) { return a->stream_index && a->q_hub > 0 && a->q_hub < a->stream_q_hi; }
+
 inline int validate(const gnan_spmm_args* a) {
   GNAN_REQUIRE(a != nullptr, "spmm: null args");
   GNAN_REQUIRE(a->n_rows >= 0 && a->n_cols >= 0, "spmm: negative size");
@@ -467,7 +470,12 @@ inline int validate(const gnan_spmm_args* a) {
                  a->stream_q_hi <= (a->hub_index ? a->hub_q_lo : a->n_rows) && a->stream_code >= 0 && a->stream_code < 4 && a->D <= 4,
                  "spmm: incomplete pair stream plan (class tables, chunk and slot tables, rows behind the tiled runs and before the hub "
                  "rows, one hop code below 4)");
-  }
+    // the hub rows through the stream: its last rows, in place of a hub-row plan and of the blocked hub segments
+    GNAN_REQUIRE(a->q_hub == 0 || (a->q_hub > a->stream_q_lo && a->q_hub <= a->stream_q_hi),
+                 "spmm: q_hub must be 0 or a row in (stream_q_lo, stream_q_hi] (got %lld)", static_cast<long long>(a->q_hub));
+    GNAN_REQUIRE(!stream_takes_hubs(a) || (a->stream_q_hi == a->n_rows && a->hub_index == nullptr && a->n_long == 0),
+                 "spmm: hub rows in the pair stream need the stream to end at n_rows, no blocked hub segments and no hub-row plan");
+  }   // (q_hub, at the struct's end, is read beside a pair stream only)
   if (a->n_long > 0) {
     GNAN_REQUIRE(a->rowptr != nullptr || (a->n_long == a->n_rows && a->long_threshold == 0),
                  "spmm: a row plan for the dense layout must slice every row (n_long == n_rows, long_threshold == 0)");
@@ -537,7 +545,7 @@ inline Params make_params(const gnan_spmm_args* a) {
     p.seg_q_lo = a->seg_q_lo; p.seg_q_hi = a->seg_q_hi;
     p.seg_partial = static_cast<float*>(a->workspace) + seg_partial_offset(a);
   } else if (a->stream_index) {   // (validate(): no classed row plan beside it) the pair stream's rows: skipped by the row blocks alike
-    p.seg_q_lo = a->stream_q_lo; p.seg_q_hi = a->stream_q_hi;
+    p.seg_q_lo = a->stream_q_lo; p.seg_q_hi = a->stream_q_hi;     // (with hub rows in the stream: to n_rows — tile blocks alone are left)
   }
   p.hub_index = a->hub_index; p.hub_seg_start = a->hub_seg_start; p.hub_seg_row = a->hub_seg_row; p.hub_seg_slot = a->hub_seg_slot;
   p.hub_row_slot_ptr = a->hub_row_slot_ptr; p.hub_cls_seg_ptr = a->hub_cls_seg_ptr;

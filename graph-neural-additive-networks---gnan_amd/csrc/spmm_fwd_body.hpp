@@ -627,6 +627,7 @@ int launch(const gnan_spmm_args* a, bool dense, bool smalld, hipStream_t st) {
                              : (walked + rows_per_block - 1) / rows_per_block + p.n_slice_blocks + p.n_hub_blocks + p.n_seg_blocks +
                                    p.n_tile_blocks;
   if (blocks > 0x7fffffffLL) return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: too many rows for one launch");
+  if (blocks == 0) return GNAN_OK;   // (every row is the pair stream's and no run is tiled: nothing for this kernel, and no empty grid)
   const dim3 grid(static_cast<unsigned>(blocks)), block(256);
   if (p.s_by_code) {
     if constexpr (VEC <= 4 && VEC * LPR <= 32) {  // validate(): fp32 rows of at most 32 columns, CSR layout

@@ -20,6 +20,10 @@
 // block) windows of partial and are issued together, so a line is fetched once (a thread per row walking its own run touched the
 // same lines again many iterations later, after other waves' traffic: 1.9 times the bytes).  Behind a barrier thread i adds its row's
 // floats from the tile in row_seg order, keeping its sum and its place across tiles.  No atomics, nothing between workgroups.
+//
+// The range may run to the last row (gnan_spmm_args.q_hub): a class's queue then ends with the hub rows' pairs, which the stream's kernel
+// takes like any other, and the hub rows — thousands of segments each — get a combine of their own, a wave per row
+// (spmm_stream_hub_combine_kernel below); the combine above takes the rows in front of them.
 #include "spmm_common.hpp"
 
 namespace {
@@ -177,6 +181,48 @@ __global__ __launch_bounds__(256) void spmm_stream_combine_kernel(const Params p
   if (mine) combine_store<true>(p, q, o, y, sp.code);
 }
 
+// combine of the hub rows at the stream's end (gnan_spmm_args.q_hub): stream rows [r_hub, sp.n_rows), a WAVE per row, four rows per
+// workgroup, no barrier, no LDS.  Lane l adds partial[row_seg[s]] for s = s0 + l, s0 + l + 64, ... in that order (a hub row's segments of
+// one (class, block) are consecutive floats of partial and row_seg is read coalesced), the 64 lane sums meet in spmm_hub_combine_kernel's
+// fixed xor butterfly, then combine_store<true> as the rows above.  The longest C4 row owns some 7 000 segments — more than a hundred
+// turns of a lane — so the loads run ahead of the adds: kHubFly gathers in flight per lane, the NEXT batch's row_seg entries requested
+// before this batch's gathers are consumed (one exposed latency per batch, not two), the adds in index order whatever arrives first;
+// and the waves take the rows LAST FIRST (the copy is degree-sorted: the longest rows start at once instead of forming the launch's
+// tail).  One fixed shape per row, decided by the plan alone: bit-reproducible.
+constexpr int kHubFly = 8;
+
+__global__ __launch_bounds__(256) void spmm_stream_hub_combine_kernel(const Params p, const StreamParams sp, const int r_hub) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int k = static_cast<int>(blockIdx.x) * (blockDim.x / kWave) + static_cast<int>(threadIdx.x) / kWave;
+  if (k >= sp.n_rows - r_hub) return;   // (the whole wave)
+  const int r = sp.n_rows - 1 - k;
+  const int s0 = sp.row_slot_ptr[r], s1 = sp.row_slot_ptr[r + 1];    // (the plan: s0 < s1 <= n_seg, a row of the stream owns a segment)
+  float y = 0.f;
+  int sg[kHubFly];
+#pragma unroll
+  for (int u = 0; u < kHubFly; ++u) {   // no branch around a load: an entry past the row's end reads its last entry again, dropped below
+    const int j = s0 + lane + kWave * u;
+    sg[u] = sp.row_seg[j < s1 ? j : s1 - 1];
+  }
+  for (int s = s0 + lane; s < s1; s += kWave * kHubFly) {
+    float v[kHubFly];
+#pragma unroll
+    for (int u = 0; u < kHubFly; ++u) v[u] = sp.partial[sg[u]];
+#pragma unroll
+    for (int u = 0; u < kHubFly; ++u) {
+      const int j = s + kWave * (kHubFly + u);
+      sg[u] = sp.row_seg[j < s1 ? j : s1 - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < kHubFly; ++u) y = s + kWave * u < s1 ? y + v[u] : y;   // (a select: the dropped float may be anything)
+  }
+#pragma unroll
+  for (int off = kWave / 2; off >= 1; off >>= 1) y += __shfl_xor(y, off);
+  if (lane != 0) return;
+  const int64_t q = sp.q_lo + r;
+  combine_store<true>(p, q, out_row(p, q, q), y, sp.code);
+}
+
 StreamParams stream_params(const gnan_spmm_args* a) {
   StreamParams sp;
   sp.S = static_cast<const float*>(a->S); sp.W = a->W; sp.s_stride = a->s_stride;
@@ -214,8 +260,15 @@ int gnan::launch_stream(const gnan_spmm_args* a, int lpr, hipStream_t st) {
 int gnan::launch_stream_combine(const gnan_spmm_args* a, hipStream_t st) {
   if (a->stream_index == nullptr) return GNAN_OK;
   const Params p = make_params(a);
-  const StreamParams sp = stream_params(a);
+  StreamParams sp = stream_params(a);
+  const int n_all = sp.n_rows;
+  if (stream_takes_hubs(a)) sp.n_rows = static_cast<int>(a->q_hub - a->stream_q_lo);   // the rows in front of the hub rows (validate(): >= 1)
   const unsigned nb = static_cast<unsigned>((sp.n_rows + kCombineRows - 1) / kCombineRows);
   hipLaunchKernelGGL(spmm_stream_combine_kernel, dim3(nb), dim3(256), 0, st, p, sp);
-  return gnan::check_launch("spmm_stream_combine_kernel");
+  if (int rc = gnan::check_launch("spmm_stream_combine_kernel")) return rc;
+  if (sp.n_rows == n_all) return GNAN_OK;
+  const int r_hub = sp.n_rows;      // ... and the hub rows [r_hub, n_all) behind them, a wave each
+  sp.n_rows = n_all;
+  hipLaunchKernelGGL(spmm_stream_hub_combine_kernel, dim3(static_cast<unsigned>((n_all - r_hub + 3) / 4)), dim3(256), 0, st, p, sp, r_hub);
+  return gnan::check_launch("spmm_stream_hub_combine_kernel");
 }

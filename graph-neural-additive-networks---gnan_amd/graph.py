@@ -402,12 +402,18 @@ class HopGraph:
                             if wide_plans.holds_packed(self) and self.n_rows > 0 and min(key[:3]) >= 1 else None)
 
     def pair_stream_plan(self, min_pairs: int, block_rows: int, n_blocks: int, chunk_pairs: int,
-                         max_pairs: int = LONG_ROW_THRESHOLD) -> Optional[PairStreamPlan]:
+                         max_pairs: Optional[int] = LONG_ROW_THRESHOLD, hub_blocks: Optional[int] = None) -> Optional[PairStreamPlan]:
         """The pairs of the rows of ``min_pairs .. max_pairs`` listed pairs of a DEGREE-SORTED copy (one range ``[q_lo, q_hi)``) as a
         stream per column class, ordered by popularity block of :meth:`column_blocks`, then by row, and cut into chunks of
         ``chunk_pairs`` entries: :class:`PairStreamPlan`, cached.  ``None`` where no row qualifies, the range's pairs carry more than one hop
-        code (one weight per row, in the combine), ``chunk_pairs`` is no positive multiple of 16, or the packed entries cannot hold the graph."""
-        key = (int(min_pairs), int(block_rows), int(n_blocks), int(chunk_pairs), int(max_pairs))
+        code (one weight per row, in the combine), ``chunk_pairs`` is no positive multiple of 16, or the packed entries cannot hold the graph.
+        ``max_pairs=None``: no upper limit — the range ``[q_lo, n_rows)`` ends with the hub rows ``[plan.q_hub, n_rows)``, whose pairs
+        follow the other rows' in every class's queue under ``hub_blocks`` ranked blocks of their own (default: ``n_blocks``)."""
+        key = (int(min_pairs), int(block_rows), int(n_blocks), int(chunk_pairs), None if max_pairs is None else int(max_pairs))
+        if max_pairs is None:
+            key += (int(n_blocks if hub_blocks is None else hub_blocks),)
+            if key[5] < 1:
+                return None
         return self._cached(("pair_stream", *key), lambda: wide_plans.pair_stream_plan(self, *key)
                             if wide_plans.holds_packed(self, 4) and self.n_rows > 0 and min(key[:4]) >= 1 and key[3] % 16 == 0 else None)
 

@@ -74,6 +74,12 @@ class ClassedRowPlan:
         a.seg_q_lo, a.seg_q_hi, a.n_seg, a.seg_max_per_class = self.q_lo, self.q_hi, self.n_seg, self.max_per_class
 
 
+def drop_slice_plan(a) -> None:
+    """The hub rows leave the slice plan (no slice blocks, no fix-up launch); long_threshold stays: the row blocks leave them out by it."""
+    a.long_rows = a.long_slice_ptr = a.cls_index = a.cls_slice_start = a.cls_slice_row = a.cls_slot_slice = None
+    a.n_long = a.n_slices = a.cls_n_slots = 0
+
+
 @dataclass
 class BlockedHubPlan:
     """:meth:`HopGraph.blocked_hub_plan`: the pairs of the hub rows ``[q_lo, n_rows)`` of a degree-sorted copy as SEGMENTS of at most
@@ -98,9 +104,7 @@ class BlockedHubPlan:
     nbytes = property(_tensor_bytes)
 
     def bind(self, a) -> None:
-        # the hub rows leave the slice plan (no slice blocks, no fix-up launch); long_threshold stays: the row blocks leave them out by it
-        a.long_rows = a.long_slice_ptr = a.cls_index = a.cls_slice_start = a.cls_slice_row = a.cls_slot_slice = None
-        a.n_long = a.n_slices = a.cls_n_slots = 0
+        drop_slice_plan(a)
         a.hub_index, a.hub_seg_start, a.hub_seg_row = _lib.ptr(self.index), _lib.ptr(self.seg_start), _lib.ptr(self.seg_row)
         a.hub_seg_slot, a.hub_row_slot_ptr = _lib.ptr(self.seg_slot), _lib.ptr(self.row_slot_ptr)
         a.hub_cls_seg_ptr, a.hub_q_lo, a.n_hub = _lib.ptr(self.cls_seg_ptr), self.q_lo, self.n_hub
@@ -112,7 +116,11 @@ class PairStreamPlan:
     """:meth:`HopGraph.pair_stream_plan`: the pairs of rows ``[q_lo, q_hi)`` of a degree-sorted copy, all of hop code ``code``, as one
     STREAM per column class ``col & 7``: by popularity block, then by row, cut into chunks of ``chunk_pairs`` entries; a SEGMENT is a
     maximal run of one row inside a chunk and its last entry carries :data:`STREAM_LAST` (``gnan_spmm_args.stream_*`` in
-    include/gnan_hip.h states the layout).  ``seg_slot``, the inverse of ``row_seg``, is computed on demand: the library does not read it."""
+    include/gnan_hip.h states the layout).  ``seg_slot``, the inverse of ``row_seg``, is computed on demand: the library does not read it.
+    A range without an upper limit ends with the hub rows ``[q_hub, q_hi)`` (more than :data:`LONG_ROW_THRESHOLD` pairs; ``q_hub == q_hi``
+    without one): the same stream and a combine of their own (``gnan_spmm_args.q_hub``).  A class's queue then lists the rows in front of
+    the hub rows first, pair for pair as the plan to :data:`LONG_ROW_THRESHOLD` does — those rows keep their segments — and the hub rows'
+    pairs behind them, by ``hub_blocks`` ranked blocks of their own, then by row (``block_pairs``: the first part's blocks, then theirs)."""
     q_lo: int
     q_hi: int
     min_pairs: int
@@ -130,6 +138,9 @@ class PairStreamPlan:
     row_seg: torch.Tensor         # int32 [n_seg] a permutation
     row_slot_ptr: torch.Tensor    # int32 [q_hi - q_lo + 1]
     block_pairs: list             # pairs per block, 0 .. n_blocks (for the record)
+    q_hub: int = 0                # first hub row of the range (0 or q_hi: none)
+    max_hub_segs: int = 0         # segments of the hub row that lists the most (for the record and the tests: the library does not
+                                  # read it — a wave per hub row whatever its length; one device read-back at build time)
 
     @property
     def seg_slot(self) -> torch.Tensor:
@@ -146,6 +157,9 @@ class PairStreamPlan:
         a.stream_row_seg, a.stream_row_slot_ptr = _lib.ptr(self.row_seg), _lib.ptr(self.row_slot_ptr)      # (stream_seg_slot: not read)
         a.stream_q_lo, a.stream_q_hi, a.stream_chunk, a.stream_code = self.q_lo, self.q_hi, self.chunk_pairs, self.code
         a.n_stream_seg, a.stream_max_chunks_per_class = self.n_seg, self.max_chunks_per_class
+        a.q_hub = self.q_hub
+        if 0 < self.q_hub < self.q_hi:     # (the library's own reading of q_hub) the hub rows ride the stream: they leave the slice plan as BlockedHubPlan.bind takes them out
+            drop_slice_plan(a)
 
 
 def holds_packed(g, max_codes: int = 8, int32_pairs: bool = True) -> bool:
@@ -313,12 +327,20 @@ def blocked_hub_plan(g, block_rows: int, n_blocks: int, cap: int, threshold: int
                           cls_ptr.to(torch.int32), block_pairs, torch.bincount(seg_cb % NB, minlength=NB).tolist())
 
 
-def pair_stream_plan(g, min_pairs: int, block_rows: int, n_blocks: int, chunk: int, max_pairs: int) -> Optional[PairStreamPlan]:
+def pair_stream_plan(g, min_pairs: int, block_rows: int, n_blocks: int, chunk: int, max_pairs: Optional[int],
+                     hub_blocks: Optional[int] = None) -> Optional[PairStreamPlan]:
     dev, K, NB = g.device, HUB_CLASSES, n_blocks + 1
     rng = sorted_range(g, "pair_stream_plan", min_pairs, max_pairs)
     if rng is None:
         return None
     deg, q_lo, q_hi, R, e0, e1 = rng
+    if e1 - e0 >= 2 ** 31:                                              # (int32 pair, chunk and segment pointers)
+        return None
+    q_hub = q_hi                                                         # (a range with an upper limit names no hub rows)
+    if max_pairs is None:
+        q_hub = min(max(int(torch.searchsorted(deg, torch.tensor([LONG_ROW_THRESHOLD + 1], device=deg.device))), q_lo), q_hi)
+        if q_hub == q_lo:                                                # (hub rows alone: no row for the first combine)
+            return None
     codes = g.code[e0:e1]
     code = int(codes[0])
     if bool((codes != code).any()):
@@ -326,6 +348,13 @@ def pair_stream_plan(g, min_pairs: int, block_rows: int, n_blocks: int, chunk: i
     c = g.col[e0:e1].long()
     blk = g.column_blocks(block_rows, n_blocks)[c]
     row = rows_of_pairs(deg, q_lo, q_hi)
+    if q_hub < q_hi:
+        # a class's queue: the rows in front of the hub rows FIRST, exactly as the plan to LONG_ROW_THRESHOLD lists them (the same chunk
+        # cuts, hence the same segments and the same bits for those rows), then the hub rows by their own ``hub_blocks`` ranked blocks —
+        # numbered behind the others', so that the one key orders both parts
+        HB = (n_blocks if hub_blocks is None else int(hub_blocks)) + 1
+        blk = torch.where(row >= q_hub - q_lo, NB + g.column_blocks(block_rows, HB - 1)[c], blk)
+        NB += HB
     key = queue_key(c, row, R, blk, NB)                      # class, block, row; the sort keeps a row's pair order
     block_pairs = torch.bincount(blk, minlength=NB).tolist()
     order = torch.argsort(key, stable=True)
@@ -350,8 +379,10 @@ def pair_stream_plan(g, min_pairs: int, block_rows: int, n_blocks: int, chunk: i
     seg_row = row[first]
     row_seg = torch.argsort(seg_row, stable=True)                      # row by row, a row's segments in queue order
     row_slot_ptr = ptr_from_counts(torch.bincount(seg_row, minlength=R))
+    max_hub_segs = int((row_slot_ptr[q_hub - q_lo + 1:] - row_slot_ptr[q_hub - q_lo:-1]).max()) if q_hub < q_hi else 0
     v = v | (last.long() << 31)
     index = signed32(v).to(torch.int32).contiguous()
     return PairStreamPlan(q_lo, q_hi, int(min_pairs), int(block_rows), int(n_blocks), int(chunk), code, n_seg, n_chunks,
                           int(n_chunk_cls.max()), index, cls_pair_ptr.to(torch.int32), cls_chunk_ptr.to(torch.int32),
-                          chunk_first_seg.to(torch.int32), row_seg.to(torch.int32), row_slot_ptr.to(torch.int32), block_pairs)
+                          chunk_first_seg.to(torch.int32), row_seg.to(torch.int32), row_slot_ptr.to(torch.int32), block_pairs,
+                          q_hub, max_hub_segs)

@@ -739,6 +739,13 @@ typedef struct gnan_spmm_args {
   int32_t stream_max_chunks_per_class;
   /* (the struct grew at its end) */
   const int32_t* stream_row_seg;         /* [n_stream_seg] a permutation: every row's segments, in queue order */
+  /* (the struct grew at its end) the hub rows through the pair stream: 0, or a row in (stream_q_lo, stream_q_hi].  Below stream_q_hi it
+   * says that the stream runs to the last row (stream_q_hi == n_rows; hub_index must be NULL and n_long 0) and that its rows
+   * [q_hub, n_rows) are the hub rows, of many segments each: the stream's kernel takes their pairs as every other pair of the queue,
+   * the combine pass above takes the rows [stream_q_lo, q_hub) only, and a second pass takes a hub row per wave — lane l adds
+   * partial[stream_row_seg[s]] for s = first + l, first + l + 64, ... in that order, the 64 lane sums meet in a fixed xor butterfly,
+   * then the folded weight, the rest and self terms as above.  The row blocks of spmm_kernel skip [stream_q_lo, n_rows).  No atomics. */
+  int64_t q_hub;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
