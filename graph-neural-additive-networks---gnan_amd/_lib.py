@@ -183,6 +183,7 @@ class SpmmArgs(C.Structure):
         ("n_stream_seg", C.c_int32), ("stream_max_chunks_per_class", C.c_int32),
         ("stream_row_seg", C.c_void_p),         # every row's segments in queue order: partial[s] is segment s's float (stream_seg_slot: not read)
         ("q_hub", C.c_int64),                   # first hub row of a pair stream that ends with the hub rows (0 or stream_q_hi: none)
+        ("lone_rows", C.c_int32),               # self_sum route: the rows without a pair a thread each (spmm_lone_kernel), out of the tiles
     ]
 
 
@@ -197,12 +198,24 @@ class SpmmLaunchInfo(C.Structure):
         ("row_q0", C.c_int64), ("short_tile", C.c_int32 * (SHORT_LMAX + 1)),
         ("n_seg_blocks", C.c_int32), ("n_segs", C.c_int32), ("n_hub_seg_blocks", C.c_int32), ("n_hub_segs", C.c_int32),
         ("n_stream_blocks", C.c_int32), ("n_stream_segs", C.c_int32),
+        ("n_lone_rows", C.c_int64), ("n_lone_blocks", C.c_int32), ("n_tile_blocks_skipped", C.c_int32),
     ]
 
-    def as_dict(self) -> dict:
-        d = {name: getattr(self, name) for name, _ in self._fields_}
+    LONE_FIELDS = ("n_lone_rows", "n_lone_blocks", "n_tile_blocks_skipped")
+
+    def as_dict(self) -> "LaunchPartition":
+        """spmm_kernel's partition as a dict (two calls that partition alike compare equal, with or without ``self_sum``); what the
+        lone rows' kernel takes beside it (``gnan_spmm_args.lone_rows``) is the attribute ``lone`` of the result."""
+        d = LaunchPartition({name: getattr(self, name) for name, _ in self._fields_ if name not in self.LONE_FIELDS})
         d["short_tile"] = list(self.short_tile)
+        d.lone = {name: getattr(self, name) for name in self.LONE_FIELDS}
         return d
+
+
+class LaunchPartition(dict):
+    """``SpmmLaunchInfo.as_dict()``: the fields of spmm_kernel's grid, and ``lone`` — rows, workgroups and unlaunched tile workgroups
+    of spmm_lone_kernel, all zero off its route."""
+    lone: dict = {}
 
 
 class ClassedPlanArgs(C.Structure):

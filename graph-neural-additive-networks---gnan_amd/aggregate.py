@@ -86,6 +86,7 @@ CLASSED_MIN_ROW_BYTES = 128    # ... from operand rows of this many bytes (fp32 
 CLASSED_MIN_NNZ = 1 << 24      # ... on graphs of at least this many pairs
 SHORT_ROW_TILES = True         # wide forward over a degree-sorted copy: rows of at most SHORT_ROW_LMAX pairs in tiles of many rows per wave
 SHORT_ROW_LMAX = 4             # (gnan_spmm_args.short_*; the library takes them where its kernel variant serves the call)
+LONE_ROWS = True               # reference-order inference (self_sum): the tiled rows that list no pair a thread each (gnan_spmm_args.lone_rows)
 CLASSED_ROWS = True            # reference-order inference (self_sum): the row walk's longer rows a lane group per (row, column class)
 CLASSED_ROWS_MIN_NNZ = 1 << 24     # ... on graphs of at least this many pairs (its own gate: not CLASSED_MIN_NNZ)
 CLASSED_ROWS_MIN_PAIRS = 33        # ... rows of this many pairs up to the hub threshold (HopGraph.classed_row_plan); swept on C4: DESIGN.md 4.1
@@ -250,6 +251,8 @@ def spmm_launch(g: HopGraph, S: torch.Tensor, lut: Optional[torch.Tensor], use_c
         if self_sum.dtype != torch.float32 or self_sum.dim() != 2 or self_sum.shape[1] != n_out or not self_sum.is_contiguous():
             raise ValueError("self_sum must be a contiguous float32 [parts, n_rows] tensor")
         a.self_sum, a.self_parts = _lib.ptr(self_sum), int(self_sum.shape[0])
+        # the rows that list no pair a thread each, out of the tiles (csrc/spmm_lone.hip): same bits, the tile partition as reported
+        a.lone_rows = int(LONE_ROWS and a.short_lmax > 0)
         # what the plans of this route share: the packed degree-sorted copy walked in tiles, fp32 rows, the fused one-channel read-out
         # with a rest total, the default hub threshold.  Each plan adds its switch, its size gate and its own terms
         if (scatter == 2 and a.packed_index and a.short_lmax > 0 and reduce_cr == 1 and s_total is not None

@@ -17,8 +17,8 @@
 //
 // This file: the forward's entry points and routing, the persistent narrow kernel, the hub rows' fix-up, the combine passes of the
 // classed rows and of the blocked hub segments, and the shell sums.
-// spmm_kernel itself is csrc/spmm_fwd_body.hpp (an object per VEC), the pair stream's two kernels are csrc/spmm_stream.hip, the
-// gradients are csrc/spmm_grad.hip, what they share is csrc/spmm_common.hpp.
+// spmm_kernel itself is csrc/spmm_fwd_body.hpp (an object per VEC), the pair stream's two kernels are csrc/spmm_stream.hip, the lone
+// rows' kernel is csrc/spmm_lone.hip, the gradients are csrc/spmm_grad.hip, what they share is csrc/spmm_common.hpp.
 #include "spmm_common.hpp"
 
 namespace {
@@ -518,6 +518,7 @@ extern "C" int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_
   out->n_slice_blocks = p.n_slice_blocks; out->n_tile_blocks = p.n_tile_blocks; out->n_tiles = p.n_tiles;
   out->row_q0 = p.row_q0;
   for (int L = 0; L <= GNAN_SHORT_LMAX; ++L) out->short_tile[L] = p.short_tile[L];
+  out->n_lone_rows = p.lone_n; out->n_lone_blocks = gnan::lone_blocks(p.lone_n); out->n_tile_blocks_skipped = p.n_tile_blocks - lone_tile_blocks(p);
   return GNAN_OK;
 }
 
@@ -538,6 +539,9 @@ extern "C" int gnan_spmm_fwd(const gnan_spmm_args* a, gnan_stream_t stream) {
   const int rc = r.vec == 8 ? gnan::launch_lpr<8>(a, r.lpr, r.dense, r.smalld, st)
                             : (r.vec == 4 ? gnan::launch_lpr<4>(a, r.lpr, r.dense, r.smalld, st) : gnan::launch_lpr<1>(a, r.lpr, r.dense, r.smalld, st));
   if (rc) return rc;
+  if (r.vec == 4 && r.smalld) {      // (validate(): the flag comes with self_sum, which pick_route() admits on this variant only)
+    if (int rc2 = gnan::launch_lone(a, r.lpr, st)) return rc2;      // the lone rows, beside spmm_kernel: disjoint output rows
+  }
   if (int rc2 = launch_fixup(p, st)) return rc2;
   if (int rc2 = launch_hub_combine(p, st)) return rc2;
   if (int rc2 = launch_seg_combine(p, st)) return rc2;

@@ -85,6 +85,13 @@ struct Params {
   float* hub_partial;
   int64_t hub_q_lo;
   int n_hub, n_hub_blocks;
+  // the lone rows a thread each (gnan_spmm_args.lone_rows; set by plan_tiles where run 0 is tiled on the SELF route): rows
+  // [short_row[0], short_row[0] + lone_n) are spmm_lone_kernel's (csrc/spmm_lone.hip) and tile_lo = short_tile[1] is the first tile
+  // that runs.  All three are read on the HOST only: the launch hands spmm_kernel the partition with the tiles numbered from tile_lo
+  // (leave_lone_tiles) — read by the kernel, whether as one argument or three, they cost its SELF instances 12 B of scratch
+  int lone;        // the request
+  int64_t lone_n;
+  int tile_lo;
 };
 
 __device__ __forceinline__ int64_t load_rowptr(const Params& p, int64_t i) {
@@ -332,6 +339,21 @@ __device__ __forceinline__ float dpp_row(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
+// A lane group's butterfly (LPR >= 16 lanes, aligned: whole DPP rows): every lane ends with the sum of the group's values, added in the
+// pairs that __shfl_xor with offsets 1, 2, 4, ... LPR / 2 adds.  After the two quad steps the four lanes of a quad hold one value, so
+// row_half_mirror and row_mirror meet the same two numbers as the xor steps 4 and 8 — same bits, no LDS crossbar for the first four steps.
+template <int LPR>
+__device__ __forceinline__ float group_sum(float r) {
+  static_assert(LPR >= 16, "whole DPP rows");
+  r += dpp_row<0xB1>(r);    // quad_perm [1, 0, 3, 2]: lane ^ 1
+  r += dpp_row<0x4E>(r);    // quad_perm [2, 3, 0, 1]: lane ^ 2
+  r += dpp_row<0x141>(r);   // row_half_mirror: the other quad of the eight
+  r += dpp_row<0x140>(r);   // row_mirror: the other half of the sixteen
+#pragma unroll
+  for (int off = 16; off < LPR; off <<= 1) r += __shfl_xor(r, off);
+  return r;
+}
+
 // Short-row tiles (short_tile, csrc/spmm_fwd_body.hpp): rows of exactly L pairs that one lane group takes at a time
 __host__ __device__ constexpr int short_rows_per_group(int L) { return L == 0 ? 8 : (8 / L > 0 ? 8 / L : 1); }
 
@@ -413,6 +435,7 @@ inline int validate(const gnan_spmm_args* a) {
                        a->self_parts >= 1 && a->hot_rows == 0 && a->shell_out == nullptr))
     return gnan::fail(GNAN_ERR_UNSUPPORTED, "spmm: self_sum is served over a packed degree-sorted copy (scatter_out 2) with a global "
                       "small-D table, fp32 rows and reduce_cr == 1 (self_parts >= 1)");
+  GNAN_REQUIRE(!a->lone_rows || a->self_sum, "spmm: lone_rows (the rows without a pair, a thread each) is served on the self_sum route only");
   if (a->reduce_cr != 0) {
     const int cr = a->reduce_cr;
     if (!(cr == 1 || cr == 2 || cr == 4) || a->W % cr != 0)
@@ -559,6 +582,9 @@ inline Params make_params(const gnan_spmm_args* a) {
   }
   p.n_tile_blocks = p.n_tiles = 0;
   p.row_q0 = 0;
+  p.lone = a->lone_rows != 0 && a->self_sum != nullptr;
+  p.lone_n = 0;
+  p.tile_lo = 0;
   for (int L = 0; L <= GNAN_SHORT_LMAX + 1; ++L) p.short_row[L] = L <= p.short_lmax + 1 && runs ? a->short_row[L] : 0;
   for (int L = 0; L <= GNAN_SHORT_LMAX; ++L) {
     p.short_pair[L] = L <= p.short_lmax && runs ? a->short_pair[L] : 0;
@@ -594,6 +620,11 @@ inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld, int 
     p.n_tiles = static_cast<int>(t);
     p.n_tile_blocks = static_cast<int>((t + 3) / 4);
     p.row_q0 = p.short_row[p.short_lmax + 1];
+    // the lone rows leave the tiles (the partition above is reported as it is; the launch drops run 0's tiles: leave_lone_tiles)
+    if (p.lone && p.self_sum && p.short_row[1] > p.short_row[0]) {
+      p.lone_n = p.short_row[1] - p.short_row[0];
+      p.tile_lo = p.short_tile[1];         // (short_lmax >= 1: run 1's first tile is set)
+    }
   } else {
     p.short_lmax = 0;
   }
@@ -618,6 +649,18 @@ inline int plan_tiles(Params& p, int vec, int lpr, bool dense, bool smalld, int 
   return GNAN_OK;
 }
 
+
+// Tile workgroups of the launch once the lone rows have left (plan_tiles' tile_lo): run 0's tiles are not run, the others keep their
+// order.  lone_tile_blocks: what is launched of n_tile_blocks; leave_lone_tiles: the same partition numbered from tile_lo, for the
+// kernel — short_tile[1] becomes 0, so short_tiles() finds run 1 or a later one for every tile and run 0 is never entered.
+inline int lone_tile_blocks(const Params& p) { return p.tile_lo > 0 ? (p.n_tiles - p.tile_lo + 3) / 4 : p.n_tile_blocks; }
+inline void leave_lone_tiles(Params& p) {
+  if (p.tile_lo <= 0) return;
+  p.n_tile_blocks = lone_tile_blocks(p);
+  p.n_tiles -= p.tile_lo;
+  for (int L = 1; L <= p.short_lmax; ++L) p.short_tile[L] -= p.tile_lo;
+  p.tile_lo = 0;
+}
 
 // The one switch over the lanes per row: f(std::integral_constant<int, LPR>{}) for lpr in {1, 2, ..., 64}.
 template <class F>
@@ -668,4 +711,8 @@ int launch_lpr(const gnan_spmm_args* a, int lpr, bool dense, bool smalld, hipStr
 int stream_blocks(const gnan_spmm_args* a, int lpr);
 int launch_stream(const gnan_spmm_args* a, int lpr, hipStream_t st);
 int launch_stream_combine(const gnan_spmm_args* a, hipStream_t st);
+// The lone rows (gnan_spmm_args.lone_rows; csrc/spmm_lone.hip, an object of its own): a thread per row of run 0, launched beside
+// spmm_kernel — the two write disjoint rows.  Returns at once where plan_tiles names no lone row.
+int launch_lone(const gnan_spmm_args* a, int lpr, hipStream_t st);
+int lone_blocks(int64_t lone_n);      // its workgroups for plan_tiles' lone_n rows
 }  // namespace gnan

@@ -268,6 +268,21 @@ __device__ __forceinline__ void short_tile(const Params& p, int64_t qg, int64_t 
     s[j].zero();
     if (j < nr * L && col_ok) s[j].load(p.S, static_cast<int64_t>(en & kPackMask), p.s_stride, cw);
   }
+  // SELF: what the rows' epilogues read is requested here, once and ahead of the row loop — the lane's columns of s_total (the same for
+  // every row) and, by lane sub < nr, the self term of its row — so that no load is waited for inside the loop.  Not the self terms
+  // of run L = 1: eight gathers in flight and eight rows' weights held — with a ninth value live through the loop the 16-lane instance
+  // (W <= 64) spilled 12 B of scratch at 8 waves/SIMD, wherever the read was placed; that run reads a_i in its row's epilogue
+  constexpr bool kSelfAhead = SELF && L != 1;
+  Vec<VEC> tot_all;
+  float a_self = 0.f;
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) tot_all.v[v] = 0.f;
+  if constexpr (SELF) {
+    if (col_ok && p.s_total) tot_all = load_vec<VEC>(p.s_total + cw);
+  }
+  if constexpr (kSelfAhead) {
+    if (sub < nr) a_self = self_term(p, orow);
+  }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (r >= nr) break;
@@ -286,36 +301,54 @@ __device__ __forceinline__ void short_tile(const Params& p, int64_t qg, int64_t 
     }
     const float w_rest = __shfl(wrv[4 * r / LPR], (4 * r) % LPR, LPR);
     const int64_t o = __shfl(orow, r, LPR);
-    float red[4] = {0.f, 0.f, 0.f, 0.f};
-    if (col_ok) {
-      if (p.s_total) {
-        const Vec<VEC> tot = load_vec<VEC>(p.s_total + cw);
+    if constexpr (SELF) {
+      // (validate(): reduce_cr == 1) one channel sum: the additions of the general epilogue below for that case, in the same order —
+      // the rest term, the lane's columns onto 0.f, the group's butterfly (group_sum: the same pairs), the self term
+      float y = 0.f;
+      if (col_ok) {
+        if (p.s_total) {
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) acc.v[v] = fmaf(w_rest, tot.v[v], acc.v[v]);
+          for (int v = 0; v < VEC; ++v) acc.v[v] = fmaf(w_rest, tot_all.v[v], acc.v[v]);
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y += acc.v[v];
       }
-      if (p.reduce_cr == 0) {
-        store_vec<VEC>(p.Y + o * p.y_stride + cw, acc);
+      y = group_sum<LPR>(y);
+      const float w_self = __shfl(wv[4 * r / LPR], (4 * r) % LPR, LPR);   // row r's folded code-0 weight sits in lane 4 r
+      if constexpr (kSelfAhead) {
+        const float a = __shfl(a_self, r, LPR);
+        if (sub == 0) p.Y[o * p.y_stride] = fmaf(w_self, a, y);
       } else {
+        if (sub == 0) p.Y[o * p.y_stride] = fmaf(w_self, self_term(p, o), y);
+      }
+    } else {
+      float red[4] = {0.f, 0.f, 0.f, 0.f};
+      if (col_ok) {
+        if (p.s_total) {
+          const Vec<VEC> tot = load_vec<VEC>(p.s_total + cw);
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          const int ch = (cw + v) & (p.reduce_cr - 1);  // reduce_cr is a power of two
+          for (int v = 0; v < VEC; ++v) acc.v[v] = fmaf(w_rest, tot.v[v], acc.v[v]);
+        }
+        if (p.reduce_cr == 0) {
+          store_vec<VEC>(p.Y + o * p.y_stride + cw, acc);
+        } else {
 #pragma unroll
-          for (int c = 0; c < 4; ++c) red[c] += ch == c ? acc.v[v] : 0.f;
+          for (int v = 0; v < VEC; ++v) {
+            const int ch = (cw + v) & (p.reduce_cr - 1);  // reduce_cr is a power of two
+#pragma unroll
+            for (int c = 0; c < 4; ++c) red[c] += ch == c ? acc.v[v] : 0.f;
+          }
         }
       }
-    }
-    if (p.reduce_cr) {   // (rows_body's epilogue, for output row o)
+      if (p.reduce_cr) {   // (rows_body's epilogue, for output row o)
 #pragma unroll
-      for (int off = 1; off < LPR; off <<= 1) {
+        for (int off = 1; off < LPR; off <<= 1) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) red[c] += __shfl_xor(red[c], off);
-      }
-      // the self pair's term (gnan_spmm_args.self_sum; validate(): reduce_cr == 1): row r's folded code-0 weight sits in lane 4 r
-      float w_self = 0.f;
-      if constexpr (SELF) w_self = __shfl(wv[4 * r / LPR], (4 * r) % LPR, LPR);
-      if (sub == 0) {
-        if constexpr (SELF) red[0] = fmaf(w_self, self_term(p, o), red[0]);
-        for (int c = 0; c < p.reduce_cr; ++c) p.Y[o * p.y_stride + c] = red[c];
+          for (int c = 0; c < 4; ++c) red[c] += __shfl_xor(red[c], off);
+        }
+        if (sub == 0) {
+          for (int c = 0; c < p.reduce_cr; ++c) p.Y[o * p.y_stride + c] = red[c];
+        }
       }
     }
   }
@@ -360,7 +393,7 @@ __device__ __forceinline__ void short_tiles(const Params& p, int t) {
 // seg_partial[(q - seg_q_lo) * 8 + c]; the combine pass (spmm_seg_combine_kernel, csrc/spmm.hip) adds a row's classes, the rest term
 // and the self term.  Weights as rows_body folds them under SMALLD; 16 index entries per round, four gathers in flight,
 // no branch around a gather: a slot past the segment's end reads the segment's last row again (an L1 hit) and is dropped by a select.
-// No LDS, no barrier, no atomics; the lane butterfly's first four steps are DPP row operations (dpp_row, csrc/spmm_common.hpp).
+// No LDS, no barrier, no atomics; the lane butterfly's first four steps are DPP row operations (group_sum, csrc/spmm_common.hpp).
 
 // HUB: the blocked hub segments (gnan_spmm_args.hub_*) — the same body over the hub plan's arrays; the float goes to the segment's slot
 // of the row-major enumeration, hub_partial[hub_seg_slot[s]] (spmm_hub_combine_kernel, csrc/spmm.hip, adds a row's slots).
@@ -425,12 +458,7 @@ __device__ __forceinline__ void seg_body(const Params& p, const int blk) {
 #pragma unroll
   for (int v = 0; v < VEC; ++v) r += acc.v[v];
   r = col_ok ? r : 0.f;
-  r += dpp_row<0xB1>(r);    // quad_perm [1, 0, 3, 2]: lane ^ 1
-  r += dpp_row<0x4E>(r);    // quad_perm [2, 3, 0, 1]: lane ^ 2
-  r += dpp_row<0x141>(r);   // row_half_mirror: the other quad of the eight (its four lanes hold one value)
-  r += dpp_row<0x140>(r);   // row_mirror: the other half of the sixteen
-#pragma unroll
-  for (int off = 16; off < LPR; off <<= 1) r += __shfl_xor(r, off);
+  r = group_sum<LPR>(r);
   if constexpr (HUB) {
     if (sub == 0) p.hub_partial[p.hub_seg_slot[s]] = r;
   } else {
@@ -619,6 +647,7 @@ int launch(const gnan_spmm_args* a, bool dense, bool smalld, hipStream_t st) {
   const int rows_per_block = 4 * G;
   Params p = make_params(a);
   if (int rc = plan_tiles(p, VEC, LPR, dense, smalld, a->seg_max_per_class, a->hub_seg_max_per_class)) return rc;
+  leave_lone_tiles(p);     // (the lone rows: csrc/spmm_lone.hip)
   const int n_slices = p.n_slices;
   // (the classed rows are taken in segments; so are the rows from hub_q_lo on, n_rows without a blocked hub plan)
   const int64_t walked = p.hub_q_lo - p.row_q0 - (p.seg_q_hi - p.seg_q_lo);

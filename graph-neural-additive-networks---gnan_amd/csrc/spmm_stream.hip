@@ -48,18 +48,7 @@ struct StreamParams {
 
 constexpr unsigned kStreamLast = 1u << 31;
 
-// the lane group's sum of r over its LPR lanes: seg_body's butterfly (four DPP row steps, ds_bpermute above 16 lanes)
-template <int LPR>
-__device__ __forceinline__ float group_sum(float r) {
-  r += dpp_row<0xB1>(r);    // quad_perm [1, 0, 3, 2]: lane ^ 1
-  r += dpp_row<0x4E>(r);    // quad_perm [2, 3, 0, 1]: lane ^ 2
-  r += dpp_row<0x141>(r);   // row_half_mirror: the other quad of the eight (its four lanes hold one value)
-  r += dpp_row<0x140>(r);   // row_mirror: the other half of the sixteen
-#pragma unroll
-  for (int off = 16; off < LPR; off <<= 1) r += __shfl_xor(r, off);
-  return r;
-}
-
+// (the lane group's sum over its LPR lanes: group_sum, csrc/spmm_common.hpp)
 template <int LPR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 void spmm_stream_kernel(const StreamParams p) {

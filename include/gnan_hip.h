@@ -746,6 +746,13 @@ typedef struct gnan_spmm_args {
    * partial[stream_row_seg[s]] for s = first + l, first + l + 64, ... in that order, the 64 lane sums meet in a fixed xor butterfly,
    * then the folded weight, the rest and self terms as above.  The row blocks of spmm_kernel skip [stream_q_lo, n_rows).  No atomics. */
   int64_t q_hub;
+  /* (the struct grew at its end) the lone rows a thread each: on the self_sum route (GNAN_ERR_BAD_ARG without self_sum) the rows of the
+   * short-row run L = 0 — they list no pair, so Y[i] = fmaf(wt(i, 0) - wt(i, D-1), a_i, sum_c wt(i, D-1) s_total[c]) and nothing else —
+   * leave the tiles for a kernel of their own (spmm_lone_kernel, one thread per row) wherever the library takes the runs in tiles at
+   * all; run 0's tiles are not run, and the tile workgroups they filled are not launched (the tiles behind them, four to a workgroup
+   * in their order, close up).  The tile partition gnan_spmm_fwd_describe reports stays what it is without the flag, and so do the
+   * output bits.  0 (the default): off */
+  int32_t lone_rows;
 } gnan_spmm_args;
 
 size_t gnan_spmm_fwd_workspace_bytes(const gnan_spmm_args* a);
@@ -776,6 +783,10 @@ typedef struct gnan_spmm_launch_info {
   int32_t n_hub_segs;            /* blocked hub segments */
   int32_t n_stream_blocks;       /* workgroups of the pair stream's own launch (a multiple of 8); 0: no pair stream */
   int32_t n_stream_segs;         /* pair stream segments */
+  /* (the struct grew at its end) gnan_spmm_args.lone_rows; all zero without the flag and where no run is tiled */
+  int64_t n_lone_rows;           /* rows of run 0 that spmm_lone_kernel takes, a thread each */
+  int32_t n_lone_blocks;         /* its workgroups (256 rows each); 0: no launch */
+  int32_t n_tile_blocks_skipped; /* of n_tile_blocks, the workgroups that are not launched: run 0's short_tile[1] tiles are not run */
 } gnan_spmm_launch_info;
 
 int gnan_spmm_fwd_describe(const gnan_spmm_args* a, gnan_spmm_launch_info* out);
