@@ -594,6 +594,29 @@ class AttrInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class AttrColsArgs(C.Structure):
+    _fields_ = [
+        ("n_cols", C.c_int64), ("n_src", C.c_int64), ("n_rows", C.c_int64), ("rowptr_t", C.c_void_p), ("rowptr_is64", C.c_int32),
+        ("row", C.c_void_p), ("code", C.c_void_p), ("col_ids", C.c_void_p), ("row_ids", C.c_void_p), ("n_row_ids", C.c_int64),
+        ("S", C.c_void_p), ("W", C.c_int32), ("s_stride", C.c_int64),
+        ("lut", C.c_void_p), ("lut_row_stride", C.c_int64), ("D", C.c_int32), ("Cw", C.c_int32),
+        ("cnt", C.c_void_p), ("cnt_stride", C.c_int64), ("rest_from_total", C.c_int32),
+        ("B", C.c_void_p), ("b_stride", C.c_int64), ("nnz", C.c_int64), ("max_col_pairs", C.c_int64),
+        ("item_ptr", C.c_void_p), ("n_items", C.c_int64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AttrColsInfo(C.Structure):
+    _fields_ = [
+        ("chunk_pairs", C.c_int32), ("bin_passes", C.c_int32), ("block_size", C.c_int32), ("items_per_block", C.c_int32),
+        ("launches", C.c_int32), ("lds_bytes", C.c_int32), ("t_block_rows", C.c_int32), ("t_blocks", C.c_int64),
+        ("max_col_chunks", C.c_int64), ("n_items", C.c_int64), ("workspace_bytes", C.c_size_t),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 _lib: Optional[C.CDLL] = None
 
 # every symbol include/gnan_hip.h declares: (name, restype, argtypes)
@@ -754,6 +777,9 @@ SYMBOLS = {
     "gnan_attr_rows_workspace_bytes": (C.c_size_t, [C.POINTER(AttrArgs)]),
     "gnan_attr_rows_describe": (C.c_int, [C.POINTER(AttrArgs), C.POINTER(AttrInfo)]),
     "gnan_attr_rows": (C.c_int, [C.POINTER(AttrArgs), C.c_void_p]),
+    "gnan_attr_cols_workspace_bytes": (C.c_size_t, [C.POINTER(AttrColsArgs)]),
+    "gnan_attr_cols_describe": (C.c_int, [C.POINTER(AttrColsArgs), C.POINTER(AttrColsInfo)]),
+    "gnan_attr_cols": (C.c_int, [C.POINTER(AttrColsArgs), C.c_void_p]),
 }
 
 

@@ -3,7 +3,10 @@
 
 ``A[q, d, w] = wt(i_q, d, w % Cw) * sum of S[j, w] over the nodes j in shell d of row i_q`` and ``A.sum(1)`` is
 ``rho_aggregate``'s row.  Device tensors only; no autograd.  :func:`gnan_amd.interpret.explain`
-is the model-level front."""
+is the model-level front.
+
+By source node (``gnan_attr_cols``, csrc/attr_cols.hip): ``B[p, d, w] = S[j_p, w] * sum over the requested rows i that see node
+j_p at hop d of wt(i, d, w % Cw)`` — :func:`source_attributions`, with :func:`gnan_amd.interpret.explain_sources` in front."""
 from __future__ import annotations
 
 from typing import Optional
@@ -111,3 +114,93 @@ def prepare(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool, rows
     ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=g.device) if need else None
     a.workspace, a.workspace_bytes = _lib.ptr(ws), need
     return Launch(a, A, (g, S, lut, rows, s_total, keep, ws), pairs)
+
+
+# =============================================================================
+# by source node: gnan_attr_cols (csrc/attr_cols.hip)
+# =============================================================================
+def describe_sources(a: _lib.AttrColsArgs) -> dict:
+    """``gnan_attr_cols_describe``: chunk length, bin passes, launches, LDS bytes, blocks of the T sum (host-only)."""
+    info = _lib.AttrColsInfo()
+    _lib.check(_lib.lib().gnan_attr_cols_describe(a, info), "gnan_attr_cols_describe")
+    return info.as_dict()
+
+
+class SourceLaunch(Launch):
+    """One prepared call of ``gnan_attr_cols``; ``pairs``: listed pairs of the requested sources (walked once)."""
+
+    def run(self) -> torch.Tensor:
+        if self.A.shape[0]:
+            _lib.check(_lib.lib().gnan_attr_cols(self.args, _lib.stream_of(self.A)), "gnan_attr_cols")
+        return self.A
+
+
+@torch.no_grad()
+def source_attributions(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool, rows: Optional[torch.Tensor] = None,
+                        cols: Optional[torch.Tensor] = None, rest_from_total: Optional[bool] = None) -> torch.Tensor:
+    """``B [P, D, W]`` float32: what source node ``cols[p]`` (every node by default) adds, at hop ``d``, to column ``w`` of the SUM
+    of the outputs of ``rows`` (every row by default; any order, a row that repeats counts as often as it occurs) —
+    ``B[p, d, w] = S[j_p, w] * sum over the requested rows i that see j_p at hop d of wt(i, d, w % Cw)``.
+
+    ``g`` is the forward graph (its cached transpose is walked); ``S``, ``lut``, ``use_cnt`` as in :func:`shell_attributions`.
+    ``rest_from_total`` (default: ``g`` is a CSR): the rest shell counts every pair NOT listed below ``D - 1`` — the sum of the
+    requested rows' rest weights minus the listed ones.  ``B.sum(0)`` equals ``shell_attributions(...).sum(0)`` for the same rows."""
+    return prepare_sources(g, S, lut, use_cnt, rows, cols, rest_from_total).run()
+
+
+@torch.no_grad()
+def prepare_sources(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool, rows: Optional[torch.Tensor] = None,
+                    cols: Optional[torch.Tensor] = None, rest_from_total: Optional[bool] = None) -> SourceLaunch:
+    """Everything of :func:`source_attributions` but the launches (tools/explain_sources_time.py times ``run`` alone)."""
+    _lib.require_device(S, lut, g.code, rows if torch.is_tensor(rows) else None, cols if torch.is_tensor(cols) else None)
+    if S.dim() != 2 or S.shape[0] != g.n_cols:
+        raise ValueError(f"S must be [n_cols={g.n_cols}, W], got {tuple(S.shape)}")
+    S = _rows(S.detach().float())
+    lut = lut.detach().float().contiguous()
+    if lut.dim() not in (2, 3) or lut.shape[-2] != g.n_codes or (lut.dim() == 3 and lut.shape[0] != g.n_rows):
+        raise ValueError(f"lut must be [D={g.n_codes}, Cw] or [n_rows={g.n_rows}, D, Cw], got {tuple(lut.shape)}")
+    if rest_from_total is None:
+        rest_from_total = not g.is_dense
+    ids = lambda v: torch.as_tensor(v, device=g.device).to(torch.int32).contiguous().view(-1)      # noqa: E731
+    rows = None if rows is None else ids(rows)
+    cols = None if cols is None else ids(cols)
+    P = g.n_cols if cols is None else cols.numel()
+    D, W = g.n_codes, S.shape[1]
+    nbytes = P * D * W * 4
+    if nbytes > ATTR_MAX_BYTES:
+        raise _lib.GnanHipError(f"source_attributions: the result [{P}, {D}, {W}] float32 takes {nbytes} bytes, above ATTR_MAX_BYTES = "
+                                f"{ATTR_MAX_BYTES}: pass `cols` in batches")
+    B = torch.empty((P, D, W), dtype=torch.float32, device=g.device)
+    t = g.transposed()
+    per_row = lut.dim() == 3
+    a = _lib.AttrColsArgs(n_cols=P, n_src=g.n_cols, n_rows=g.n_rows, code=_lib.ptr(t.code), col_ids=_lib.ptr(cols),
+                          row_ids=_lib.ptr(rows), n_row_ids=-1 if rows is None else rows.numel(), S=_lib.ptr(S), W=W,
+                          s_stride=S.stride(0), lut=_lib.ptr(lut), lut_row_stride=D * lut.shape[-1] if per_row else 0, D=D,
+                          Cw=lut.shape[-1], rest_from_total=int(bool(rest_from_total)), B=_lib.ptr(B), b_stride=D * W)
+    if use_cnt:
+        a.cnt, a.cnt_stride = _lib.ptr(g.cnt), g.cnt.stride(0)
+    if not g.is_dense:
+        a.rowptr_t, a.rowptr_is64 = _lib.ptr(t.rowptr), int(t.rowptr.dtype == torch.int64)
+        a.row, a.nnz = _lib.ptr(t.col), g.nnz
+    if P == 0:
+        return SourceLaunch(a, B, (), 0)
+    keep, pairs = None, P * g.n_rows
+    if not g.is_dense:
+        # framework arithmetic on P integers: chunks per requested source, their prefix sum, the longest column
+        chunk = describe_sources(a)["chunk_pairs"]
+        deg = (t.rowptr[1:] - t.rowptr[:-1]).long()
+        if cols is not None:
+            deg = deg[cols.long()]
+        ptr = torch.zeros(P + 1, dtype=torch.int64, device=g.device)
+        torch.cumsum(((deg + (chunk - 1)) // chunk).clamp_(min=1), 0, out=ptr[1:])
+        n_items, longest, pairs = torch.stack([ptr[-1], deg.max(), deg.sum()]).tolist()
+        a.max_col_pairs = longest
+        if n_items > P:
+            if n_items > 0x7fffffff:
+                raise _lib.GnanHipError(f"source_attributions: {n_items} work items exceed one launch: pass `cols` in batches")
+            keep = ptr.to(torch.int32)
+            a.item_ptr, a.n_items = _lib.ptr(keep), n_items
+    need = _lib.lib().gnan_attr_cols_workspace_bytes(a)
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=g.device) if need else None
+    a.workspace, a.workspace_bytes = _lib.ptr(ws), need
+    return SourceLaunch(a, B, (g, t, S, lut, rows, cols, keep, ws), pairs)

@@ -11,7 +11,8 @@ torch so that autograd differentiates it —
 * the per-feature networks run as batched matrix products over chunks of features (GNAN.py:57-62 without the Python loop);
 * the aggregation is one gather of the per-(row, shell) weights and one matrix product (dense inputs), or an ``index_add`` over the
   listed pairs plus the rest-bucket term (hop-coded CSR inputs);
-* ``shell_attributions`` keeps that aggregation's terms apart by shell — what ``interpret.explain`` returns for such a module.
+* ``shell_attributions`` keeps that aggregation's terms apart by shell — what ``interpret.explain`` returns for such a module;
+  ``source_attributions`` keeps them apart by source node and shell (``interpret.explain_sources``).
 
 Nothing here imports ``oracle/`` (test infrastructure) and nothing under ``tests -m gpu``, ``bench.py``'s timed region or
 ``__graft_entry__.smoke()`` reaches this file.  It is also an independent restatement the HIP kernels can be compared with
@@ -208,6 +209,42 @@ def shell_attributions(g: HopGraph, S: torch.Tensor, wt: torch.Tensor, rows: Opt
     if with_rest:
         Z[:, D - 1] = S.sum(dim=0, keepdim=True) - Z[:, : D - 1].sum(dim=1)
     return wt[ids].repeat(1, 1, W // cw) * Z
+
+
+def source_attributions(g: HopGraph, S: torch.Tensor, wt: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                        cols: Optional[torch.Tensor] = None, with_rest: Optional[bool] = None) -> torch.Tensor:
+    """The terms :func:`aggregate` sums over the requested rows, kept apart by SOURCE node and shell: ``B[p, d, w] = S[j_p, w] *
+    sum over the requested rows i that see j_p in shell d of wt[i, d, w % C_rho]``, ``[n_sources, D, W]``.  A row that repeats in
+    ``rows`` counts as often as it occurs.  ``with_rest`` (default: a CSR): the rest shell is every pair not listed below ``D - 1``
+    — the requested rows' rest weights summed, minus the listed pairs' (SURVEY.md A.4).  ``B.sum(0)`` is
+    ``shell_attributions(...).sum(0)``."""
+    D, cw = g.n_codes, wt.shape[-1]
+    W = S.shape[1]
+    if W % cw:
+        raise ValueError("operand width must be a multiple of the weight-channel count")
+    if with_rest is None:
+        with_rest = not g.is_dense
+    ids = torch.arange(g.n_rows) if rows is None else torch.as_tensor(rows, dtype=torch.int64).view(-1)
+    src = torch.arange(g.n_cols) if cols is None else torch.as_tensor(cols, dtype=torch.int64).view(-1)
+    mult = torch.bincount(ids, minlength=g.n_rows).to(wt.dtype)               # how often a row is requested
+    if g.is_dense:
+        row_of = torch.arange(g.n_rows).repeat_interleave(g.n_cols)
+        col = torch.arange(g.n_cols).repeat(g.n_rows)
+        code = g.code.long().reshape(-1)
+    else:
+        rowptr = g.rowptr.long()
+        row_of = torch.repeat_interleave(torch.arange(g.n_rows), rowptr[1:] - rowptr[:-1])
+        col, code = g.col.long(), g.code.long()
+    keep = mult[row_of] > 0
+    if with_rest:
+        keep = keep & (code < D - 1)                                          # pairs coded past the cover count through T
+    row_of, col, shell = row_of[keep], col[keep], code[keep].clamp(max=D - 1)
+    m = mult[row_of].unsqueeze(-1)
+    V = torch.zeros((g.n_cols * D, cw), dtype=wt.dtype).index_add_(0, col * D + shell, m * wt[row_of, shell]).view(g.n_cols, D, cw)
+    if with_rest:
+        listed = torch.zeros((g.n_cols, cw), dtype=wt.dtype).index_add_(0, col, m * wt[row_of, D - 1])
+        V[:, D - 1] = (mult.unsqueeze(-1) * wt[:, D - 1]).sum(dim=0, keepdim=True) - listed
+    return V[src].repeat(1, 1, W // cw) * S[src].unsqueeze(1)
 
 
 def _rho_lut(module, g: HopGraph) -> torch.Tensor:

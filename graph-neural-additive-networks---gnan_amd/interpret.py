@@ -9,7 +9,8 @@ bends, which a value grid can only approximate.  Device tensors in, device tenso
 
 :func:`explain` goes from the global curves to one prediction: every term ``(feature k, distance d)`` of the sum that IS the
 model's output for a node of a graph (``gnan_attr_rows`` on the HIP path, ``cpu_route.shell_attributions`` for a module that
-lives on the CPU)."""
+lives on the CPU).  :func:`explain_sources` turns the same sum by SOURCE node: what every node of the graph adds to the outputs asked
+for (``gnan_attr_cols`` / ``cpu_route.source_attributions``)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -153,4 +154,76 @@ def explain(model, data, rows=None, node_ids=None) -> Explanation:
             gk = cpu_route.shape_functions(h, nam._stacked("fs", nam.fs), False) if cpu \
                 else feature_mlps(h.contiguous(), nam._stacked("fs", nam.fs), sum_features=False)
             out.readout_by_feature = gk.view(F, -1)                           # [F, out_channels]  models.py:380-381
+    return out
+
+
+# =============================================================================
+# per-prediction explanations by source node: "which nodes does the prediction come from"
+# =============================================================================
+@dataclass
+class SourceExplanation:
+    """The outputs of ``rows``, summed, decomposed by SOURCE node: ``by_feature_distance[p, k, d, c]`` is what feature ``k`` of node
+    ``sources[p]`` adds to channel ``c`` of those outputs from hop ``hops[d]`` (the hop at which the row sees the node;
+    ``hops[-1] = inf``: the rows that do not list it).  A row that repeats in ``rows`` counts as often as it occurs.
+    ``by_node[p] = by_feature_distance[p].sum((0, 1))``; over all sources it sums to the sum of the rows' outputs — a graph task's
+    output before a read-out.  ``hidden_by_node [P, F]`` (graph task with a NAM read-out, all rows requested): each node's share of
+    ``Explanation.hidden``."""
+    sources: torch.Tensor
+    rows: torch.Tensor
+    hops: torch.Tensor
+    by_feature_distance: torch.Tensor
+    by_node: torch.Tensor
+    hidden_by_node: Optional[torch.Tensor] = None
+
+
+@torch.no_grad()
+def explain_sources(model, data, rows=None, node_ids=None, sources=None) -> SourceExplanation:
+    """Attributions of ``model``'s outputs for ``rows`` (``node_ids``: the same; default: every node) to the nodes ``sources``
+    (default: every node; any order, repeats allowed) — the model in ``eval()`` mode, the same model cover as :func:`explain`.
+    A module on the GPU runs ``gnan_attr_cols`` (device inputs only); a module that lives on the CPU, called with CPU inputs, runs
+    ``cpu_route.source_attributions``.  The result's bytes grow as ``P * F * D * C``: ``attribution.ATTR_MAX_BYTES`` bounds them,
+    pass ``sources`` in batches beyond."""
+    from . import attribution, cpu_route
+    from .modules import NAM, StandaloneTensorGNAN, TensorGNAN, _GNANCore
+    if model.training:
+        raise _lib.GnanHipError("explain_sources() describes the model in eval() mode (training-mode Dropout has no fixed decomposition)")
+    if rows is None:
+        rows = node_ids
+    x = data if torch.is_tensor(data) else data.x
+    cpu = cpu_route.applies(model, x)
+    if not cpu:
+        _lib.require_device(x)
+    dev = x.device
+
+    def ids_of(v):
+        return torch.as_tensor(list(v) if not torch.is_tensor(v) else v).to(device=dev, dtype=torch.int64).view(-1)
+    everything = torch.arange(x.shape[0], device=dev)
+    row_ids = everything if rows is None else ids_of(rows)
+    src_ids = everything if sources is None else ids_of(sources)
+    f = model._stacked("fs", model.fs)
+    fx = cpu_route.shape_functions(x, f, False) if cpu else feature_mlps(x, f, sum_features=False)      # [N, F * C]
+    F, C = x.shape[1], fx.shape[1] // x.shape[1]
+    if isinstance(model, NAM):                                                # no graph: a node is its own only source, at distance 0
+        mult = torch.bincount(row_ids, minlength=x.shape[0]).to(torch.float32)
+        bfd = (fx.float() * mult.unsqueeze(1))[src_ids].view(-1, F, 1, C).contiguous()
+        return SourceExplanation(src_ids, row_ids, torch.zeros(1, device=dev), bfd, bfd.sum(dim=2).sum(dim=1))
+    pre = isinstance(model, StandaloneTensorGNAN) and bool(model.normalize_rho)
+    use_cnt = (not isinstance(model, StandaloneTensorGNAN)) and bool(model.normalize_rho)
+    if cpu:
+        want = True if isinstance(model, _GNANCore) else bool(model.normalize_rho)
+        g = cpu_route.graph_of(model, data, want_norm=want)
+        wt = cpu_route._pre_rho_weights(model, g) if pre else cpu_route.shell_weights(g, cpu_route._rho_lut(model, g), use_cnt)
+        B = cpu_route.source_attributions(g, fx, wt, None if rows is None else row_ids, None if sources is None else src_ids)
+    else:
+        g = model.hop_graph(data)
+        lut = model._lut_pre_rho(g) if pre else model._lut_global(g)
+        B = attribution.source_attributions(g, fx, lut, use_cnt, None if rows is None else row_ids,
+                                            None if sources is None else src_ids)
+    D = g.n_codes
+    bfd = B.view(-1, D, F, C).permute(0, 2, 1, 3).contiguous()                # [P, F, D, C]
+    hops = torch.arange(D, dtype=torch.float32, device=dev)
+    hops[D - 1] = float("inf")
+    out = SourceExplanation(src_ids, row_ids, hops, bfd, bfd.sum(dim=2).sum(dim=1))
+    if getattr(model, "is_graph_task", False) and rows is None and isinstance(model, TensorGNAN) and model.readout_n_layers > 0:
+        out.hidden_by_node = bfd.sum(dim=2).view(-1, F)                       # [P, F]  (f is one wide; models.py:379 before the node sum)
     return out

@@ -2135,6 +2135,88 @@ int gnan_attr_rows_describe(const gnan_attr_args* a, gnan_attr_info* out);
 int gnan_attr_rows(const gnan_attr_args* a, gnan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attributions by SOURCE node (added under ABI 51; csrc/attr_cols.hip, gnan_amd.attribution.source_attributions): the
+ * column-side sum "which nodes does the prediction come from".  Requested target rows i_q (q = 0..R-1: row_ids, or every
+ * forward row when n_row_ids < 0; any order, a row that repeats counts as often as it occurs), requested source nodes j_p
+ * (p = 0..n_cols-1: col_ids, or p itself), wt(i, d, c) = lut[(i,) d, c] / max(cnt[i, d], 1) exactly as in gnan_attr_args:
+ *
+ *   V[p, d, c]   = sum over q with shell(i_q, j_p) == d of wt(i_q, d, c)         d < D-1; shell = min(code, D-1) of the listed pair
+ *   V[p, D-1, c] = the same over the pairs coded >= D-1                                          (rest_from_total == 0: dense layouts)
+ *   V[p, D-1, c] = T[c] - sum over q with (i_q, j_p) listed at code < D-1 of wt(i_q, D-1, c),
+ *                  T[c] = sum over q of wt(i_q, D-1, c)                                          (rest_from_total != 0: a CSR's rest bucket)
+ *   B[p, d, w]   = V[p, d, w % Cw] * S[j_p, w]
+ *
+ * With the same rows, sum_p B[p, d, w] = sum_q A[q, d, w] of gnan_attr_rows, and sum_{p, d} B[p, d, w] is the sum over the
+ * requested rows of gnan_spmm_fwd's column w.  Every stored pair counts, duplicates included.  d is the hop at which row i
+ * sees j.  B is [n_cols, D, W] fp32 with b_stride floats between sources.
+ *
+ * The adjacency is the TRANSPOSED one (HopGraph.transposed(), gnan_csr_transpose): rowptr_t [n_src + 1] (int32, or int64 with
+ * rowptr_is64), and per pair the forward row id `row` and its code; or, with rowptr_t == NULL, the dense code matrix
+ * [n_src, n_rows] (entry (j, i): the code at which row i sees j).  cnt and a per-row lut are the FORWARD graph's, indexed by
+ * the forward row.  A listed code >= D-1 is clamped before it indexes anything.  Ids in row_ids / col_ids outside their
+ * range are ignored (a source out of range gets a row of zeros).
+ *
+ * Launches: the multiplicities of row_ids are counted into the workspace with integer atomicAdd (n_row_ids >= 0 only); T is
+ * summed over the forward rows in blocks of gnan_attr_cols_info.t_block_rows, the blocks added in block order; a column is
+ * walked ONCE (not per operand column) in chunks of chunk_pairs pairs from its start, one wave per chunk, lanes owning pairs,
+ * lane-private bins in LDS reduced in a fixed order; columns of more than one chunk keep partials in the workspace, added in
+ * chunk order; the rest shell is T minus the listed sum; a streaming epilogue multiplies by S once.  The (shell, channel)
+ * bins d * Cw + c are taken in passes of 64.  No floating-point atomic, no workgroup waits for another: a source's bits
+ * depend on its own pairs and on the set of requested rows only.  item_ptr / n_items / max_col_pairs as item_ptr / n_items /
+ * max_row_pairs of gnan_attr_args, per requested source.  Cover: 2 <= D <= GNAN_MAX_CODES (GNAN_ERR_UNSUPPORTED beyond,
+ * naming limit and value), any W >= 1, Cw dividing W, any column length, n_row_ids == 0, n_cols == 0.  Null pointers, short
+ * strides, Cw not dividing W are GNAN_ERR_BAD_ARG, a short workspace GNAN_ERR_WORKSPACE — all before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_attr_cols_args {
+  int64_t n_cols;            /* requested (output) sources P */
+  int64_t n_src;             /* source nodes: rows of S and of the transposed adjacency */
+  int64_t n_rows;            /* forward rows: rows of cnt and of a per-row lut, columns of the dense code matrix */
+  const void* rowptr_t;      /* NULL => dense layout */
+  int32_t rowptr_is64;
+  const int32_t* row;        /* forward-row id per pair (CSR) */
+  const uint8_t* code;
+  const int32_t* col_ids;    /* optional [n_cols] */
+  const int32_t* row_ids;    /* [n_row_ids]; ignored when n_row_ids < 0 */
+  int64_t n_row_ids;         /* < 0 => every forward row once */
+  const float* S;            /* [n_src, W] */
+  int32_t W;
+  int64_t s_stride;
+  const float* lut;          /* [D, Cw] or [n_rows, D, Cw] */
+  int64_t lut_row_stride;    /* 0 => one table */
+  int32_t D;
+  int32_t Cw;
+  const int32_t* cnt;        /* optional [n_rows, cnt_stride] */
+  int64_t cnt_stride;
+  int32_t rest_from_total;
+  float* B;                  /* [n_cols, D, W] */
+  int64_t b_stride;          /* >= D * W */
+  int64_t nnz;               /* listed pairs (CSR) where known; 0 = unknown */
+  int64_t max_col_pairs;     /* CSR: pairs of the longest requested column (item_ptr == NULL: sizes every column's chunk list) */
+  const int32_t* item_ptr;   /* optional [n_cols + 1] */
+  int64_t n_items;
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_attr_cols_args;
+
+typedef struct gnan_attr_cols_info {
+  int32_t chunk_pairs;       /* pairs per work item (one wave) */
+  int32_t bin_passes;        /* walks of a chunk: ceil(D * Cw / 64) */
+  int32_t block_size;
+  int32_t items_per_block;   /* waves of a workgroup, one work item each */
+  int32_t launches;
+  int32_t lds_bytes;
+  int32_t t_block_rows;      /* forward rows per block of the T sum */
+  int64_t t_blocks;          /* 0 without rest_from_total */
+  int64_t max_col_chunks;    /* chunks of the longest column (max_col_pairs, or n_rows for the dense layout) */
+  int64_t n_items;
+  size_t workspace_bytes;
+} gnan_attr_cols_info;
+
+size_t gnan_attr_cols_workspace_bytes(const gnan_attr_cols_args* a);
+int gnan_attr_cols_describe(const gnan_attr_cols_args* a, gnan_attr_cols_info* out);
+int gnan_attr_cols(const gnan_attr_cols_args* a, gnan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph hygiene for captured steps (gnan_amd/graphed.py; nothing comparable in the reference, which issues every
  * epoch's launches from Python, trainer.py:23-86).  `graph` is a hipGraph_t obtained by stream capture and not yet
  * instantiated: every memset node is replaced by a kernel node performing the same fill, with the same dependencies
