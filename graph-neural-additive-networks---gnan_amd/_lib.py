@@ -617,6 +617,33 @@ class AttrColsInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class AttrReduceArgs(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.c_void_p), ("rowptr_is64", C.c_int32),
+        ("col", C.c_void_p), ("code", C.c_void_p), ("row_ids", C.c_void_p),
+        ("S", C.c_void_p), ("W", C.c_int32), ("s_stride", C.c_int64),
+        ("lut", C.c_void_p), ("lut_row_stride", C.c_int64), ("D", C.c_int32), ("Cw", C.c_int32),
+        ("cnt", C.c_void_p), ("cnt_stride", C.c_int64), ("s_total", C.c_void_p),
+        ("group_ptr", C.c_void_p), ("n_groups", C.c_int64), ("block_ptr", C.c_void_p), ("group_block_ptr", C.c_void_p),
+        ("n_blocks", C.c_int64), ("block_first", C.c_int64), ("block_count", C.c_int64), ("max_row_pairs", C.c_int64),
+        ("item_ptr", C.c_void_p), ("item_first", C.c_int64), ("item_count", C.c_int64), ("combine", C.c_int32),
+        ("partials", C.c_void_p), ("partials_bytes", C.c_size_t), ("M", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AttrReduceInfo(C.Structure):
+    _fields_ = [
+        ("col_tiles", C.c_int32), ("shell_passes", C.c_int32), ("pass_shells", C.c_int32), ("chunk_pairs", C.c_int32),
+        ("block_rows", C.c_int32), ("block_size", C.c_int32), ("combine_runs", C.c_int32), ("launches", C.c_int32),
+        ("lds_bytes", C.c_int32), ("n_blocks", C.c_int64), ("n_long_items", C.c_int64), ("long_items_bytes", C.c_size_t),
+        ("partials_bytes", C.c_size_t), ("plan_int_bytes", C.c_size_t),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 _lib: Optional[C.CDLL] = None
 
 # every symbol include/gnan_hip.h declares: (name, restype, argtypes)
@@ -780,6 +807,9 @@ SYMBOLS = {
     "gnan_attr_cols_workspace_bytes": (C.c_size_t, [C.POINTER(AttrColsArgs)]),
     "gnan_attr_cols_describe": (C.c_int, [C.POINTER(AttrColsArgs), C.POINTER(AttrColsInfo)]),
     "gnan_attr_cols": (C.c_int, [C.POINTER(AttrColsArgs), C.c_void_p]),
+    "gnan_attr_reduce_workspace_bytes": (C.c_size_t, [C.POINTER(AttrReduceArgs)]),
+    "gnan_attr_reduce_describe": (C.c_int, [C.POINTER(AttrReduceArgs), C.POINTER(AttrReduceInfo)]),
+    "gnan_attr_reduce": (C.c_int, [C.POINTER(AttrReduceArgs), C.c_void_p]),
 }
 
 

@@ -6,7 +6,11 @@
 is the model-level front.
 
 By source node (``gnan_attr_cols``, csrc/attr_cols.hip): ``B[p, d, w] = S[j_p, w] * sum over the requested rows i that see node
-j_p at hop d of wt(i, d, w % Cw)`` — :func:`source_attributions`, with :func:`gnan_amd.interpret.explain_sources` in front."""
+j_p at hop d of wt(i, d, w % Cw)`` — :func:`source_attributions`, with :func:`gnan_amd.interpret.explain_sources` in front.
+
+Reduced over groups of rows (``gnan_attr_reduce``, csrc/attr_reduce.hip): the float64 moments ``sum A``, ``sum |A|``, ``sum A^2`` of the
+terms over groups of requested rows, and of a row's total over the shells, without ``A`` itself — :func:`reduced_attributions`, with
+:func:`gnan_amd.interpret.importance` in front."""
 from __future__ import annotations
 
 from typing import Optional
@@ -204,3 +208,143 @@ def prepare_sources(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bo
     ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=g.device) if need else None
     a.workspace, a.workspace_bytes = _lib.ptr(ws), need
     return SourceLaunch(a, B, (g, t, S, lut, rows, cols, keep, ws), pairs)
+
+
+# =============================================================================
+# reduced over groups of rows: gnan_attr_reduce (csrc/attr_reduce.hip)
+# =============================================================================
+ATTR_REDUCE_MAX_WORKSPACE = 1 << 30     # chunk partials of long rows one launch may hold; beyond, several launches cut at block boundaries
+
+
+def describe_reduced(a: _lib.AttrReduceArgs) -> dict:
+    """``gnan_attr_reduce_describe``: chunk length, rows per block, shell passes, launches, LDS bytes and the workspace split into
+    chunk partials, block partials and the plan's integers (host-only)."""
+    info = _lib.AttrReduceInfo()
+    _lib.check(_lib.lib().gnan_attr_reduce_describe(a, info), "gnan_attr_reduce_describe")
+    return info.as_dict()
+
+
+class ReducedLaunch(Launch):
+    """The prepared calls of ``gnan_attr_reduce`` for one result ``A = M [G, 3, D + 1, W]``: one call per range of blocks, the last
+    one adds the groups' block partials.  ``pairs``: listed pairs of the requested rows."""
+
+    def __init__(self, calls: list, M: torch.Tensor, keep: tuple, pairs: int):
+        super().__init__(calls[-1], M, keep, pairs)
+        self.calls = calls
+
+    def run(self) -> torch.Tensor:
+        if self.A.numel():
+            st = _lib.stream_of(self.A)
+            for a in self.calls:
+                _lib.check(_lib.lib().gnan_attr_reduce(a, st), "gnan_attr_reduce")
+        return self.A
+
+
+@torch.no_grad()
+def reduced_attributions(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool, rows: Optional[torch.Tensor] = None,
+                         group_ptr: Optional[torch.Tensor] = None, s_total: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``M [G, 3, D + 1, W]`` float64: over the requested rows ``group_ptr[g] .. group_ptr[g + 1] - 1`` of group ``g`` (positions in
+    ``rows``; default: one group of all requested rows), ``M[g, 0] = sum a``, ``M[g, 1] = sum |a|``, ``M[g, 2] = sum a^2`` of the
+    float32 terms ``a = shell_attributions(...)[q, d, w]`` for ``d < D``; slot ``d = D`` holds the same moments of a row's total over
+    the shells.  The ``[R, D, W]`` array is never formed; inputs as :func:`shell_attributions`.  An empty group gives zeros."""
+    return prepare_reduced(g, S, lut, use_cnt, rows, group_ptr, s_total).run()
+
+
+@torch.no_grad()
+def prepare_reduced(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bool, rows: Optional[torch.Tensor] = None,
+                    group_ptr: Optional[torch.Tensor] = None, s_total: Optional[torch.Tensor] = None) -> ReducedLaunch:
+    """Everything of :func:`reduced_attributions` but the launches (tools/importance_time.py times ``run`` alone)."""
+    _lib.require_device(S, lut, g.code, s_total, rows if torch.is_tensor(rows) else None)
+    if S.dim() != 2 or S.shape[0] != g.n_cols:
+        raise ValueError(f"S must be [n_cols={g.n_cols}, W], got {tuple(S.shape)}")
+    S = _rows(S.detach().float())
+    lut = lut.detach().float().contiguous()
+    if lut.dim() not in (2, 3) or lut.shape[-2] != g.n_codes or (lut.dim() == 3 and lut.shape[0] != g.n_rows):
+        raise ValueError(f"lut must be [D={g.n_codes}, Cw] or [n_rows={g.n_rows}, D, Cw], got {tuple(lut.shape)}")
+    if s_total is not None:
+        s_total = s_total.detach().float().contiguous()
+    if rows is not None:
+        rows = torch.as_tensor(rows, device=g.device).to(torch.int32).contiguous().view(-1)
+    R = g.n_rows if rows is None else rows.numel()
+    D, W = g.n_codes, S.shape[1]
+    dev = g.device
+    gp = gp_host = None
+    G = 1
+    if group_ptr is not None:
+        # the device copy is checked here; the library checks the host copy again
+        gp = torch.as_tensor(group_ptr).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        if gp.numel() < 1:
+            raise ValueError("group_ptr must hold at least one entry")
+        gp_host = gp.cpu()
+        if int(gp_host[0]) != 0 or int(gp_host[-1]) != R or bool((gp_host[1:] < gp_host[:-1]).any()):
+            raise ValueError(f"group_ptr must rise from 0 to the number of requested rows ({R}) without a step down")
+        G = gp.numel() - 1
+    per_row = lut.dim() == 3
+    a = _lib.AttrReduceArgs(n_rows=R, n_cols=g.n_cols, code=_lib.ptr(g.code), row_ids=_lib.ptr(rows), S=_lib.ptr(S), W=W,
+                            s_stride=S.stride(0), lut=_lib.ptr(lut), lut_row_stride=D * lut.shape[-1] if per_row else 0, D=D,
+                            Cw=lut.shape[-1], s_total=_lib.ptr(s_total), group_ptr=_lib.ptr(gp_host), n_groups=G)
+    if use_cnt:
+        a.cnt, a.cnt_stride = _lib.ptr(g.cnt), g.cnt.stride(0)
+    if not g.is_dense:
+        a.rowptr, a.rowptr_is64 = _lib.ptr(g.rowptr), int(g.rowptr.dtype == torch.int64)
+        a.col = _lib.ptr(g.col)
+    info = describe_reduced(a)
+    chunk, br = info["chunk_pairs"], info["block_rows"]
+    M = torch.empty((G, 3, D + 1, W), dtype=torch.float64, device=dev)
+    # framework arithmetic on integers: the blocks of every group, the chunk items of the long rows
+    if gp is None:
+        n_blocks = -(-R // br)
+        block_ptr = gbp = None
+        starts = torch.arange(n_blocks + 1, dtype=torch.int64).mul_(br).clamp_(max=R)            # host
+    else:
+        nb_g = (gp_host[1:] - gp_host[:-1] + (br - 1)) // br
+        gbp_host = torch.zeros(G + 1, dtype=torch.int64)
+        torch.cumsum(nb_g, 0, out=gbp_host[1:])
+        n_blocks = int(gbp_host[-1])
+        gid = torch.repeat_interleave(torch.arange(G), nb_g)
+        starts = torch.full((n_blocks + 1,), R, dtype=torch.int64)
+        starts[:-1] = gp_host[gid] + (torch.arange(n_blocks) - gbp_host[gid]) * br
+        block_ptr, gbp = starts.to(dev), gbp_host.to(dev)
+    a.block_ptr, a.group_block_ptr, a.n_blocks = _lib.ptr(block_ptr), _lib.ptr(gbp), n_blocks
+    partials = torch.empty(n_blocks * 3 * (D + 1) * W, dtype=torch.float64, device=dev)
+    a.partials, a.partials_bytes, a.M = _lib.ptr(partials), partials.numel() * 8, _lib.ptr(M)
+    item_ptr, pairs = None, R * g.n_cols
+    if g.is_dense:
+        uc = -(-g.n_cols // chunk) if g.n_cols > chunk else 0
+        item_at = starts * uc                                                                  # chunk items before each block
+    else:
+        deg = (g.rowptr[1:] - g.rowptr[:-1]).long()
+        if rows is not None:
+            deg = deg[rows.long()]
+        ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        n_items = longest = pairs = 0
+        if R:
+            nch = (deg + (chunk - 1)) // chunk
+            torch.cumsum(torch.where(nch > 1, nch, torch.zeros_like(nch)), 0, out=ptr[1:])
+            n_items, longest, pairs = torch.stack([ptr[-1], deg.max(), deg.sum()]).tolist()
+        if n_items > 0x7fffffff:
+            raise _lib.GnanHipError(f"reduced_attributions: {n_items} chunk items exceed an int32 plan: pass `rows` in batches")
+        item_ptr = ptr.to(torch.int32)
+        a.item_ptr, a.max_row_pairs = _lib.ptr(item_ptr), longest
+        item_at = ptr[starts.to(dev)].cpu() if n_items else torch.zeros(n_blocks + 1, dtype=torch.int64)
+    # launches: cut at block boundaries where the chunk partials of one launch would exceed ATTR_REDUCE_MAX_WORKSPACE
+    item_bytes = D * W * 4
+    cuts = [0]
+    if int(item_at[-1]) * item_bytes > ATTR_REDUCE_MAX_WORKSPACE:
+        at = item_at.tolist()
+        for b in range(1, n_blocks):
+            if (at[b + 1] - at[cuts[-1]]) * item_bytes > ATTR_REDUCE_MAX_WORKSPACE and b > cuts[-1]:
+                cuts.append(b)
+    cuts.append(n_blocks)
+    calls, need = [], 0
+    for b0, b1 in zip(cuts[:-1], cuts[1:]):
+        c = _lib.AttrReduceArgs.from_buffer_copy(a)
+        c.block_first, c.block_count = b0, b1 - b0
+        c.item_first, c.item_count = int(item_at[b0]), int(item_at[b1] - item_at[b0])
+        c.combine = int(b1 == n_blocks)
+        need = max(need, _lib.lib().gnan_attr_reduce_workspace_bytes(c))
+        calls.append(c)
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev) if need else None
+    for c in calls:
+        c.workspace, c.workspace_bytes = _lib.ptr(ws), need
+    return ReducedLaunch(calls, M, (g, S, lut, rows, s_total, gp_host, block_ptr, gbp, item_ptr, partials, ws), pairs)

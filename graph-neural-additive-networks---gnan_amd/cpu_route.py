@@ -247,6 +247,37 @@ def source_attributions(g: HopGraph, S: torch.Tensor, wt: torch.Tensor, rows: Op
     return V[src].repeat(1, 1, W // cw) * S[src].unsqueeze(1)
 
 
+REDUCE_BATCH_BYTES = 1 << 26        # the [rows, D, W] terms :func:`reduced_attributions` forms at a time
+
+
+def reduced_attributions(g: HopGraph, S: torch.Tensor, wt: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                         group_ptr: Optional[torch.Tensor] = None, with_rest: Optional[bool] = None) -> torch.Tensor:
+    """``M [G, 3, D + 1, W]`` float64, the definition of ``gnan_attr_reduce`` in plain torch: the moments ``sum a``, ``sum |a|``,
+    ``sum a^2`` of the terms of :func:`shell_attributions` over the requested rows ``group_ptr[g] .. group_ptr[g + 1] - 1`` of
+    group ``g`` (positions in ``rows``; default: one group of all of them); slot ``D`` holds the same moments of a row's total
+    over the shells, added in shell order in float64.  The terms are taken in row batches, never all at once."""
+    D, W = g.n_codes, S.shape[1]
+    ids = torch.arange(g.n_rows) if rows is None else torch.as_tensor(rows, dtype=torch.int64).view(-1)
+    R = ids.numel()
+    gp = torch.tensor([0, R]) if group_ptr is None else torch.as_tensor(group_ptr, dtype=torch.int64).view(-1).cpu()
+    if gp.numel() < 1 or int(gp[0]) != 0 or int(gp[-1]) != R or bool((gp[1:] < gp[:-1]).any()):
+        raise ValueError(f"group_ptr must rise from 0 to the number of requested rows ({R}) without a step down")
+    G = gp.numel() - 1
+    M = torch.zeros((G, 3, D + 1, W), dtype=torch.float64)
+    group_of = torch.repeat_interleave(torch.arange(G), gp[1:] - gp[:-1])
+    step = max(1, REDUCE_BATCH_BYTES // (D * W * 8))
+    for r0 in range(0, R, step):
+        a = shell_attributions(g, S, wt, ids[r0:r0 + step], with_rest).double()          # [r, D, W]
+        t = torch.zeros((a.shape[0], W), dtype=torch.float64)
+        for d in range(D):                                                    # shell order
+            t = t + a[:, d]
+        a = torch.cat([a, t.unsqueeze(1)], dim=1)                             # [r, D + 1, W]
+        who = group_of[r0:r0 + step]
+        for j, v in enumerate((a, a.abs(), a * a)):
+            M[:, j].index_add_(0, who, v)
+    return M
+
+
 def _rho_lut(module, g: HopGraph) -> torch.Tensor:
     """``rho`` on the D distinct distances of the graph, ``[D, C_rho]`` (the same float32 inputs the reference feeds per pair)."""
     return _rho(module, hop_inputs(g.n_codes, "cpu"))

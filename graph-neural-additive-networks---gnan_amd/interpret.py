@@ -10,7 +10,9 @@ bends, which a value grid can only approximate.  Device tensors in, device tenso
 :func:`explain` goes from the global curves to one prediction: every term ``(feature k, distance d)`` of the sum that IS the
 model's output for a node of a graph (``gnan_attr_rows`` on the HIP path, ``cpu_route.shell_attributions`` for a module that
 lives on the CPU).  :func:`explain_sources` turns the same sum by SOURCE node: what every node of the graph adds to the outputs asked
-for (``gnan_attr_cols`` / ``cpu_route.source_attributions``)."""
+for (``gnan_attr_cols`` / ``cpu_route.source_attributions``).  :func:`importance` is the global chart: the mean, mean magnitude and rms of
+those terms over all nodes, a mask or the nodes of each class (``gnan_attr_reduce`` / ``cpu_route.reduced_attributions``), formed without
+storing a term per row."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -84,6 +86,59 @@ def contribution_heatmap(model, max_hop: int, value: float = 1.0) -> torch.Tenso
 
 
 # =============================================================================
+# the shared preamble of explain / explain_sources / importance: operand, graph, weight table
+# =============================================================================
+@dataclass
+class _Terms:
+    """What the three attribution fronts start from: ``fx [N, F * C]`` (the shape functions of every node, the operand), and — but
+    for a NAM, which has no graph — the hop graph, the weight table (``lut`` on the HIP path, per-row ``wt`` on the CPU route) and
+    whether the shell sizes divide it."""
+    x: torch.Tensor
+    cpu: bool
+    fx: torch.Tensor
+    F: int
+    C: int
+    nam: bool
+    g: object = None
+    table: Optional[torch.Tensor] = None
+    use_cnt: bool = False
+
+
+def _terms(model, data, who: str) -> _Terms:
+    from . import batched, cpu_route
+    from .modules import NAM, StandaloneTensorGNAN, _GNANCore
+    if isinstance(model, batched.TensorGNAN):
+        raise _lib.GnanHipError(f"{who}() covers the single-graph modules; batched.TensorGNAN evaluates many graphs per call")
+    if model.training:
+        raise _lib.GnanHipError(f"{who}() describes the model in eval() mode (training-mode Dropout has no fixed decomposition)")
+    x = data if torch.is_tensor(data) else data.x
+    cpu = cpu_route.applies(model, x)
+    if not cpu:
+        _lib.require_device(x)
+    f = model._stacked("fs", model.fs)
+    fx = cpu_route.shape_functions(x, f, False) if cpu else feature_mlps(x, f, sum_features=False)      # [N, F * C]
+    t = _Terms(x, cpu, fx, x.shape[1], fx.shape[1] // x.shape[1], isinstance(model, NAM))
+    if t.nam:
+        return t
+    pre = isinstance(model, StandaloneTensorGNAN) and bool(model.normalize_rho)
+    t.use_cnt = (not isinstance(model, StandaloneTensorGNAN)) and bool(model.normalize_rho)
+    if cpu:
+        want = True if isinstance(model, _GNANCore) else bool(model.normalize_rho)
+        t.g = cpu_route.graph_of(model, data, want_norm=want)
+        t.table = cpu_route._pre_rho_weights(model, t.g) if pre else cpu_route.shell_weights(t.g, cpu_route._rho_lut(model, t.g), t.use_cnt)
+    else:
+        t.g = model.hop_graph(data)
+        t.table = model._lut_pre_rho(t.g) if pre else model._lut_global(t.g)
+    return t
+
+
+def _hops(D: int, dev) -> torch.Tensor:
+    hops = torch.arange(D, dtype=torch.float32, device=dev)
+    hops[D - 1] = float("inf")
+    return hops
+
+
+# =============================================================================
 # per-prediction explanations: the (feature, distance) terms of rows
 # =============================================================================
 @dataclass
@@ -110,40 +165,25 @@ def explain(model, data, rows=None, node_ids=None) -> Explanation:
     The result's bytes grow as ``R * F * D * C``: ``attribution.ATTR_MAX_BYTES`` bounds them, pass ``rows`` in batches beyond."""
     from . import attribution, cpu_route
     from .functional import column_sums
-    from .modules import NAM, StandaloneTensorGNAN, TensorGNAN, _GNANCore
-    if model.training:
-        raise _lib.GnanHipError("explain() describes the model in eval() mode (training-mode Dropout has no fixed decomposition)")
+    from .modules import TensorGNAN
+    t = _terms(model, data, "explain")
     if rows is None:
         rows = node_ids
-    x = data if torch.is_tensor(data) else data.x
-    cpu = cpu_route.applies(model, x)
-    if not cpu:
-        _lib.require_device(x)
+    x, cpu, fx, F, C, g = t.x, t.cpu, t.fx, t.F, t.C, t.g
     dev = x.device
     if rows is not None:
         rows = torch.as_tensor(list(rows) if not torch.is_tensor(rows) else rows).to(device=dev, dtype=torch.int64).view(-1)
-    f = model._stacked("fs", model.fs)
-    fx = cpu_route.shape_functions(x, f, False) if cpu else feature_mlps(x, f, sum_features=False)      # [N, F * C]
-    F, C = x.shape[1], fx.shape[1] // x.shape[1]
     ids = torch.arange(x.shape[0], device=dev) if rows is None else rows
-    if isinstance(model, NAM):                                                # no graph: one "distance", the node itself
+    if t.nam:                                                                 # no graph: one "distance", the node itself
         bfd = fx.float()[ids].view(-1, F, 1, C).contiguous()
         return Explanation(ids, bfd, torch.zeros(1, device=dev), bfd.sum(dim=2).sum(dim=1))
-    pre = isinstance(model, StandaloneTensorGNAN) and bool(model.normalize_rho)
-    use_cnt = (not isinstance(model, StandaloneTensorGNAN)) and bool(model.normalize_rho)
     if cpu:
-        want = True if isinstance(model, _GNANCore) else bool(model.normalize_rho)
-        g = cpu_route.graph_of(model, data, want_norm=want)
-        wt = cpu_route._pre_rho_weights(model, g) if pre else cpu_route.shell_weights(g, cpu_route._rho_lut(model, g), use_cnt)
-        A = cpu_route.shell_attributions(g, fx, wt, rows)
+        A = cpu_route.shell_attributions(g, fx, t.table, rows)
     else:
-        g = model.hop_graph(data)
-        lut = model._lut_pre_rho(g) if pre else model._lut_global(g)
-        A = attribution.shell_attributions(g, fx, lut, use_cnt, rows, None if g.is_dense else column_sums(fx))
+        A = attribution.shell_attributions(g, fx, t.table, t.use_cnt, rows, None if g.is_dense else column_sums(fx))
     D = g.n_codes
     bfd = A.view(-1, D, F, C).permute(0, 2, 1, 3).contiguous()                # [R, F, D, C]
-    hops = torch.arange(D, dtype=torch.float32, device=dev)
-    hops[D - 1] = float("inf")
+    hops = _hops(D, dev)
     out = Explanation(ids, bfd, hops, bfd.sum(dim=2).sum(dim=1))
     if getattr(model, "is_graph_task", False) and rows is None:
         out.graph_by_feature_distance = bfd.sum(dim=0)                        # [F, D, C]  (framework arithmetic: DESIGN.md section 6)
@@ -184,15 +224,11 @@ def explain_sources(model, data, rows=None, node_ids=None, sources=None) -> Sour
     ``cpu_route.source_attributions``.  The result's bytes grow as ``P * F * D * C``: ``attribution.ATTR_MAX_BYTES`` bounds them,
     pass ``sources`` in batches beyond."""
     from . import attribution, cpu_route
-    from .modules import NAM, StandaloneTensorGNAN, TensorGNAN, _GNANCore
-    if model.training:
-        raise _lib.GnanHipError("explain_sources() describes the model in eval() mode (training-mode Dropout has no fixed decomposition)")
+    from .modules import TensorGNAN
+    t = _terms(model, data, "explain_sources")
     if rows is None:
         rows = node_ids
-    x = data if torch.is_tensor(data) else data.x
-    cpu = cpu_route.applies(model, x)
-    if not cpu:
-        _lib.require_device(x)
+    x, cpu, fx, F, C, g = t.x, t.cpu, t.fx, t.F, t.C, t.g
     dev = x.device
 
     def ids_of(v):
@@ -200,30 +236,97 @@ def explain_sources(model, data, rows=None, node_ids=None, sources=None) -> Sour
     everything = torch.arange(x.shape[0], device=dev)
     row_ids = everything if rows is None else ids_of(rows)
     src_ids = everything if sources is None else ids_of(sources)
-    f = model._stacked("fs", model.fs)
-    fx = cpu_route.shape_functions(x, f, False) if cpu else feature_mlps(x, f, sum_features=False)      # [N, F * C]
-    F, C = x.shape[1], fx.shape[1] // x.shape[1]
-    if isinstance(model, NAM):                                                # no graph: a node is its own only source, at distance 0
+    if t.nam:                                                                 # no graph: a node is its own only source, at distance 0
         mult = torch.bincount(row_ids, minlength=x.shape[0]).to(torch.float32)
         bfd = (fx.float() * mult.unsqueeze(1))[src_ids].view(-1, F, 1, C).contiguous()
         return SourceExplanation(src_ids, row_ids, torch.zeros(1, device=dev), bfd, bfd.sum(dim=2).sum(dim=1))
-    pre = isinstance(model, StandaloneTensorGNAN) and bool(model.normalize_rho)
-    use_cnt = (not isinstance(model, StandaloneTensorGNAN)) and bool(model.normalize_rho)
     if cpu:
-        want = True if isinstance(model, _GNANCore) else bool(model.normalize_rho)
-        g = cpu_route.graph_of(model, data, want_norm=want)
-        wt = cpu_route._pre_rho_weights(model, g) if pre else cpu_route.shell_weights(g, cpu_route._rho_lut(model, g), use_cnt)
-        B = cpu_route.source_attributions(g, fx, wt, None if rows is None else row_ids, None if sources is None else src_ids)
+        B = cpu_route.source_attributions(g, fx, t.table, None if rows is None else row_ids, None if sources is None else src_ids)
     else:
-        g = model.hop_graph(data)
-        lut = model._lut_pre_rho(g) if pre else model._lut_global(g)
-        B = attribution.source_attributions(g, fx, lut, use_cnt, None if rows is None else row_ids,
+        B = attribution.source_attributions(g, fx, t.table, t.use_cnt, None if rows is None else row_ids,
                                             None if sources is None else src_ids)
     D = g.n_codes
     bfd = B.view(-1, D, F, C).permute(0, 2, 1, 3).contiguous()                # [P, F, D, C]
-    hops = torch.arange(D, dtype=torch.float32, device=dev)
-    hops[D - 1] = float("inf")
+    hops = _hops(D, dev)
     out = SourceExplanation(src_ids, row_ids, hops, bfd, bfd.sum(dim=2).sum(dim=1))
     if getattr(model, "is_graph_task", False) and rows is None and isinstance(model, TensorGNAN) and model.readout_n_layers > 0:
         out.hidden_by_node = bfd.sum(dim=2).view(-1, F)                       # [P, F]  (f is one wide; models.py:379 before the node sum)
     return out
+
+
+# =============================================================================
+# global importance: the attributions' moments over groups of rows
+# =============================================================================
+@dataclass
+class Importance:
+    """How much feature ``k`` at distance ``hops[d]`` contributes to channel ``c`` over the rows of group ``g`` — the moments of
+    :class:`Explanation`'s ``by_feature_distance`` over each group, formed without it: ``mean``, ``mean_abs`` (the global importance
+    chart) and ``rms``, each ``[G, F, D, C]``; ``feature_mean``, ``feature_mean_abs`` and ``feature_rms`` ``[G, F, C]`` are the same
+    moments of a feature's TOTAL over the distances (``mean |sum_d A|``, which the per-distance moments cannot give).  ``rows``: the
+    requested rows in the order the groups take them (sorted stably by label); ``group_labels [G]`` the distinct labels, ascending;
+    ``count [G]`` the rows of each group.  Statistics, ``count`` and ``hops`` are float64.  ``mean * count`` summed over ``(k, d)`` is
+    the sum of the model's outputs over the group."""
+    rows: torch.Tensor
+    group_labels: torch.Tensor
+    count: torch.Tensor
+    hops: torch.Tensor
+    mean: torch.Tensor
+    mean_abs: torch.Tensor
+    rms: torch.Tensor
+    feature_mean: torch.Tensor
+    feature_mean_abs: torch.Tensor
+    feature_rms: torch.Tensor
+
+
+@torch.no_grad()
+def importance(model, data, rows=None, node_ids=None, groups=None) -> Importance:
+    """Global importance of ``model`` on ``data`` over ``rows`` (``node_ids``: the same; default: every node), optionally apart by
+    ``groups`` — one integer label per requested row, the class for example.  The model cover and refusals are :func:`explain`'s.  A
+    module on the GPU runs ``gnan_attr_reduce`` (the ``[R, F, D, C]`` terms are never stored, so no ``ATTR_MAX_BYTES`` applies);
+    a module that lives on the CPU, called with CPU inputs, runs ``cpu_route.reduced_attributions``."""
+    from . import attribution, cpu_route
+    from .functional import column_sums
+    t = _terms(model, data, "importance")
+    if rows is None:
+        rows = node_ids
+    x, fx, F, C, g = t.x, t.fx, t.F, t.C, t.g
+    dev = x.device
+
+    def ints(v):
+        return torch.as_tensor(list(v) if not torch.is_tensor(v) else v).to(device=dev, dtype=torch.int64).view(-1)
+    ids = torch.arange(x.shape[0], device=dev) if rows is None else ints(rows)
+    R = ids.numel()
+    gp = None
+    labels, count = torch.zeros(1, dtype=torch.int64, device=dev), torch.full((1,), R, dtype=torch.int64, device=dev)
+    if groups is not None:
+        lab = ints(groups)
+        if lab.numel() != R:
+            raise ValueError(f"groups must hold one label per requested row ({R}), got {lab.numel()}")
+        order = torch.sort(lab, stable=True).indices
+        ids = ids[order]
+        labels, count = torch.unique_consecutive(lab[order], return_counts=True)
+        gp = torch.zeros(labels.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(count, 0, out=gp[1:])
+    G = labels.numel()
+    if t.nam:                                                                 # no graph: one "distance"; framework arithmetic on [R, F * C]
+        a = fx.double()[ids]
+        who = torch.repeat_interleave(torch.arange(G, device=dev), count)
+        M = torch.zeros((G, 3, 2, F * C), dtype=torch.float64, device=dev)
+        for j, v in enumerate((a, a.abs(), a * a)):
+            M[:, j, 0].index_add_(0, who, v)
+        M[:, :, 1] = M[:, :, 0]
+        D = 1
+        hops = torch.zeros(1, dtype=torch.float64, device=dev)
+    else:
+        D = g.n_codes
+        hops = _hops(D, dev).double()
+        if t.cpu:
+            M = cpu_route.reduced_attributions(g, fx, t.table, ids, gp)
+        else:
+            M = attribution.reduced_attributions(g, fx, t.table, t.use_cnt, None if rows is None and groups is None else ids, gp,
+                                                 None if g.is_dense else column_sums(fx))
+    M = M.view(G, 3, D + 1, F, C).permute(0, 1, 3, 2, 4)                      # [G, 3, F, D + 1, C]
+    n = count.double().clamp_min(1.0).view(G, 1, 1, 1)
+    mean, mean_abs, rms = M[:, 0] / n, M[:, 1] / n, (M[:, 2] / n).sqrt()
+    return Importance(ids, labels, count.double(), hops, mean[:, :, :D].contiguous(), mean_abs[:, :, :D].contiguous(),
+                      rms[:, :, :D].contiguous(), mean[:, :, D].contiguous(), mean_abs[:, :, D].contiguous(), rms[:, :, D].contiguous())

@@ -2217,6 +2217,98 @@ int gnan_attr_cols_describe(const gnan_attr_cols_args* a, gnan_attr_cols_info* o
 int gnan_attr_cols(const gnan_attr_cols_args* a, gnan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attributions reduced over groups of rows (added under ABI 51; csrc/attr_reduce.hip, gnan_amd.attribution.reduced_attributions):
+ * the moments of gnan_attr_rows' terms over groups of requested rows, without the [n_rows, D, W] array.  With a[q, d, w] the
+ * fp32 value A[q, d, w] defined above (codes past the cover clamped to the rest shell, the rest shell from s_total where given,
+ * cnt divided as max(cnt, 1), the weight once on the combined shell sum) and group g the requested rows
+ * q = group_ptr[g] .. group_ptr[g + 1] - 1 (group_ptr == NULL: one group of all n_rows rows):
+ *
+ *   M[g, 0, d, w] = sum_q (double)a      M[g, 1, d, w] = sum_q |(double)a|      M[g, 2, d, w] = sum_q (double)a^2         d < D
+ *   M[g, j, D, w] = the same three moments of t[q, w] = sum_{d < D} (double)a[q, d, w], added in shell order in fp64
+ *
+ * M is [n_groups, 3, D + 1, W] fp64, contiguous.  A group without rows gives exact zeros; a row that repeats counts as often
+ * as it occurs.  Adjacency, row_ids, S, lut, cnt, s_total as in gnan_attr_args.
+ *
+ * Plan (gnan_attr_reduce_info): a group is cut into blocks of block_rows consecutive requested rows from the group's start (a
+ * block never straddles a group boundary; the last block of a group may be short).  The caller hands the blocks over as
+ * device arrays: block_ptr [n_blocks + 1] int64, the positions of the blocks' first rows in the list of requested rows, and
+ * group_block_ptr [n_groups + 1] int64, each group's first block.  Both may be NULL where group_ptr is NULL (uniform blocks
+ * of block_rows rows).  group_ptr itself is a HOST array: a non-monotone one, or one that does not start at 0 and end at
+ * n_rows, is refused; a caller whose group_ptr lives on the device checks it there.
+ *
+ * Launches: (1) rows of more than chunk_pairs pairs are walked in chunks from the row's start, one wave per (chunk, tile of 64
+ * columns), raw partial sums to `workspace`; item_ptr [n_rows + 1] int32 (device) is the prefix sum of the chunks of those LONG
+ * rows (a row of at most one chunk has none), or NULL: every row has the chunks of the longest one (max_row_pairs; dense:
+ * n_cols).  (2) one workgroup per (block, tile of 64 columns): a wave per row at a time (rows wave, wave + 4, ... of the block),
+ * lanes own operand columns, shells in passes of pass_shells; the row's D terms become the moments in fp64 registers, the four
+ * waves are added in wave order and the block's partial goes to `partials` [n_blocks, 3, D + 1, W] fp64.  (3) with `combine`
+ * set, a group's block partials are added into M: sixteen runs of consecutive blocks, each in block order, the runs in run
+ * order.  No floating-point atomic, no workgroup waits for another; a group's bits depend on its own rows, in their order.
+ * A call may cover a range of blocks only (block_first, block_count; item_first, item_count: the chunk items of the rows of
+ * those blocks, which size `workspace`): every such call deposits into the common `partials`, the last one sets `combine`, and
+ * the bits do not depend on the split.  Cover and refusals as gnan_attr_rows: 2 <= D <= GNAN_MAX_CODES, W >= 1, Cw | W, strides,
+ * null pointers, a NULL col beside a rowptr, group_ptr, block range, short `partials` are refused, a short workspace is
+ * GNAN_ERR_WORKSPACE — all before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_attr_reduce_args {
+  int64_t n_rows;            /* requested rows R */
+  int64_t n_cols;            /* rows of S */
+  const void* rowptr;        /* NULL => dense layout */
+  int32_t rowptr_is64;
+  const int32_t* col;
+  const uint8_t* code;
+  const int32_t* row_ids;    /* optional [n_rows] */
+  const float* S;            /* [n_cols, W] */
+  int32_t W;
+  int64_t s_stride;
+  const float* lut;          /* [D, Cw] or [n_adj_rows, D, Cw] */
+  int64_t lut_row_stride;    /* 0 => one table */
+  int32_t D;
+  int32_t Cw;
+  const int32_t* cnt;        /* optional [n_adj_rows, cnt_stride] */
+  int64_t cnt_stride;
+  const float* s_total;      /* optional [W] */
+  const int64_t* group_ptr;  /* HOST [n_groups + 1], or NULL: one group */
+  int64_t n_groups;          /* ignored (1) when group_ptr == NULL */
+  const int64_t* block_ptr;        /* device [n_blocks + 1]; NULL only with group_ptr == NULL */
+  const int64_t* group_block_ptr;  /* device [n_groups + 1]; NULL only with group_ptr == NULL */
+  int64_t n_blocks;          /* blocks of all groups */
+  int64_t block_first;       /* this call: blocks block_first .. block_first + block_count - 1 */
+  int64_t block_count;
+  int64_t max_row_pairs;     /* CSR: pairs of the longest requested row (item_ptr == NULL: sizes every row's chunk list) */
+  const int32_t* item_ptr;   /* optional [n_rows + 1]: chunk items of the long rows */
+  int64_t item_first;        /* this call: chunk items item_first .. item_first + item_count - 1 (item_ptr given) */
+  int64_t item_count;
+  int32_t combine;           /* != 0: add the groups' block partials into M after this call's blocks */
+  double* partials;          /* [n_blocks, 3, D + 1, W] */
+  size_t partials_bytes;
+  double* M;                 /* [n_groups, 3, D + 1, W]; may be NULL without `combine` */
+  void* workspace;           /* this call's chunk partials */
+  size_t workspace_bytes;
+} gnan_attr_reduce_args;
+
+typedef struct gnan_attr_reduce_info {
+  int32_t col_tiles;         /* tiles of 64 operand columns */
+  int32_t shell_passes;      /* walks of a row: ceil(D / pass_shells) */
+  int32_t pass_shells;
+  int32_t chunk_pairs;       /* pairs per chunk item; a row of at most this many is walked by one wave of the block kernel */
+  int32_t block_rows;        /* requested rows per block (a group's last block may be shorter) */
+  int32_t block_size;        /* threads of the block kernel */
+  int32_t combine_runs;      /* runs of consecutive blocks the combine kernel adds per group */
+  int32_t launches;          /* of this call */
+  int32_t lds_bytes;         /* of the block kernel */
+  int64_t n_blocks;          /* what the plan must hold: sum over the groups of ceil(rows / block_rows) */
+  int64_t n_long_items;      /* chunk items of this call */
+  size_t long_items_bytes;   /* n_long_items * D * W floats: == gnan_attr_reduce_workspace_bytes */
+  size_t partials_bytes;     /* n_blocks * 3 * (D + 1) * W doubles */
+  size_t plan_int_bytes;     /* the caller's integer arrays: item_ptr, block_ptr, group_block_ptr */
+} gnan_attr_reduce_info;
+
+size_t gnan_attr_reduce_workspace_bytes(const gnan_attr_reduce_args* a);
+int gnan_attr_reduce_describe(const gnan_attr_reduce_args* a, gnan_attr_reduce_info* out);
+int gnan_attr_reduce(const gnan_attr_reduce_args* a, gnan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph hygiene for captured steps (gnan_amd/graphed.py; nothing comparable in the reference, which issues every
  * epoch's launches from Python, trainer.py:23-86).  `graph` is a hipGraph_t obtained by stream capture and not yet
  * instantiated: every memset node is replaced by a kernel node performing the same fill, with the same dependencies
