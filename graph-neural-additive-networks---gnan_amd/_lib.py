@@ -644,6 +644,27 @@ class AttrReduceInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class AttrBlocksArgs(C.Structure):
+    _fields_ = [
+        ("code", C.c_void_p), ("node_off", C.c_void_p), ("code_off", C.c_void_p), ("n_graphs", C.c_int64),
+        ("total_nodes", C.c_int64), ("max_nodes", C.c_int64), ("S", C.c_void_p), ("W", C.c_int32), ("s_stride", C.c_int64),
+        ("lut", C.c_void_p), ("lut_row_stride", C.c_int64), ("D", C.c_int32), ("Cw", C.c_int32),
+        ("cnt", C.c_void_p), ("cnt_stride", C.c_int64), ("B", C.c_void_p), ("b_stride", C.c_int64), ("T", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+class AttrBlocksInfo(C.Structure):
+    _fields_ = [
+        ("tile_cols", C.c_int32), ("col_tiles", C.c_int32), ("bin_passes", C.c_int32), ("row_chunk", C.c_int32),
+        ("row_slices", C.c_int32), ("block_size", C.c_int32), ("launches", C.c_int32), ("lds_bytes", C.c_int32),
+        ("n_tiles", C.c_int64), ("v_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 _lib: Optional[C.CDLL] = None
 
 # every symbol include/gnan_hip.h declares: (name, restype, argtypes)
@@ -810,6 +831,9 @@ SYMBOLS = {
     "gnan_attr_reduce_workspace_bytes": (C.c_size_t, [C.POINTER(AttrReduceArgs)]),
     "gnan_attr_reduce_describe": (C.c_int, [C.POINTER(AttrReduceArgs), C.POINTER(AttrReduceInfo)]),
     "gnan_attr_reduce": (C.c_int, [C.POINTER(AttrReduceArgs), C.c_void_p]),
+    "gnan_attr_blocks_workspace_bytes": (C.c_size_t, [C.POINTER(AttrBlocksArgs)]),
+    "gnan_attr_blocks_describe": (C.c_int, [C.POINTER(AttrBlocksArgs), C.POINTER(AttrBlocksInfo)]),
+    "gnan_attr_blocks": (C.c_int, [C.POINTER(AttrBlocksArgs), C.c_void_p]),
 }
 
 

@@ -10,7 +10,11 @@ j_p at hop d of wt(i, d, w % Cw)`` — :func:`source_attributions`, with :func:`
 
 Reduced over groups of rows (``gnan_attr_reduce``, csrc/attr_reduce.hip): the float64 moments ``sum A``, ``sum |A|``, ``sum A^2`` of the
 terms over groups of requested rows, and of a row's total over the shells, without ``A`` itself — :func:`reduced_attributions`, with
-:func:`gnan_amd.interpret.importance` in front."""
+:func:`gnan_amd.interpret.importance` in front.
+
+A batch of graphs (``gnan_attr_blocks``, csrc/attr_blocks.hip): the by-source-node terms of EVERY graph of a ``HopBlocks`` batch and their
+sums per graph, in at most three launches whatever the number of graphs — :func:`block_attributions`, with
+:func:`gnan_amd.interpret.explain_graphs` / ``importance_graphs`` in front."""
 from __future__ import annotations
 
 from typing import Optional
@@ -348,3 +352,85 @@ def prepare_reduced(g: HopGraph, S: torch.Tensor, lut: torch.Tensor, use_cnt: bo
     for c in calls:
         c.workspace, c.workspace_bytes = _lib.ptr(ws), need
     return ReducedLaunch(calls, M, (g, S, lut, rows, s_total, gp_host, block_ptr, gbp, item_ptr, partials, ws), pairs)
+
+
+# =============================================================================
+# a batch of graphs, by source node and by graph: gnan_attr_blocks (csrc/attr_blocks.hip)
+# =============================================================================
+def describe_blocks(a: _lib.AttrBlocksArgs) -> dict:
+    """``gnan_attr_blocks_describe``: column tiles, bin passes, row-chunk length, launches, LDS bytes, the workspace (host-only)."""
+    info = _lib.AttrBlocksInfo()
+    _lib.check(_lib.lib().gnan_attr_blocks_describe(a, info), "gnan_attr_blocks_describe")
+    return info.as_dict()
+
+
+class BlocksLaunch(Launch):
+    """One prepared call of ``gnan_attr_blocks``: ``B`` (or None) and ``T`` (or None) are what :meth:`run` returns; ``pairs``: the
+    ``sum n_g^2`` codes of the batch (walked once per bin pass)."""
+
+    def __init__(self, args: _lib.AttrBlocksArgs, B, T, keep: tuple, pairs: int):
+        super().__init__(args, B, keep, pairs)
+        self.B, self.T = B, T
+
+    def run(self):
+        out = self.B if self.B is not None else self.T
+        if self.args.n_graphs:
+            _lib.check(_lib.lib().gnan_attr_blocks(self.args, _lib.stream_of(out)), "gnan_attr_blocks")
+        return self.B, self.T
+
+
+@torch.no_grad()
+def block_attributions(blocks, S: torch.Tensor, lut: torch.Tensor, cnt: Optional[torch.Tensor] = None, want_nodes: bool = True,
+                       want_graphs: bool = True):
+    """``(B, T)`` for ALL graphs of ``blocks`` (:class:`gnan_amd.batched.HopBlocks`) in one call: ``B [N, D, W]`` float32 — what node
+    ``j`` adds, at hop ``d``, to column ``w`` of the summed output of ITS graph, :func:`source_attributions` of every graph alone —
+    and ``T [G, D, W]``, its sum over the nodes of each graph in node order (an empty graph: zeros).  ``want_nodes`` / ``want_graphs``:
+    which of the two is formed (the other is None; each has the bits it has alone).
+
+    ``S [N, W]`` float32 operand rows; ``lut [D, Cw]`` or ``[N, D, Cw]`` (pre-rho: per forward row), ``D = blocks.n_codes``; ``cnt
+    [N, D]`` int32 divides by the shell sizes (the slot layout: hops below ``D - 1`` in their columns, the unreachable pairs in the
+    last).  A code of 255 and every listed code ``>= D - 1`` count for the rest shell."""
+    return prepare_blocks(blocks, S, lut, cnt, want_nodes, want_graphs).run()
+
+
+@torch.no_grad()
+def prepare_blocks(blocks, S: torch.Tensor, lut: torch.Tensor, cnt: Optional[torch.Tensor] = None, want_nodes: bool = True,
+                   want_graphs: bool = True) -> BlocksLaunch:
+    """Everything of :func:`block_attributions` but the launches (tools/explain_graphs_time.py times ``run`` alone)."""
+    if getattr(blocks, "slots", False):
+        raise _lib.GnanHipError("block_attributions: these blocks are the slots of a captured step: their sizes live on the device only")
+    if not (want_nodes or want_graphs):
+        raise ValueError("block_attributions: one of want_nodes / want_graphs must be set")
+    _lib.require_device(S, lut, blocks.code, cnt)
+    G, N, D = blocks.n_graphs, blocks.total_nodes, blocks.n_codes
+    if S.dim() != 2 or S.shape[0] != N:
+        raise ValueError(f"S must be [total_nodes={N}, W], got {tuple(S.shape)}")
+    S = _rows(S.detach().float())
+    lut = lut.detach().float().contiguous()
+    if lut.dim() not in (2, 3) or lut.shape[-2] != D or (lut.dim() == 3 and lut.shape[0] != N):
+        raise ValueError(f"lut must be [D={D}, Cw] or [total_nodes={N}, D, Cw], got {tuple(lut.shape)}")
+    if cnt is not None:
+        if cnt.dim() != 2 or cnt.shape[0] != N or cnt.shape[1] < D or cnt.dtype != torch.int32:
+            raise ValueError(f"cnt must be int32 [total_nodes={N}, >= D={D}], got {cnt.dtype} {tuple(cnt.shape)}")
+        cnt = cnt if cnt.stride(1) == 1 else cnt.contiguous()
+    W = S.shape[1]
+    dev = S.device
+    B = T = None
+    if want_nodes:
+        nbytes = N * D * W * 4
+        if nbytes > ATTR_MAX_BYTES:
+            raise _lib.GnanHipError(f"block_attributions: the result [{N}, {D}, {W}] float32 takes {nbytes} bytes, above ATTR_MAX_BYTES = "
+                                    f"{ATTR_MAX_BYTES}: pass the graphs in batches")
+        B = torch.empty((N, D, W), dtype=torch.float32, device=dev)
+    if want_graphs:
+        T = torch.empty((G, D, W), dtype=torch.float32, device=dev)
+    a = _lib.AttrBlocksArgs(code=_lib.ptr(blocks.code), node_off=_lib.ptr(blocks.node_off), code_off=_lib.ptr(blocks.code_off),
+                            n_graphs=G, total_nodes=N, max_nodes=blocks.max_nodes, S=_lib.ptr(S), W=W, s_stride=S.stride(0),
+                            lut=_lib.ptr(lut), lut_row_stride=D * lut.shape[-1] if lut.dim() == 3 else 0, D=D, Cw=lut.shape[-1],
+                            B=_lib.ptr(B), b_stride=D * W, T=_lib.ptr(T))
+    if cnt is not None:
+        a.cnt, a.cnt_stride = _lib.ptr(cnt), cnt.stride(0)
+    need = _lib.lib().gnan_attr_blocks_workspace_bytes(a)
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev) if need else None
+    a.workspace, a.workspace_bytes = _lib.ptr(ws), need
+    return BlocksLaunch(a, B, T, (blocks, S, lut, cnt, ws), int(blocks.code.numel()))

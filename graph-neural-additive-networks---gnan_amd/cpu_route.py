@@ -342,3 +342,21 @@ def forward_models_tensor(module, inputs) -> torch.Tensor:
         return forward_nam(module.readout_nam, hidden).T                                            # [C, 1]  models.py:380-384
     S = shape_functions(inputs.x, module._stacked("fs", module.fs), True, _drop(module))
     return _readout(module, aggregate(g, S, wt))
+
+
+def block_attributions(blocks, S: torch.Tensor, wt: torch.Tensor, want_nodes: bool = True, want_graphs: bool = True):
+    """``gnan_attr_blocks`` in plain torch: ``(B [N, D, W], T [G, D, W])`` for the graphs of ``blocks`` (a
+    :class:`gnan_amd.batched.HopBlocks` whose tensors live on the CPU) — graph by graph through :func:`source_attributions` on the
+    graph's dense code block, ``T[g]`` the sum of its rows of ``B``.  ``wt [N, D, C_rho]``: the weights per forward row (already
+    divided by the shell sizes where the model normalises)."""
+    D, W = blocks.n_codes, S.shape[1]
+    B = torch.zeros((blocks.total_nodes, D, W), dtype=S.dtype)
+    T = torch.zeros((blocks.n_graphs, D, W), dtype=S.dtype)
+    n0 = c0 = 0
+    for gi, n in enumerate(blocks.sizes):
+        if n:
+            g = HopGraph(n_rows=n, n_cols=n, n_codes=D, code=blocks.code[c0: c0 + n * n].view(n, n), cnt=None)
+            B[n0: n0 + n] = source_attributions(g, S[n0: n0 + n], wt[n0: n0 + n], with_rest=False)
+            T[gi] = B[n0: n0 + n].sum(dim=0)
+        n0, c0 = n0 + n, c0 + n * n
+    return (B if want_nodes else None), (T if want_graphs else None)

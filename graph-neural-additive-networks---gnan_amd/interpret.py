@@ -12,7 +12,8 @@ model's output for a node of a graph (``gnan_attr_rows`` on the HIP path, ``cpu_
 lives on the CPU).  :func:`explain_sources` turns the same sum by SOURCE node: what every node of the graph adds to the outputs asked
 for (``gnan_attr_cols`` / ``cpu_route.source_attributions``).  :func:`importance` is the global chart: the mean, mean magnitude and rms of
 those terms over all nodes, a mask or the nodes of each class (``gnan_attr_reduce`` / ``cpu_route.reduced_attributions``), formed without
-storing a term per row."""
+storing a term per row.  :func:`explain_graphs` / :func:`importance_graphs` ask the same of a whole :class:`GraphBatch` of graphs in one
+pass (``gnan_attr_blocks`` / ``cpu_route.block_attributions``): graph-level models, per graph and per node."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -330,3 +331,285 @@ def importance(model, data, rows=None, node_ids=None, groups=None) -> Importance
     mean, mean_abs, rms = M[:, 0] / n, M[:, 1] / n, (M[:, 2] / n).sqrt()
     return Importance(ids, labels, count.double(), hops, mean[:, :, :D].contiguous(), mean_abs[:, :, :D].contiguous(),
                       rms[:, :, :D].contiguous(), mean[:, :, D].contiguous(), mean_abs[:, :, D].contiguous(), rms[:, :, D].contiguous())
+
+
+# =============================================================================
+# a batch of graphs in one pass: per-graph and per-node terms (gnan_attr_blocks / cpu_route.block_attributions)
+# =============================================================================
+IMPORTANCE_NODES_PER_PASS = 1 << 18     # nodes of the graphs importance_graphs() hands to one gnan_attr_blocks call
+
+
+@dataclass
+class GraphBatch:
+    """Many graphs for :func:`explain_graphs` / :func:`importance_graphs`: the node features ``x [N, F]`` of all graphs, node after
+    node, their hop codes as :class:`gnan_amd.batched.HopBlocks` (``D = blocks.n_codes``: the batch's largest hop + 2) and the shell
+    sizes ``cnt [N, D]`` int32 in the slot layout — column ``d < D - 1``: the pairs of the row coded ``d``; the last column: its
+    unreachable pairs; a hop no pair of the row has: 0 (every reader takes ``max(cnt, 1)``).  ``sizes``: the graphs' node counts,
+    on the host."""
+    x: torch.Tensor
+    blocks: object
+    cnt: Optional[torch.Tensor]
+    sizes: list
+
+    @property
+    def n_graphs(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def total_nodes(self) -> int:
+        return sum(self.sizes)
+
+    @property
+    def n_codes(self) -> int:
+        return self.blocks.n_codes
+
+    @staticmethod
+    def shell_counts(blocks) -> torch.Tensor:
+        """``cnt [N, D]`` of ``blocks`` in the slot layout: one ``bincount`` over the ``sum n_g^2`` codes (integer, exact)."""
+        dev = blocks.code.device
+        G, N, D = blocks.n_graphs, blocks.total_nodes, blocks.n_codes
+        if blocks.code.numel() == 0:
+            return torch.zeros((N, D), dtype=torch.int32, device=dev)
+        sizes = torch.tensor(blocks.sizes, dtype=torch.int64, device=dev)
+        graph_of = torch.repeat_interleave(torch.arange(G, device=dev), sizes * sizes)
+        local = torch.arange(blocks.code.numel(), device=dev) - blocks.code_off.long()[graph_of]
+        row = blocks.node_off.long()[graph_of] + local // sizes[graph_of]
+        shell = blocks.code.long().clamp_(max=D - 1)                          # 255 (unreachable inside the block) -> the last column
+        return torch.bincount(row * D + shell, minlength=N * D).view(N, D).to(torch.int32)
+
+    @staticmethod
+    def _of(x, blocks) -> "GraphBatch":
+        return GraphBatch(x, blocks, GraphBatch.shell_counts(blocks), list(blocks.sizes))
+
+    @staticmethod
+    def from_datas(datas) -> "GraphBatch":
+        """From objects with ``x [n_g, F]`` and ``edge_index [2, E_g]`` (the graph's own node ids), as ``attach_hop_graphs`` takes them:
+        the codes of all graphs by ``HopBlocks.from_edge_index`` (one ``gnan_bfs_blocks`` launch).  Objects that live on the CPU
+        carry the reference's dense ``node_distances`` (or a ``gnan_graph``) instead; their codes are read off it."""
+        from .batched import HopBlocks
+        from .graph import cat_edges
+        datas = list(datas)
+        if not datas:
+            raise ValueError("GraphBatch.from_datas: no graph")
+        sizes = [int(d.x.shape[0]) for d in datas]
+        x = torch.cat([d.x for d in datas], dim=0)
+        if x.is_cuda:
+            _lib.require_device(*[d.edge_index for d in datas])
+            ei, graph_of = cat_edges([d.edge_index for d in datas], sizes, x.device)
+            return GraphBatch._of(x, HopBlocks.from_edge_index(ei, graph_of, len(sizes), sizes=sizes))
+        from . import cpu_route
+        gs = [getattr(d, "gnan_graph", None) or cpu_route.graph_from_dense(d.node_distances, None) for d in datas]
+        if any(not g.is_dense for g in gs):
+            raise _lib.GnanHipError("GraphBatch holds dense hop blocks: a graph held as CSR goes through explain / explain_sources")
+        code = torch.cat([g.code.reshape(-1) for g in gs])
+        node_off, code_off = HopBlocks._offsets(sizes, "cpu")
+        return GraphBatch._of(x, HopBlocks(code, node_off, code_off, sizes, max(g.n_codes for g in gs) - 2))
+
+    @staticmethod
+    def from_edge_index(x: torch.Tensor, edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: Optional[int] = None) -> "GraphBatch":
+        """From a PyG-style batch on the device: ``x [N, F]``, ``edge_index [2, E]`` with global node ids, the sorted ``batch [N]``."""
+        from .batched import HopBlocks
+        _lib.require_device(x, edge_index, batch)
+        return GraphBatch._of(x, HopBlocks.from_edge_index(edge_index, batch, num_graphs))
+
+    def graphs(self, g0: int, g1: int) -> "GraphBatch":
+        """The graphs ``g0 .. g1 - 1`` as a batch of their own (views of this one's tensors, fresh offsets)."""
+        from .batched import HopBlocks
+        b = self.blocks
+        sizes = self.sizes[g0:g1]
+        n0, c0 = sum(self.sizes[:g0]), sum(s * s for s in self.sizes[:g0])
+        n1, c1 = n0 + sum(sizes), c0 + sum(s * s for s in sizes)
+        node_off, code_off = HopBlocks._offsets(sizes, b.code.device)
+        return GraphBatch(self.x[n0:n1], HopBlocks(b.code[c0:c1], node_off, code_off, sizes, b.n_codes - 2),
+                          None if self.cnt is None else self.cnt[n0:n1], sizes)
+
+
+@dataclass
+class _GraphTerms:
+    """The preamble of the batch fronts: operand rows, weight table (``lut`` for the kernel; per-row ``wt`` on the CPU route), and
+    the counts the kernel divides by (None: none, or already inside the table)."""
+    batch: GraphBatch
+    cpu: bool
+    fx: torch.Tensor
+    F: int
+    C: int
+    table: torch.Tensor
+    cnt: Optional[torch.Tensor]
+
+
+def _graph_terms(model, batch, who: str) -> _GraphTerms:
+    from . import batched, cpu_route
+    from .modules import StandaloneTensorGNAN, TensorGNAN
+    covered = isinstance(model, (batched.TensorGNAN, StandaloneTensorGNAN, TensorGNAN)) and bool(getattr(model, "is_graph_task", False))
+    if not covered:
+        raise _lib.GnanHipError(f"{who}() covers graph-level models (TensorGNAN with is_graph_task, batched.TensorGNAN with "
+                                f"is_graph_task); {type(model).__name__} here predicts per node or has no graph: use explain / "
+                                "explain_sources on one graph")
+    if model.training:
+        raise _lib.GnanHipError(f"{who}() describes the model in eval() mode (training-mode Dropout has no fixed decomposition)")
+    raw = isinstance(model, batched.TensorGNAN)
+    if raw and not isinstance(batch, GraphBatch):
+        x_batch, dist, bv = batch                                             # what its forward takes
+        _lib.require_device(x_batch)
+        blocks = model._blocks(dist, bv)
+        if blocks is None:
+            raise _lib.GnanHipError(f"{who}(): dist_batch is not block-diagonal over a sorted batch_vector")
+        batch = GraphBatch(x_batch, blocks, None, list(blocks.sizes))
+    if not isinstance(batch, GraphBatch):
+        raise ValueError(f"{who}() takes a GraphBatch (GraphBatch.from_datas / from_edge_index)")
+    if getattr(batch.blocks, "slots", False):
+        raise _lib.GnanHipError(f"{who}(): these blocks are the slots of a captured step: their sizes live on the device only")
+    x = batch.x
+    cpu = cpu_route.applies(model, x, batch.blocks.code)
+    if cpu and raw:
+        raise _lib.GnanHipError("batched.TensorGNAN has no CPU route: move the module and the batch to the GPU")
+    if not cpu:
+        _lib.require_device(x, batch.blocks.code, batch.cnt)
+    D, N = batch.n_codes, batch.total_nodes
+    f, rho = model._stacked("fs", model.fs), model._stacked("rho", [model.rho])
+    fx = cpu_route.shape_functions(x, f, False) if cpu else feature_mlps(x, f, sum_features=False)      # [N, F * C]: ONE call
+    F = x.shape[1]
+    t = _GraphTerms(batch, cpu, fx, F, fx.shape[1] // F, None, None)
+    norm = (not raw) and bool(model.normalize_rho)
+    if norm and batch.cnt is None:
+        raise ValueError(f"{who}(): the model normalises by the shell sizes, the batch carries no cnt")
+    pre = norm and isinstance(model, StandaloneTensorGNAN)
+    dev = x.device
+    if cpu:
+        u = hop_inputs(D, "cpu")
+        den = batch.cnt.clamp_min(1).float() if norm else None
+        if pre:
+            t.table = cpu_route._rho(model, u.unsqueeze(0) / den).view(N, D, -1)
+        else:
+            lut = cpu_route._rho(model, u)
+            t.table = lut.unsqueeze(0) / den.unsqueeze(-1) if norm else lut.unsqueeze(0).expand(N, -1, -1)
+    elif raw:
+        hops = torch.arange(D - 1, dtype=torch.float32, device=dev).view(-1, 1)                 # rho on the raw hop counts
+        t.table = torch.cat([feature_mlps(hops, rho, sum_features=False), torch.zeros(1, rho.C, device=dev)], dim=0)
+    elif pre:
+        from .functional import rho_row_lut
+        t.table = rho_row_lut(batch.cnt, hop_inputs(D, dev), rho)                               # [N, D, C]
+    else:
+        t.table = feature_mlps(hop_inputs(D, dev).view(-1, 1), rho, sum_features=False)         # [D, C_rho]: ONE call
+        t.cnt = batch.cnt if norm else None
+    return t
+
+
+def _block_terms(t: _GraphTerms, batch: GraphBatch, n0: int, want_nodes: bool, want_graphs: bool):
+    """``(B, T)`` of ``batch`` — the whole batch of ``t`` or a run of its graphs whose first node is ``n0``."""
+    from . import attribution, cpu_route
+    n1 = n0 + batch.total_nodes
+    table = t.table if t.table.dim() == 2 else t.table[n0:n1]
+    if t.cpu:
+        return cpu_route.block_attributions(batch.blocks, t.fx[n0:n1], table, want_nodes, want_graphs)
+    return attribution.block_attributions(batch.blocks, t.fx[n0:n1], table, None if t.cnt is None else t.cnt[n0:n1], want_nodes, want_graphs)
+
+
+@dataclass
+class GraphExplanations:
+    """The outputs of the ``G`` graphs of a batch, decomposed: ``by_graph[g, k, d, c]`` is what feature ``k`` at hop ``hops[d]``
+    (``hops[-1] = inf``: the unreachable pairs) adds to channel ``c`` of graph ``g``'s output before a read-out — graph ``g``'s
+    ``Explanation.graph_by_feature_distance``; ``output[g] = by_graph[g].sum((0, 1))``.  ``by_node_feature_distance[j, k, d, c]`` /
+    ``by_node[j]``: the share of node ``j`` (``graph_of[j]`` names its graph, ``node_off`` the graphs' first nodes) in ITS graph's
+    output; None under ``by_node=False``.  With a NAM read-out (``models.TensorGNAN``): ``hidden [G, F]``, ``hidden_by_node [N, F]``
+    and ``readout_by_feature[g, k] = g_k(hidden[g, k])``, whose sum over ``k`` is the model's output for graph ``g``."""
+    node_off: torch.Tensor
+    graph_of: torch.Tensor
+    hops: torch.Tensor
+    by_graph: torch.Tensor
+    output: torch.Tensor
+    by_node_feature_distance: Optional[torch.Tensor] = None
+    by_node: Optional[torch.Tensor] = None
+    hidden: Optional[torch.Tensor] = None
+    hidden_by_node: Optional[torch.Tensor] = None
+    readout_by_feature: Optional[torch.Tensor] = None
+
+
+@torch.no_grad()
+def explain_graphs(model, batch, by_node: bool = True) -> GraphExplanations:
+    """Every graph of ``batch`` (:class:`GraphBatch`; for ``batched.TensorGNAN`` also what its forward takes: ``(x_batch, HopBlocks
+    or dense dist_batch, batch_vector)``) explained in one pass — the model in ``eval()`` mode.  A module on the GPU runs
+    ``gnan_attr_blocks``: the launches do not grow with the number of graphs; a module that lives on the CPU, with a CPU batch,
+    runs ``cpu_route.block_attributions``.  Covers graph-level ``TensorGNAN`` modules and ``batched.TensorGNAN``.  The per-node
+    result's bytes grow as ``N * F * D * C``: ``attribution.ATTR_MAX_BYTES`` bounds them, pass the graphs in batches beyond
+    (:meth:`GraphBatch.graphs`) or ask for ``by_node=False``."""
+    from . import cpu_route
+    from .modules import TensorGNAN
+    t = _graph_terms(model, batch, "explain_graphs")
+    batch = t.batch
+    G, N, D, F, C = batch.n_graphs, batch.total_nodes, batch.n_codes, t.F, t.C
+    dev = batch.x.device
+    B, T = _block_terms(t, batch, 0, by_node, True)
+    by_graph = T.view(G, D, F, C).permute(0, 2, 1, 3).contiguous()            # [G, F, D, C]
+    sizes = torch.tensor(batch.sizes, dtype=torch.int64)
+    node_off = torch.zeros(G + 1, dtype=torch.int64)
+    torch.cumsum(sizes, 0, out=node_off[1:])
+    graph_of = torch.repeat_interleave(torch.arange(G), sizes).to(dev)
+    out = GraphExplanations(node_off.to(dev), graph_of, _hops(D, dev), by_graph, by_graph.sum(dim=2).sum(dim=1))
+    if by_node:
+        out.by_node_feature_distance = B.view(N, D, F, C).permute(0, 2, 1, 3).contiguous()          # [N, F, D, C]
+        out.by_node = out.by_node_feature_distance.sum(dim=2).sum(dim=1)
+    if isinstance(model, TensorGNAN) and model.readout_n_layers > 0:
+        nam = model.readout_nam
+        out.hidden = by_graph.sum(dim=2).view(G, F)                           # models.py:379, every graph's row
+        if by_node:
+            out.hidden_by_node = out.by_node_feature_distance.sum(dim=2).view(N, F)
+        stacked = nam._stacked("fs", nam.fs)
+        gk = cpu_route.shape_functions(out.hidden, stacked, False) if t.cpu \
+            else feature_mlps(out.hidden.contiguous(), stacked, sum_features=False)             # ONE call on [G, F]
+        out.readout_by_feature = gk.view(G, F, -1)
+    return out
+
+
+@dataclass
+class GraphImportance:
+    """The moments of :class:`GraphExplanations`' ``by_graph`` over the GRAPHS of each group: ``mean``, ``mean_abs`` and ``rms``
+    ``[Gr, F, D, C]``; ``feature_mean``, ``feature_mean_abs``, ``feature_rms`` ``[Gr, F, C]`` the same of a feature's total over the
+    distances.  ``group_labels [Gr]``: the distinct labels, ascending; ``count [Gr]``: the graphs of each.  All float64.
+    ``mean * count`` summed over ``(k, d)`` is the sum of the group's outputs before a read-out."""
+    group_labels: torch.Tensor
+    count: torch.Tensor
+    hops: torch.Tensor
+    mean: torch.Tensor
+    mean_abs: torch.Tensor
+    rms: torch.Tensor
+    feature_mean: torch.Tensor
+    feature_mean_abs: torch.Tensor
+    feature_rms: torch.Tensor
+
+
+@torch.no_grad()
+def importance_graphs(model, batch, groups=None, max_nodes_per_pass: int = IMPORTANCE_NODES_PER_PASS) -> GraphImportance:
+    """Which feature at which distance matters over the graphs of ``batch``, optionally apart by ``groups`` — one integer label per
+    graph, the class for example.  The per-node terms are never stored: ``gnan_attr_blocks`` gives the per-graph sums alone, over
+    runs of consecutive graphs of at most ``max_nodes_per_pass`` nodes (a larger graph is a run of its own; a graph's bits do not
+    depend on the run it falls into); the moments are formed in float64 on the ``G * F * D * C`` numbers.  Model cover and refusals
+    as :func:`explain_graphs`."""
+    t = _graph_terms(model, batch, "importance_graphs")
+    batch = t.batch
+    G, D, F, C = batch.n_graphs, batch.n_codes, t.F, t.C
+    dev = batch.x.device
+    lab = torch.zeros(G, dtype=torch.int64, device=dev) if groups is None else \
+        torch.as_tensor(list(groups) if not torch.is_tensor(groups) else groups).to(device=dev, dtype=torch.int64).view(-1)
+    if lab.numel() != G:
+        raise ValueError(f"groups must hold one label per graph ({G}), got {lab.numel()}")
+    parts, g0, n0 = [], 0, 0
+    while g0 < G:
+        g1, nodes = g0, 0
+        while g1 < G and (g1 == g0 or nodes + batch.sizes[g1] <= max_nodes_per_pass):
+            nodes += batch.sizes[g1]
+            g1 += 1
+        run = batch if (g0, g1) == (0, G) else batch.graphs(g0, g1)
+        parts.append(_block_terms(t, run, n0, False, True)[1])
+        g0, n0 = g1, n0 + nodes
+    T = torch.cat(parts, dim=0) if len(parts) > 1 else parts[0]
+    a = T.view(G, D, F, C).permute(0, 2, 1, 3).double()                       # [G, F, D, C]
+    a = torch.cat([a, a.sum(dim=2, keepdim=True)], dim=2)                     # slot D: a feature's total over the distances
+    labels, who, count = torch.unique(lab, sorted=True, return_inverse=True, return_counts=True)
+    M = torch.zeros((labels.numel(), 3, F, D + 1, C), dtype=torch.float64, device=dev)
+    for j, v in enumerate((a, a.abs(), a * a)):
+        M[:, j].index_add_(0, who, v)
+    n = count.double().clamp_min(1.0).view(-1, 1, 1, 1)
+    mean, mean_abs, rms = M[:, 0] / n, M[:, 1] / n, (M[:, 2] / n).sqrt()
+    return GraphImportance(labels, count.double(), _hops(D, dev).double(), mean[:, :, :D].contiguous(), mean_abs[:, :, :D].contiguous(),
+                           rms[:, :, :D].contiguous(), mean[:, :, D].contiguous(), mean_abs[:, :, D].contiguous(), rms[:, :, D].contiguous())

@@ -2309,6 +2309,80 @@ int gnan_attr_reduce_describe(const gnan_attr_reduce_args* a, gnan_attr_reduce_i
 int gnan_attr_reduce(const gnan_attr_reduce_args* a, gnan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attributions of a BATCH of graphs (added under ABI 51; csrc/attr_blocks.hip, gnan_amd.attribution.block_attributions): per
+ * source node and per graph, for all graphs of a batch in one call.  The batch holds G graphs with N = sum n_g nodes as
+ * gnan_amd.batched.HopBlocks keeps them: `code`, the [n_g, n_g] uint8 blocks back to back (entry (i, j): the hop at which row i
+ * sees node j; 255 = not listed), node_off [G + 1] int32 and code_off [G + 1] int64, all on the device.  Operand rows S [N, W],
+ * weight table lut [D, Cw] (shared) or [N, D, Cw] (per forward row), Cw | W, optional shell sizes cnt [N, D].  For nodes i, j
+ * of the same graph g, d(i, j) = min(code_g[i, j], D - 1): 255 and every listed code >= D - 1 fall into the rest shell and
+ * never index past it.
+ *
+ *   wt(i, d, c) = lut[(i,) d, c] / max(cnt[i, d], 1)                       (no cnt: lut itself)
+ *   V[j, d, c]  = sum over the nodes i of j's graph with d(i, j) == d of wt(i, d, c)
+ *   B[j, d, w]  = V[j, d, w % Cw] * S[j, w]                                what node j adds to its graph's summed output
+ *   T[g, d, w]  = sum over the nodes j of graph g, in node order, of B[j, d, w]
+ *
+ * B restricted to graph g is gnan_attr_cols' result for that graph alone (dense layout, every row requested once,
+ * rest_from_total == 0); no pair of two different graphs exists.  B is [N, D, W] fp32 with b_stride floats between nodes, T is
+ * [G, D, W] fp32, contiguous; a graph without nodes has a row of zeros in T.  Either output may be NULL, not both; each has the
+ * bits it has alone (T is summed from V and S, never from B).
+ *
+ * Launches (at most three, whatever G): (1) one workgroup per tile of tile_cols consecutive columns of one graph — workgroup
+ * g * col_tiles + t, col_tiles = ceil(max_nodes / tile_cols), a tile past the graph's last column leaves at once; lanes own
+ * columns (a row's codes are one coalesced read), the waves own row_slices interleaved row slices, lane-private bins in LDS,
+ * the (shell, channel) bins d * Cw + c in passes of 64; the weights of row_chunk rows are staged in LDS once per chunk (one
+ * division per (row, bin)); a lane adds its rows in row order, the slices are added in the tree (s0 + s1) + (s2 + s3); V goes to
+ * the workspace [N, D * Cw].  (2) B = V * S, streaming.  (3) T: a thread per (graph, shell, column), nodes in node order.  No
+ * floating-point atomic, no arrival counter, no workgroup waits for another: the bits of graph g's rows of B and of T[g] depend
+ * on graph g's data alone — not on its place in the batch, the other graphs or the launch.
+ *
+ * Cover: any n_g >= 0, 0 <= G <= 2^31 - 1 with G * col_tiles <= 2^31 - 1 (GNAN_ERR_UNSUPPORTED beyond, advising batches),
+ * 2 <= D <= GNAN_MAX_CODES (GNAN_ERR_UNSUPPORTED naming limit and value), W >= 1, Cw | W.  max_nodes must be at least the
+ * largest n_g (the columns beyond it would not be walked).  Null pointers, both outputs NULL, short strides, Cw not dividing
+ * W are GNAN_ERR_BAD_ARG, a short workspace GNAN_ERR_WORKSPACE — all before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gnan_attr_blocks_args {
+  const uint8_t* code;       /* packed [n_g, n_g] blocks */
+  const int32_t* node_off;   /* [n_graphs + 1] */
+  const int64_t* code_off;   /* [n_graphs + 1] */
+  int64_t n_graphs;
+  int64_t total_nodes;       /* N: rows of S, cnt, a per-row lut, B */
+  int64_t max_nodes;         /* >= the largest n_g */
+  const float* S;            /* [N, W] */
+  int32_t W;
+  int64_t s_stride;
+  const float* lut;          /* [D, Cw] or [N, D, Cw] */
+  int64_t lut_row_stride;    /* 0 => one table */
+  int32_t D;
+  int32_t Cw;
+  const int32_t* cnt;        /* optional [N, cnt_stride] */
+  int64_t cnt_stride;
+  float* B;                  /* [N, D, W] or NULL */
+  int64_t b_stride;          /* >= D * W */
+  float* T;                  /* [n_graphs, D, W] or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+} gnan_attr_blocks_args;
+
+typedef struct gnan_attr_blocks_info {
+  int32_t tile_cols;         /* columns per tile (one lane each) */
+  int32_t col_tiles;         /* tiles of the widest graph: ceil(max_nodes / tile_cols) */
+  int32_t bin_passes;        /* walks of a tile: ceil(D * Cw / 64) */
+  int32_t row_chunk;         /* rows whose weights are staged at a time */
+  int32_t row_slices;        /* interleaved row slices (waves) of a tile, added in a fixed tree */
+  int32_t block_size;
+  int32_t launches;
+  int32_t lds_bytes;         /* of the walk: the slices' bins and the staged weights */
+  int64_t n_tiles;           /* workgroups of the walk: n_graphs * col_tiles */
+  size_t v_bytes;            /* V [N, D * Cw] floats: the whole workspace */
+  size_t workspace_bytes;
+} gnan_attr_blocks_info;
+
+size_t gnan_attr_blocks_workspace_bytes(const gnan_attr_blocks_args* a);
+int gnan_attr_blocks_describe(const gnan_attr_blocks_args* a, gnan_attr_blocks_info* out);
+int gnan_attr_blocks(const gnan_attr_blocks_args* a, gnan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph hygiene for captured steps (gnan_amd/graphed.py; nothing comparable in the reference, which issues every
  * epoch's launches from Python, trainer.py:23-86).  `graph` is a hipGraph_t obtained by stream capture and not yet
  * instantiated: every memset node is replaced by a kernel node performing the same fill, with the same dependencies
